@@ -217,7 +217,11 @@ int dtof_render_stripes_async(dtof_scene *scene, uint32_t seed, uint32_t spp, in
  * floats, `plane_stride_floats` apart (0 = dense).  Film k of the batched offsets is plane k; the alpha film of an rgba scene (dtof_scene_info::has_alpha,
  * FilmFlags::Alpha, src/films/hdrfilm.cpp:172-177; ImageBlock::put of aovs[3], integrator.cpp:528-533) is plane n_offsets.  A call that would write more planes than were
  * declared fails with DTOF_ERR_INVALID instead of writing past the buffer; planes = 0 (the default) declares nothing: rgb scenes write their n_offsets planes, rgba scenes
- * are refused.  A band shard that renders into a padded slab (pointer = slab + halo rows) passes the slab's size as the stride. */
+ * are refused.  A band shard that renders into a padded slab (pointer = slab + halo rows) passes the slab's size as the stride.  The planes must not overlap: when a
+ * call writes more than one plane and a stride is declared, the stride must hold every film row the call can write -- rows [max(first - h, 0), min(last + 1 + h,
+ * crop_height)) for its first and last rendered rows (the band of dtof_render_rows, the first and last stripe row of dtof_render_stripes) and the filter's halo h
+ * (dtof_scene_info::filter_halo) -- times crop_width * 4 floats; a smaller stride fails with DTOF_ERR_INVALID before anything is launched.  The layout is state of
+ * the scene: it holds for every later call until it is declared again. */
 int dtof_scene_set_film_layout(dtof_scene *scene, int32_t planes, uint64_t plane_stride_floats);
 /* HDRFilm::develop (src/films/hdrfilm.cpp:305-406) on device buffers: rgb = RGB / (W == 0 ? 1 : W). */
 int dtof_develop(const float *d_film_rgbw, float *d_rgb, int64_t n_pixels);

@@ -181,6 +181,7 @@ class Scene:
     def __init__(self, handle):
         self._h = handle
         self.last_stats = None
+        self._film_layout = (0, 0)
 
     def __del__(self):
         try:
@@ -230,8 +231,16 @@ class Scene:
 
     def set_film_layout(self, planes, plane_stride_floats=0):
         """Declare the caller's device film for render_rows / render_stripes (dtof_scene_set_film_layout): `planes` RGBW planes, `plane_stride_floats` apart (0 = dense
-        H * W * 4).  An rgba scene needs n_offsets + 1 planes -- the alpha film lies behind the colour films -- and is refused until they are declared."""
+        H * W * 4).  An rgba scene needs n_offsets + 1 planes -- the alpha film lies behind the colour films -- and is refused until they are declared.  With more
+        than one plane, a stride too small for the rows a call writes (its rows plus the filter's halo) is refused by that call."""
         _check(_lib().dtof_scene_set_film_layout(self._h, int(planes), int(plane_stride_floats)))
+        self._film_layout = (int(planes), int(plane_stride_floats))
+
+    @property
+    def film_layout(self):
+        """(planes, plane_stride_floats) as last declared with set_film_layout; (0, 0) = nothing declared.  A helper that declares a layout of its own
+        (distributed.render_sharded / render_striped) puts this one back."""
+        return getattr(self, "_film_layout", (0, 0))
 
     def film_planes(self, n_offsets=1):
         """RGBW planes the device-film calls write for `n_offsets` batched offsets: one more for the alpha film of an rgba scene"""

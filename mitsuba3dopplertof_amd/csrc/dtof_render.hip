@@ -296,7 +296,9 @@ struct StageTimer {
 
 // The device-film entry points write K colour planes and, for an rgba film, the alpha plane behind them into memory whose size only the caller knows: an rgba scene is
 // refused until the caller has declared a film of K + 1 planes (a caller written for rgb films would have its buffer overrun), and a declared count is checked either way.
-static uint64_t caller_film_stride(const dtof_scene *sc, int n_offsets) {
+// [row_lo, row_hi): the film rows whose lanes the call renders.  Their splats reach `halo` rows further (the reconstruction filter), so with more than one plane a
+// declared stride must hold rows [max(row_lo - halo, 0), min(row_hi + halo, H)) or plane k + 1 would be added into plane k: such a call is refused before any launch.
+static uint64_t caller_film_stride(const dtof_scene *sc, int n_offsets, int32_t row_lo, int32_t row_hi) {
     const HostSensor &se = sc->host.sensor;
     const int need = (n_offsets <= 0 ? 1 : n_offsets) + (se.alpha ? 1 : 0);
     if (se.alpha && sc->film_planes < need)
@@ -304,7 +306,23 @@ static uint64_t caller_film_stride(const dtof_scene *sc, int n_offsets) {
     if (sc->film_planes != 0 && sc->film_planes < need)
         throw std::runtime_error("the device film was declared with " + std::to_string(sc->film_planes) + " planes, this call writes " + std::to_string(need));
     const uint64_t full = (uint64_t) se.crop_w * se.crop_h * 4;
+    if (need > 1 && sc->film_plane_stride != 0) {
+        const int32_t halo = se.filter == FILTER_BOX ? 0 : (int32_t) std::ceil(se.filter_radius - .5f);
+        const int32_t r0 = std::max(row_lo, 0), r1 = std::min(row_hi, se.crop_h);
+        const int32_t lo = std::max(r0 - halo, 0), hi = std::min(r1 + halo, se.crop_h);
+        const uint64_t reach = r1 > r0 ? (uint64_t) (hi - lo) * se.crop_w * 4 : 0;   // an empty band writes nothing
+        if (sc->film_plane_stride < reach)
+            throw std::runtime_error("the declared plane stride of " + std::to_string(sc->film_plane_stride) + " floats is smaller than the " + std::to_string(reach) +
+                                     " floats of film rows [" + std::to_string(lo) + ", " + std::to_string(hi) + ") this call writes: the planes would overlap");
+    }
     return sc->film_plane_stride ? sc->film_plane_stride : full;
+}
+// the rows [first, last + 1) that hold the stripes [first_row + k * stripe_period, ... + stripe_rows) below the film's height (the mapping of render_rows)
+static std::pair<int32_t, int32_t> stripe_span(const dtof_scene *sc, int32_t first_row, int32_t stripe_rows, int32_t stripe_period) {
+    const int32_t h = sc->host.sensor.crop_h, first = std::max(first_row, 0);
+    const int64_t span = std::max<int64_t>(h - first, 0), v_rows = (span / stripe_period) * stripe_rows + std::min<int64_t>(span % stripe_period, stripe_rows);
+    if (v_rows == 0) return {first, first};
+    return {first, (int32_t) (first + ((v_rows - 1) / stripe_rows) * stripe_period + (v_rows - 1) % stripe_rows + 1)};
 }
 
 // The wavefront loop over pixel rows [row_begin,row_end); accumulates into d_film (K films, sc->film_stride_call floats apart).
@@ -882,7 +900,7 @@ int dtof_render_rows(dtof_scene *sc, uint32_t seed, uint32_t spp, int32_t row_be
     return guarded([&] {
         if (!sc || !d_film) throw std::runtime_error("null argument");
         sc->stop = false;
-        sc->film_stride_call = caller_film_stride(sc, n_offsets);
+        sc->film_stride_call = caller_film_stride(sc, n_offsets, row_begin, row_end);
         render_rows(sc, seed, spp, row_begin, row_end, offsets, n_offsets, d_film, stats);
     });
 }
@@ -891,9 +909,9 @@ int dtof_render_rows_async(dtof_scene *sc, uint32_t seed, uint32_t spp, int32_t 
     return guarded([&] {
         if (!sc || !d_film) throw std::runtime_error("null argument");
         sc->stop = false;
+        sc->film_stride_call = caller_film_stride(sc, n_offsets, row_begin, row_end);   // a refused film leaves the next call synchronous
         dtof_render_stats local;
         sc->defer_next = true;
-        sc->film_stride_call = caller_film_stride(sc, n_offsets);
         try { render_rows(sc, seed, spp, row_begin, row_end, offsets, n_offsets, d_film, &local); }
         catch (...) { sc->defer_next = false; if (sc->deferred.empty()) sc->events_used = 0; throw; }   // the events the failed frame took go back to the pool
     });
@@ -928,9 +946,10 @@ int dtof_render_stripes_async(dtof_scene *sc, uint32_t seed, uint32_t spp, int32
         if (!sc || !d_film) throw std::runtime_error("null argument");
         if (first_row < 0 || stripe_rows <= 0 || stripe_period < stripe_rows) throw std::runtime_error("invalid stripe layout");
         sc->stop = false;
+        const std::pair<int32_t, int32_t> rows = stripe_span(sc, first_row, stripe_rows, stripe_period);
+        sc->film_stride_call = caller_film_stride(sc, n_offsets, rows.first, rows.second);
         dtof_render_stats local;
         sc->defer_next = true;
-        sc->film_stride_call = caller_film_stride(sc, n_offsets);
         try { render_rows(sc, seed, spp, first_row, sc->host.sensor.crop_h, offsets, n_offsets, d_film, &local, nullptr, 0, 0, (uint32_t) stripe_rows, (uint32_t) stripe_period); }
         catch (...) { sc->defer_next = false; if (sc->deferred.empty()) sc->events_used = 0; throw; }
     });
@@ -980,7 +999,8 @@ int dtof_render_stripes(dtof_scene *sc, uint32_t seed, uint32_t spp, int32_t fir
         if (!sc || !d_film) throw std::runtime_error("null argument");
         if (first_row < 0 || stripe_rows <= 0 || stripe_period < stripe_rows) throw std::runtime_error("invalid stripe layout");
         sc->stop = false;
-        sc->film_stride_call = caller_film_stride(sc, n_offsets);
+        const std::pair<int32_t, int32_t> rows = stripe_span(sc, first_row, stripe_rows, stripe_period);
+        sc->film_stride_call = caller_film_stride(sc, n_offsets, rows.first, rows.second);
         render_rows(sc, seed, spp, first_row, sc->host.sensor.crop_h, offsets, n_offsets, d_film, stats, nullptr, 0, 0, (uint32_t) stripe_rows, (uint32_t) stripe_period);
     });
 }

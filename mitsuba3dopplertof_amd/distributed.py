@@ -139,10 +139,14 @@ def render_striped(scene, seed=0, spp=0, stripe_rows=16, group=None):
     dev = torch.device("cuda", torch.cuda.current_device())
     planes = scene.film_planes()                  # 2 for an rgba film: the alpha film is one more RGBW plane behind the colour film
     film = torch.zeros((planes, H, W, 4), dtype=torch.float32, device=dev)
-    scene.set_film_layout(planes)
-    torch.cuda.synchronize()
     first, rows, period = stripe_layout(world, rank, stripe_rows)
-    scene.render_stripes(film.data_ptr(), seed, spp, first, rows, period)
+    caller = scene.film_layout
+    scene.set_film_layout(planes)
+    try:
+        torch.cuda.synchronize()
+        scene.render_stripes(film.data_ptr(), seed, spp, first, rows, period)
+    finally:
+        scene.set_film_layout(*caller)             # the layout is state of the scene: the caller's own calls find theirs again
     film = reduce_film(film, rank, world, group)
     if rank != 0:
         return None
@@ -180,9 +184,13 @@ def render_sharded(scene, seed=0, spp=0, halo=None, group=None):
     r0, r1 = row_band(H, world, rank)
     planes, rows = scene.film_planes(), padded_rows(H, world, halo)
     film = torch.zeros((planes, rows, W, 4), dtype=torch.float32, device=dev)
+    caller = scene.film_layout
     scene.set_film_layout(planes, rows * W * 4)   # the planes of the padded film lie a whole padded film apart
-    torch.cuda.synchronize()
-    scene.render_rows(film.data_ptr() + halo * W * 4 * 4, seed=seed, spp=spp, row_begin=r0, row_end=r1)
+    try:
+        torch.cuda.synchronize()
+        scene.render_rows(film.data_ptr() + halo * W * 4 * 4, seed=seed, spp=spp, row_begin=r0, row_end=r1)
+    finally:
+        scene.set_film_layout(*caller)
     p0, p1 = slab_range(H, world, rank, halo)
     # a band of ALL planes as one slab of rows, [rows, planes * W, 4]: one gather moves it and the overlap-add works on rows
     slab = film[:, p0:p1].permute(1, 0, 2, 3).reshape(p1 - p0, planes * W, 4).contiguous()
