@@ -145,21 +145,30 @@ constexpr uint32_t kResidentNodes = 1024;   // TLAS nodes the stage holds (= kRe
 uint32_t resident_lds_bytes(const RenderParams &rp, const ResidentStage &resident, uint32_t stack_depth, uint32_t waves);
 uint32_t device_lds_limit();   // hipDeviceAttributeMaxSharedMemoryPerBlock of the current device (160 KiB on gfx950), minus the kernels' static LDS
 
+// The launchers' development switches, read once per frame with the others (dtof_render.hip: read_switches, which lists them)
+struct LaunchSwitches {
+    int defer = 2;                              // DTOF_DEFER: ray kernels as a pair of launches (0 when the frame's workspace has no DEFER lists)
+    bool trace8 = true, nodes16 = true, tlas_lds = true, stage = true;   // DTOF_TRACE8 / NODES16 / TLAS_LDS / STAGE
+    bool xcd_set = false; uint32_t xcd_remap = 0;                          // DTOF_XCD_REMAP, when set
+    uint32_t trace_block = 0;                   // DTOF_TRACE_BLOCK: 64 / 128 / 256, 0 = automatic
+    int splat = 0;                              // DTOF_SPLAT: 0 automatic, 1 dpp, 2 generic
+};
+
 // kernels (dtof_kernels.hip)
 void launch_generate(const RenderParams &rp, const Queues &q, hipStream_t s);
 void launch_sum_counts(const uint32_t *counts, uint32_t n_seg, uint32_t n_rows, unsigned long long *out, hipStream_t s);
 uint32_t segments_for(uint32_t n_lanes);   // number of queue segments (count slots) for a batch
 void launch_trace(const uint8_t *scene, uint32_t scene_bytes, const RenderParams &rp, const Queues &q,
-                  const uint32_t *qin, const uint32_t *count_in, uint32_t stack_depth, hipStream_t s);
+                  const uint32_t *qin, const uint32_t *count_in, uint32_t stack_depth, const LaunchSwitches &ls, hipStream_t s);
 void launch_shade(const uint8_t *scene, uint32_t scene_bytes, const RenderParams &rp, const Queues &q,
                   const uint32_t *qin, const uint32_t *count_in, uint32_t *qout,
                   uint32_t *alive_out, uint32_t *shadow_out, uint32_t depth, bool fused, bool trace_next,
-                  uint32_t stack_depth, hipStream_t s, bool first = false, LaneDebug *dbg = nullptr,   // first: generate + primary trace inline (fused only)
+                  uint32_t stack_depth, const LaunchSwitches &ls, hipStream_t s, bool first = false, LaneDebug *dbg = nullptr,   // first: generate + primary trace inline (fused only)
                   const ResidentStage *resident = nullptr, float *film = nullptr, uint64_t film_stride = 0);   // film: the launch covers the whole path and splats its lanes itself
 void launch_shadow(const uint8_t *scene, uint32_t scene_bytes, const RenderParams &rp, const Queues &q,
-                   const uint32_t *count_in, uint32_t stack_depth, hipStream_t s);
-void launch_velocity(const uint8_t *scene, uint32_t scene_bytes, const RenderParams &rp, const Queues &q, uint32_t stack_depth, hipStream_t s);
-void launch_splat(const RenderParams &rp, const Queues &q, float *film, uint64_t plane_stride, hipStream_t s);
+                   const uint32_t *count_in, uint32_t stack_depth, const LaunchSwitches &ls, hipStream_t s);
+void launch_velocity(const uint8_t *scene, uint32_t scene_bytes, const RenderParams &rp, const Queues &q, uint32_t stack_depth, const LaunchSwitches &ls, hipStream_t s);
+void launch_splat(const RenderParams &rp, const Queues &q, float *film, uint64_t plane_stride, const LaunchSwitches &ls, hipStream_t s);
 void launch_develop(const float *film, float *rgb, int64_t n_pixels, hipStream_t s);
 void launch_develop_rgba(const float *film, const float *alpha_film, float *rgba, int64_t n_pixels, hipStream_t s);   // pixel_format = rgba (hdrfilm.cpp:339-400)
 void launch_lane_dump(const RenderParams &rp, const Queues &q, LaneDebug *out, hipStream_t s);

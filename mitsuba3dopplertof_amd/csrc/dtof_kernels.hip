@@ -55,7 +55,7 @@ constexpr uint32_t kTlasLds8 = 16;
 // the blocks that share an XCD a CONTIGUOUS run of segments (= a band of the image for the primary and shadow rays), so each L2 mostly holds the geometry of its band.
 // Which block traces which segment changes nothing in the results.  MEASURED on the mesh room (512 x 512 x 64 spp, 522 k triangles; profiles/r05_mesh_room.txt), run = blocks
 // an XCD gets in a row: off 6.90 G rays/s | 8 (one segment) 6.90 | 64 6.05 | 512 (ONE PIXEL ROW) 7.23 | 1 024 7.15 | 2 048 7.12 | 4 096 6.91 | a whole band per XCD 5.68 (the
-// bands cost different amounts: the XCDs finish one after the other).  Default: one pixel row per run for scenes with a BLAS (xcd_run below); DTOF_XCD_REMAP=<run> | 0 overrides.
+// bands cost different amounts: the XCDs finish one after the other).  Default: one pixel row per run for scenes with a BLAS (ray_shape below); DTOF_XCD_REMAP=<run> | 0 overrides.
 // `run` = consecutive segments one XCD gets before the next XCD's run starts (a whole-image band per XCD -- run = n / 8 -- LOST 18 % on the mesh room: the bands cost
 // different amounts and the XCDs finish one after the other); blocks beyond the last full group of 8 runs keep their index.
 DTOF_D uint32_t xcd_remap(uint32_t orig, uint32_t n, uint32_t run) {
@@ -537,51 +537,14 @@ __global__ void k_lane_dump_rays(RenderParams rp, Queues q, LaneDebug *out) {
 // 1024^2 x 32 spp, one box): 4 KB blob staged 3.84 ms vs 4.28 ms unstaged, 9 KB 4.63 vs 5.16, 30 KB 10.39 vs 7.90 (every 64-lane shade
 // block and every 256-lane trace block copies the blob; the L1 hit rate of the unstaged kernels is 99 % on such scenes).
 constexpr uint32_t kLdsSceneLimit = 16 * 1024;
-// Block size of the unstaged k_trace / k_shadow instantiations.  One wave per block when some mesh has its own BLAS: those
-// traversals are long and divergent, and a 256-thread block keeps its LDS and wave slots until its slowest wave is done (mesh room,
-// 522 k triangles: 20.1 -> 16.6 ms per frame).  Scenes of many small objects (Domino: 1 025 instances of a 12-triangle cube) are
-// faster with four waves sharing a CU's L1 on the same TLAS / object records (71.3 vs 75.3 ms).  DTOF_TRACE_BLOCK = 64 | 128 | 256
-// overrides (experiments).
-// the eight-waves-per-SIMD ray kernels (k_trace / k_shadow<false, true, 64, true>): one-wave blocks of an unstaged scene whose meshes sit behind a BLAS and that has no
-// analytic shape (their float64 code does not fit 64 VGPRs), stacks no deeper than the LDS part + the overflow array.  DTOF_TRACE8=0 keeps the six-wave kernels (A/B).
-static inline bool eight_wave_rays(const RenderParams &rp, uint32_t stage_words, uint32_t block, uint32_t stack_depth);
-static inline uint32_t unstaged_block(const RenderParams &rp) {
-    static const uint32_t env = [] { const char *e = getenv("DTOF_TRACE_BLOCK"); int b = e ? atoi(e) : 0; return (uint32_t) (b == 64 || b == 128 || b == 256 ? b : 0); }();
-    return env ? env : (rp.has_blas ? 64u : (uint32_t) kBlock);
-}
-
-
-static inline uint32_t xcd_run(const RenderParams &rp, uint32_t stage_words, uint32_t block) {
-    if (const char *e = getenv("DTOF_XCD_REMAP")) return (uint32_t) atoi(e);   // read per call: A/B runs
-    if (stage_words != 0 || !rp.has_blas) return 0;                              // scenes staged in LDS and scenes of small objects: L2 locality is not what they wait for
-    const uint64_t row_blocks = (uint64_t) rp.crop_w * rp.spp / block;
-    return (uint32_t) (row_blocks >= 8 && row_blocks <= (1u << 20) ? row_blocks : 0);
-}
-static inline int defer_rays(const Queues &q) {   // DTOF_DEFER=0: one launch per ray kernel (A/B, tests); 1: every ray kernel as a pair; 2: all but the primary rays'; 3: the shadow rays' only.  The workspace has the lists only for scenes with a BLAS (render_rows)
-    const char *e = getenv("DTOF_DEFER"); const int v = e ? atoi(e) : 2;   // (measured: profiles/r05_mesh_room.txt section 8 -- primary rays that reach a blob already fill their waves)
-    return q.cand != nullptr ? v : 0;
-}
-static inline bool half_nodes(const RenderParams &rp) {   // DTOF_NODES16=0: the 64-byte float nodes (A/B, tests)
-    const char *e = getenv("DTOF_NODES16"); const bool off = e && e[0] == '0';
-    return !off && rp.has_nodes16;
-}
-static inline bool tlas_in_lds(const RenderParams &rp) {   // DTOF_TLAS_LDS=0: the TLAS is walked in global memory like the BLAS (A/B, tests)
-    const char *e = getenv("DTOF_TLAS_LDS"); const bool off = e && e[0] == '0';
-    return !off && rp.n_tlas_nodes != 0 && rp.n_tlas_nodes <= kTlasLds8;
-}
-static inline bool eight_wave_rays(const RenderParams &rp, uint32_t stage_words, uint32_t block, uint32_t stack_depth) {
-    const char *e = getenv("DTOF_TRACE8"); const bool off = e && e[0] == '0';   // read per call (a few launches per frame): tests and A/B runs switch it inside one process
-    return !off && stage_words == 0 && block == 64 && rp.has_tris && rp.has_blas && !rp.has_analytic && stack_depth <= kLdsStack8 + kOvfStack8;   // (whatever the materials: the ray kernels only intersect)
-}
 void launch_generate(const RenderParams &rp, const Queues &q, hipStream_t s) {
     if (rp.n_lanes == 0) return;
     hipLaunchKernelGGL(k_generate, dim3(nblk(rp.n_lanes)), dim3(kBlock), 0, s, rp, q);
 }
 // the scene is staged into LDS if it is small AND leaves room for the traversal stacks within the 64 KiB a block may ask for
 constexpr uint32_t kLdsBlockLimit = 64 * 1024;
-static inline uint32_t stage_words_for(uint32_t scene_bytes, uint32_t stack = 0) {
-    static const bool off = [] { const char *e = getenv("DTOF_STAGE"); return e && e[0] == '0'; }();   // DTOF_STAGE=0: never stage the scene into LDS (measurement)
-    if (off) return 0;
+static inline uint32_t stage_words_for(uint32_t scene_bytes, uint32_t stack, const LaunchSwitches &ls) {
+    if (!ls.stage) return 0;
     const uint32_t w = (scene_bytes + 15) / 16;
     return scene_bytes <= kLdsSceneLimit && w * 16 + stack + 64 <= kLdsBlockLimit ? w : 0;
 }
@@ -603,38 +566,82 @@ __global__ void k_sum_counts(const uint32_t *counts, uint32_t n_seg, unsigned lo
 }
 void launch_sum_counts(const uint32_t *counts, uint32_t n_seg, uint32_t n_rows, unsigned long long *out, hipStream_t s) {
     if (!n_rows) return;
-    (void) hipMemsetAsync(out, 0, (size_t) n_rows * sizeof(unsigned long long), s);
+    if (hipMemsetAsync(out, 0, (size_t) n_rows * sizeof(unsigned long long), s) != hipSuccess) throw std::runtime_error("hipMemsetAsync(sums) failed");
     hipLaunchKernelGGL(k_sum_counts, dim3(n_rows, kSumSlices), dim3(256), 0, s, counts, n_seg, out);
 }
 uint32_t segments_for(uint32_t n_lanes) { return nseg(n_lanes); }
 
-void launch_trace(const uint8_t *scene, uint32_t scene_bytes, const RenderParams &rp, const Queues &q,
-                  const uint32_t *qin, const uint32_t *count_in, uint32_t stack_depth, hipStream_t s) {
-    if (rp.n_lanes == 0) return;
-    const uint32_t sw = stage_words_for(scene_bytes, stack_bytes(stack_depth)), block = sw ? kBlock : unstaged_block(rp);
-    const bool w8 = eight_wave_rays(rp, sw, block, stack_depth), tl = w8 && tlas_in_lds(rp), h16 = w8 && half_nodes(rp);
-    const uint32_t lds = sw * 16 + stack_bytes(w8 ? kLdsStack8 : stack_depth, block) + (tl ? kTlasLds8 * 64u : 0u), grid = nseg(rp.n_lanes) * (kSeg / block);
-    check_lds(lds);
-    Queues qx = q; qx.xcd_remap = xcd_run(rp, sw, block);
-#define DTOF_LAUNCH_TRACE(L, M, B) hipLaunchKernelGGL((k_trace<L, M, B>), dim3(grid), dim3(B), lds, s, scene, scene_bytes, sw, qx, qin, count_in, rp.n_lanes, 0u)
-    if (w8 && h16 && (defer_rays(q) == 1 || (defer_rays(q) == 2 && qin != nullptr))) {   // two launches: the TLAS walk of every ray, then the BLAS walks of the rays that reached a mesh, packed (k_trace_deferred)
-        const uint32_t n_seg = nseg(rp.n_lanes);
-        (void) hipMemsetAsync(q.defer_cnt, 0, (size_t) n_seg * 4, s);
-        if (tl) hipLaunchKernelGGL((k_trace<false, true, 64, true, true, true, true>), dim3(grid), dim3(64), lds, s, scene, scene_bytes, sw, qx, qin, count_in, rp.n_lanes, rp.n_tlas_nodes);
-        else hipLaunchKernelGGL((k_trace<false, true, 64, true, false, true, true>), dim3(grid), dim3(64), lds, s, scene, scene_bytes, sw, qx, qin, count_in, rp.n_lanes, 0u);
-        hipLaunchKernelGGL((k_trace_deferred<true>), dim3(grid), dim3(64), stack_bytes(kLdsStack8, 64), s, scene, qx, n_seg);
+// Launch shape of a ray kernel (k_trace / k_shadow): staged scene or not, block, LDS, grid, XCD run, and the instantiation.
+//  - block of the unstaged kernels: one wave when some mesh has its own BLAS -- those traversals are long and divergent, and a 256-thread block keeps its LDS and wave
+//    slots until its slowest wave is done (mesh room, 522 k triangles: 20.1 -> 16.6 ms per frame); scenes of many small objects (Domino: 1 025 instances of a
+//    12-triangle cube) are faster with four waves sharing a CU's L1 on the same TLAS / object records (71.3 vs 75.3 ms)
+//  - XCD run: scenes staged in LDS and scenes of small objects do not wait for L2 locality
+//  - w8: the eight-waves-per-SIMD kernels, for one-wave blocks of an unstaged scene whose meshes sit behind a BLAS and that has no analytic shape (their float64 code
+//    does not fit 64 VGPRs), stacks no deeper than the LDS part + the overflow array (whatever the materials: the ray kernels only intersect); with the TLAS in LDS
+//    (tl) and half-float nodes (h16)
+//  - pair (DEFER): the TLAS walk of every ray, then the BLAS walks of the rays that reached a mesh, packed.  The two families differ: trace rays pair in DEFER mode 1,
+//    and in mode 2 unless they are the primary rays (no input queue); shadow rays in every mode but 0
+struct RayShape { uint32_t sw, block, lds, grid, xcd; bool w8, tl, h16, nodes16, pair; };
+static RayShape ray_shape(uint32_t scene_bytes, const RenderParams &rp, uint32_t stack_depth, const LaunchSwitches &ls, bool shadow, bool primary) {
+    RayShape r;
+    r.sw = stage_words_for(scene_bytes, stack_bytes(stack_depth), ls);
+    r.block = r.sw ? kBlock : ls.trace_block ? ls.trace_block : rp.has_blas ? 64u : (uint32_t) kBlock;
+    r.w8 = ls.trace8 && r.sw == 0 && r.block == 64 && rp.has_tris && rp.has_blas && !rp.has_analytic && stack_depth <= kLdsStack8 + kOvfStack8;
+    r.nodes16 = ls.nodes16 && rp.has_nodes16;
+    r.tl = r.w8 && ls.tlas_lds && rp.n_tlas_nodes != 0 && rp.n_tlas_nodes <= kTlasLds8; r.h16 = r.w8 && r.nodes16;
+    r.pair = r.h16 && (shadow ? ls.defer != 0 : ls.defer == 1 || (ls.defer == 2 && !primary));
+    r.lds = r.sw * 16 + stack_bytes(r.w8 ? kLdsStack8 : stack_depth, r.block) + (r.tl ? kTlasLds8 * 64u : 0u); r.grid = nseg(rp.n_lanes) * (kSeg / r.block);
+    check_lds(r.lds);
+    const uint64_t row_blocks = (uint64_t) rp.crop_w * rp.spp / r.block;
+    r.xcd = ls.xcd_set ? ls.xcd_remap : r.sw != 0 || !rp.has_blas ? 0u : (uint32_t) (row_blocks >= 8 && row_blocks <= (1u << 20) ? row_blocks : 0);
+    return r;
+}
+// the two ray-kernel families: one instantiation of the kernel, and the second launch of a DEFER pair
+struct TraceRays {
+    const uint8_t *scene; uint32_t scene_bytes; const RenderParams &rp; const Queues &q; const uint32_t *qin, *count_in;
+    template <bool L, bool M, int B, bool W8 = false, bool TL = false, bool H16 = false, bool DEFER = false> void run(const RayShape &r, uint32_t tlas_nodes, hipStream_t s) const {
+        hipLaunchKernelGGL((k_trace<L, M, B, W8, TL, H16, DEFER>), dim3(r.grid), dim3(B), r.lds, s, scene, scene_bytes, r.sw, q, qin, count_in, rp.n_lanes, tlas_nodes);
     }
-    else if (w8 && h16) { if (tl) hipLaunchKernelGGL((k_trace<false, true, 64, true, true, true>), dim3(grid), dim3(64), lds, s, scene, scene_bytes, sw, qx, qin, count_in, rp.n_lanes, rp.n_tlas_nodes);
-                     else hipLaunchKernelGGL((k_trace<false, true, 64, true, false, true>), dim3(grid), dim3(64), lds, s, scene, scene_bytes, sw, qx, qin, count_in, rp.n_lanes, 0u); }
-    else if (tl) hipLaunchKernelGGL((k_trace<false, true, 64, true, true>), dim3(grid), dim3(64), lds, s, scene, scene_bytes, sw, qx, qin, count_in, rp.n_lanes, rp.n_tlas_nodes);
-    else if (w8) hipLaunchKernelGGL((k_trace<false, true, 64, true>), dim3(grid), dim3(64), lds, s, scene, scene_bytes, sw, qx, qin, count_in, rp.n_lanes, 0u);
-    else if (sw) { if (rp.has_tris) DTOF_LAUNCH_TRACE(true, true, kBlock); else DTOF_LAUNCH_TRACE(true, false, kBlock); }
-    else if (block == 64 && rp.has_tris && rp.has_blas && half_nodes(rp))   // (a scene with a BLAS AND analytic shapes: six waves, every shape's code, half-float nodes)
-        hipLaunchKernelGGL((k_trace<false, true, 64, false, false, true>), dim3(grid), dim3(64), lds, s, scene, scene_bytes, sw, qx, qin, count_in, rp.n_lanes, 0u);
-    else if (block == 64)  { if (rp.has_tris) DTOF_LAUNCH_TRACE(false, true, 64); else DTOF_LAUNCH_TRACE(false, false, 64); }
-    else if (block == 128) { if (rp.has_tris) DTOF_LAUNCH_TRACE(false, true, 128); else DTOF_LAUNCH_TRACE(false, false, 128); }
-    else                   { if (rp.has_tris) DTOF_LAUNCH_TRACE(false, true, kBlock); else DTOF_LAUNCH_TRACE(false, false, kBlock); }
-#undef DTOF_LAUNCH_TRACE
+    void deferred(const RayShape &r, hipStream_t s) const { hipLaunchKernelGGL((k_trace_deferred<true>), dim3(r.grid), dim3(64), stack_bytes(kLdsStack8, 64), s, scene, q, nseg(rp.n_lanes)); }
+};
+struct ShadowRays {
+    const uint8_t *scene; uint32_t scene_bytes; const RenderParams &rp; const Queues &q; const uint32_t *count_in;
+    template <bool L, bool M, int B, bool W8 = false, bool TL = false, bool H16 = false, bool DEFER = false> void run(const RayShape &r, uint32_t tlas_nodes, hipStream_t s) const {
+        hipLaunchKernelGGL((k_shadow<L, M, B, W8, TL, H16, DEFER>), dim3(r.grid), dim3(B), r.lds, s, scene, scene_bytes, r.sw, rp, q, count_in, tlas_nodes);
+    }
+    void deferred(const RayShape &r, hipStream_t s) const { hipLaunchKernelGGL((k_shadow_deferred<true>), dim3(r.grid), dim3(64), stack_bytes(kLdsStack8, 64), s, scene, rp, q, nseg(rp.n_lanes)); }
+};
+// the instantiation of family F that the shape selects (F::q carries the XCD run; `q` is the batch's queues)
+template <class F> static void launch_rays(const F &f, const RenderParams &rp, const Queues &q, const RayShape &r, hipStream_t s) {
+    const uint32_t tn = r.tl ? rp.n_tlas_nodes : 0u;
+    if (r.pair) {
+        if (hipMemsetAsync(q.defer_cnt, 0, (size_t) nseg(rp.n_lanes) * 4, s) != hipSuccess) throw std::runtime_error("hipMemsetAsync(defer_cnt) failed");
+        if (r.tl) f.template run<false, true, 64, true, true, true, true>(r, tn, s); else f.template run<false, true, 64, true, false, true, true>(r, tn, s);
+        f.deferred(r, s);
+    }
+    else if (r.h16) { if (r.tl) f.template run<false, true, 64, true, true, true>(r, tn, s); else f.template run<false, true, 64, true, false, true>(r, tn, s); }
+    else if (r.tl) f.template run<false, true, 64, true, true>(r, tn, s);
+    else if (r.w8) f.template run<false, true, 64, true>(r, tn, s);
+    else if (r.sw) { if (rp.has_tris) f.template run<true, true, kBlock>(r, tn, s); else f.template run<true, false, kBlock>(r, tn, s); }
+    else if (r.block == 64 && rp.has_tris && rp.has_blas && r.nodes16)   // (a scene with a BLAS AND analytic shapes: six waves, every shape's code, half-float nodes)
+        f.template run<false, true, 64, false, false, true>(r, tn, s);
+    else if (r.block == 64)  { if (rp.has_tris) f.template run<false, true, 64>(r, tn, s); else f.template run<false, false, 64>(r, tn, s); }
+    else if (r.block == 128) { if (rp.has_tris) f.template run<false, true, 128>(r, tn, s); else f.template run<false, false, 128>(r, tn, s); }
+    else                     { if (rp.has_tris) f.template run<false, true, kBlock>(r, tn, s); else f.template run<false, false, kBlock>(r, tn, s); }
+}
+void launch_trace(const uint8_t *scene, uint32_t scene_bytes, const RenderParams &rp, const Queues &q,
+                  const uint32_t *qin, const uint32_t *count_in, uint32_t stack_depth, const LaunchSwitches &ls, hipStream_t s) {
+    if (rp.n_lanes == 0) return;
+    const RayShape r = ray_shape(scene_bytes, rp, stack_depth, ls, false, qin == nullptr);
+    Queues qx = q; qx.xcd_remap = r.xcd;
+    launch_rays(TraceRays { scene, scene_bytes, rp, qx, qin, count_in }, rp, q, r, s);
+}
+void launch_shadow(const uint8_t *scene, uint32_t scene_bytes, const RenderParams &rp, const Queues &q,
+                   const uint32_t *count_in, uint32_t stack_depth, const LaunchSwitches &ls, hipStream_t s) {
+    if (rp.n_lanes == 0) return;
+    const RayShape r = ray_shape(scene_bytes, rp, stack_depth, ls, true, false);
+    Queues qx = q; qx.xcd_remap = r.xcd;
+    launch_rays(ShadowRays { scene, scene_bytes, rp, qx, count_in }, rp, q, r, s);
 }
 uint32_t resident_lds_bytes(const RenderParams &rp, const ResidentStage &resident, uint32_t stack_depth, uint32_t waves) {
     static_assert(kResidentNodes == kResNodes, "resident stage size");
@@ -652,7 +659,7 @@ uint32_t device_lds_limit() {
 void launch_shade(const uint8_t *scene, uint32_t scene_bytes, const RenderParams &rp, const Queues &q,
                   const uint32_t *qin, const uint32_t *count_in, uint32_t *qout,
                   uint32_t *alive_out, uint32_t *shadow_out, uint32_t depth, bool fused, bool trace_next,
-                  uint32_t stack_depth, hipStream_t s, bool first, LaneDebug *dbg, const ResidentStage *resident, float *film, uint64_t film_stride) {
+                  uint32_t stack_depth, const LaunchSwitches &ls, hipStream_t s, bool first, LaneDebug *dbg, const ResidentStage *resident, float *film, uint64_t film_stride) {
     if (rp.n_lanes == 0) return;
     if (first && !fused) throw std::runtime_error("the first-bounce kernel exists in the fused pipeline only");
     const bool k4 = rp.n_offsets != 1;
@@ -678,7 +685,7 @@ void launch_shade(const uint8_t *scene, uint32_t scene_bytes, const RenderParams
     // + the instance memo; a flat scene with one instance keeps the instance matrix there as well (k_shade: memo_m_lds) and needs no traversal stack beyond one entry
     const bool memo_m = fused && !rp.has_tris && !rp.has_spec && rp.flat_objects != 0 && rp.memo_obj != 0xffffffffu;   // = the condition of k_shade's memo_m_lds in the instantiations launch_shade_plain picks
     const uint32_t shade_stack = fused ? stack_bytes(memo_m ? 1u : stack_depth, kShadeBlock) + (memo_m ? 2u : 1u) * kMemoWords * kMemoStride * 4 : 0;
-    const uint32_t sw = stage_words_for(scene_bytes, shade_stack), grid = nseg(rp.n_lanes) * (first && rp.chunk_blocks > 1 ? rp.chunk_blocks : 1u), lds = sw * 16 + shade_stack;
+    const uint32_t sw = stage_words_for(scene_bytes, shade_stack, ls), grid = nseg(rp.n_lanes) * (first && rp.chunk_blocks > 1 ? rp.chunk_blocks : 1u), lds = sw * 16 + shade_stack;
     check_lds(lds);
     const ShadeLaunch L = { sw != 0, first ? 2 : fused ? 1 : 0, 0u, grid, lds, s,
                             { scene, scene_bytes, sw, rp, q, qin, count_in, qout, alive_out, shadow_out, depth, trace_next ? 1u : 0u, dbg, film, film_stride, nseg(rp.n_lanes), 0u, 0u, 0u, 0u } };
@@ -687,52 +694,23 @@ void launch_shade(const uint8_t *scene, uint32_t scene_bytes, const RenderParams
     else if (rp.has_tris) launch_shade_mesh(rp.has_area != 0, k4, L);
     else launch_shade_plain(rp.has_area != 0, k4, L);
 }
-void launch_shadow(const uint8_t *scene, uint32_t scene_bytes, const RenderParams &rp, const Queues &q,
-                   const uint32_t *count_in, uint32_t stack_depth, hipStream_t s) {
+void launch_velocity(const uint8_t *scene, uint32_t scene_bytes, const RenderParams &rp, const Queues &q, uint32_t stack_depth, const LaunchSwitches &ls, hipStream_t s) {
     if (rp.n_lanes == 0) return;
-    const uint32_t sw = stage_words_for(scene_bytes, stack_bytes(stack_depth)), block = sw ? kBlock : unstaged_block(rp);
-    const bool w8 = eight_wave_rays(rp, sw, block, stack_depth), tl = w8 && tlas_in_lds(rp), h16 = w8 && half_nodes(rp);
-    const uint32_t lds = sw * 16 + stack_bytes(w8 ? kLdsStack8 : stack_depth, block) + (tl ? kTlasLds8 * 64u : 0u), grid = nseg(rp.n_lanes) * (kSeg / block);
-    check_lds(lds);
-    Queues qx = q; qx.xcd_remap = xcd_run(rp, sw, block);
-#define DTOF_LAUNCH_SHADOW(L, M, B) hipLaunchKernelGGL((k_shadow<L, M, B>), dim3(grid), dim3(B), lds, s, scene, scene_bytes, sw, rp, qx, count_in, 0u)
-    if (w8 && h16 && defer_rays(q)) {
-        const uint32_t n_seg = nseg(rp.n_lanes);
-        (void) hipMemsetAsync(q.defer_cnt, 0, (size_t) n_seg * 4, s);
-        if (tl) hipLaunchKernelGGL((k_shadow<false, true, 64, true, true, true, true>), dim3(grid), dim3(64), lds, s, scene, scene_bytes, sw, rp, qx, count_in, rp.n_tlas_nodes);
-        else hipLaunchKernelGGL((k_shadow<false, true, 64, true, false, true, true>), dim3(grid), dim3(64), lds, s, scene, scene_bytes, sw, rp, qx, count_in, 0u);
-        hipLaunchKernelGGL((k_shadow_deferred<true>), dim3(grid), dim3(64), stack_bytes(kLdsStack8, 64), s, scene, rp, qx, n_seg);
-    }
-    else if (w8 && h16) { if (tl) hipLaunchKernelGGL((k_shadow<false, true, 64, true, true, true>), dim3(grid), dim3(64), lds, s, scene, scene_bytes, sw, rp, qx, count_in, rp.n_tlas_nodes);
-                     else hipLaunchKernelGGL((k_shadow<false, true, 64, true, false, true>), dim3(grid), dim3(64), lds, s, scene, scene_bytes, sw, rp, qx, count_in, 0u); }
-    else if (tl) hipLaunchKernelGGL((k_shadow<false, true, 64, true, true>), dim3(grid), dim3(64), lds, s, scene, scene_bytes, sw, rp, qx, count_in, rp.n_tlas_nodes);
-    else if (w8) hipLaunchKernelGGL((k_shadow<false, true, 64, true>), dim3(grid), dim3(64), lds, s, scene, scene_bytes, sw, rp, qx, count_in, 0u);
-    else if (sw) { if (rp.has_tris) DTOF_LAUNCH_SHADOW(true, true, kBlock); else DTOF_LAUNCH_SHADOW(true, false, kBlock); }
-    else if (block == 64 && rp.has_tris && rp.has_blas && half_nodes(rp))
-        hipLaunchKernelGGL((k_shadow<false, true, 64, false, false, true>), dim3(grid), dim3(64), lds, s, scene, scene_bytes, sw, rp, qx, count_in, 0u);
-    else if (block == 64)  { if (rp.has_tris) DTOF_LAUNCH_SHADOW(false, true, 64); else DTOF_LAUNCH_SHADOW(false, false, 64); }
-    else if (block == 128) { if (rp.has_tris) DTOF_LAUNCH_SHADOW(false, true, 128); else DTOF_LAUNCH_SHADOW(false, false, 128); }
-    else                   { if (rp.has_tris) DTOF_LAUNCH_SHADOW(false, true, kBlock); else DTOF_LAUNCH_SHADOW(false, false, kBlock); }
-#undef DTOF_LAUNCH_SHADOW
-}
-void launch_velocity(const uint8_t *scene, uint32_t scene_bytes, const RenderParams &rp, const Queues &q, uint32_t stack_depth, hipStream_t s) {
-    if (rp.n_lanes == 0) return;
-    uint32_t sw = stage_words_for(scene_bytes, stack_bytes(stack_depth)), lds = sw * 16 + stack_bytes(stack_depth);
+    uint32_t sw = stage_words_for(scene_bytes, stack_bytes(stack_depth), ls), lds = sw * 16 + stack_bytes(stack_depth);
     check_lds(lds);
     if (sw) hipLaunchKernelGGL(k_velocity<true>, dim3(nblk(rp.n_lanes)), dim3(kBlock), lds, s, scene, scene_bytes, sw, rp, q);
     else hipLaunchKernelGGL(k_velocity<false>, dim3(nblk(rp.n_lanes)), dim3(kBlock), lds, s, scene, scene_bytes, sw, rp, q);
 }
-void launch_splat(const RenderParams &rp, const Queues &q, float *film, uint64_t plane_stride, hipStream_t s) {
+void launch_splat(const RenderParams &rp, const Queues &q, float *film, uint64_t plane_stride, const LaunchSwitches &ls, hipStream_t s) {
     if (rp.n_lanes == 0) return;
     size_t stride = (size_t) plane_stride;   // floats between the films of the batched offsets
     bool fast = rp.filter == FILTER_TENT && rp.filter_radius <= 1.f && rp.filter_radius > .5f && rp.spp_log2 != 0xffffffffu && rp.spp >= 2;
-    static const int env_splat = [] { const char *e = getenv("DTOF_SPLAT"); std::string v = e ? e : ""; return v == "dpp" ? 1 : v == "generic" ? 2 : 0; }();   // A/B switches
     // footprint of the filter in pixels (ImageBlock::put: the pixels within ceil(radius - 0.5) of the sample's): 1 (box), 3 or 5 take the
     // eight-samples-per-lane kernel when spp is a power of two >= 16
     const int reach = rp.filter == FILTER_BOX ? 0 : (int) ceilf(rp.filter_radius - .5f);
     // the Lanczos filter (default radius 3: a 7 x 7 footprint) always takes the per-lane kernel
     const bool lanczos = rp.filter == FILTER_LANCZOS;
-    if ((rp.filter == FILTER_BOX || (reach >= 1 && reach <= 2)) && !lanczos && rp.spp_log2 != 0xffffffffu && rp.spp >= 2 * kSplatPer && env_splat == 0) {
+    if ((rp.filter == FILTER_BOX || (reach >= 1 && reach <= 2)) && !lanczos && rp.spp_log2 != 0xffffffffu && rp.spp >= 2 * kSplatPer && ls.splat == 0) {
         const uint32_t groups = rp.n_lanes / kSplatPer, seg8 = rp.spp / kSplatPer < 64 ? rp.spp / kSplatPer : 64;
         const int n = 2 * reach + 1;
         const uint32_t lds = (kBlock / seg8) * n * n * 16u;
@@ -748,7 +726,7 @@ void launch_splat(const RenderParams &rp, const Queues &q, float *film, uint64_t
         }
     }
     const bool small_pow2_tent = fast && rp.spp < 2 * kSplatPer;   // 2, 4, 8 spp under the radius-1 tent: k_splat_tent3 (one DPP segment per pixel)
-    if ((rp.filter == FILTER_BOX || (reach >= 1 && reach <= 2)) && !lanczos && !small_pow2_tent && env_splat == 0) {
+    if ((rp.filter == FILTER_BOX || (reach >= 1 && reach <= 2)) && !lanczos && !small_pow2_tent && ls.splat == 0) {
         // any other sample count: one thread per pixel; enough threads to fill the chip (parts of a pixel's samples, each >= 8, when the frame is small)
         const uint32_t n_pixels = rp.n_lanes / rp.spp, n = 2 * reach + 1;
         uint32_t parts = 1;
@@ -763,7 +741,7 @@ void launch_splat(const RenderParams &rp, const Queues &q, float *film, uint64_t
 #undef DTOF_SPLAT_PIXEL
         return;
     }
-    if (fast && env_splat != 2) {
+    if (fast && ls.splat != 2) {
         uint32_t seg = rp.spp < 64 ? rp.spp : 64;
         hipLaunchKernelGGL(k_splat_tent3, dim3(nblk(rp.n_lanes)), dim3(kBlock), 0, s, rp, q, film, stride, seg);
     } else {

@@ -51,13 +51,8 @@ template <typename T> struct DevBuf {
 // per-iteration count slots of a batch (statistics + the queue counts of the previous iteration); reused cyclically beyond that.
 // DTOF_STAT_SLOTS shrinks it so that the tests can exercise the wrap-around with short paths.
 static const uint32_t kMaxIter = [] { const char *e = getenv("DTOF_STAT_SLOTS"); int v = e ? atoi(e) : 0; return (uint32_t) (v >= 2 ? v : 256); }();
-static uint64_t target_batch_lanes() {   // lanes per wavefront batch (DTOF_BATCH_LANES overrides)
-    // 2^27 lanes (26 GB of workspace at 200 B per lane, 40 GB with four offset films -- of 288): every launch ends with a tail in which the CUs run dry one after the
-    // other, and a Domino frame in 32 launches of 2^24 lanes lost 7 % to it (C5 206 -> 193 ms, C4 44.8 -> 41.1; profiles/r03_batch_lanes.txt); one launch per C4 frame
-    // instead of two is another 2 % (34.86 -> 34.14 ms, profiles/r04_domino_waves_batch.txt).  render_range halves the batch until its workspace fits the free device memory.
-    const char *e = getenv("DTOF_BATCH_LANES"); const uint64_t x = e ? strtoull(e, nullptr, 10) : 0; const uint64_t v = x ? x : (1ull << 27);   // read per call: tests of the batch seams set it
-    return v;
-}
+// the stages a frame's launches are timed by (StageTimer, dtof_render_stats) and named after (roctx ranges)
+enum Stage { kStageGenerate, kStageTrace, kStageShade, kStageShadow, kStageSplat, kStageFirst, kStageCount };
 
 struct Workspace {
     DevBuf<float4> ray_a, ray_b, st_a, st_b, res, sh_a, sh_b, sh_c;
@@ -67,11 +62,9 @@ struct Workspace {
     DevBuf<float2> pos, st_c;
     DevBuf<uint2> rng_b;
     DevBuf<LaneDebug> dbg;
-    DevBuf<float4> valid;   // Queues::valid_out, only when asked for (ensure_valid)
-    DevBuf<uint4> cand; DevBuf<uint32_t> defer_idx, defer_cnt;   // Queues::cand / defer_idx / defer_cnt, only for scenes whose ray kernels run as a pair of launches (ensure_defer)
+    DevBuf<float4> valid;   // Queues::valid_out
+    DevBuf<uint4> cand; DevBuf<uint32_t> defer_idx, defer_cnt;   // Queues::cand / defer_idx / defer_cnt
     uint32_t capacity = 0; int k = 0;
-    void ensure_valid() { valid.ensure(capacity); }
-    void ensure_defer() { cand.ensure(capacity); defer_idx.ensure(capacity); defer_cnt.ensure(segments_for(capacity)); }
     void ensure(uint32_t cap, int n_offsets) {
         if (cap <= capacity && n_offsets <= k) return;
         capacity = std::max(cap, capacity); k = std::max(n_offsets, k);
@@ -80,12 +73,18 @@ struct Workspace {
         hit.ensure(capacity); hit_t.ensure(capacity); rng_a.ensure(capacity); hit_id.ensure(capacity); q0.ensure(capacity); q1.ensure(capacity);
         counts.ensure(2 * (size_t) kMaxIter * segments_for(capacity) + 16); pos.ensure(capacity); rng_b.ensure(capacity); st_c.ensure(capacity);   // + the segment counter of the resident kernel
     }
-    Queues queues() {
+    // the queues of a batch of up to `cap` lanes; valid_out only when asked for, the DEFER lists only for frames whose ray kernels run as a pair of launches
+    Queues prepare(uint32_t cap, int n_offsets, bool want_valid, bool defer, uint32_t id_shift) {
+        ensure(cap, n_offsets);
+        if (want_valid) valid.ensure(capacity);
+        if (defer) { cand.ensure(capacity); defer_idx.ensure(capacity); defer_cnt.ensure(segments_for(capacity)); }
         Queues q; memset(&q, 0, sizeof q);
         q.ray_a = ray_a.p; q.ray_b = ray_b.p; q.hit = hit.p; q.hit_t = hit_t.p; q.hit_id = hit_id.p; q.st_a = st_a.p; q.st_b = st_b.p; q.rng_a = rng_a.p; q.rng_b = rng_b.p; q.st_c = st_c.p;
         q.res = res.p; q.pos = pos.p; q.sh_a = sh_a.p; q.sh_b = sh_b.p; q.sh_c = sh_c.p; q.q[0] = q0.p; q.q[1] = q1.p;
         q.counts = counts.p; q.capacity = capacity; q.valid_out = valid.p;
         q.seg_counter = counts.p + 2 * (size_t) kMaxIter * segments_for(capacity);
+        if (defer) { q.cand = cand.p; q.defer_idx = defer_idx.p; q.defer_cnt = defer_cnt.p; }
+        q.id_shift = id_shift;
         return q;
     }
 };
@@ -99,8 +98,8 @@ struct dtof_scene {
     DevBuf<uint8_t> d_blob; bool uploaded = false;
     Workspace ws, ws2;                       // one per in-flight batch
     DevBuf<float> d_film, d_rgb;
-    // the caller's device film as declared with dtof_scene_set_film_layout (0 = not declared: colour planes only, W * H * 4 apart), and the plane distance of the running call
-    int32_t film_planes = 0; uint64_t film_plane_stride = 0, film_stride_call = 0;
+    // the caller's device film as declared with dtof_scene_set_film_layout (0 = not declared: colour planes only, W * H * 4 apart)
+    int32_t film_planes = 0; uint64_t film_plane_stride = 0;
     DevBuf<unsigned long long> d_sums;       // [batch][2*kMaxIter] per-iteration totals (survivors, shadow rays)
     DevBuf<uint2> d_pass_rng;                // multi-pass renders: [lane][3] stream states between the passes
     uint32_t id_shift = 24;                  // Queues::id_shift of this scene
@@ -110,8 +109,8 @@ struct dtof_scene {
     // reusable statistics plumbing (creating events / pinned memory per call costs ~0.3 ms)
     std::vector<hipEvent_t> event_pool; size_t events_used = 0;
     // frames enqueued by dtof_render_rows_async and not collected yet: their events (frame, stages) and launch counters; no host synchronisation until dtof_async_collect
-    struct DeferredFrame { hipEvent_t ev0, ev1; std::vector<std::pair<hipEvent_t, hipEvent_t>> ev[6]; dtof_render_stats counters; };
-    std::vector<DeferredFrame> deferred; bool defer_next = false;
+    struct DeferredFrame { hipEvent_t ev0, ev1; std::vector<std::pair<hipEvent_t, hipEvent_t>> ev[kStageCount]; dtof_render_stats counters; };
+    std::vector<DeferredFrame> deferred;
     uint32_t *pinned_counts = nullptr; size_t pinned_words = 0;
     hipEvent_t take_event() {
         if (events_used == event_pool.size()) { hipEvent_t e; if (hipEventCreate(&e) != hipSuccess) throw std::runtime_error("hipEventCreate failed"); event_pool.push_back(e); }
@@ -269,30 +268,30 @@ struct Roctx {
     }
 };
 static const Roctx &roctx() { static const Roctx r; return r; }
-static const char *const kStageNames[6] = { "dtof:generate", "dtof:trace", "dtof:shade", "dtof:shadow", "dtof:splat", "dtof:first" };
+static const char *const kStageNames[kStageCount] = { "dtof:generate", "dtof:trace", "dtof:shade", "dtof:shadow", "dtof:splat", "dtof:first" };
 
 struct StageTimer {
-    bool on; dtof_scene *sc; std::vector<std::pair<hipEvent_t, hipEvent_t>> ev[6];
+    bool on; dtof_scene *sc; std::vector<std::pair<hipEvent_t, hipEvent_t>> ev[kStageCount];
     StageTimer(bool enabled, dtof_scene *scene) : on(enabled), sc(scene) { if (sc->deferred.empty()) sc->events_used = 0; }   // the events of uncollected frames stay taken
-    int begin(int stage, hipStream_t s) {
+    int begin(Stage stage, hipStream_t s) {
         if (roctx().push) roctx().push(kStageNames[stage]);
         if (!on) return -1;
         hipEvent_t a = sc->take_event(), b = sc->take_event();
         ev[stage].emplace_back(a, b); HIP_CHECK(hipEventRecord(a, s));
         return (int) ev[stage].size() - 1;
     }
-    void end(int stage, int idx, hipStream_t s) {
+    void end(Stage stage, int idx, hipStream_t s) {
         if (on) HIP_CHECK(hipEventRecord(ev[stage][idx].second, s));
         if (roctx().push) roctx().pop();
         static const bool sync_each = [] { const char *e = getenv("DTOF_SYNC_LAUNCHES"); return e && e[0] == '1'; }();   // debugging: which stage of a frame never finishes?
         if (sync_each) { fprintf(stderr, "[dtof] %s enqueued ...", kStageNames[stage]); fflush(stderr); HIP_CHECK(hipStreamSynchronize(s)); fprintf(stderr, " done\n"); fflush(stderr); }
     }
-    double total(int stage) {
-        double ms = 0;
-        for (auto &p : ev[stage]) { float t = 0; HIP_CHECK(hipEventElapsedTime(&t, p.first, p.second)); ms += t; }
-        return ms;
-    }
 };
+double stage_ms(const std::vector<std::pair<hipEvent_t, hipEvent_t>> &ev) {
+    double ms = 0;
+    for (auto &p : ev) { float t = 0; HIP_CHECK(hipEventElapsedTime(&t, p.first, p.second)); ms += t; }
+    return ms;
+}
 
 // The device-film entry points write K colour planes and, for an rgba film, the alpha plane behind them into memory whose size only the caller knows: an rgba scene is
 // refused until the caller has declared a film of K + 1 planes (a caller written for rgb films would have its buffer overrun), and a declared count is checked either way.
@@ -317,7 +316,7 @@ static uint64_t caller_film_stride(const dtof_scene *sc, int n_offsets, int32_t 
     }
     return sc->film_plane_stride ? sc->film_plane_stride : full;
 }
-// the rows [first, last + 1) that hold the stripes [first_row + k * stripe_period, ... + stripe_rows) below the film's height (the mapping of render_rows)
+// the rows [first, last + 1) that hold the stripes [first_row + k * stripe_period, ... + stripe_rows) below the film's height (the mapping of plan_lanes)
 static std::pair<int32_t, int32_t> stripe_span(const dtof_scene *sc, int32_t first_row, int32_t stripe_rows, int32_t stripe_period) {
     const int32_t h = sc->host.sensor.crop_h, first = std::max(first_row, 0);
     const int64_t span = std::max<int64_t>(h - first, 0), v_rows = (span / stripe_period) * stripe_rows + std::min<int64_t>(span % stripe_period, stripe_rows);
@@ -325,240 +324,315 @@ static std::pair<int32_t, int32_t> stripe_span(const dtof_scene *sc, int32_t fir
     return {first, (int32_t) (first + ((v_rows - 1) / stripe_rows) * stripe_period + (v_rows - 1) % stripe_rows + 1)};
 }
 
-// The wavefront loop over pixel rows [row_begin,row_end); accumulates into d_film (K films, sc->film_stride_call floats apart).
-// lane_dump != nullptr: evaluate only lanes [dump_begin, dump_begin + dump_n) and copy their records out.
-// stripe_rows > 0: the rows are the stripes [row_begin + k * stripe_period, ... + stripe_rows) below row_end (interleaved shards).
-void render_rows(dtof_scene *sc, uint32_t seed, uint32_t spp, int32_t row_begin, int32_t row_end,
-                 const float *offsets, int n_offsets, float *d_film, dtof_render_stats *stats,
-                 LaneDebug *lane_dump = nullptr, uint64_t dump_begin = 0, uint64_t dump_n = 0,
-                 uint32_t stripe_rows = 0, uint32_t stripe_period = 0) {
-    if (!sc->host.has_sensor) throw std::runtime_error("the scene does not contain a sensor");
-    ensure_device(sc);
-    const HostSensor &se = sc->host.sensor;
-    const uint64_t film_stride = sc->film_stride_call ? sc->film_stride_call : (uint64_t) se.crop_w * se.crop_h * 4;
-    if (spp == 0) spp = sc->pp.sample_count;
-    if (spp == 0) throw std::runtime_error("sample count must be positive");
-    // SamplingIntegrator::render (integrator.cpp:121-135,227-245): spp_per_pass = min(samples_per_pass, spp) must divide spp; a wavefront
-    // of more than 2^32 - 1 lanes is split into more passes (integer division, as written there), and Sampler::set_samples_per_wavefront
-    // (sampler.cpp:75-83) insists that the sample count is a multiple of the samples per pass.  `spp` below is the samples per PASS.
-    const uint32_t sample_count = spp;
-    uint32_t n_passes = 1;
-    {
-        uint32_t per_pass = sc->pp.samples_per_pass == 0xffffffffu || sc->pp.samples_per_pass == 0 ? spp : std::min(sc->pp.samples_per_pass, spp);
-        if (spp % per_pass != 0) throw std::runtime_error("sample_count (" + std::to_string(spp) + ") must be a multiple of spp_per_pass (" + std::to_string(per_pass) + ").");
-        const uint64_t wavefront = (uint64_t) se.crop_w * se.crop_h * per_pass, limit = 0xffffffffull;
-        if (wavefront > limit) {
-            per_pass /= (uint32_t) ((wavefront + limit - 1) / limit);
-            if (per_pass == 0 || spp % per_pass != 0) throw std::runtime_error("sample_count should be a multiple of samples_per_wavefront!");
-        }
-        n_passes = spp / per_pass; spp = per_pass;
+// One call of the renderer, as the entry points fill it in.  The film layout the caller declared (dtof_scene_set_film_layout) stays scene state.
+struct RenderRequest {
+    uint32_t seed = 0, spp = 0;                   // spp 0: the sampler's sample count
+    int32_t row_begin = 0, row_end = 0;           // film rows [row_begin, row_end)
+    bool stripes = false; int32_t stripe_rows = 0, stripe_period = 0;   // stripes: only the rows [row_begin + k * stripe_period, ... + stripe_rows) (interleaved shards)
+    const float *offsets = nullptr; int n_offsets = 0;
+    float *film = nullptr; uint64_t film_stride = 0;   // K films (and the alpha film behind them) film_stride floats apart
+    dtof_render_stats *stats = nullptr;
+    LaneDebug *lane_dump = nullptr; uint64_t dump_begin = 0, dump_n = 0;   // lane_dump != nullptr: evaluate only lanes [dump_begin, dump_begin + dump_n) and copy their records out
+    bool deferred = false;                        // dtof_render_rows_async: timings by events, no counters read back, no synchronisation at the end
+};
+
+// What the frame plan derives from the scene's arrays and blob header, each array walked once.  Computed per call and never cached on the scene.
+struct SceneTraits {
+    int32_t has_spec = 0;                 // the every-BSDF (SPEC) kernels; 2: ... whose BSDF chain loops over two records (blendbsdf)
+    bool has_tris = false, has_analytic = false, has_blas = false, has_nodes16 = false;
+    bool surface_emitters = false, has_env = false, null_lobe = false;
+    uint32_t env_index = 0, n_instances = 0, last_instance = 0;
+    uint64_t blas_triangles = 0;          // triangles behind per-mesh BLASes
+    uint32_t n_nodes = 0, n_tlas_nodes = 0, n_objects = 0, stack_depth = 0, flat_off = 0;
+    bool resident_layout = false; uint32_t small_off = 0, small_words = 0;   // the blob's record block can be the resident stage's
+};
+SceneTraits scene_traits(const dtof_scene &sc) {
+    const HostScene &hs = sc.host; const HostSensor &se = hs.sensor;
+    const BlobHeader *bh = (const BlobHeader *) sc.blob.data();
+    SceneTraits t;
+    // SPEC: every BSDF but the diffuse one, masks, normal maps, textures, spot / directional / environment emitters, and cameras other than the
+    // pinhole one (the diffuse-only kernels generate perspective rays only: generate_lane<PERSPECTIVE_ONLY>)
+    bool spec = !hs.textures.empty() || se.thinlens || se.orthographic, blend = false;
+    for (auto &sh : hs.shapes) {
+        spec |= sh.bsdf != BSDF_DIFFUSE || sh.masked || sh.tex_normal >= 0 || sh.blend_other;
+        blend |= sh.blend_other != nullptr;
+        t.has_analytic |= sh.kind == SHAPE_SPHERE || sh.kind == SHAPE_DISK || sh.kind == SHAPE_CYLINDER;   // analytic shapes of the MESH instantiations
+        // a BSDF with a null lobe (`mask`, `thindielectric`) leaves valid_ray unset -- over the whole chain of material records behind a shape (a blend's partner, the
+        // back side of a two-BSDF twosided, and whatever those carry in turn), so that a nesting the loader learns to accept later cannot slip one past this test
+        for (const HostShape *m = &sh; m; m = m->blend_other.get())
+            t.null_lobe |= m->masked || m->bsdf == BSDF_THINDIELECTRIC || m->bsdf == BSDF_NULL;
     }
-    uint64_t total_lanes = (uint64_t) se.crop_w * se.crop_h * spp;   // lanes of one pass (the wavefront)
+    for (size_t i = 0; i < hs.emitters.size(); ++i) {
+        const auto kind = hs.emitters[i].kind;
+        t.surface_emitters |= kind == EMITTER_AREA || kind == EMITTER_CONSTANT || kind == EMITTER_ENVMAP;   // the environment is "hit" by the rays that leave the scene
+        spec |= kind == EMITTER_SPOT || kind == EMITTER_DIRECTIONAL || kind == EMITTER_CONSTANT || kind == EMITTER_ENVMAP;
+        if (kind == EMITTER_CONSTANT || kind == EMITTER_ENVMAP) { t.has_env = true; t.env_index = (uint32_t) i; }
+    }
+    t.has_spec = blend ? 2 : spec ? 1 : 0;
+    // anything but rectangles: the instantiations with triangle / sphere code.  The SPEC shade kernels are MESH instantiations (full 16-byte hit
+    // record), so the trace kernels of the split pipeline must write that record for them too: a rectangle-only scene with textures (or any other
+    // SPEC feature) counts as "has_tris" -- the compact 4-byte record is for the plain rectangle-only kernels
+    t.has_tris = bh->n_tris != 0 || t.has_analytic || t.has_spec;
+    const DShape *dshapes = (const DShape *) (sc.blob.data() + bh->off_shapes);
+    for (uint32_t i = 0; i < bh->n_shapes; ++i)
+        if (dshapes[i].kind == SHAPE_MESH && dshapes[i].blas_root != kNoChild) { t.has_blas = true; t.blas_triangles += dshapes[i].n_tris; }
+    const DObject *dobj = (const DObject *) (sc.blob.data() + bh->off_objects);
+    for (uint32_t i = 0; i < bh->n_objects; ++i) if (dobj[i].kind == OBJ_INSTANCE) { ++t.n_instances; t.last_instance = i; }
+    t.has_nodes16 = bh->off_nodes16 != 0; t.n_nodes = bh->n_nodes; t.n_tlas_nodes = bh->n_tlas_nodes; t.n_objects = bh->n_objects;
+    t.stack_depth = bh->tlas_depth; t.flat_off = bh->off_flat;
+    // groups | shapes | emitters | triangles | shading data | intersection records: one block of at most 24 KiB in a blob too large to stage whole
+    const uint32_t small_bytes = bh->off_tables - bh->off_groups;
+    t.resident_layout = bh->n_nodes > 0 && sc.blob.size() > 16 * 1024 && bh->off_shapes > bh->off_groups && bh->off_emitters > bh->off_groups && bh->off_tris > bh->off_groups &&
+                        bh->off_shading >= bh->off_tris && bh->off_isect >= bh->off_shading && bh->off_tables >= bh->off_isect && small_bytes <= 24 * 1024;
+    t.small_off = bh->off_groups; t.small_words = (small_bytes + 15) / 16;
+    return t;
+}
+
+// What one launch of the bounce loop covers when it starts at an iteration
+struct LaunchSpan { uint32_t span, chunk_blocks, res_units; bool next_runs, splat_here; };
+
+// Every decision of a frame, taken before its first launch.  The batch loop reads it and sets only the per-batch and per-launch fields of its copy of rp.
+struct FramePlan {
+    RenderParams rp;                      // the frame's parameters, with the scene's flags and the kernel choices they carry
+    SceneTraits traits;
+    uint32_t n_passes = 1, run_passes = 1, dump_pass = 0;
+    uint64_t lanes_per_row = 0, first = 0, last = 0, batch = 1;   // every pass: lanes [first, last) in batches of `batch`
+    int n_streams = 1;
+    bool fused = false, first_inline = false, skip_tail = false, fuse_splat_ok = false;
+    uint32_t max_inline = 1, chunk_segs = 0, res_units = 1;
+    ResidentStage resident;
+    LaunchSwitches launch;                // launch.defer: the DEFER mode, 0 when the workspaces have no DEFER lists
+    // does iteration `it` of the bounce loop run?  (the reference's last iteration only looks for emitter hits, dopplertofpath.cpp:136-171: skip_tail drops it)
+    bool iteration_runs(uint32_t it) const { return it < rp.max_depth && !(it + 1 >= rp.max_depth && skip_tail); }
+    LaunchSpan launch_span(uint32_t it, bool first, uint32_t n_seg) const {
+        // The fused first-bounce kernel runs up to max_inline iterations itself, the path state in registers; multi-pass renders, whose stream states must be in
+        // memory between the passes, one per launch.  (One compacted launch per iteration instead lost: profiles/r04_compaction_ab.txt.)
+        LaunchSpan l; l.span = 1;
+        if (first && n_passes == 1) while (l.span < max_inline && iteration_runs(it + l.span)) ++l.span;
+        l.next_runs = iteration_runs(it + l.span);
+        // small frames whose whole path runs inline: one block per 64-lane chunk (8 x the waves); the count slots it adds into are zeroed first
+        const bool whole_path = first && !l.next_runs;
+        l.chunk_blocks = whole_path && n_seg <= chunk_segs ? kChunkBlocks : 1u;
+        // parts of a segment as the resident kernel's work units shorten the launch's tail (kept for a frame sharded over many GPUs); their count slots are added into
+        l.res_units = whole_path ? res_units : 1u;
+        // fused splat: every wave of a whole-path launch holds the 64 samples of one pixel and adds their footprint to the film itself (no round trip through q.res)
+        l.splat_here = whole_path && fuse_splat_ok;
+        return l;
+    }
+};
+
+// Call validation and the split into passes and lane ranges.  SamplingIntegrator::render (integrator.cpp:121-135,227-245): spp_per_pass = min(samples_per_pass, spp)
+// must divide spp; a wavefront of more than 2^32 - 1 lanes is split into more passes (integer division, as written there), and Sampler::set_samples_per_wavefront
+// (sampler.cpp:75-83) insists that the sample count is a multiple of the samples per pass.  rp.spp is the samples per PASS.
+void plan_lanes(FramePlan &p, const dtof_scene *sc, const RenderRequest &rq) {
+    const HostSensor &se = sc->host.sensor;
+    uint32_t spp = rq.spp ? rq.spp : sc->pp.sample_count;
+    if (spp == 0) throw std::runtime_error("sample count must be positive");
+    const uint32_t sample_count = spp;
+    uint32_t per_pass = sc->pp.samples_per_pass == 0xffffffffu || sc->pp.samples_per_pass == 0 ? spp : std::min(sc->pp.samples_per_pass, spp);
+    if (spp % per_pass != 0) throw std::runtime_error("sample_count (" + std::to_string(spp) + ") must be a multiple of spp_per_pass (" + std::to_string(per_pass) + ").");
+    const uint64_t wavefront = (uint64_t) se.crop_w * se.crop_h * per_pass, limit = 0xffffffffull;
+    if (wavefront > limit) {
+        per_pass /= (uint32_t) ((wavefront + limit - 1) / limit);
+        if (per_pass == 0 || spp % per_pass != 0) throw std::runtime_error("sample_count should be a multiple of samples_per_wavefront!");
+    }
+    p.n_passes = spp / per_pass; spp = per_pass;
+    const uint64_t total_lanes = (uint64_t) se.crop_w * se.crop_h * spp;   // lanes of one pass (the wavefront)
     if (sc->pp.time_sampling != TIME_UNIFORM && sc->pp.stratify_each_interval && sample_count < (uint32_t) sc->pp.time_correlate_number)
         throw std::runtime_error("sample count must be at least time_correlate_number when per-interval stratification is on");
     if (sc->pp.integrator == 0 && sc->pp.sampler_kind == SAMPLER_CORRELATED && sc->pp.time_sampling == TIME_ANTITHETIC_MIRROR && sc->pp.time_correlate_number != 2)
         throw std::runtime_error("antithetic_mirror time sampling needs time_correlate_number == 2");   // Assert(m_time_correlate_number == 2), correlated.cpp:142
-    RenderParams rp = make_params(sc, seed, spp, offsets, n_offsets, sample_count);
-    rp.n_passes = n_passes;
+    p.rp = make_params(sc, rq.seed, spp, rq.offsets, rq.n_offsets, sample_count);
+    p.rp.n_passes = p.n_passes;
     // lane dumps address (pass, lane) as pass * wavefront + lane and must stay inside one pass
-    uint32_t dump_pass = 0;
-    if (lane_dump) {
-        dump_pass = (uint32_t) (dump_begin / total_lanes); dump_begin %= total_lanes;
-        if (dump_pass >= n_passes || dump_begin + dump_n > total_lanes) throw std::runtime_error("lane range exceeds the wavefront");
+    uint64_t dump_begin = rq.dump_begin;
+    if (rq.lane_dump) {
+        p.dump_pass = (uint32_t) (dump_begin / total_lanes); dump_begin %= total_lanes;
+        if (p.dump_pass >= p.n_passes || dump_begin + rq.dump_n > total_lanes) throw std::runtime_error("lane range exceeds the wavefront");
     }
-    row_begin = std::max(row_begin, 0); row_end = std::min(row_end, se.crop_h);
-    uint64_t lanes_per_row = (uint64_t) se.crop_w * spp;
-    uint64_t first = lane_dump ? dump_begin : lanes_per_row * (uint64_t) row_begin;
-    uint64_t last = lane_dump ? dump_begin + dump_n : lanes_per_row * (uint64_t) std::max(row_end, row_begin);
-    if (last > total_lanes) throw std::runtime_error("lane range exceeds the wavefront");
-    if (stripe_rows) {   // virtual rows [0, V): the rows of this shard's stripes in ascending order
-        if (stripe_period < stripe_rows) throw std::runtime_error("stripe period must be at least the stripe height");
+    const int32_t row_begin = std::max(rq.row_begin, 0), row_end = std::min(rq.row_end, se.crop_h);
+    p.lanes_per_row = (uint64_t) se.crop_w * spp;
+    p.first = rq.lane_dump ? dump_begin : p.lanes_per_row * (uint64_t) row_begin;
+    p.last = rq.lane_dump ? dump_begin + rq.dump_n : p.lanes_per_row * (uint64_t) std::max(row_end, row_begin);
+    if (p.last > total_lanes) throw std::runtime_error("lane range exceeds the wavefront");
+    if (rq.stripes) {   // virtual rows [0, V): the rows of this shard's stripes in ascending order
+        const uint32_t stripe_rows = (uint32_t) rq.stripe_rows, stripe_period = (uint32_t) rq.stripe_period;
         const uint64_t span = (uint64_t) std::max(row_end - row_begin, 0), full = span / stripe_period, rest = span % stripe_period;
         const uint64_t v_rows = full * stripe_rows + std::min<uint64_t>(rest, stripe_rows);
-        rp.stripe_rows = stripe_rows; rp.stripe_period = stripe_period; rp.stripe_first = (uint32_t) row_begin; rp.lanes_per_row = (uint32_t) lanes_per_row;
+        RenderParams &rp = p.rp;
+        rp.stripe_rows = stripe_rows; rp.stripe_period = stripe_period; rp.stripe_first = (uint32_t) row_begin; rp.lanes_per_row = (uint32_t) p.lanes_per_row;
         rp.d_lanes_per_row = make_fastdiv(rp.lanes_per_row); rp.d_stripe_rows = make_fastdiv(stripe_rows);
-        first = 0; last = v_rows * lanes_per_row;
+        p.first = 0; p.last = v_rows * p.lanes_per_row;
     }
-    uint64_t batch = lane_dump ? std::min<uint64_t>(target_batch_lanes(), std::max<uint64_t>(dump_n, 1))
-                               : std::max<uint64_t>(1, target_batch_lanes() / lanes_per_row) * lanes_per_row;
-    batch = std::min<uint64_t>(batch, std::max<uint64_t>(last - first, 1));
-    if (batch > sc->ws.capacity) {   // a workspace that has to grow: keep it within the free device memory (168 B + 32 B per offset film per lane, two copies with two streams)
+    p.run_passes = rq.lane_dump ? p.dump_pass + 1 : p.n_passes;   // a lane dump of pass k needs the stream states passes 0 .. k-1 leave
+}
+
+// Every decision of the frame.  The development switches of the frame path are read here, once per frame, and nowhere else:
+//   switch              default     selects
+//   DTOF_PIPELINE       auto        split | fused: the pipeline
+//   DTOF_STREAMS        1           2: two batches in flight on two streams (measured gain 0 % Cornell .. 7 % Domino; it blurs per-stage timing)
+//   DTOF_FUSE_FIRST     1           0: separate k_generate + k_trace launches instead of the fused first-bounce kernel
+//   DTOF_INSTANCE_MEMO  1           0: no instance memo
+//   DTOF_FLAT           1           0: fused rectangle-only scenes keep the TLAS instead of testing every object (trace_flat)
+//   DTOF_RESIDENT       16 / 12 / 8 waves per block of the resident first-bounce kernel, 8 | 12 | 16 (anything else: off); default 12 for every-BSDF scenes, 8 with several films
+//   DTOF_RESIDENT_HALF  1           0: a TLAS of 1 025 .. 2 048 nodes takes the classic launch instead of half-float LDS planes (k_shade: RH16)
+//   DTOF_FUSE_SPLAT     1           0: the splat kernel instead of the first-bounce kernel's own splat
+//   DTOF_INLINE_ITERS   kMaxInline  iterations the first-bounce kernel runs back to back (1 .. kMaxInline)
+//   DTOF_CHUNK_SEGS     8192        frames up to this many segments whose whole path runs inline: one block per 64-lane chunk
+//   DTOF_RES_UNITS      1           work units per segment of a resident launch covering the whole path, 1 | 2 | 4 | 8 (measured and left off: profiles/r05_resident_units.txt)
+//   DTOF_BATCH_LANES    2^27        lanes per wavefront batch
+//   DTOF_DEFER          2           BLAS scenes' ray kernels as a pair of launches: 0 never, 1 every one, 2 all but the primary rays' (profiles/r05_mesh_room.txt section 8:
+//                                   primary rays that reach a blob already fill their waves), 3 the shadow rays' only
+//   DTOF_TRACE8         1           0: the six-wave ray kernels instead of the eight-wave ones
+//   DTOF_NODES16        1           0: the 64-byte float nodes instead of their half-float copy
+//   DTOF_TLAS_LDS       1           0: the eight-wave ray kernels walk the TLAS in global memory like the BLAS
+//   DTOF_XCD_REMAP      auto        blocks per XCD run of the unstaged ray kernels (0: no remap)
+//   DTOF_TRACE_BLOCK    auto        64 | 128 | 256: block of the unstaged ray kernels
+//   DTOF_STAGE          1           0: never stage the scene into LDS
+//   DTOF_SPLAT          auto        dpp | generic: that splat kernel
+// Process-wide instead: DTOF_STAT_SLOTS (sizes the count slots), DTOF_ROCTX and DTOF_SYNC_LAUNCHES (debugging aids).
+FramePlan plan_frame(const dtof_scene *sc, const RenderRequest &rq) {
+    const auto num = [](const char *name, int dflt) { const char *e = getenv(name); return e ? atoi(e) : dflt; };
+    const auto on = [](const char *name) { const char *e = getenv(name); return !(e && e[0] == '0'); };
+    const auto str = [](const char *name) { const char *e = getenv(name); return std::string(e ? e : ""); };
+    const std::string env_pipeline = str("DTOF_PIPELINE"), env_splat = str("DTOF_SPLAT");
+    const int env_streams = num("DTOF_STREAMS", 1), env_inline = num("DTOF_INLINE_ITERS", (int) kMaxInline), env_units = num("DTOF_RES_UNITS", 1), env_block = num("DTOF_TRACE_BLOCK", 0);
+    const char *env_resident = getenv("DTOF_RESIDENT"), *env_batch = getenv("DTOF_BATCH_LANES");
+    const uint64_t batch_lanes = env_batch && strtoull(env_batch, nullptr, 10) ? strtoull(env_batch, nullptr, 10) : (1ull << 27);
+    FramePlan p;
+    LaunchSwitches &ls = p.launch;
+    ls.defer = num("DTOF_DEFER", 2); ls.trace8 = on("DTOF_TRACE8"); ls.nodes16 = on("DTOF_NODES16"); ls.tlas_lds = on("DTOF_TLAS_LDS"); ls.stage = on("DTOF_STAGE");
+    ls.xcd_set = getenv("DTOF_XCD_REMAP") != nullptr; ls.xcd_remap = (uint32_t) num("DTOF_XCD_REMAP", 0);
+    ls.trace_block = (uint32_t) (env_block == 64 || env_block == 128 || env_block == 256 ? env_block : 0);
+    ls.splat = env_splat == "dpp" ? 1 : env_splat == "generic" ? 2 : 0;
+    p.max_inline = (uint32_t) (env_inline < 1 ? 1 : env_inline > (int) kMaxInline ? (int) kMaxInline : env_inline);
+    p.chunk_segs = (uint32_t) num("DTOF_CHUNK_SEGS", 8192);
+    p.res_units = (uint32_t) (env_units == 1 || env_units == 2 || env_units == 4 || env_units == 8 ? env_units : 1);
+
+    plan_lanes(p, sc, rq);
+    const SceneTraits &t = p.traits = scene_traits(*sc);
+    const HostSensor &se = sc->host.sensor;
+    RenderParams &rp = p.rp;
+    // batches of 2^27 lanes (26 GB of workspace at 200 B per lane, 40 GB with four offset films -- of 288): every launch ends with a tail in which the CUs run dry one after
+    // the other, and a Domino frame in 32 launches of 2^24 lanes lost 7 % to it (C5 206 -> 193 ms, C4 44.8 -> 41.1; profiles/r03_batch_lanes.txt); one launch per C4
+    // frame instead of two is another 2 % (34.86 -> 34.14 ms, profiles/r04_domino_waves_batch.txt)
+    p.batch = rq.lane_dump ? std::min<uint64_t>(batch_lanes, std::max<uint64_t>(rq.dump_n, 1)) : std::max<uint64_t>(1, batch_lanes / p.lanes_per_row) * p.lanes_per_row;
+    p.batch = std::min<uint64_t>(p.batch, std::max<uint64_t>(p.last - p.first, 1));
+    if (p.batch > sc->ws.capacity) {   // a workspace that has to grow: keep it within the free device memory (168 B + 32 B per offset film per lane, two copies with two streams)
         size_t free_b = 0, total_b = 0;
         if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) {
             const uint64_t per_lane = 168 + 32ull * (uint64_t) std::max<int32_t>(rp.n_offsets, 1);
-            while (batch > (1ull << 22) && batch * per_lane * 2 > (uint64_t) free_b + (uint64_t) sc->ws.capacity * per_lane) batch = std::max<uint64_t>(1, (batch / 2) / lanes_per_row) * lanes_per_row;
+            while (p.batch > (1ull << 22) && p.batch * per_lane * 2 > (uint64_t) free_b + (uint64_t) sc->ws.capacity * per_lane) p.batch = std::max<uint64_t>(1, (p.batch / 2) / p.lanes_per_row) * p.lanes_per_row;
         }
     }
-    // Two batches are kept in flight on two HIP streams (each with its own workspace): the VALU-bound
-    // trace/shadow kernels of one batch overlap the HBM-bound shade kernel of the other.
-    static const int env_streams = [] { const char *e = getenv("DTOF_STREAMS"); int v = e ? atoi(e) : 1; return v == 2 ? 2 : 1; }();   // default 1: measured gain of 2 is 0% (Cornell) .. 7% (Domino) and it blurs per-stage timing
-    const int n_streams = (lane_dump || n_passes > 1) ? 1 : env_streams;   // the passes of a lane follow each other on one stream
-    // Pipeline choice.  "fused" runs occlusion + continuation traversal inside the shade kernel (one kernel per bounce), "split" runs
-    // k_trace -> k_shade -> k_shadow per bounce.
-    // DTOF_PIPELINE=split|fused overrides the automatic choice below.
-    const int env_pipeline = [] { const char *e = getenv("DTOF_PIPELINE"); std::string v = e ? e : ""; return v == "split" ? 0 : v == "fused" ? 1 : 2; }();   // read per call: tests switch it
-    const BlobHeader *bh = (const BlobHeader *) sc->blob.data();
-    static const bool env_fuse_first = [] { const char *e = getenv("DTOF_FUSE_FIRST"); return !(e && e[0] == '0'); }();
-    bool only_rectangles = bh->n_tris == 0;
-    for (auto &sh : sc->host.shapes) only_rectangles &= sh.kind == SHAPE_RECT;
-    // auto: fused (one kernel per bounce, and the first-bounce kernel running up to four iterations with the path state in registers) unless large
-    // meshes sit behind their own BLAS -- deep per-mesh traversals diverge inside the fat shade kernel (mesh room, 522 k triangles: 19.8 ms fused
-    // vs 16.1 ms split) -- or reflectances are textured (6.7 vs 5.8 ms).  Everything else measured faster fused once the fused kernels were
-    // capped at 168 VGPRs = 3 waves / SIMD (512 x 512 x 64: Cornell boxes 5.26 -> 4.60 ms, area light 7.12 -> 6.13, sphere light 6.42 -> 4.83,
+    // Two streams: the VALU-bound trace/shadow kernels of one batch overlap the HBM-bound shade kernel of the other.  The passes of a lane follow each other on one stream.
+    p.n_streams = (rq.lane_dump || p.n_passes > 1 || env_streams != 2) ? 1 : 2;
+    // Pipeline.  "fused" runs occlusion + continuation traversal inside the shade kernel (one kernel per bounce, and the first-bounce kernel running up to four
+    // iterations with the path state in registers), "split" runs k_trace -> k_shade -> k_shadow per bounce.  Automatic: fused unless large meshes sit behind their own
+    // BLAS -- deep per-mesh traversals diverge inside the fat shade kernel (mesh room, 522 k triangles: 19.8 ms fused vs 16.1 ms split; 18 k triangles still run faster
+    // fused, 11.2 vs 12.1 ms, 132 k do not, 16.1 vs 13.7 ms) -- or reflectances are textured (6.7 vs 5.8 ms).  Everything else measured faster fused once the fused
+    // kernels were capped at 168 VGPRs = 3 waves / SIMD (512 x 512 x 64: Cornell boxes 5.26 -> 4.60 ms, area light 7.12 -> 6.13, sphere light 6.42 -> 4.83,
     // disk 5.30 -> 3.90, Domino 1024 x 1024 x 128 with its 1 025 instances 69.5 -> 62.2 ms; profiles/r02_pipeline_choice.txt).
-    uint64_t blas_triangles = 0;   // triangles behind per-mesh BLASes: 18 k still run faster fused (11.2 vs 12.1 ms), 132 k do not (16.1 vs 13.7 ms)
-    {
-        const DShape *dshapes = (const DShape *) (sc->blob.data() + bh->off_shapes);
-        for (uint32_t i = 0; i < bh->n_shapes; ++i) if (dshapes[i].kind == SHAPE_MESH && dshapes[i].blas_root != kNoChild) blas_triangles += dshapes[i].n_tris;
+    p.fused = env_pipeline == "split" ? false : env_pipeline == "fused" ? true : t.blas_triangles <= 32768 && sc->host.textures.empty();
+    if (p.n_streams == 2 && !rq.lane_dump && p.last - p.first <= p.batch && p.last - p.first >= 2 * p.lanes_per_row) {
+        const uint64_t rows = (p.last - p.first) / p.lanes_per_row;
+        p.batch = ((rows + 1) / 2) * p.lanes_per_row;   // one batch would serialise: cut it in two row bands
     }
-    (void) only_rectangles;
-    const bool fused = env_pipeline == 2 ? (blas_triangles <= 32768 && sc->host.textures.empty()) : env_pipeline == 1;
-    if (n_streams == 2 && !lane_dump && last - first <= batch && last - first >= 2 * lanes_per_row) {
-        uint64_t rows = (last - first) / lanes_per_row;
-        batch = ((rows + 1) / 2) * lanes_per_row;                // one batch would serialise: cut it in two row bands
-    }
-    sc->ws.ensure((uint32_t) batch, rp.n_offsets);
-    if (n_streams == 2) sc->ws2.ensure((uint32_t) batch, rp.n_offsets);
-    if (lane_dump) sc->ws.dbg.ensure(batch);
-    Queues qs[2] = { sc->ws.queues(), n_streams == 2 ? sc->ws2.queues() : sc->ws.queues() };
-    qs[0].id_shift = qs[1].id_shift = sc->id_shift;
-
-    hipStream_t ss[2] = { sc->stream, n_streams == 2 ? sc->stream2 : sc->stream };
-    const uint8_t *blob = sc->d_blob.p; uint32_t blob_bytes = (uint32_t) sc->blob.size();
-    const uint32_t stack_depth = ((const BlobHeader *) sc->blob.data())->tlas_depth;
-    bool has_surface_emitters = false;          // area emitters make the emitter-hit term (and the last iteration) live
-    for (auto &e : sc->host.emitters) has_surface_emitters |= e.kind == EMITTER_AREA || e.kind == EMITTER_CONSTANT || e.kind == EMITTER_ENVMAP;   // the environment is "hit" by the rays that leave the scene
-    rp.has_area = has_surface_emitters;
-    for (auto &sh : sc->host.shapes) rp.has_spec |= sh.bsdf != BSDF_DIFFUSE || sh.masked || sh.tex_normal >= 0 || sh.blend_other;
-    for (auto &e : sc->host.emitters) rp.has_spec |= e.kind == EMITTER_SPOT || e.kind == EMITTER_DIRECTIONAL;
-    rp.has_spec |= !sc->host.textures.empty();
-    rp.has_spec |= se.thinlens || se.orthographic;   // the diffuse-only kernels generate perspective rays only (generate_lane<PERSPECTIVE_ONLY>)
-    for (size_t ei = 0; ei < sc->host.emitters.size(); ++ei) if (sc->host.emitters[ei].kind == EMITTER_CONSTANT || sc->host.emitters[ei].kind == EMITTER_ENVMAP) { rp.has_env = 1; rp.env_index = (uint32_t) ei; rp.has_spec = 1; }
+    rp.has_area = t.surface_emitters;   // area emitters make the emitter-hit term (and the last iteration) live
+    rp.has_spec = t.has_spec; rp.has_tris = t.has_tris; rp.has_analytic = t.has_analytic ? 1 : 0;
+    if (t.has_env) { rp.has_env = 1; rp.env_index = t.env_index; }
     // valid_ray leaves the kernels only when somebody reads it: the alpha channel of an rgba film (integrator.cpp:528-533) and the lane dumps
-    rp.want_valid = (lane_dump || se.alpha) ? 1 : 0;
-    if (rp.want_valid) { sc->ws.ensure_valid(); if (n_streams == 2) sc->ws2.ensure_valid(); qs[0].valid_out = sc->ws.valid.p; qs[1].valid_out = n_streams == 2 ? sc->ws2.valid.p : sc->ws.valid.p; }
-    rp.hide_emitters = sc->pp.hide_emitters;   // textured reflectances are looked up in the SPEC instantiations only   // the spot branch lives in the SPEC instantiations (keeps the common kernels lean)
-    bool has_spheres = false;
-    for (auto &sh : sc->host.shapes) has_spheres |= sh.kind == SHAPE_SPHERE || sh.kind == SHAPE_DISK || sh.kind == SHAPE_CYLINDER;   // analytic shapes of the MESH instantiations
-    // anything but rectangles: the instantiations with triangle / sphere code.  The SPEC shade kernels are MESH instantiations (full 16-byte hit
-    // record), so the trace kernels of the split pipeline must write that record for them too: a rectangle-only scene with textures (or any other
-    // SPEC feature) counts as "has_tris" -- the compact 4-byte record is for the plain rectangle-only kernels
-    for (auto &sh : sc->host.shapes) if (sh.blend_other) rp.has_spec = 2;   // blendbsdf: the instantiations whose BSDF chain loops over two records
-    rp.has_tris = bh->n_tris != 0 || has_spheres || rp.has_spec;
-    rp.has_analytic = has_spheres ? 1 : 0;
-    {   // deep per-mesh traversals diverge: see unstaged_block() in dtof_kernels.hip
-        const DShape *dshapes = (const DShape *) (sc->blob.data() + bh->off_shapes);
-        rp.n_tlas_nodes = bh->n_tlas_nodes; rp.has_nodes16 = bh->off_nodes16 != 0;
-        for (uint32_t i = 0; i < bh->n_shapes; ++i) rp.has_blas |= dshapes[i].kind == SHAPE_MESH && dshapes[i].blas_root != kNoChild;
-        if (rp.has_blas && rp.has_nodes16 && !rp.has_analytic) {   // the eight-wave ray kernels of such scenes run as a pair of launches (dtof_kernels.hip: DEFER): 20 bytes per lane of lists
-            sc->ws.ensure_defer(); if (n_streams == 2) sc->ws2.ensure_defer();
-            Workspace &w1 = n_streams == 2 ? sc->ws2 : sc->ws;
-            qs[0].cand = sc->ws.cand.p; qs[0].defer_idx = sc->ws.defer_idx.p; qs[0].defer_cnt = sc->ws.defer_cnt.p;
-            qs[1].cand = w1.cand.p; qs[1].defer_idx = w1.defer_idx.p; qs[1].defer_cnt = w1.defer_cnt.p;
-        }
+    rp.want_valid = (rq.lane_dump || se.alpha) ? 1 : 0;
+    rp.hide_emitters = sc->pp.hide_emitters;
+    rp.n_tlas_nodes = t.n_tlas_nodes; rp.has_nodes16 = t.has_nodes16; rp.has_blas = t.has_blas;   // deep per-mesh traversals diverge: see ray_shape() in dtof_kernels.hip
+    // the eight-wave ray kernels of scenes with a BLAS and no analytic shape can run as a pair of launches, with 20 bytes per lane of lists
+    if (!(t.has_blas && t.has_nodes16 && !t.has_analytic)) ls.defer = 0;
+    // instance memo (dtof_traverse.h): pays when there is exactly one instance object, which then nearly every ray visits
+    rp.memo_obj = p.fused && t.n_instances == 1 && on("DTOF_INSTANCE_MEMO") ? t.last_instance : 0xffffffffu;
+    // a handful of rectangles: test them all instead of walking a tree (trace_flat in dtof_traverse.h)
+    rp.flat_objects = p.fused && !rp.has_tris && t.flat_off != 0 && on("DTOF_FLAT") ? t.n_objects : 0u;
+    rp.flat_off = t.flat_off;
+    // Resident stage of the fused first-bounce kernel (k_shade<..., RESW>): scenes whose blob is too large to stage whole but whose TLAS (at most kResidentNodes nodes,
+    // twice that as half-float planes, no per-mesh BLAS) and small records fit one CU's LDS beside the stack columns -- Domino: 1 024 nodes, one shared 12-triangle cube.
+    // Waves: 16 (128 VGPRs) beat 12 once the nodes come from LDS, K = 4 too (Domino 44.2 vs 47.8 ms, C5 181.0 vs 192.7; profiles/r03_resident_stage_ab.txt,
+    // r04_domino_waves_batch.txt); the every-BSDF kernels hold more state: 12 for one film, 8 for four (profiles/r03_resident_spec_waves.txt).
+    const int waves = env_resident ? atoi(env_resident) : (rp.has_spec ? (rp.n_offsets > 1 ? 8 : 12) : 16);
+    if (p.fused && (waves == 8 || waves == 12 || waves == 16) && rp.has_tris && !rp.has_blas && t.resident_layout &&
+        (t.n_nodes <= kResidentNodes || (on("DTOF_RESIDENT_HALF") && t.has_nodes16 && t.n_nodes <= 2 * kResidentNodes))) {
+        p.resident.small_off = t.small_off; p.resident.small_words = t.small_words; p.resident.waves = (uint32_t) waves;
+        rp.res_half = t.n_nodes > kResidentNodes ? 1u : 0u;
+        // the stage must fit the CU's LDS beside the stack columns (a deep TLAS needs many): fewer waves per block while it does not, none if 8 do not either
+        const uint32_t limit = device_lds_limit();
+        while (p.resident.waves && resident_lds_bytes(rp, p.resident, t.stack_depth, p.resident.waves) > limit) p.resident.waves = p.resident.waves > 8 ? p.resident.waves - 4 : 0;
     }
-    rp.memo_obj = 0xffffffffu;
-    {   // instance memo (dtof_traverse.h): pays when there is exactly one instance object, which then nearly every ray visits
-        const DObject *dobj = (const DObject *) (sc->blob.data() + bh->off_objects);
-        uint32_t n_inst = 0, last_inst = 0;
-        for (uint32_t i = 0; i < bh->n_objects; ++i) if (dobj[i].kind == OBJ_INSTANCE) { ++n_inst; last_inst = i; }
-        static const bool env_memo = [] { const char *e = getenv("DTOF_INSTANCE_MEMO"); return !(e && e[0] == '0'); }();
-        if (fused && n_inst == 1 && env_memo) rp.memo_obj = last_inst;
-    }
-    {   // a handful of rectangles: test them all instead of walking a tree (trace_flat in dtof_traverse.h; DTOF_FLAT=0 keeps the TLAS)
-        static const bool env_flat = [] { const char *e = getenv("DTOF_FLAT"); return !(e && e[0] == '0'); }();
-        rp.flat_objects = fused && !rp.has_tris && bh->off_flat != 0 && env_flat ? bh->n_objects : 0u;
-        rp.flat_off = bh->off_flat;
-    }
-    // Resident stage of the fused first-bounce kernel (dtof_kernels.hip, k_shade<..., RESW>): scenes whose blob is too large to stage whole but whose
-    // TLAS (at most kResidentNodes nodes, no per-mesh BLAS) and small records fit one CU's LDS beside the stack columns -- Domino: 1 024 nodes, one
-    // shared 12-triangle cube, 1 025 instance records that stay in global memory.  DTOF_RESIDENT=0 switches it off, =8 / =12 / =16 set the waves per block.
-    ResidentStage resident;
-    {
-        // 16 waves per CU (4 per SIMD, 128 VGPRs) beat 12 (168 VGPRs) once the nodes come from LDS: 44.2 vs 47.8 ms on Domino (profiles/r03_resident_stage_ab.txt)
-        // (round 3: the K = 4 kernels spilled too much at 128 VGPRs -- C5 218 ms with 12 waves, 232 ms with 16; with the shorter traversal code of round 4 it is the other way
-        //  round: 192.7 ms with 12 waves, 181.0 with 16, profiles/r04_domino_waves_batch.txt)
-        // (the every-BSDF kernels hold more state: 12 waves for one film, 8 for four -- 3.64 ms against 4.07 at 16, 5.15 ms against 5.82 at 12 on a Domino field of rough
-        //  plastic cubes; profiles/r03_resident_spec_waves.txt)
-        int env_res = [&] { const char *e = getenv("DTOF_RESIDENT"); return e ? atoi(e) : (rp.has_spec ? (rp.n_offsets > 1 ? 8 : 12) : 16); }();   // read per call: tests and A/B runs switch it
-        const bool half_env = [] { const char *e = getenv("DTOF_RESIDENT_HALF"); return !(e && e[0] == '0'); }();   // a TLAS of 1 025 .. 2 048 nodes as half-float LDS planes (k_shade: RH16); =0: such scenes take the classic launch
-        const uint32_t small_off = bh->off_groups, small_bytes = bh->off_tables - bh->off_groups;          // groups | shapes | emitters | triangles | shading data | intersection records
-        if (fused && (env_res == 8 || env_res == 12 || env_res == 16) && rp.has_tris && !rp.has_blas && bh->n_nodes > 0 && (bh->n_nodes <= kResidentNodes || (half_env && bh->off_nodes16 != 0 && bh->n_nodes <= 2 * kResidentNodes)) && blob_bytes > 16 * 1024 &&
-            bh->off_shapes > bh->off_groups && bh->off_emitters > bh->off_groups && bh->off_tris > bh->off_groups && bh->off_shading >= bh->off_tris && bh->off_isect >= bh->off_shading && bh->off_tables >= bh->off_isect && small_bytes <= 24 * 1024) {
-            resident.small_off = small_off; resident.small_words = (small_bytes + 15) / 16; resident.waves = (uint32_t) env_res;
-            rp.res_half = bh->n_nodes > kResidentNodes ? 1u : 0u;
-            // the stage must fit the CU's LDS beside the stack columns (a deep TLAS needs many): fewer waves per block while it does not, none if 8 do not either
-            const uint32_t limit = device_lds_limit();
-            while (resident.waves && resident_lds_bytes(rp, resident, stack_depth, resident.waves) > limit) resident.waves = resident.waves > 8 ? resident.waves - 4 : 0;
-        }
-    }
+    // the 16-bit traversal of the resident kernels (dtof_traverse.h: NOBLAS, encode_child16) holds for these scenes only
+    if (p.resident.waves && rp.has_blas) throw std::runtime_error("internal error: the resident stage was chosen for a scene with a per-mesh BLAS");
+    if (p.resident.waves && (rp.res_half || rp.n_offsets > 1) && t.n_objects >= 0x7fff)
+        throw std::runtime_error("internal error: the resident stage with 16-bit child references was chosen for a scene of " + std::to_string(t.n_objects) + " objects");
+    // Without surface emitters the last iteration contributes nothing and is skipped -- unless further passes follow, whose streams depend on the six draws every
+    // active lane makes in it -- and unless a path can still be invalid when it gets there: a null lobe leaves valid_ray unset, and a non-null vertex of the last
+    // iteration sets it (dopplertofpath.cpp:252-253), which decides whether the path returns what it gathered or 0 (:279-282); the alpha channel / the lane dump's
+    // `valid` likewise depend on the hit of that iteration when max_depth is 1
+    p.skip_tail = !t.surface_emitters && p.n_passes == 1 && !t.null_lobe && !rp.want_valid;
+    // fused pipeline: the first bounce kernel generates the lanes and traces the primary rays itself
+    p.first_inline = p.fused && rp.integrator != INTEGRATOR_VELOCITY && p.iteration_runs(0) && on("DTOF_FUSE_FIRST");
+    // exactly one wave per pixel, one film: measured (profiles/r04_fused_splat_ab.txt) -- with more waves per pixel (C3: 256 spp) or four films (C5) the separate
+    // splat kernel, which sums 8 samples per lane before it reduces, is faster
+    p.fuse_splat_ok = on("DTOF_FUSE_SPLAT") && p.fused && !rq.lane_dump && p.n_passes == 1 && !se.alpha && rp.filter == FILTER_TENT && rp.filter_radius <= 1.f &&
+                      rp.filter_radius > .5f && rp.spp_log2 == 6 && rp.n_offsets == 1 && rq.film != nullptr;
+    return p;
+}
+
+// The wavefront loop of one call: the plan's batches, each through the bounce loop, accumulated into rq.film.
+void render_rows(dtof_scene *sc, const RenderRequest &rq) {
+    if (!sc->host.has_sensor) throw std::runtime_error("the scene does not contain a sensor");
+    ensure_device(sc);
+    const FramePlan p = plan_frame(sc, rq);
+    RenderParams rp = p.rp;
+    dtof_render_stats *const stats = rq.stats;
+    Queues qs[2];   // one workspace per in-flight batch
+    qs[0] = sc->ws.prepare((uint32_t) p.batch, rp.n_offsets, rp.want_valid, p.launch.defer != 0, sc->id_shift);
+    qs[1] = p.n_streams == 2 ? sc->ws2.prepare((uint32_t) p.batch, rp.n_offsets, rp.want_valid, p.launch.defer != 0, sc->id_shift) : qs[0];
+    if (rq.lane_dump) sc->ws.dbg.ensure(p.batch);
+    hipStream_t ss[2] = { sc->stream, p.n_streams == 2 ? sc->stream2 : sc->stream };
+    const uint8_t *blob = sc->d_blob.p; const uint32_t blob_bytes = (uint32_t) sc->blob.size(), stack_depth = p.traits.stack_depth;
     StageTimer tm(stats != nullptr, sc);
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     struct EventGuard { hipEvent_t e = nullptr; ~EventGuard() { if (e) (void) hipEventDestroy(e); } } g_fork, g_join;   // released on every exit path
-    if (n_streams == 2) { HIP_CHECK(hipEventCreateWithFlags(&g_fork.e, hipEventDisableTiming)); HIP_CHECK(hipEventCreateWithFlags(&g_join.e, hipEventDisableTiming)); }
-    hipEvent_t ev_fork = g_fork.e, ev_join = g_join.e;
+    if (p.n_streams == 2) { HIP_CHECK(hipEventCreateWithFlags(&g_fork.e, hipEventDisableTiming)); HIP_CHECK(hipEventCreateWithFlags(&g_join.e, hipEventDisableTiming)); }
     if (stats) { memset(stats, 0, sizeof *stats); ev0 = sc->take_event(); ev1 = sc->take_event(); HIP_CHECK(hipEventRecord(ev0, ss[0])); }
-    if (n_streams == 2) { HIP_CHECK(hipEventRecord(ev_fork, ss[0])); HIP_CHECK(hipStreamWaitEvent(ss[1], ev_fork, 0)); }
-    std::vector<uint64_t> h_counts; std::vector<uint32_t> batch_lanes, batch_iters, batch_inline;   // batch_inline: iterations the first-bounce launch of the batch covered (fused pipeline)
-    // per-iteration totals of every batch: sized ONCE (DevBuf::ensure reallocates without copying, and a hipFree in the middle of the
-    // frame would also synchronise the device)
-    const uint32_t run_passes = lane_dump ? dump_pass + 1 : n_passes;   // a lane dump of pass k needs the stream states passes 0 .. k-1 leave
-    const bool deferred = sc->defer_next; sc->defer_next = false;   // dtof_render_rows_async: timings by events, no counters read back, no synchronisation at the end
-    if (stats && !deferred && last > first) sc->d_sums.ensure((size_t) ((last - first + batch - 1) / batch) * run_passes * 2 * kMaxIter);
-    if (n_passes > 1 && last > first) {   // stream states carried from pass to pass (Sampler::advance keeps the RNGs running, sampler.cpp:52-55)
-        sc->d_pass_rng.ensure((size_t) (last - first) * 3);
-        rp.pass_rng = sc->d_pass_rng.p; rp.pass_first = (uint32_t) first;
+    if (p.n_streams == 2) { HIP_CHECK(hipEventRecord(g_fork.e, ss[0])); HIP_CHECK(hipStreamWaitEvent(ss[1], g_fork.e, 0)); }
+    std::vector<uint32_t> batch_lanes, batch_iters, batch_inline;   // batch_inline: iterations the first-bounce launch of the batch covered (fused pipeline)
+    // per-iteration totals of every batch: sized ONCE (DevBuf::ensure reallocates without copying, and a hipFree in the middle of the frame would also synchronise the device)
+    if (stats && !rq.deferred && p.last > p.first) sc->d_sums.ensure((size_t) ((p.last - p.first + p.batch - 1) / p.batch) * p.run_passes * 2 * kMaxIter);
+    if (p.n_passes > 1 && p.last > p.first) {   // stream states carried from pass to pass (Sampler::advance keeps the RNGs running, sampler.cpp:52-55)
+        sc->d_pass_rng.ensure((size_t) (p.last - p.first) * 3);
+        rp.pass_rng = sc->d_pass_rng.p; rp.pass_first = (uint32_t) p.first;
     }
-    // the reference's last iteration only looks for emitter hits; without surface emitters it contributes nothing and is skipped --
-    // unless further passes follow, whose streams depend on the six draws every active lane makes in it
-    // -- and unless a path can still be invalid when it gets there: a BSDF with a null lobe (`mask`, `thindielectric`) leaves valid_ray unset, and a non-null
-    // vertex of the last iteration sets it (dopplertofpath.cpp:252-253), which decides whether the path returns what it gathered or 0 (:279-282); the alpha
-    // channel / the lane dump's `valid` likewise depend on the hit of that iteration when max_depth is 1
-    // (over the whole chain of material records behind a shape -- a blend's partner, the back side of a two-BSDF twosided, and whatever those carry in turn -- so that a
-    // nesting the loader learns to accept later cannot slip a null lobe past this test)
-    bool has_null_lobe = false;
-    for (auto &sh : sc->host.shapes)
-        for (const HostShape *m = &sh; m; m = m->blend_other.get())
-            has_null_lobe |= m->masked || m->bsdf == BSDF_THINDIELECTRIC || m->bsdf == BSDF_NULL;
-    const bool env_fuse_splat = [] { const char *e = getenv("DTOF_FUSE_SPLAT"); return !(e && e[0] == '0'); }();   // read per call: the parity test of the two splat paths switches it
-    const bool fuse_splat_ok = env_fuse_splat && fused && !lane_dump && n_passes == 1 && !se.alpha && rp.filter == FILTER_TENT && rp.filter_radius <= 1.f && rp.filter_radius > .5f &&
-                               rp.spp_log2 == 6 && rp.n_offsets == 1 && d_film != nullptr;   // exactly one wave per pixel, one film: measured (profiles/r04_fused_splat_ab.txt) -- with more
-                               // waves per pixel (C3: 256 spp) or four films (C5) the separate splat kernel, which sums 8 samples per lane before it reduces, is faster
-    const bool skip_tail = !has_surface_emitters && n_passes == 1 && !has_null_lobe && !rp.want_valid;
-
+    const bool velocity = rp.integrator == INTEGRATOR_VELOCITY;
     // The host runs at most two batches ahead of the device: dtof_cancel (Integrator::cancel, integrator.h:96-109) is looked at when a
     // batch is enqueued, so an unbounded run-ahead would leave nothing to cancel once the launches of a long render are queued.
     hipEvent_t batch_done[2] = { sc->take_event(), sc->take_event() };
     uint32_t batch_index = 0;
-    for (uint32_t pass = 0; pass < run_passes; ++pass)
-    for (uint64_t b0 = first; b0 < last; b0 += batch, ++batch_index) {
+    for (uint32_t pass = 0; pass < p.run_passes; ++pass)
+    for (uint64_t b0 = p.first; b0 < p.last; b0 += p.batch, ++batch_index) {
         rp.pass = pass;
-        const bool dump_now = lane_dump && pass == dump_pass;
+        const bool dump_now = rq.lane_dump && pass == p.dump_pass;
         if (batch_index >= 2) HIP_CHECK(hipEventSynchronize(batch_done[batch_index & 1]));
         if (sc->stop.load()) break;
         const Queues &q = qs[batch_index & 1]; hipStream_t s = ss[batch_index & 1];
-        rp.lane_base = (uint32_t) b0; rp.n_lanes = (uint32_t) std::min<uint64_t>(batch, last - b0);
+        rp.lane_base = (uint32_t) b0; rp.n_lanes = (uint32_t) std::min<uint64_t>(p.batch, p.last - b0);
         const uint32_t n_seg = segments_for(rp.n_lanes);
-        // does iteration 0 of the bounce loop run at all?  (same conditions as the loop head below)
-        const bool loop_runs = rp.integrator != INTEGRATOR_VELOCITY && rp.max_depth > 0 && !(1 >= rp.max_depth && skip_tail);
-        // fused pipeline: the first bounce kernel generates the lanes and traces the primary rays itself (DTOF_FUSE_FIRST=0 keeps
-        // the separate k_generate + k_trace launches)
-        const bool first_inline = fused && loop_runs && env_fuse_first;
         int t = -1;
-        if (rp.want_valid && !loop_runs && rp.integrator != INTEGRATOR_VELOCITY) HIP_CHECK(hipMemsetAsync(q.valid_out, 0, (size_t) rp.n_lanes * sizeof(float4), s));   // max_depth == 0: { 0, false } (dopplertofpath.cpp:87-88)
-        if (!first_inline) {
-            t = tm.begin(0, s); launch_generate(rp, q, s); tm.end(0, t, s);
+        if (rp.want_valid && !velocity && !p.iteration_runs(0)) HIP_CHECK(hipMemsetAsync(q.valid_out, 0, (size_t) rp.n_lanes * sizeof(float4), s));   // max_depth == 0: { 0, false } (dopplertofpath.cpp:87-88)
+        if (!p.first_inline) {
+            t = tm.begin(kStageGenerate, s); launch_generate(rp, q, s); tm.end(kStageGenerate, t, s);
             if (dump_now) launch_lane_dump_rays(rp, q, sc->ws.dbg.p, s);
         }
         const uint32_t *qin = nullptr, *count_in = nullptr; uint32_t it = 0;
         bool fused_splat_done = false;   // the first-bounce kernel of this batch splatted its lanes itself
-        if (rp.integrator == INTEGRATOR_VELOCITY) { t = tm.begin(1, s); launch_velocity(blob, blob_bytes, rp, q, stack_depth, s); tm.end(1, t, s); }
-        for (;; ++it) {
-            if (rp.integrator == INTEGRATOR_VELOCITY) break;
-            if (it >= rp.max_depth) break;
-            // the last iteration of the reference only looks for emitter hits (dopplertofpath.cpp:136-171);
-            // without surface emitters it cannot contribute and is skipped
-            if (it + 1 >= rp.max_depth && skip_tail) break;
+        if (velocity) { t = tm.begin(kStageTrace, s); launch_velocity(blob, blob_bytes, rp, q, stack_depth, p.launch, s); tm.end(kStageTrace, t, s); }
+        for (; !velocity && p.iteration_runs(it); ++it) {
             if (it >= 8 && (it & 3) == 0) {   // unbounded depth: stop once every segment has drained
                 std::vector<uint32_t> alive(n_seg);
                 HIP_CHECK(hipMemcpyAsync(alive.data(), count_in, (size_t) n_seg * 4, hipMemcpyDeviceToHost, s));
@@ -566,82 +640,56 @@ void render_rows(dtof_scene *sc, uint32_t seed, uint32_t spp, int32_t row_begin,
                 uint64_t sum = 0; for (uint32_t v : alive) sum += v;
                 if (sum == 0) break;
             }
-            const bool first = first_inline && it == 0;
-            // The first-bounce kernel of the fused pipeline runs up to kMaxInline iterations of the loop itself, the path state in registers
-            // (RenderParams::inline_iters; DTOF_INLINE_ITERS=1 keeps one launch per iteration).  Multi-pass renders, whose stream states must be
-            // in memory between the passes, take one iteration per launch; lane dumps (dtof_sample_lanes) run the same inline kernel as renders.
-            // (One compacted launch per iteration instead -- for open scenes, whose paths mostly leave after a bounce -- was built and measured in round 4 and lost:
-            // profiles/r04_compaction_ab.txt, tools/experiments/r04_after_hit_compaction.patch.)
-            uint32_t span = 1;
-            if (first && n_passes == 1) {
-                const char *e = getenv("DTOF_INLINE_ITERS");   // read per call: tests switch it
-                const int v = e ? atoi(e) : (int) kMaxInline;
-                const uint32_t max_inline = (uint32_t) (v < 1 ? 1 : v > (int) kMaxInline ? (int) kMaxInline : v);
-                while (span < max_inline && (it + span) < rp.max_depth && !(it + span + 1 >= rp.max_depth && skip_tail)) ++span;   // the loop head's conditions for iteration it + span
-            }
-            rp.inline_iters = span;
-            it += span - 1;   // `it` is now the last iteration this launch covers
-            {   // small frames whose whole path runs inline: one block per 64-lane chunk (8 x the waves); the count slots it adds into are zeroed first
-                const bool whole_path = first && !((it + 1 < rp.max_depth) && !(it + 2 >= rp.max_depth && skip_tail));
-                const uint32_t env_chunk_segs = [] { const char *e = getenv("DTOF_CHUNK_SEGS"); return e ? (uint32_t) atoi(e) : 8192u; }();   // frames up to this many segments (A/B switch; read per call: tests switch it)
-                rp.chunk_blocks = whole_path && n_seg <= env_chunk_segs ? kChunkBlocks : 1u;
-                // The resident kernel's waves take their work from a counter; a launch ends with a tail in which they run out one after the other, as long as the last unit
-                // they started (a 512-lane segment = eight chunks of three bounces: ~0.7 ms on Domino).  When nothing is compacted for a later launch the unit can be a part
-                // of a segment (DTOF_RES_UNITS = units per segment, 1 / 2 / 4 / 8; the statistics slots are then added into, like those of the chunked small frames).
-                // MEASURED and OFF (profiles/r05_resident_units.txt): the shorter tail does not pay for the units' overhead on one GPU -- C4 33.20 ms at one unit per segment,
-                // 34.13 at two, 35.98 at four; C5 170.8 against 179.3 ms at four.  Kept as a switch for launches a fraction of this size (a frame sharded over many GPUs).
-                const uint32_t env_units = [] { const char *e = getenv("DTOF_RES_UNITS"); const int v = e ? atoi(e) : 1; return (uint32_t) (v == 1 || v == 2 || v == 4 || v == 8 ? v : 1); }();
-                rp.res_units = whole_path ? env_units : 1u;
-                if (rp.chunk_blocks > 1 || (rp.res_units > 1 && resident.waves)) HIP_CHECK(hipMemsetAsync(q.counts, 0, (size_t) 2 * (it + 1) * n_seg * 4, s));
-            }
-            // does iteration it+1 run?  (same conditions as the loop head)
-            const bool next_runs = (it + 1 < rp.max_depth) && !(it + 2 >= rp.max_depth && skip_tail);
-            // Fused splat: the first-bounce launch covers the whole path and every wave holds the 64 samples of one pixel -- it reduces their footprint values itself
-            // and adds them to the film (k_shade; tent filter with a 3 x 3 footprint, 64 samples per pixel, one film, one pass, no alpha film, no lane dump).  The result then
-            // never goes through q.res / q.pos and k_splat_x8's round trip through HBM.  DTOF_FUSE_SPLAT=0 keeps the splat kernel (A/B).
-            const bool splat_here = first && !next_runs && fuse_splat_ok && rp.chunk_blocks <= kChunkBlocks;
-            if (!fused || (it == 0 && !first)) { t = tm.begin(1, s); launch_trace(blob, blob_bytes, rp, q, qin, count_in, stack_depth, s); tm.end(1, t, s); if (stats) stats->n_launches_trace++; }
+            const bool first = p.first_inline && it == 0;
+            const LaunchSpan l = p.launch_span(it, first, n_seg);
+            rp.inline_iters = l.span; rp.chunk_blocks = l.chunk_blocks; rp.res_units = l.res_units;
+            it += l.span - 1;   // `it` is now the last iteration this launch covers
+            if (l.chunk_blocks > 1 || (l.res_units > 1 && p.resident.waves)) HIP_CHECK(hipMemsetAsync(q.counts, 0, (size_t) 2 * (it + 1) * n_seg * 4, s));
+            if (!p.fused || (it == 0 && !first)) { t = tm.begin(kStageTrace, s); launch_trace(blob, blob_bytes, rp, q, qin, count_in, stack_depth, p.launch, s); tm.end(kStageTrace, t, s); if (stats) stats->n_launches_trace++; }
             // per-iteration count slots; beyond kMaxIter iterations (unbounded depth, paths that russian roulette keeps alive that long)
             // the slots are reused -- only the statistics lose those iterations, no path is cut short
             uint32_t *qout = q.q[it & 1], *alive_out = q.counts + (size_t) (2 * (it % kMaxIter)) * n_seg, *shadow_out = alive_out + n_seg;
-            const int st_shade = first ? 5 : 2;
-            t = tm.begin(st_shade, s); launch_shade(blob, blob_bytes, rp, q, qin, count_in, qout, alive_out, shadow_out, it + 1 - span, fused, next_runs, stack_depth, s, first, first && dump_now ? sc->ws.dbg.p : nullptr, &resident, splat_here ? d_film : nullptr, film_stride); tm.end(st_shade, t, s);
-            fused_splat_done |= splat_here;
-            if (stats && splat_here) stats->n_fused_splat_launches++;
-            if (stats && first) { stats->n_launches_first++; stats->n_inline_iterations += span; batch_inline.push_back(span); }
-            if (!fused) { t = tm.begin(3, s); launch_shadow(blob, blob_bytes, rp, q, shadow_out, stack_depth, s); tm.end(3, t, s); if (stats) stats->n_launches_shadow++; }
+            const Stage st_shade = first ? kStageFirst : kStageShade;
+            t = tm.begin(st_shade, s);
+            launch_shade(blob, blob_bytes, rp, q, qin, count_in, qout, alive_out, shadow_out, it + 1 - l.span, p.fused, l.next_runs, stack_depth, p.launch, s, first,
+                         first && dump_now ? sc->ws.dbg.p : nullptr, &p.resident, l.splat_here ? rq.film : nullptr, rq.film_stride);
+            tm.end(st_shade, t, s);
+            fused_splat_done |= l.splat_here;
+            if (stats && l.splat_here) stats->n_fused_splat_launches++;
+            if (stats && first) { stats->n_launches_first++; stats->n_inline_iterations += l.span; batch_inline.push_back(l.span); }
+            if (!p.fused) { t = tm.begin(kStageShadow, s); launch_shadow(blob, blob_bytes, rp, q, shadow_out, stack_depth, p.launch, s); tm.end(kStageShadow, t, s); if (stats) stats->n_launches_shadow++; }
             if (stats) stats->n_launches_shade++;
             qin = qout; count_in = alive_out;
         }
-        if (n_passes > 1 && pass + 1 < run_passes) launch_pass_save(rp, q, s);
+        if (p.n_passes > 1 && pass + 1 < p.run_passes) launch_pass_save(rp, q, s);
         if (dump_now) {
             launch_lane_dump(rp, q, sc->ws.dbg.p, s);
-            HIP_CHECK(hipMemcpyAsync(lane_dump + (b0 - first), sc->ws.dbg.p, (size_t) rp.n_lanes * sizeof(LaneDebug), hipMemcpyDeviceToHost, s));
+            HIP_CHECK(hipMemcpyAsync(rq.lane_dump + (b0 - p.first), sc->ws.dbg.p, (size_t) rp.n_lanes * sizeof(LaneDebug), hipMemcpyDeviceToHost, s));
             HIP_CHECK(hipStreamSynchronize(s));
-        } else if (!lane_dump && !fused_splat_done) {
-            t = tm.begin(4, s); launch_splat(rp, q, d_film, film_stride, s);
-            if (se.alpha) {   // the alpha film (plane K behind the K offset films): the same splat over (valid, 0, 0) -- ImageBlock::put of aovs[3] (integrator.cpp:528-533)
+        } else if (!rq.lane_dump && !fused_splat_done) {
+            t = tm.begin(kStageSplat, s); launch_splat(rp, q, rq.film, rq.film_stride, p.launch, s);
+            if (sc->host.sensor.alpha) {   // the alpha film (plane K behind the K offset films): the same splat over (valid, 0, 0) -- ImageBlock::put of aovs[3] (integrator.cpp:528-533)
                 RenderParams ra = rp; ra.n_offsets = 1;
                 Queues qa = q; qa.res = q.valid_out;
-                launch_splat(ra, qa, d_film + (size_t) rp.n_offsets * film_stride, film_stride, s);
+                launch_splat(ra, qa, rq.film + (size_t) rp.n_offsets * rq.film_stride, rq.film_stride, p.launch, s);
             }
-            tm.end(4, t, s);
+            tm.end(kStageSplat, t, s);
         }
         HIP_CHECK(hipGetLastError());   // a rejected launch (LDS size, launch bounds, grid) must not pass for an empty film
         HIP_CHECK(hipEventRecord(batch_done[batch_index & 1], s));
         if (stats) {   // per-iteration totals of this batch are reduced on the device; one small copy after the last batch
             const uint32_t it_counted = std::min<uint32_t>(it, kMaxIter);
-            if (it_counted && !deferred) launch_sum_counts(q.counts, n_seg, 2 * it_counted, sc->d_sums.p + (size_t) batch_index * 2 * kMaxIter, s);
+            if (it_counted && !rq.deferred) launch_sum_counts(q.counts, n_seg, 2 * it_counted, sc->d_sums.p + (size_t) batch_index * 2 * kMaxIter, s);
             batch_lanes.push_back(rp.n_lanes); batch_iters.push_back(it_counted);
             stats->n_batches++;
         }
     }
-    if (n_streams == 2) { HIP_CHECK(hipEventRecord(ev_join, ss[1])); HIP_CHECK(hipStreamWaitEvent(ss[0], ev_join, 0)); }
+    if (p.n_streams == 2) { HIP_CHECK(hipEventRecord(g_join.e, ss[1])); HIP_CHECK(hipStreamWaitEvent(ss[0], g_join.e, 0)); }
     hipStream_t s = ss[0];
-    if (stats && deferred) {
+    if (stats && rq.deferred) {
         HIP_CHECK(hipEventRecord(ev1, s));
         dtof_scene::DeferredFrame f; f.ev0 = ev0; f.ev1 = ev1; f.counters = *stats;
-        for (int k = 0; k < 6; ++k) f.ev[k] = tm.ev[k];
+        for (int k = 0; k < kStageCount; ++k) f.ev[k] = tm.ev[k];
         for (uint32_t b : batch_lanes) f.counters.n_paths += b;
         sc->deferred.push_back(std::move(f));
         if (sc->stop.load()) throw std::runtime_error("cancelled");
@@ -652,10 +700,11 @@ void render_rows(dtof_scene *sc, uint32_t seed, uint32_t spp, int32_t row_begin,
         float ms = 0; HIP_CHECK(hipEventElapsedTime(&ms, ev0, ev1)); stats->ms_total = ms;
         std::vector<unsigned long long> sums(batch_lanes.size() * 2 * (size_t) kMaxIter);
         if (!sums.empty()) HIP_CHECK(hipMemcpy(sums.data(), sc->d_sums.p, sums.size() * 8, hipMemcpyDeviceToHost));
+        std::vector<uint64_t> h_counts;
         for (size_t b = 0; b < batch_lanes.size(); ++b)
             for (uint32_t i = 0; i < 2 * batch_iters[b]; ++i) h_counts.push_back(sums[b * 2 * kMaxIter + i]);
-        stats->ms_generate = tm.total(0); stats->ms_trace = tm.total(1); stats->ms_first = tm.total(5); stats->ms_shade = tm.total(2) + stats->ms_first;
-        stats->ms_shadow = tm.total(3); stats->ms_splat = tm.total(4);
+        stats->ms_generate = stage_ms(tm.ev[kStageGenerate]); stats->ms_trace = stage_ms(tm.ev[kStageTrace]); stats->ms_first = stage_ms(tm.ev[kStageFirst]);
+        stats->ms_shade = stage_ms(tm.ev[kStageShade]) + stats->ms_first; stats->ms_shadow = stage_ms(tm.ev[kStageShadow]); stats->ms_splat = stage_ms(tm.ev[kStageSplat]);
         size_t off = 0;
         for (size_t b = 0; b < batch_lanes.size(); ++b) {
             stats->n_paths += batch_lanes[b];
@@ -671,6 +720,22 @@ void render_rows(dtof_scene *sc, uint32_t seed, uint32_t spp, int32_t row_begin,
         HIP_CHECK(hipStreamSynchronize(s));
     }
     if (sc->stop.load()) throw std::runtime_error("cancelled");
+}
+
+// The device-film entry points: the null and stripe checks, the caller's film layout, and for the async forms the events a refused frame took go back to the pool
+void render_device_film(dtof_scene *sc, RenderRequest rq) {
+    if (!sc || !rq.film) throw std::runtime_error("null argument");
+    if (rq.stripes) {
+        if (rq.row_begin < 0 || rq.stripe_rows <= 0 || rq.stripe_period < rq.stripe_rows) throw std::runtime_error("invalid stripe layout");
+        rq.row_end = sc->host.sensor.crop_h;
+    }
+    sc->stop = false;
+    const std::pair<int32_t, int32_t> rows = rq.stripes ? stripe_span(sc, rq.row_begin, rq.stripe_rows, rq.stripe_period) : std::make_pair(rq.row_begin, rq.row_end);
+    rq.film_stride = caller_film_stride(sc, rq.n_offsets, rows.first, rows.second);
+    dtof_render_stats local;
+    if (rq.deferred) rq.stats = &local;
+    try { render_rows(sc, rq); }
+    catch (...) { if (rq.deferred && sc->deferred.empty()) sc->events_used = 0; throw; }
 }
 
 std::map<std::string, std::string> to_map(const char *const *names, const char *const *values, int n) {
@@ -897,24 +962,15 @@ int dtof_scene_export(const dtof_scene *sc, int kind, float *out, size_t cap, si
 
 int dtof_render_rows(dtof_scene *sc, uint32_t seed, uint32_t spp, int32_t row_begin, int32_t row_end,
                      const float *offsets, int n_offsets, float *d_film, dtof_render_stats *stats) {
-    return guarded([&] {
-        if (!sc || !d_film) throw std::runtime_error("null argument");
-        sc->stop = false;
-        sc->film_stride_call = caller_film_stride(sc, n_offsets, row_begin, row_end);
-        render_rows(sc, seed, spp, row_begin, row_end, offsets, n_offsets, d_film, stats);
-    });
+    RenderRequest rq; rq.seed = seed; rq.spp = spp; rq.row_begin = row_begin; rq.row_end = row_end;
+    rq.offsets = offsets; rq.n_offsets = n_offsets; rq.film = d_film; rq.stats = stats;
+    return guarded([&] { render_device_film(sc, rq); });
 }
 
 int dtof_render_rows_async(dtof_scene *sc, uint32_t seed, uint32_t spp, int32_t row_begin, int32_t row_end, const float *offsets, int n_offsets, float *d_film) {
-    return guarded([&] {
-        if (!sc || !d_film) throw std::runtime_error("null argument");
-        sc->stop = false;
-        sc->film_stride_call = caller_film_stride(sc, n_offsets, row_begin, row_end);   // a refused film leaves the next call synchronous
-        dtof_render_stats local;
-        sc->defer_next = true;
-        try { render_rows(sc, seed, spp, row_begin, row_end, offsets, n_offsets, d_film, &local); }
-        catch (...) { sc->defer_next = false; if (sc->deferred.empty()) sc->events_used = 0; throw; }   // the events the failed frame took go back to the pool
-    });
+    RenderRequest rq; rq.seed = seed; rq.spp = spp; rq.row_begin = row_begin; rq.row_end = row_end;
+    rq.offsets = offsets; rq.n_offsets = n_offsets; rq.film = d_film; rq.deferred = true;
+    return guarded([&] { render_device_film(sc, rq); });
 }
 int dtof_scene_set_film_layout(dtof_scene *sc, int32_t planes, uint64_t plane_stride_floats) {
     return guarded([&] {
@@ -942,17 +998,9 @@ int dtof_scene_set_stream(dtof_scene *sc, void *hip_stream) {
 }
 int dtof_render_stripes_async(dtof_scene *sc, uint32_t seed, uint32_t spp, int32_t first_row, int32_t stripe_rows, int32_t stripe_period,
                               const float *offsets, int n_offsets, float *d_film) {
-    return guarded([&] {
-        if (!sc || !d_film) throw std::runtime_error("null argument");
-        if (first_row < 0 || stripe_rows <= 0 || stripe_period < stripe_rows) throw std::runtime_error("invalid stripe layout");
-        sc->stop = false;
-        const std::pair<int32_t, int32_t> rows = stripe_span(sc, first_row, stripe_rows, stripe_period);
-        sc->film_stride_call = caller_film_stride(sc, n_offsets, rows.first, rows.second);
-        dtof_render_stats local;
-        sc->defer_next = true;
-        try { render_rows(sc, seed, spp, first_row, sc->host.sensor.crop_h, offsets, n_offsets, d_film, &local, nullptr, 0, 0, (uint32_t) stripe_rows, (uint32_t) stripe_period); }
-        catch (...) { sc->defer_next = false; if (sc->deferred.empty()) sc->events_used = 0; throw; }
-    });
+    RenderRequest rq; rq.seed = seed; rq.spp = spp; rq.row_begin = first_row; rq.stripes = true; rq.stripe_rows = stripe_rows; rq.stripe_period = stripe_period;
+    rq.offsets = offsets; rq.n_offsets = n_offsets; rq.film = d_film; rq.deferred = true;
+    return guarded([&] { render_device_film(sc, rq); });
 }
 int dtof_clear_async(dtof_scene *sc, void *d_ptr, size_t bytes) {
     return guarded([&] {
@@ -976,15 +1024,14 @@ int dtof_async_collect(dtof_scene *sc, dtof_render_stats *sum, double *frame_ms,
         HIP_CHECK(hipStreamSynchronize(sc->stream));
         memset(sum, 0, sizeof *sum);
         *n_frames = (uint32_t) sc->deferred.size();
-        auto total = [](const std::vector<std::pair<hipEvent_t, hipEvent_t>> &v) { double ms = 0; for (auto &p : v) { float t = 0; HIP_CHECK(hipEventElapsedTime(&t, p.first, p.second)); ms += t; } return ms; };
         uint32_t i = 0;
         for (auto &f : sc->deferred) {
             float t = 0; HIP_CHECK(hipEventElapsedTime(&t, f.ev0, f.ev1));
             if (frame_ms && i < capacity) frame_ms[i] = t;
             ++i;
             sum->ms_total += t;
-            sum->ms_generate += total(f.ev[0]); sum->ms_trace += total(f.ev[1]); sum->ms_first += total(f.ev[5]); sum->ms_shade += total(f.ev[2]) + total(f.ev[5]);
-            sum->ms_shadow += total(f.ev[3]); sum->ms_splat += total(f.ev[4]);
+            sum->ms_generate += stage_ms(f.ev[kStageGenerate]); sum->ms_trace += stage_ms(f.ev[kStageTrace]); sum->ms_first += stage_ms(f.ev[kStageFirst]);
+            sum->ms_shade += stage_ms(f.ev[kStageShade]) + stage_ms(f.ev[kStageFirst]); sum->ms_shadow += stage_ms(f.ev[kStageShadow]); sum->ms_splat += stage_ms(f.ev[kStageSplat]);
             sum->n_paths += f.counters.n_paths; sum->n_batches += f.counters.n_batches;
             sum->n_launches_trace += f.counters.n_launches_trace; sum->n_launches_shade += f.counters.n_launches_shade; sum->n_launches_shadow += f.counters.n_launches_shadow;
             sum->n_launches_first += f.counters.n_launches_first; sum->n_inline_iterations += f.counters.n_inline_iterations; sum->n_fused_splat_launches += f.counters.n_fused_splat_launches;
@@ -995,14 +1042,9 @@ int dtof_async_collect(dtof_scene *sc, dtof_render_stats *sum, double *frame_ms,
 
 int dtof_render_stripes(dtof_scene *sc, uint32_t seed, uint32_t spp, int32_t first_row, int32_t stripe_rows, int32_t stripe_period,
                         const float *offsets, int n_offsets, float *d_film, dtof_render_stats *stats) {
-    return guarded([&] {
-        if (!sc || !d_film) throw std::runtime_error("null argument");
-        if (first_row < 0 || stripe_rows <= 0 || stripe_period < stripe_rows) throw std::runtime_error("invalid stripe layout");
-        sc->stop = false;
-        const std::pair<int32_t, int32_t> rows = stripe_span(sc, first_row, stripe_rows, stripe_period);
-        sc->film_stride_call = caller_film_stride(sc, n_offsets, rows.first, rows.second);
-        render_rows(sc, seed, spp, first_row, sc->host.sensor.crop_h, offsets, n_offsets, d_film, stats, nullptr, 0, 0, (uint32_t) stripe_rows, (uint32_t) stripe_period);
-    });
+    RenderRequest rq; rq.seed = seed; rq.spp = spp; rq.row_begin = first_row; rq.stripes = true; rq.stripe_rows = stripe_rows; rq.stripe_period = stripe_period;
+    rq.offsets = offsets; rq.n_offsets = n_offsets; rq.film = d_film; rq.stats = stats;
+    return guarded([&] { render_device_film(sc, rq); });
 }
 
 int dtof_develop(const float *d_film, float *d_rgb, int64_t n_pixels) {
@@ -1024,8 +1066,9 @@ int dtof_render_offsets(dtof_scene *sc, uint32_t seed, uint32_t spp, const float
         const int planes = k + (se.alpha ? 1 : 0), ch = se.alpha ? 4 : 3;   // rgba: one more film plane for the alpha channel, four channels out
         sc->d_film.ensure(px * 4 * planes); sc->d_rgb.ensure(px * ch * k);
         HIP_CHECK(hipMemsetAsync(sc->d_film.p, 0, px * 4 * planes * sizeof(float), sc->stream));
-        sc->film_stride_call = px * 4;   // the library's own film
-        render_rows(sc, seed, spp, 0, se.crop_h, offsets, n_offsets, sc->d_film.p, stats);
+        RenderRequest rq; rq.seed = seed; rq.spp = spp; rq.row_end = se.crop_h; rq.offsets = offsets; rq.n_offsets = n_offsets;
+        rq.film = sc->d_film.p; rq.film_stride = px * 4; rq.stats = stats;   // the library's own film
+        render_rows(sc, rq);
         if (se.alpha) for (int i = 0; i < k; ++i) launch_develop_rgba(sc->d_film.p + px * 4 * i, sc->d_film.p + px * 4 * k, sc->d_rgb.p + px * 4 * i, (int64_t) px, sc->stream);
         else launch_develop(sc->d_film.p, sc->d_rgb.p, (int64_t) px * k, sc->stream);
         HIP_CHECK(hipMemcpyAsync(out_rgb, sc->d_rgb.p, px * ch * k * sizeof(float), hipMemcpyDeviceToHost, sc->stream));
@@ -1047,7 +1090,8 @@ int dtof_sample_lanes_valid(dtof_scene *sc, uint32_t seed, uint32_t spp, uint64_
         sc->stop = false;
         if (n == 0) return;
         std::vector<LaneDebug> lanes(n);
-        render_rows(sc, seed, spp, 0, 0, nullptr, 0, nullptr, nullptr, lanes.data(), lane_begin, n);
+        RenderRequest rq; rq.seed = seed; rq.spp = spp; rq.lane_dump = lanes.data(); rq.dump_begin = lane_begin; rq.dump_n = n;
+        render_rows(sc, rq);
         for (uint64_t i = 0; i < n; ++i) { memcpy(out + 12 * i, &lanes[i], 48); if (valid) valid[i] = lanes[i].valid != 0.f ? 1u : 0u; }
     });
 }
