@@ -197,7 +197,8 @@ void launch_camera_rays(const RenderParams &rp, const float *in, float *out, uin
 void launch_ray_query(const uint8_t *scene, const float *rays, float *out, int32_t *ids, float *uv4, uint32_t n, bool any, uint32_t stack_depth, hipStream_t s);
 
 #ifdef DTOF_TRAVERSAL_STATS
-bool read_traversal_stats(unsigned long long *out8);
+constexpr uint32_t kTravStats = 24;   // counter slots (dtof_traverse.h)
+bool read_traversal_stats(unsigned long long *out8);   // all kTravStats slots
 void register_traversal_stats_reader(bool (*reader)(unsigned long long *acc8));
 #endif
 

@@ -1342,12 +1342,16 @@ int dtof_ray_test(dtof_scene *sc, uint32_t n, const float *rays8, int32_t *occlu
 
 #ifdef DTOF_TRAVERSAL_STATS
 // development builds (make STATS=1): read and reset the traversal counters of dtof_traverse.h
-int dtof_debug_traversal_stats(unsigned long long *out8) {
+// (`n` of the kTravStats slots into out8; dtof_debug_traversal_stats: the first 16)
+int dtof_debug_traversal_stats_n(unsigned long long *out8, uint32_t n) {
     return guarded([&] {
         HIP_CHECK(hipDeviceSynchronize());
-        if (!read_traversal_stats(out8)) throw HipError("hipMemcpyFromSymbol(g_trav_stats) failed");
+        unsigned long long all[kTravStats];
+        if (!read_traversal_stats(all)) throw HipError("hipMemcpyFromSymbol(g_trav_stats) failed");
+        for (uint32_t i = 0; i < n && i < kTravStats; ++i) out8[i] = all[i];
     });
 }
+int dtof_debug_traversal_stats(unsigned long long *out8) { return dtof_debug_traversal_stats_n(out8, 16); }
 #endif
 
 }  // extern "C"

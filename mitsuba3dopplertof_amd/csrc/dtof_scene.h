@@ -34,7 +34,7 @@ struct BlobHeader {
     uint32_t off_nodes, off_objects, off_groups, off_shapes, off_tris, off_shading, off_emitters;
     uint32_t total_bytes, off_tables, tlas_depth, off_flat;      // off_tables: face distributions of mesh emitters (float / uint32 words)   // tlas_depth: stack entries a traversal can need (TLAS depth + deepest BLAS)
     uint32_t off_isect, n_tlas_nodes, off_nodes16;   // off_nodes16: DNode16[n_nodes] of scenes with a BLAS (0: none), see below;           // n_tlas_nodes: the first nodes of the array are the TLAS (the BLAS of the meshes follow)
-                           // off_isect: DTriIsect[n_tris], what the triangle test reads   // off_flat: DFlatObject[n_objects] of a rectangle-only scene of at most kFlatObjects objects, else 0
+                           // off_isect: DTriIsect[n_tris], what the triangle test reads   // off_flat: DFlatObject[n_objects], DFlatKinds, DFlatZ[n_objects] of a rectangle-only scene of at most kFlatObjects objects, else 0
 };
 static_assert(sizeof(BlobHeader) == 80, "BlobHeader");
 // One top-level object of a small rectangle-only scene as trace_flat (dtof_traverse.h) reads it with ONE scalar load: a plain rectangle's
@@ -45,6 +45,11 @@ constexpr uint32_t kFlatObjects = 8;
 // profiles/r03_ubench_valu_rate.txt).
 struct DFlatObject { float c0[3]; uint32_t instance; float c1[3]; uint32_t pad1; float c2[3]; uint32_t pad2; float c3[3]; uint32_t pad3; };   // 64 B; instance: 0 plain rectangle, 1 instance (general path), 2 instance of ONE rectangle (matrix = that rectangle's, in the group's space)
 static_assert(sizeof(DFlatObject) == 64, "DFlatObject");
+// The DFlatObject table is followed by ONE DFlatKinds record and then one DFlatZ per object: the z row of each matrix in 16 bytes, all that trace_flat reads of an object
+// before it knows whether the full test is needed (dtof_flat_cull.h), and the instance marks as bit masks for scalar registers.
+struct DFlatKinds { uint32_t general, memo, pad[2]; };   // bit i: DFlatObject i has instance == 1 | instance == 2
+struct DFlatZ { float z[4]; };                            // c0[2], c1[2], c2[2], c3[2] of the same record
+static_assert(sizeof(DFlatKinds) == 16 && sizeof(DFlatZ) == 16, "DFlatZ");
 
 constexpr uint32_t kLeafFlag = 0x80000000u;
 // TLAS leaves only: the object behind this leaf holds a mesh with a BLAS of its own (bit 30; the object index is the 30 bits below).  The ray kernels of large meshes can

@@ -4,6 +4,7 @@
 #include "dtof_kernels.h"
 #include "dtof_scene.h"
 #include "dtof_math.h"
+#include "dtof_flat_cull.h"
 
 #ifndef DTOF_D
 #define DTOF_D __device__ __forceinline__
@@ -68,13 +69,16 @@ struct Hit { float t, u, v; uint32_t obj, shape, prim; };
 // [14] POISON HITS: in these builds k_shade gives the path state of every lane that has no path (beyond the end of its segment) a recognisable pattern (kPoisonState) and
 //      counts it wherever path state leaves the registers -- queue stores, the LDS columns, the inline iterations' hand-over.  Must stay 0: the K = 4 incident of round 3
 //      (profiles/r03_k4_uninitialised.txt, profiles/r05_k4_root_cause.txt) was a film that depended on the INITIAL value of those registers.
+// [15] BLAS node steps (wave)
+// [16 .. 19] trace_flat, occlusion rays: rectangles whose z row was tested (lane), ... that it settled as certain misses (lane), z-row tests (wave), full tests (wave:
+//      the waves in which some lane still needed it);  [20 .. 23] the same for closest-hit rays.  dtof_debug_traversal_stats reads slots 0 .. 15, dtof_debug_traversal_stats_n all.
 #ifdef DTOF_TRAVERSAL_STATS
 // every translation unit with kernels counts into its own copy (no relocatable device code); each registers a reader, read_traversal_stats sums and resets them all
-static __device__ unsigned long long g_trav_stats[16];
+static __device__ unsigned long long g_trav_stats[kTravStats];
 static bool read_tu_traversal_stats(unsigned long long *acc8) {
-    unsigned long long v[16], zero[16] = { 0 };
-    if (hipMemcpyFromSymbol(v, HIP_SYMBOL(g_trav_stats), 128) != hipSuccess || hipMemcpyToSymbol(HIP_SYMBOL(g_trav_stats), zero, 128) != hipSuccess) return false;
-    for (int i = 0; i < 16; ++i) acc8[i] += v[i];
+    unsigned long long v[kTravStats], zero[kTravStats] = { 0 };
+    if (hipMemcpyFromSymbol(v, HIP_SYMBOL(g_trav_stats), sizeof v) != hipSuccess || hipMemcpyToSymbol(HIP_SYMBOL(g_trav_stats), zero, sizeof zero) != hipSuccess) return false;
+    for (uint32_t i = 0; i < kTravStats; ++i) acc8[i] += v[i];
     return true;
 }
 static const int g_trav_stats_registered = (register_traversal_stats_reader(read_tu_traversal_stats), 0);
@@ -471,6 +475,9 @@ DTOF_D bool trace_deferred(const SceneView &sv, uint32_t *stack, uint4 cand, V3 
 // ~40 instructions per rectangle cost less than the ~55 per node step + ~60 per leaf visit of the binary tree at 0.5 lane utilisation.
 // Hits are those of trace_scene bit for bit: same rect_hit arithmetic, smallest t wins, ties go to the lowest object index
 // (ascending order + strict <).  Instances take intersect_object (one uniform branch).
+// Each rectangle test starts with the z row of its matrix (local z of the ray's origin and direction) and the certain-miss test of dtof_flat_cull.h; when no active lane
+// of the wave can hit the rectangle, the wave branches over the rest of the test (the xy rows, the IEEE division, the u / v checks).  Shadow rays of a closed room never
+// cross a wall between two points inside it, and rays skip the walls behind them: of the ~37 instructions of a test, ~10 remain.
 typedef const uint8_t __attribute__((address_space(4))) *ConstBytes;
 // DTOF_FLAT_PK=1: the rectangle transform of trace_flat as packed multiply-adds (v_pk_fma_f32 with the matrix entries as SGPR-pair operands: two
 // multiply-adds in the 4 cycles ONE scalar-operand v_fma_f32 takes, profiles/r03_ubench_valu_rate.txt).  Bit-exact; measured on C2: 3 % fewer VALU
@@ -490,6 +497,14 @@ DTOF_D FlatRecord flat_load(const DFlatObject __attribute__((address_space(4))) 
     r.z0 = f->c0[2]; r.z1 = f->c1[2]; r.z2 = f->c2[2]; r.z3 = f->c3[2];
     return r;
 }
+// the z rows of the point and the direction (xf_point / xf_vector, z components): zrow.x = local z of the origin, zrow.y = that of the direction
+DTOF_D F2 flat_zrow(float z0, float z1, float z2, float z3, V3 ro, V3 rd) {
+#if DTOF_FLAT_PK   // (same entries, different vectors: one packed multiply-add per column; the direction's leading product becomes fma(m, d, -0), which equals m * d)
+    return __builtin_elementwise_fma(F2{ z2, z2 }, F2{ ro.z, rd.z }, __builtin_elementwise_fma(F2{ z1, z1 }, F2{ ro.y, rd.y }, __builtin_elementwise_fma(F2{ z0, z0 }, F2{ ro.x, rd.x }, F2{ z3, -0.f })));
+#else
+    return F2{ fmaf(z2, ro.z, fmaf(z1, ro.y, fmaf(z0, ro.x, z3))), fmaf(z2, rd.z, fmaf(z1, rd.y, z0 * rd.x)) };
+#endif
+}
 template <bool ANY, bool MEMO>
 DTOF_D bool trace_flat(const SceneView &sv, ConstBytes flat_table, uint32_t flat_off, uint32_t n_objects, uint32_t *stack, V3 o, V3 d, float time, float maxt, Hit &best) {
     typedef const DFlatObject __attribute__((address_space(4))) *ConstFlat;
@@ -497,24 +512,25 @@ DTOF_D bool trace_flat(const SceneView &sv, ConstBytes flat_table, uint32_t flat
     best.t = maxt; best.u = best.v = 0.f; best.obj = 0xffffffffu; best.shape = 0; best.prim = 0;
     bool occluded = false;
     DTOF_STAT(0);
-    auto test = [&](const FlatRecord &rec, uint32_t oi) {   // rect_hit on a plain rectangle's record
-        V3 ro = o, rd = d;
-        if (rec.instance == 2) {   // (uniform) the one memoised instance: into its space first, as intersect_object does (instance.cpp:101-114)
+    // the ray in the space of object `oi`: the world ray, or -- the one memoised instance -- moved there first, as intersect_object does (instance.cpp:101-114)
+    auto to_object = [&](bool memo_instance, V3 &ro, V3 &rd) {
+        ro = o; rd = d;
+        if (memo_instance) {
             float inv[12]; instance_memo_load(sv, inv);
             ro = xf_point(inv, o); rd = xf_vector(inv, d);
         }
+    };
+    // rect_hit on a rectangle's record, the ray (ro, rd) in its space and z = flat_zrow of it
+    auto test = [&](const FlatRecord &rec, uint32_t oi, V3 ro, V3 rd, F2 z) {
         // xf_point / xf_vector with the matrix entries as scalar operands, two multiply-adds per instruction: the x and y rows of the point as one pair,
-        // those of the direction as another, the z rows of point AND direction as the third (same entries, different vectors).  Each half is the IEEE
-        // operation of the scalar form, in its order; the direction's leading product becomes fma(m, d, -0), which equals m * d for every input.
+        // those of the direction as another.  Each half is the IEEE operation of the scalar form, in its order; the direction's leading product becomes
+        // fma(m, d, -0), which equals m * d for every input.
 #if DTOF_FLAT_PK
         const F2 lo_xy = __builtin_elementwise_fma(rec.c2, F2{ ro.z, ro.z }, __builtin_elementwise_fma(rec.c1, F2{ ro.y, ro.y }, __builtin_elementwise_fma(rec.c0, F2{ ro.x, ro.x }, rec.c3)));
         const F2 ld_xy = __builtin_elementwise_fma(rec.c2, F2{ rd.z, rd.z }, __builtin_elementwise_fma(rec.c1, F2{ rd.y, rd.y }, rec.c0 * F2{ rd.x, rd.x }));
-        const F2 z = __builtin_elementwise_fma(F2{ rec.z2, rec.z2 }, F2{ ro.z, rd.z }, __builtin_elementwise_fma(F2{ rec.z1, rec.z1 }, F2{ ro.y, rd.y },
-                                               __builtin_elementwise_fma(F2{ rec.z0, rec.z0 }, F2{ ro.x, rd.x }, F2{ rec.z3, -0.f })));
 #else   // the scalar form (one multiply-add per instruction, matrix entries as SGPR operands: 4 cycles each), kept for A/B timing
         const F2 lo_xy = F2{ fmaf(rec.c2.x, ro.z, fmaf(rec.c1.x, ro.y, fmaf(rec.c0.x, ro.x, rec.c3.x))), fmaf(rec.c2.y, ro.z, fmaf(rec.c1.y, ro.y, fmaf(rec.c0.y, ro.x, rec.c3.y))) };
         const F2 ld_xy = F2{ fmaf(rec.c2.x, rd.z, fmaf(rec.c1.x, rd.y, rec.c0.x * rd.x)), fmaf(rec.c2.y, rd.z, fmaf(rec.c1.y, rd.y, rec.c0.y * rd.x)) };
-        const F2 z = F2{ fmaf(rec.z2, ro.z, fmaf(rec.z1, ro.y, fmaf(rec.z0, ro.x, rec.z3))), fmaf(rec.z2, rd.z, fmaf(rec.z1, rd.y, rec.z0 * rd.x)) };
 #endif
         const float t = -z.x / z.y;
         const float u = fmaf(ld_xy.x, t, lo_xy.x), v = fmaf(ld_xy.y, t, lo_xy.y);
@@ -526,35 +542,57 @@ DTOF_D bool trace_flat(const SceneView &sv, ConstBytes flat_table, uint32_t flat
             best.t = take ? t : best.t; best.u = take ? u : best.u; best.v = take ? v : best.v; best.obj = take ? oi : best.obj;   // best.shape stays 0: the instances, which may set it, come after the rectangles
         }
     };
-    // Two record buffers take turns (the loop is unrolled by two), so the next record's scalar load flies while the current one is tested
-    // and no register is copied from one iteration to the next.  Instances are noted in a mask and intersected after the rectangles: the
-    // tie rule of intersect_object (equal t goes to the lower object index) does not depend on the order of the visits.
+    // Instances are noted in a mask and intersected after the rectangles: the tie rule of intersect_object (equal t goes to the lower object index) does not depend on
+    // the order of the visits.
     uint32_t instances = 0, oi = 0;
 #if DTOF_FLAT_LDS
-    // The records come from the scene copy staged in LDS, every lane reading the same address (a broadcast, four ds_read_b128 per record): the matrix entries are then
-    // VGPR operands of the multiply-adds, which issue at full rate -- as SGPR operands (scalar loads from the blob) each of the 21 costs two issue slots
-    // (profiles/r03_ubench_valu_rate.txt).
+    // The records come from the scene copy staged in LDS, every lane reading the same address (a broadcast): the matrix entries are then VGPR operands of the
+    // multiply-adds, which issue at full rate -- as SGPR operands (scalar loads from the blob) each of the 21 costs two issue slots (profiles/r03_ubench_valu_rate.txt).
+    // First the object's z row (ONE ds_read_b128 from the DFlatZ table behind the records) and the certain-miss test; the rest of the record (four ds_read_b128) only
+    // where a lane of the wave still needs the full test.  The instance marks are two scalar loads.
     const DFlatObject *lt = (const DFlatObject *) (sv.base + flat_off);
+    const uint4 *zt = (const uint4 *) (lt + n_objects) + 1;   // DFlatZ[n_objects], behind the DFlatKinds record
+    const DFlatKinds __attribute__((address_space(4))) *kinds = (const DFlatKinds __attribute__((address_space(4))) *) (table + n_objects);
+    const uint32_t memo_bit = MEMO && sv.memo_obj < 32u ? 1u << sv.memo_obj : 0u, memo_objs = kinds->memo & memo_bit;
+    instances = kinds->general | (kinds->memo & ~memo_bit);
+    const float far = flat_cull_far(maxt);
+    constexpr int kStat = ANY ? 16 : 20; (void) kStat;   // (stats builds)
     for (; oi < n_objects; ++oi) {
+        if ((instances >> oi) & 1u) continue;   // (uniform)
+        V3 ro, rd;
+        to_object((memo_objs >> oi) & 1u, ro, rd);
+        const uint4 zr = zt[oi];
+        const F2 z = flat_zrow(u2f(zr.x), u2f(zr.y), u2f(zr.z), u2f(zr.w), ro, rd);
+        const bool need = !flat_certain_miss(z.x, z.y, far);
+        DTOF_STAT(kStat); DTOF_STAT_WAVE(kStat + 2);
+        if (!need) DTOF_STAT(kStat + 1);
+        if (!__ballot(need)) continue;   // (uniform) no active lane can hit this rectangle
+        DTOF_STAT_WAVE(kStat + 3);
         const uint4 *rp4 = (const uint4 *) (lt + oi);
         const uint4 r0 = rp4[0], r1 = rp4[1], r2 = rp4[2], r3 = rp4[3];
-        FlatRecord a; a.instance = (uint32_t) __builtin_amdgcn_readfirstlane((int) r0.w);
+        FlatRecord a; a.instance = 0;
         a.c0 = F2{ u2f(r0.x), u2f(r0.y) }; a.c1 = F2{ u2f(r1.x), u2f(r1.y) }; a.c2 = F2{ u2f(r2.x), u2f(r2.y) }; a.c3 = F2{ u2f(r3.x), u2f(r3.y) };
-        a.z0 = u2f(r0.z); a.z1 = u2f(r1.z); a.z2 = u2f(r2.z); a.z3 = u2f(r3.z);
-        if (a.instance == 1 || (a.instance == 2 && !(MEMO && sv.memo_obj == oi))) instances |= 1u << oi; else test(a, oi);
+        test(a, oi, ro, rd, z);
     }
 #else
+    // (without the cull) Two record buffers take turns (the loop is unrolled by two), so the next record's scalar load flies while the current one is tested and no
+    // register is copied from one iteration to the next.
+    auto test_record = [&](const FlatRecord &rec, uint32_t oi) {
+        V3 ro, rd;
+        to_object(rec.instance == 2, ro, rd);
+        test(rec, oi, ro, rd, flat_zrow(rec.z0, rec.z1, rec.z2, rec.z3, ro, rd));
+    };
     FlatRecord a = flat_load(table);
     for (;;) {
         FlatRecord b;
         const bool more_b = oi + 1 < n_objects;
         if (more_b) b = flat_load(table + oi + 1);
-        if (a.instance == 1 || (a.instance == 2 && !(MEMO && sv.memo_obj == oi))) instances |= 1u << oi; else test(a, oi);
+        if (a.instance == 1 || (a.instance == 2 && !(MEMO && sv.memo_obj == oi))) instances |= 1u << oi; else test_record(a, oi);
         if (!more_b) break;
         ++oi;
         const bool more_a = oi + 1 < n_objects;
         if (more_a) a = flat_load(table + oi + 1);
-        if (b.instance == 1 || (b.instance == 2 && !(MEMO && sv.memo_obj == oi))) instances |= 1u << oi; else test(b, oi);
+        if (b.instance == 1 || (b.instance == 2 && !(MEMO && sv.memo_obj == oi))) instances |= 1u << oi; else test_record(b, oi);
         if (!more_a) break;
         ++oi;
     }

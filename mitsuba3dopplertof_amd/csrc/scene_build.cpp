@@ -542,7 +542,16 @@ std::vector<uint8_t> build_scene_blob(const HostScene &sc) {
             flat.push_back(f);
         }
     }
-    { const uint32_t at = place(flat.size() * sizeof(DFlatObject)); h.off_flat = flat.empty() ? 0u : at; }
+    DFlatKinds flat_kinds; memset(&flat_kinds, 0, sizeof flat_kinds);
+    std::vector<DFlatZ> flat_z;
+    for (size_t i = 0; i < flat.size(); ++i) {
+        const DFlatObject &f = flat[i];
+        if (f.instance == 1) flat_kinds.general |= 1u << i;
+        if (f.instance == 2) flat_kinds.memo |= 1u << i;
+        flat_z.push_back(DFlatZ{ { f.c0[2], f.c1[2], f.c2[2], f.c3[2] } });
+    }
+    const size_t flat_bytes = flat.size() * sizeof(DFlatObject) + (flat.empty() ? 0 : sizeof(DFlatKinds) + flat_z.size() * sizeof(DFlatZ));
+    { const uint32_t at = place(flat_bytes); h.off_flat = flat.empty() ? 0u : at; }
     h.total_bytes = (uint32_t) off;
     for (DShape &d : shapes) if (d.kind == SHAPE_MESH && (d.flags & SF_EMITTER)) d.emit_table += h.off_tables;
     for (DShape &d : shapes) if (d.bsdf == BSDF_ROUGHPLASTIC) d.rough_table += h.off_tables;
@@ -571,7 +580,12 @@ std::vector<uint8_t> build_scene_blob(const HostScene &sc) {
     if (!shading.empty()) memcpy(blob.data() + h.off_shading, shading.data(), shading.size() * sizeof(DTriShade));
     if (!isect.empty()) memcpy(blob.data() + h.off_isect, isect.data(), isect.size() * sizeof(DTriIsect));
     if (!tables.empty()) memcpy(blob.data() + h.off_tables, tables.data(), tables.size() * 4);
-    if (!flat.empty()) memcpy(blob.data() + h.off_flat, flat.data(), flat.size() * sizeof(DFlatObject));
+    if (!flat.empty()) {
+        uint8_t *p = blob.data() + h.off_flat;
+        memcpy(p, flat.data(), flat.size() * sizeof(DFlatObject)); p += flat.size() * sizeof(DFlatObject);
+        memcpy(p, &flat_kinds, sizeof flat_kinds); p += sizeof flat_kinds;
+        memcpy(p, flat_z.data(), flat_z.size() * sizeof(DFlatZ));
+    }
     if (!nodes16.empty()) memcpy(blob.data() + h.off_nodes16, nodes16.data(), nodes16.size() * sizeof(DNode16));
     return blob;
 }
