@@ -100,6 +100,13 @@ DTOF_HD void affine_inverse(const float *m, float *inv) {
 
 // Cephes single-precision sincos kernel (what dr::sincos is built on; Dr.Jit's source is
 // not in the reference tree).  Only mul/sub/fma/int ops => bit-identical on host and device.
+// Argument range: defined for |x| * fl(4 / pi) < 2^31, i.e. |x| < 1 686 629 760 (bit patterns below 0x4ec90fdb); beyond it, for the infinities and for NaN the
+// octant's float -> int conversion is undefined in C++ (x86 gives INT_MIN, the GPU saturates) and host, device and oracle need not agree.  What the callers pass:
+// 2 pi u with u in [0, 1] (uniform_sphere, the microfacet azimuth), phi in [-pi / 4, 3 pi / 4] (the concentric disk), theta in [0, pi] and phi in
+// [0, 2 pi (1 + 1 / (w - 1))] (the environment map), t in (-2 pi, 2 pi) (the waveforms, after fmod_pos), the spot light's angles in radians (loader), and
+// pi x and pi x / radius with |x| <= radius + 1 pixel (the Lanczos filter in splat_lane; radius = lobes, 3 by default): a few turns at most, nine orders of
+// magnitude inside the range.  (Accuracy degrades long before the range ends: the three-term Cody-Waite reduction is exact only while j has few bits.)
+// tests/math_sweep.hip compares device and host on every input of the range; the rest is its one exclusion class.
 DTOF_HD void sincos_(float x, float &s_out, float &c_out) {
     float xa = fabsf(x);
     int32_t j = (int32_t) (xa * 1.2732395447351626862f);
@@ -186,6 +193,10 @@ DTOF_HD void fresnel_dielectric(float cos_theta_i, float eta, float &r, float &c
 // Restated from the published single-precision kernels Dr.Jit's math library derives from -- Cephes expf / logf / tanf, the Cephes erff
 // series inside |x| < 1 with Abramowitz & Stegun 7.1.26 outside, M. Giles' single-precision erfinv polynomial -- with explicit fmaf, so
 // that host, device and the oracle produce the same bits.  Needed by the Beckmann distribution (microfacet.h:176-196,240-290,341-403).
+// exp_'s argument range: every float but NaN.  Above 88.72 and below -103.28 (the infinities included) it returns before the float -> int conversion of z, and
+// in between |z| <= 150; a NaN passes both comparisons and reaches (int32_t) NaN, undefined in C++ -- whatever it yields is multiplied into r = NaN and never shows
+// in the result, but it is not a defined execution, and it is the one class tests/math_sweep.hip excludes for exp_ and erf_ (erf_ passes |x| >= 1 on as -(x x)).
+// The callers pass non-positive finite arguments or -inf: -(tan^2 theta) / alpha^2 in ggx_eval, -cot^2 and -slope^2 in mf_sample_visible_11, -(x x) in erf_.
 DTOF_HD float exp_(float x) {
     if (x > 88.72283905206835f) return u2f(0x7f800000u);
     if (x < -103.278929903431851103f) return 0.f;
@@ -227,6 +238,8 @@ DTOF_HD float log_(float x) {
     y = fmaf(-0.5f, z, y);
     return fmaf(0.693359375f, fe, m + y);
 }
+// tan_'s argument range is sincos_'s: |x| * fl(4 / pi) < 2^31, NaN and the infinities excluded (the same octant conversion).  Its one caller passes 2 pi u
+// with u in [0, 1) (the azimuth of an anisotropic microfacet distribution, ggx_sample).
 DTOF_HD float tan_(float xx) {
     const float x = fabsf(xx);
     int32_t j = (int32_t) (x * 1.2732395447351626862f);

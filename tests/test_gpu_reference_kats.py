@@ -1,6 +1,8 @@
 """GPU twin of tests/test_oracle_reference_kats.py: the known answers of the reference's own unit tests
 (tests/golden/reference_kats.json.gz) held against the PRODUCT -- the device functions of the HIP kernels through
 dtof_eval_component, and the TLAS / BLAS traversal + surface interaction through dtof_ray_intersect / dtof_ray_test."""
+import ctypes as C
+
 import numpy as np
 import pytest
 
@@ -127,12 +129,43 @@ def test_report(results, capsys):
 
 
 def test_restated_math_matches_the_oracle_bit_for_bit(mi, orc):
-    """exp / log / tan / erf / erfinv / sin / cos / acos: device == oracle on a dense sweep (the Beckmann lanes depend on it)"""
+    """exp / log / tan / erf / erfinv / sin / cos / acos: device == oracle on a dense sweep (the Beckmann lanes depend on it), and on the special values: +-0,
+    denormals, the ends of each function's range, arguments next to the octant boundaries of the range reduction, huge arguments, +-inf and NaN where the
+    function is defined there (dtof_math.h: sincos_ / tan_ for |x| 4 / pi < 2^31, exp_ / erf_ for everything but NaN).  Two NaNs are equal.
+    tests/test_math_sweep_gpu.py holds the device against the host compilation on all 2^32 inputs; this is the device <-> oracle leg through the C ABI."""
     L = orc.lib()
+    s_, c_ = C.c_float(), C.c_float()
+
+    def orc_sin(x):
+        L.orc_sincos(x, C.byref(s_), C.byref(c_))
+        return s_.value
+
+    def orc_cos(x):
+        L.orc_sincos(x, C.byref(s_), C.byref(c_))
+        return c_.value
+
     sweeps = {0: ("orc_expf", np.linspace(-104, 89, 20001)), 1: ("orc_logf", np.exp(np.linspace(-100, 88, 20001))), 2: ("orc_tanf", np.linspace(-20, 20, 20001)),
-              3: ("orc_erff", np.linspace(-6, 6, 20001)), 4: ("orc_erfinvf", np.linspace(-0.999999, 0.999999, 20001)), 7: ("orc_acos", np.linspace(-1, 1, 20001))}
+              3: ("orc_erff", np.linspace(-6, 6, 20001)), 4: ("orc_erfinvf", np.linspace(-0.999999, 0.999999, 20001)), 7: ("orc_acos", np.linspace(-1, 1, 20001)),
+              5: (orc_sin, np.linspace(-20, 20, 20001)), 6: (orc_cos, np.linspace(-20, 20, 20001))}
+    f32 = lambda bits: np.array(bits, np.uint32).view(np.float32)
+    octants = (np.arange(1, 65, dtype=np.float64) * (np.pi / 4)).astype(np.float32).view(np.uint32)
+    near_octants = f32(np.concatenate([octants + np.uint32(k) for k in (-2 & 0xffffffff, -1 & 0xffffffff, 0, 1, 2)]))
+    finite = np.concatenate([f32([0x00000000, 0x80000000, 0x00000001, 0x80000001, 0x007fffff, 0x807fffff, 0x00800000, 0x80800000, 0x3f800000, 0xbf800000, 0x3f7fffff,
+                                  0xbf7fffff, 0x3f800001, 0xbf800001, 0x3f000000, 0xbf000000, 0x3effffff, 0x3f000001]), near_octants, -near_octants])
+    huge = f32([0x4b800000, 0xcb800000, 0x4e000000, 0x4ec90fda, 0xcec90fda])          # 2^24, 2^29, the last float of sincos_'s range
+    out_of_trig_range = f32([0x4ec90fdb, 0x7f7fffff, 0xff7fffff, 0x7f800000, 0xff800000])
+    nan = f32([0x7fc00000, 0xffc00000, 0x7f800001])
+    special = {0: np.concatenate([finite, huge, out_of_trig_range, f32([0x42b17217, 0x42b17218, 0x42b17219, 0xc2ce8ed0, 0xc2ce8ed1, 0xc2cff1b4, 0xc2cff1b5])]),   # around 88.72 / -103.28
+               1: np.concatenate([finite, huge, out_of_trig_range, nan]), 2: np.concatenate([finite, huge]),
+               3: np.concatenate([finite, huge, out_of_trig_range, f32([0x40400000, 0x40c00000, 0x41200000, 0xc1200000])]),
+               4: np.concatenate([finite, huge, out_of_trig_range, nan]), 7: np.concatenate([finite, huge, out_of_trig_range, nan]),
+               5: np.concatenate([finite, huge]), 6: np.concatenate([finite, huge])}
     for fn, (name, xs) in sweeps.items():
-        xs = xs.astype(np.float32)
+        xs = np.concatenate([xs.astype(np.float32), special[fn]])
         gpu = mi.eval_component("math", xs.reshape(-1, 1), [fn])[:, 0]
-        cpu = np.array([getattr(L, name)(float(x)) for x in xs], np.float32)
-        assert np.array_equal(gpu.view(np.uint32), cpu.view(np.uint32)), name
+        f = getattr(L, name) if isinstance(name, str) else name
+        cpu = np.array([f(float(x)) for x in xs], np.float32)
+        same = (gpu.view(np.uint32) == cpu.view(np.uint32)) | (np.isnan(gpu) & np.isnan(cpu))
+        assert same.all(), (name if isinstance(name, str) else name.__name__, [(hex(a), hex(b), hex(c)) for a, b, c in
+                                                                                zip(xs.view(np.uint32)[~same][:5], gpu.view(np.uint32)[~same][:5], cpu.view(np.uint32)[~same][:5])])
+    assert len(sweeps) == 8 and all(len(v) >= 60 for v in special.values())
