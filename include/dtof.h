@@ -138,6 +138,12 @@ int dtof_camera_rays(dtof_scene *scene, uint32_t n, const float *samples4, float
  * direction[3], its pdf, eta, 1 if the sampled lobe is a delta lobe, weight[3], 1 if it is a null lobe (14 floats).  `shape_index` counts the scene's shapes in
  * file order (the shapes of a shapegroup included). */
 int dtof_bsdf_eval(dtof_scene *scene, uint32_t shape_index, uint32_t n, const float *in11, float *out14);
+/* The same over a general interaction and through a chosen instantiation of that device function.  Per query 29 floats: the 11 above, then dp_du[3], dp_dv[3], n[3],
+ * sh_s[3], sh_t[3], sh_n[3] (what `normalmap` / `bumpmap` build their frames from; wi and wo stay local to sh_s, sh_t, sh_n) -> the same 14 floats.  `spec` names the
+ * instantiation the shade kernels are compiled in: 0 = the diffuse-only kernels, 1 = every BSDF / texture / adapter, 2 = ... and blendbsdf / two-BSDF twosided;
+ * -1 = the one a render of this scene runs.  A `spec` the render path could never run on that shape fails with DTOF_ERR_INVALID and writes nothing: 0 on anything but
+ * an untextured diffuse (plain or twosided), 1 on a blendbsdf or a two-BSDF twosided.  dtof_bsdf_eval is spec = 2 with the flat frame. */
+int dtof_bsdf_eval_ex(dtof_scene *scene, uint32_t shape_index, int spec, uint32_t n, const float *in29, float *out14);
 
 /* ---------------------------------------------------------------- rendering
  * Replaces Integrator::render(Scene*, uint32_t sensor_index, uint32_t seed, uint32_t spp, bool develop,

@@ -130,6 +130,7 @@ def _lib():
     L.dtof_clear_async.argtypes = [vp, vp, C.c_size_t]
     L.dtof_camera_rays.argtypes = [vp, C.c_uint32, vp, vp]
     L.dtof_bsdf_eval.argtypes = [vp, C.c_uint32, C.c_uint32, vp, vp]
+    L.dtof_bsdf_eval_ex.argtypes = [vp, C.c_uint32, C.c_int, C.c_uint32, vp, vp]
     L.dtof_scene_set_stream.argtypes = [vp, vp]
     L.dtof_scene_set_film_layout.argtypes = [vp, C.c_int32, C.c_uint64]
     L.dtof_render_stripes_async.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_int32, C.c_int32, C.c_int32, vp, C.c_int, vp]
@@ -140,6 +141,9 @@ def _lib():
     L.dtof_ray_test.argtypes = [vp, C.c_uint32, vp, vp]
     _LIB = L
     return L
+
+
+FLAT_GEOMETRY = np.array([[1, 0, 0,  0, 1, 0,  0, 0, 1,  1, 0, 0,  0, 1, 0,  0, 0, 1]], np.float32)   # dp_du, dp_dv, n, sh_s, sh_t, sh_n of dtof_bsdf_eval
 
 
 def _check(rc):
@@ -298,11 +302,17 @@ class Scene:
         _check(_lib().dtof_sample_lanes_valid(self._h, seed, spp, lane_begin, n, out.ctypes.data, valid.ctypes.data))
         return {"sample_pos": out[:, 0:2], "time": out[:, 2], "ray_o": out[:, 3:6], "ray_d": out[:, 6:9], "rgb": out[:, 9:12], "valid": valid}
 
-    def bsdf_eval(self, shape_index, queries):
-        """BSDF::eval_pdf_sample of shape `shape_index` over an (n, 11) array of (wi, wo, sample1, sample2, uv) -> (n, 14): value[3], pdf, wo[3], pdf, eta, delta, weight[3], null"""
-        q = np.ascontiguousarray(queries, np.float32).reshape(-1, 11)
+    def bsdf_eval(self, shape_index, queries, spec=-1, geometry=None):
+        """BSDF::eval_pdf_sample of shape `shape_index` over an (n, 11) array of (wi, wo, sample1, sample2, uv) -> (n, 14): value[3], pdf, wo[3], pdf, eta, delta,
+        weight[3], null.  `geometry`: (n, 18) or (18,) dp_du, dp_dv, n, sh_s, sh_t, sh_n (default: the flat frame); queries may also be (n, 29) with the geometry
+        appended.  `spec`: the instantiation of the shade kernels' BSDF function (0, 1, 2; -1 = the one a render of this scene runs)."""
+        q = np.ascontiguousarray(queries, np.float32)
+        q = q.reshape(-1, 29 if geometry is None and q.ndim == 2 and q.shape[1] == 29 else 11)
+        if q.shape[1] == 11:
+            g = FLAT_GEOMETRY if geometry is None else np.asarray(geometry, np.float32).reshape(-1, 18)
+            q = np.ascontiguousarray(np.concatenate([q, np.broadcast_to(g, (len(q), 18))], axis=1))
         out = np.zeros((len(q), 14), np.float32)
-        _check(_lib().dtof_bsdf_eval(self._h, shape_index, len(q), q.ctypes.data, out.ctypes.data))
+        _check(_lib().dtof_bsdf_eval_ex(self._h, shape_index, spec, len(q), q.ctypes.data, out.ctypes.data))
         return out
 
     def camera_rays(self, samples):

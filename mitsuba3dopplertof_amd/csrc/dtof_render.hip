@@ -1293,18 +1293,36 @@ int dtof_eval_component(int component, const float *params, int n_params, const 
     });
 }
 
-int dtof_bsdf_eval(dtof_scene *sc, uint32_t shape_index, uint32_t n, const float *in11, float *out14) {
+int dtof_bsdf_eval_ex(dtof_scene *sc, uint32_t shape_index, int spec, uint32_t n, const float *in29, float *out14) {
     return guarded([&] {
-        if (!sc || (n && (!in11 || !out14))) throw std::runtime_error("null argument");
+        if (!sc || (n && (!in29 || !out14))) throw std::runtime_error("null argument");
         const BlobHeader *bh = (const BlobHeader *) sc->blob.data();
         if (shape_index >= bh->n_shapes) throw std::runtime_error("shape index out of range");
+        if (spec == -1) spec = scene_traits(*sc).has_spec;
+        // the instantiations the render path can run on this shape: a scene's SPEC is at least what each of its shapes needs (scene_traits)
+        const DShape &sh = ((const DShape *) (sc->blob.data() + bh->off_shapes))[shape_index];
+        const bool two_records = sh.flags & (SF_BLEND | SF_TWOSIDED2);
+        const bool plain_diffuse = sh.bsdf == BSDF_DIFFUSE && !two_records && !(sh.flags & (SF_MASK | SF_NORMALMAP | SF_BUMPMAP)) && !(sh.nonlinear >> 1);
+        if (spec < 0 || spec > 2) throw std::runtime_error("dtof_bsdf_eval_ex: spec must be -1, 0, 1 or 2");
+        if (spec == 0 && !plain_diffuse) throw std::runtime_error("dtof_bsdf_eval_ex: the SPEC = 0 kernels run on untextured (twosided) diffuse shapes only");
+        if (spec == 1 && two_records) throw std::runtime_error("dtof_bsdf_eval_ex: a blendbsdf / two-BSDF twosided runs in the SPEC = 2 kernels only");
         ensure_device(sc);
-        DevBuf<float> din, dout; din.ensure((size_t) n * 11); dout.ensure((size_t) n * 14);
-        HIP_CHECK(hipMemcpy(din.p, in11, (size_t) n * 44, hipMemcpyHostToDevice));
-        launch_bsdf_eval(sc->d_blob.p, shape_index, din.p, dout.p, n, nullptr);
+        DevBuf<float> din, dout; din.ensure((size_t) n * 29); dout.ensure((size_t) n * 14);
+        HIP_CHECK(hipMemcpy(din.p, in29, (size_t) n * 29 * 4, hipMemcpyHostToDevice));
+        (spec == 0 ? launch_bsdf_eval_0 : spec == 1 ? launch_bsdf_eval_1 : launch_bsdf_eval_2)(sc->d_blob.p, shape_index, din.p, dout.p, n, nullptr);
         HIP_CHECK(hipGetLastError());
         HIP_CHECK(hipMemcpy(out14, dout.p, (size_t) n * 56, hipMemcpyDeviceToHost));
     });
+}
+int dtof_bsdf_eval(dtof_scene *sc, uint32_t shape_index, uint32_t n, const float *in11, float *out14) {
+    // the flat local frame of the reference's BSDF unit tests, spec = 2
+    std::vector<float> in29;
+    if (in11 && n) {
+        static const float flat[18] = { 1, 0, 0,  0, 1, 0,  0, 0, 1,  1, 0, 0,  0, 1, 0,  0, 0, 1 };   // dp_du, dp_dv, n, sh_s, sh_t, sh_n
+        in29.resize((size_t) n * 29);
+        for (size_t i = 0; i < n; ++i) { memcpy(&in29[i * 29], in11 + i * 11, 44); memcpy(&in29[i * 29 + 11], flat, sizeof flat); }
+    }
+    return dtof_bsdf_eval_ex(sc, shape_index, 2, n, in29.empty() ? nullptr : in29.data(), out14);
 }
 int dtof_camera_rays(dtof_scene *sc, uint32_t n, const float *samples4, float *out7) {
     return guarded([&] {

@@ -283,6 +283,31 @@ DTOF_D void bsdf_eval_pdf_sample(const SceneView &sv, const DShape *sh, Surface 
     out.val = bsdf_val; out.pdf = bsdf_pdf; out.weight = bsdf_weight; out.wo = bs_wo; out.bs_pdf = bs_pdf; out.bs_eta = bs_eta; out.bs_delta = bs_delta; out.bs_null = bs_null;
 }
 
+// BSDF::eval_pdf_sample over arrays (dtof_bsdf_eval_ex): the function above, as the SPEC instantiation the shade kernels of that level call at every path vertex.
+// in, 29 floats per query: wi[3], wo[3] (local frame), sample1, sample2[2], u, v, then the geometry normalmap / bumpmap read: dp_du[3], dp_dv[3], n[3], sh_s[3],
+// sh_t[3], sh_n[3]; out, 14 floats: value * cos[3], pdf, sampled wo[3], sample pdf, eta, delta flag, weight[3], null flag.  Each dtof_shade_*.hip file that holds a
+// SPEC's shade kernels instantiates its launcher (launch_bsdf_eval_spec<SPEC>), so this compiles next to the code it stands for.
+template <int SPEC>
+__global__ void k_bsdf_eval(const uint8_t *scene, uint32_t shape_index, const float *in, float *out, uint32_t n) {
+    uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const SceneView sv = make_view(scene);
+    const float *a = in + (size_t) i * 29;
+    Surface si;
+    si.p = mk(0, 0, 0); si.wi = mk(a[0], a[1], a[2]); si.u = a[9]; si.v = a[10]; si.shape = &sv.shapes[shape_index];
+    si.dp_du = mk(a[11], a[12], a[13]); si.dp_dv = mk(a[14], a[15], a[16]); si.n = mk(a[17], a[18], a[19]);
+    si.sh_s = mk(a[20], a[21], a[22]); si.sh_t = mk(a[23], a[24], a[25]); si.sh_n = mk(a[26], a[27], a[28]);
+    BsdfOut bo;
+    bsdf_eval_pdf_sample<SPEC>(sv, si.shape, si, mk(a[3], a[4], a[5]), true, a[6], a[7], a[8], bo);
+    float *w = out + (size_t) i * 14;
+    w[0] = bo.val.x; w[1] = bo.val.y; w[2] = bo.val.z; w[3] = bo.pdf; w[4] = bo.wo.x; w[5] = bo.wo.y; w[6] = bo.wo.z; w[7] = bo.bs_pdf; w[8] = bo.bs_eta;
+    w[9] = bo.bs_delta ? 1.f : 0.f; w[10] = bo.weight.x; w[11] = bo.weight.y; w[12] = bo.weight.z; w[13] = bo.bs_null ? 1.f : 0.f;
+}
+template <int SPEC>
+void launch_bsdf_eval_spec(const uint8_t *scene, uint32_t shape_index, const float *in, float *out, uint32_t n, hipStream_t s) {
+    if (n) hipLaunchKernelGGL(k_bsdf_eval<SPEC>, dim3(nblk(n)), dim3(kBlock), 0, s, scene, shape_index, in, out, n);
+}
+
 // FUSED = false: the "split" pipeline -- shadow rays go to the shadow queue (k_shadow commits them) and the
 //                 continuation ray is traced by the next k_trace launch.
 // FUSED = true : one kernel per bounce -- the occlusion query and the closest-hit query of the continuation ray

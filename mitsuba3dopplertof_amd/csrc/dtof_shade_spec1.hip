@@ -7,4 +7,9 @@ void launch_shade_spec1(bool k4, const ShadeLaunch &L) {
     if (k4) launch_shade_variant<true, kMaxOffsets, true, 1>(L); else launch_shade_variant<true, 1, true, 1>(L);
 }
 
+// dtof_bsdf_eval_ex, spec = 1 (k_bsdf_eval in dtof_shade.h)
+void launch_bsdf_eval_1(const uint8_t *scene, uint32_t shape_index, const float *in, float *out, uint32_t n, hipStream_t s) {
+    launch_bsdf_eval_spec<1>(scene, shape_index, in, out, n, s);
+}
+
 }  // namespace dtof

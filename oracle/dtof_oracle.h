@@ -334,6 +334,7 @@ void     orc_kat_warp(int fn, const float *in, float *out);
 void     orc_kat_frame(const float *n, float *out6);
 int      orc_kat_ray_intersect(const orc_scene *sc, const float *o, const float *d, float time, float maxt, float *out25, int32_t *ids);
 void     orc_kat_bsdf(const orc_shape *sh, const float *wi, const float *wo, const float *s3, float *out13);
+void     orc_kat_bsdf_n(const orc_shape *sh, uint32_t n, const float *in29, float *out17);   /* ... over arrays, general uv and frame, with the lobe-choice thresholds */
 void     orc_texture_eval(const orc_texture *tex, float u, float v, float *out3);
 float    orc_texture_eval_1(const orc_texture *tex, float u, float v);   /* Texture::eval_1: a 1-channel texel, the luminance of an RGB texel, the mean of a checkerboard colour */
 void     orc_kat_sphere_sample_direction(const orc_shape *sh, const float *ref, float s_x, float s_y, float *out11);

@@ -198,6 +198,7 @@ def lib():
         L.orc_kat_ray_intersect.restype = C.c_int
         L.orc_kat_ray_intersect.argtypes = [C.POINTER(OrcScene), C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_void_p, C.c_void_p]
         L.orc_kat_bsdf.argtypes = [C.POINTER(OrcShape), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.orc_kat_bsdf_n.argtypes = [C.POINTER(OrcShape), C.c_uint32, C.c_void_p, C.c_void_p]
         L.orc_kat_sphere_sample_direction.argtypes = [C.POINTER(OrcShape), C.c_void_p, C.c_float, C.c_float, C.c_void_p]
         L.orc_kat_shape_area.restype = C.c_float
         L.orc_kat_shape_area.argtypes = [C.POINTER(OrcShape)]

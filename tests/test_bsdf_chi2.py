@@ -4,7 +4,8 @@ test_twosided.py and test_blendbsdf.py (their chi2 cases).  The reference's harn
 with a BSDFAdapter) histograms the directions BSDF::sample returns over (cos theta, phi) cells and compares the counts with BSDF::pdf integrated over each
 cell; cells with few expected samples are pooled and the p-value of the chi^2 statistic must exceed the significance level.  Here the same is done with
 numpy / scipy on `orc_kat_bsdf` (eval / pdf / sample of one shape's BSDF chain: mask -> blend -> frame -> nested BSDF).  The GPU kernels are held to the
-oracle bit for bit (test_gpu_parity.py), so this pins both."""
+oracle bit for bit -- on the rendered lanes by test_gpu_parity.py, and on dense and boundary inputs of this very function (grazing and back-facing wi, sample1 on the
+lobe probabilities, uv outside [0, 1], skewed frames; every SPEC instantiation) by test_bsdf_sweep_gpu.py -- so this pins both."""
 import ctypes as C
 
 import numpy as np
