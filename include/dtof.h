@@ -188,7 +188,8 @@ int dtof_integrator_render(const dtof_integrator *integrator, const dtof_sampler
  * film (hdrfilm.cpp:235-279 channel layout) into `d_film_rgbw`, a DEVICE buffer of
  * crop_height*crop_width*4 float32 the caller zeroed (rows row_begin-r..row_end+r receive splats,
  * r = filter footprint).  n_offsets > 1 evaluates several `hetero_offset` values (in units of 2*pi
- * like the plugin property) in ONE traversal; film k lives at d_film_rgbw + k*crop_h*crop_w*4.
+ * like the plugin property) in ONE traversal; film k lives at d_film_rgbw + k*crop_h*crop_w*4
+ * (dtof_render_rows_variants: several hetero_frequency values as well).
  * offsets == NULL / n_offsets == 0 uses the integrator's own phase offset. */
 int dtof_render_rows(dtof_scene *scene, uint32_t seed, uint32_t spp, int32_t row_begin, int32_t row_end,
                      const float *offsets, int n_offsets, float *d_film_rgbw, dtof_render_stats *stats);
@@ -240,6 +241,32 @@ int dtof_develop_rgba(const float *d_film_rgbw, const float *d_alpha_film, float
 int dtof_render_offsets(dtof_scene *scene, uint32_t seed, uint32_t spp, const float *offsets, int n_offsets,
                         float *out_rgb, dtof_render_stats *stats);
 
+/* ---------------------------------------------------------------- modulation variants
+ * A modulation variant is a pair (hetero_frequency, hetero_offset), both in the units of the plugin properties of the same names
+ * (src/integrators/dopplertofpath.cpp:26-32).  Only eval_modulation_weight (:60-77) reads either of them -- sampler, time draw, camera ray, traversal, BSDF
+ * sampling, MIS and roulette do not -- so up to four variants are evaluated in ONE traversal, one film each: film k is, bit for bit per lane, the render of a scene
+ * whose integrator carries hetero_frequency = variants[k].hetero_frequency and hetero_offset = variants[k].hetero_offset (the constructor's roundings:
+ * w_d = (float) (2 pi / time * f), phase = (float) ((double) (o * 2) * pi)).  Waveform, low_frequency_component_only, w_g, g_0, g_1 and time stay the
+ * integrator's.  A homodyne / heterodyne pair of doppler_tutorials/src/utils/image_utils.py:140-199 -- (0, o) and (1, o) -- thus shares its paths.
+ * In every entry point below: variants == NULL or n_variants == 0 means the integrator's own pair; n_variants > 4, or any variants with an integrator other than
+ * `dopplertofpath`, fails with DTOF_ERR_INVALID before anything is launched.  The dtof_*_offsets / `offsets` forms are variants at the integrator's own frequency. */
+typedef struct { float hetero_frequency, hetero_offset; } dtof_modulation;
+/* dtof_render_offsets with variants: out_rgb holds n_variants developed images (replaces n_variants calls of Integrator::render, integrator.h:74-79, on n_variants
+ * integrators, program_runner.py:82-153). */
+int dtof_render_variants(dtof_scene *scene, uint32_t seed, uint32_t spp, const dtof_modulation *variants, int n_variants,
+                         float *out_rgb, dtof_render_stats *stats);
+/* dtof_render_rows / _rows_async / _stripes / _stripes_async with variants (no reference counterpart: the reference is single-device).  The film layout
+ * is the one of the offsets forms: plane k of `d_film_rgbw` is variant k, the alpha film of an rgba scene is plane n_variants, and dtof_scene_set_film_layout is
+ * checked in the same way (a call that needs more planes than declared is refused and writes nothing). */
+int dtof_render_rows_variants(dtof_scene *scene, uint32_t seed, uint32_t spp, int32_t row_begin, int32_t row_end,
+                              const dtof_modulation *variants, int n_variants, float *d_film_rgbw, dtof_render_stats *stats);
+int dtof_render_rows_variants_async(dtof_scene *scene, uint32_t seed, uint32_t spp, int32_t row_begin, int32_t row_end,
+                                    const dtof_modulation *variants, int n_variants, float *d_film_rgbw);
+int dtof_render_stripes_variants(dtof_scene *scene, uint32_t seed, uint32_t spp, int32_t first_row, int32_t stripe_rows, int32_t stripe_period,
+                                 const dtof_modulation *variants, int n_variants, float *d_film_rgbw, dtof_render_stats *stats);
+int dtof_render_stripes_variants_async(dtof_scene *scene, uint32_t seed, uint32_t spp, int32_t first_row, int32_t stripe_rows, int32_t stripe_period,
+                                       const dtof_modulation *variants, int n_variants, float *d_film_rgbw);
+
 /* Integrator::cancel / should_stop (include/mitsuba/render/integrator.h:96-109). */
 void dtof_cancel(dtof_scene *scene);
 
@@ -252,6 +279,12 @@ int dtof_sample_lanes(dtof_scene *scene, uint32_t seed, uint32_t spp, uint64_t l
 /* The same, plus the `valid` half of the (Spectrum, Mask) pair DopplerToFPathIntegrator::sample returns (src/integrators/dopplertofpath.cpp:279-282:
  * valid_ray -- the path met a vertex whose sampled lobe was not BSDFFlags::Null, or the environment is visible): 1 / 0 per lane. */
 int dtof_sample_lanes_valid(dtof_scene *scene, uint32_t seed, uint32_t spp, uint64_t lane_begin, uint64_t n, float *out_lanes12, uint32_t *out_valid);
+
+/* The same through the BATCHED kernels: the lanes are evaluated once for all variants, exactly as dtof_render_variants would, and besides the 12 floats per lane
+ * (whose rgb is variant 0's) and the valid flag, out_rgb[n_variants][n][3] receives the result of every lane in every film (max(n_variants, 1) planes) -- per
+ * variant the Spectrum that DopplerToFPathIntegrator::sample (src/integrators/dopplertofpath.cpp:79-283) returns with that variant's properties.  out_valid may be NULL. */
+int dtof_sample_lanes_variants(dtof_scene *scene, uint32_t seed, uint32_t spp, const dtof_modulation *variants, int n_variants,
+                               uint64_t lane_begin, uint64_t n, float *out_lanes12, uint32_t *out_valid, float *out_rgb);
 
 /* ---------------------------------------------------------------- sampler surface
  * Array-of-lanes form of the Sampler interface (include/mitsuba/render/sampler.h:99-168) for the

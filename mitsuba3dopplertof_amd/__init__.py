@@ -139,6 +139,13 @@ def _lib():
     L.dtof_ray_intersect.argtypes = [vp, C.c_uint32, vp, vp, vp]
     L.dtof_ray_intersect_uv.argtypes = [vp, C.c_uint32, vp, vp, vp, vp]
     L.dtof_ray_test.argtypes = [vp, C.c_uint32, vp, vp]
+    rows, stripes = [vp, C.c_uint32, C.c_uint32, C.c_int32, C.c_int32, vp, C.c_int, vp], [vp, C.c_uint32, C.c_uint32, C.c_int32, C.c_int32, C.c_int32, vp, C.c_int, vp]
+    for name, args in (("dtof_render_variants", [vp, C.c_uint32, C.c_uint32, vp, C.c_int, vp, C.POINTER(_Stats)]),
+                       ("dtof_render_rows_variants", rows + [C.POINTER(_Stats)]), ("dtof_render_rows_variants_async", rows),
+                       ("dtof_render_stripes_variants", stripes + [C.POINTER(_Stats)]), ("dtof_render_stripes_variants_async", stripes),
+                       ("dtof_sample_lanes_variants", [vp, C.c_uint32, C.c_uint32, vp, C.c_int, C.c_uint64, C.c_uint64, vp, vp, vp])):
+        if hasattr(L, name):   # a DTOF_LIB build from before the variants (A/B timing against an older commit) loads; calling what it lacks still raises
+            getattr(L, name).argtypes = args
     _LIB = L
     return L
 
@@ -177,6 +184,34 @@ def _plugin_args(d):
             raise DtofError('unsupported value type for property "%s"' % k)
     n = len(names)
     return (plugin.encode(), (C.c_char_p * max(n, 1))(*names), "".join(types).encode(), (C.c_char_p * max(n, 1))(*values), n)
+
+
+class _Modulation(C.Structure):   # dtof_modulation
+    _fields_ = [("hetero_frequency", C.c_float), ("hetero_offset", C.c_float)]
+
+
+MAX_VARIANTS = 4   # modulation variants (films) one traversal evaluates (kMaxOffsets)
+
+
+def _variant_array(variants):
+    """[(hetero_frequency, hetero_offset), ...] -> (n, 2) float32 array laid out like dtof_modulation[n]"""
+    v = np.ascontiguousarray(variants, dtype=np.float32)
+    if v.ndim != 2 or v.shape[1] != 2:
+        raise DtofError("variants must be a sequence of (hetero_frequency, hetero_offset) pairs")
+    return v
+
+
+def _batch_args(offsets, variants):
+    """The (array to keep alive, pointer, count) of a call's `offsets` or `variants` argument, and whether it is the variants form"""
+    if offsets is not None and variants is not None:
+        raise DtofError("pass either offsets or variants, not both")
+    if variants is not None:
+        v = _variant_array(variants)
+        return v, v.ctypes.data, len(v), True
+    if offsets is not None:
+        o = np.ascontiguousarray(offsets, dtype=np.float32)
+        return o, o.ctypes.data, len(o), False
+    return None, None, 0, False
 
 
 class Scene:
@@ -218,11 +253,26 @@ class Scene:
     def set_sampler(self, props):
         _check(_lib().dtof_scene_set_sampler(self._h, *_plugin_args(props)))
 
-    def render(self, seed=0, spp=0, offsets=None, sensor=0):
-        """Developed image (H, W, 3) float32 -- (H, W, 4) for an rgba film; with `offsets` (list of hetero_offset values) -> (K, H, W, 3 | 4)."""
+    def render(self, seed=0, spp=0, offsets=None, sensor=0, variants=None):
+        """Developed image (H, W, 3) float32 -- (H, W, 4) for an rgba film; with `offsets` (list of hetero_offset values) -> (K, H, W, 3 | 4).
+        `variants`: list of (hetero_frequency, hetero_offset) pairs -> (K, H, W, 3 | 4), image k that of an integrator carrying pair k; every four of them
+        share one traversal (dtof_render_variants), last_stats then sums the traversals."""
+        if offsets is not None and variants is not None:
+            raise DtofError("pass either offsets or variants, not both")
         w, h = self.size
         st = _Stats()
         ch = 4 if self.info()["has_alpha"] else 3
+        if variants is not None:
+            var = _variant_array(variants)
+            out = np.zeros((len(var), h, w, ch), np.float32)
+            total = None
+            for g in range(0, len(var), MAX_VARIANTS):
+                group, part = np.ascontiguousarray(var[g:g + MAX_VARIANTS]), out[g:g + MAX_VARIANTS]
+                _check(_lib().dtof_render_variants(self._h, seed, spp, group.ctypes.data, len(group), part.ctypes.data, C.byref(st)))
+                d = st.as_dict()
+                total = d if total is None else {k: total[k] + d[k] for k in d}
+            self.last_stats = total
+            return out
         if offsets is None:
             out = np.zeros((h, w, ch), np.float32)
             _check(_lib().dtof_render(self._h, sensor, seed, spp, out.ctypes.data, C.byref(st)))
@@ -250,21 +300,21 @@ class Scene:
         """RGBW planes the device-film calls write for `n_offsets` batched offsets: one more for the alpha film of an rgba scene"""
         return max(int(n_offsets), 1) + (1 if self.info()["has_alpha"] else 0)
 
-    def render_rows(self, d_film_ptr, seed, spp, row_begin, row_end, offsets=None):
-        """Accumulate the undeveloped RGBW film of rows [row_begin,row_end) into a DEVICE buffer (int pointer) of film_planes() planes (set_film_layout for rgba scenes)."""
+    def render_rows(self, d_film_ptr, seed, spp, row_begin, row_end, offsets=None, variants=None):
+        """Accumulate the undeveloped RGBW film of rows [row_begin,row_end) into a DEVICE buffer (int pointer) of film_planes() planes (set_film_layout for rgba scenes).
+        `variants`: up to four (hetero_frequency, hetero_offset) pairs instead of `offsets`, plane k = pair k (dtof_render_rows_variants)."""
         st = _Stats()
-        if offsets is None:
-            _check(_lib().dtof_render_rows(self._h, seed, spp, row_begin, row_end, None, 0, d_film_ptr, C.byref(st)))
-        else:
-            off = np.ascontiguousarray(offsets, dtype=np.float32)
-            _check(_lib().dtof_render_rows(self._h, seed, spp, row_begin, row_end, off.ctypes.data, len(off), d_film_ptr, C.byref(st)))
+        keep, ptr, n, is_var = _batch_args(offsets, variants)
+        fn = _lib().dtof_render_rows_variants if is_var else _lib().dtof_render_rows
+        _check(fn(self._h, seed, spp, row_begin, row_end, ptr, n, d_film_ptr, C.byref(st)))
         self.last_stats = st.as_dict()
         return self.last_stats
 
-    def render_rows_async(self, d_film_ptr, seed, spp, row_begin, row_end, offsets=None):
-        """enqueue one frame on the scene's stream without waiting for it (dtof_render_rows_async); collect() waits and returns the timings"""
-        offs = np.ascontiguousarray(offsets, np.float32) if offsets is not None else None
-        _check(_lib().dtof_render_rows_async(self._h, seed, spp, row_begin, row_end, offs.ctypes.data if offs is not None else None, len(offs) if offs is not None else 0, d_film_ptr))
+    def render_rows_async(self, d_film_ptr, seed, spp, row_begin, row_end, offsets=None, variants=None):
+        """enqueue one frame on the scene's stream without waiting for it (dtof_render_rows_async / _variants_async); collect() waits and returns the timings"""
+        keep, ptr, n, is_var = _batch_args(offsets, variants)
+        fn = _lib().dtof_render_rows_variants_async if is_var else _lib().dtof_render_rows_async
+        _check(fn(self._h, seed, spp, row_begin, row_end, ptr, n, d_film_ptr))
 
     def clear_async(self, d_ptr, nbytes):
         _check(_lib().dtof_clear_async(self._h, d_ptr, nbytes))
@@ -273,10 +323,10 @@ class Scene:
         """enqueue on the caller's HIP stream (e.g. torch.cuda.current_stream().cuda_stream); 0 / None: back to the scene's own (dtof_scene_set_stream)"""
         _check(_lib().dtof_scene_set_stream(self._h, C.c_void_p(stream_ptr or None)))
 
-    def render_stripes_async(self, d_film_ptr, seed, spp, first_row, stripe_rows, stripe_period, offsets=None):
-        off = None if offsets is None else np.ascontiguousarray(offsets, dtype=np.float32)
-        _check(_lib().dtof_render_stripes_async(self._h, seed, spp, first_row, stripe_rows, stripe_period,
-                                                None if off is None else off.ctypes.data, 0 if off is None else len(off), d_film_ptr))
+    def render_stripes_async(self, d_film_ptr, seed, spp, first_row, stripe_rows, stripe_period, offsets=None, variants=None):
+        keep, ptr, n, is_var = _batch_args(offsets, variants)
+        fn = _lib().dtof_render_stripes_variants_async if is_var else _lib().dtof_render_stripes_async
+        _check(fn(self._h, seed, spp, first_row, stripe_rows, stripe_period, ptr, n, d_film_ptr))
 
     def develop_async(self, d_film_ptr, d_rgb_ptr, n_pixels):
         _check(_lib().dtof_develop_async(self._h, d_film_ptr, d_rgb_ptr, n_pixels))
@@ -287,12 +337,12 @@ class Scene:
         _check(_lib().dtof_async_collect(self._h, C.byref(st), ms.ctypes.data, max_frames, C.byref(n)))
         return st.as_dict(), ms[:min(n.value, max_frames)].copy()
 
-    def render_stripes(self, d_film_ptr, seed, spp, first_row, stripe_rows, stripe_period, offsets=None):
+    def render_stripes(self, d_film_ptr, seed, spp, first_row, stripe_rows, stripe_period, offsets=None, variants=None):
         """Accumulate the rows of the stripes [first_row + k * stripe_period, ... + stripe_rows) (interleaved shard of one rank)."""
         st = _Stats()
-        off = None if offsets is None else np.ascontiguousarray(offsets, dtype=np.float32)
-        _check(_lib().dtof_render_stripes(self._h, seed, spp, first_row, stripe_rows, stripe_period,
-                                          None if off is None else off.ctypes.data, 0 if off is None else len(off), d_film_ptr, C.byref(st)))
+        keep, ptr, n, is_var = _batch_args(offsets, variants)
+        fn = _lib().dtof_render_stripes_variants if is_var else _lib().dtof_render_stripes
+        _check(fn(self._h, seed, spp, first_row, stripe_rows, stripe_period, ptr, n, d_film_ptr, C.byref(st)))
         self.last_stats = st.as_dict()
         return self.last_stats
 
@@ -301,6 +351,16 @@ class Scene:
         valid = np.zeros(n, np.uint32)
         _check(_lib().dtof_sample_lanes_valid(self._h, seed, spp, lane_begin, n, out.ctypes.data, valid.ctypes.data))
         return {"sample_pos": out[:, 0:2], "time": out[:, 2], "ray_o": out[:, 3:6], "ray_d": out[:, 6:9], "rgb": out[:, 9:12], "valid": valid}
+
+    def sample_lanes_variants(self, seed, spp, lane_begin, n, variants=None):
+        """sample_lanes through the batched kernels (dtof_sample_lanes_variants): the lanes are evaluated once for up to four (hetero_frequency, hetero_offset)
+        pairs; `rgb` is (K, n, 3), plane k the lanes' results with pair k, everything else is shared by the variants.  None: the integrator's own pair (K = 1)."""
+        var = None if variants is None else _variant_array(variants)
+        k = 1 if var is None or len(var) == 0 else len(var)
+        out, valid, rgb = np.zeros((n, 12), np.float32), np.zeros(n, np.uint32), np.zeros((k, n, 3), np.float32)
+        _check(_lib().dtof_sample_lanes_variants(self._h, seed, spp, None if var is None else var.ctypes.data, 0 if var is None else len(var),
+                                                 lane_begin, n, out.ctypes.data, valid.ctypes.data, rgb.ctypes.data))
+        return {"sample_pos": out[:, 0:2], "time": out[:, 2], "ray_o": out[:, 3:6], "ray_d": out[:, 6:9], "rgb": rgb, "valid": valid}
 
     def bsdf_eval(self, shape_index, queries, spec=-1, geometry=None):
         """BSDF::eval_pdf_sample of shape `shape_index` over an (n, 11) array of (wi, wo, sample1, sample2, uv) -> (n, 14): value[3], pdf, wo[3], pdf, eta, delta,
@@ -388,10 +448,12 @@ class Integrator:
             _LIB.dtof_integrator_destroy(self._h)
             self._h = C.c_void_p()
 
-    def render(self, scene, seed=0, spp=0, sensor=0, offsets=None):
-        if offsets is not None:
+    def render(self, scene, seed=0, spp=0, sensor=0, offsets=None, variants=None):
+        if offsets is not None and variants is not None:
+            raise DtofError("pass either offsets or variants, not both")
+        if offsets is not None or variants is not None:
             scene.set_integrator(self.props)
-            return scene.render(seed=seed, spp=spp, sensor=sensor, offsets=offsets)
+            return scene.render(seed=seed, spp=spp, sensor=sensor, offsets=offsets, variants=variants)
         w, h = scene.size
         st, out = _Stats(), np.zeros((h, w, 4 if scene.info()["has_alpha"] else 3), np.float32)
         _check(_lib().dtof_integrator_render(self._h, None, scene._h, sensor, seed, spp, out.ctypes.data, C.byref(st)))

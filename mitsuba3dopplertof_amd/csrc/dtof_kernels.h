@@ -9,7 +9,7 @@ namespace dtof {
 
 constexpr uint32_t kChunkBlocks = 8; // 64-lane chunks of a 512-lane queue segment (RenderParams::chunk_blocks)
 constexpr uint32_t kMaxInline = 4;  // iterations of the bounce loop the fused first-bounce kernel may run itself (RenderParams::inline_iters)
-constexpr int kMaxOffsets = 4;      // modulation offsets evaluated per traversal (K)
+constexpr int kMaxOffsets = 4;      // modulation variants (hetero_frequency, hetero_offset) evaluated per traversal (K), one film each
 
 // Everything a kernel needs besides the scene blob and the queues; passed by value.
 struct RenderParams {
@@ -32,8 +32,8 @@ struct RenderParams {
     int32_t time_sampling; float antithetic_shift; int32_t stratify;
     uint32_t n_stratum; float inv_n_stratum, inv_tcn;
     // ---- integrator (src/integrators/dopplertofpath.cpp:19-77)
-    float T, w_d, w_g, phi_coef, amp, g_1, g_0;
-    float phase[kMaxOffsets]; int32_t n_offsets;
+    float T, w_g, phi_coef, amp, g_1, g_0;
+    float w_d[kMaxOffsets], phase[kMaxOffsets]; int32_t n_offsets;   // per film: the heterodyne frequency and the phase offset (only eval_modulation_weight reads them); n_offsets = K
     int32_t wave_type, low_pass;
     uint32_t path_correlation_depth, max_depth, rr_depth;
     int32_t has_area;                             // scene has area emitters: emitter-hit term + prev_si / prev_bsdf_pdf state

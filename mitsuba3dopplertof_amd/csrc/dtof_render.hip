@@ -200,7 +200,10 @@ void set_filter(RenderParams &rp, int32_t filter, float radius, float stddev, fl
     }
 }
 // spp = samples per wavefront (per pass); sample_count = Sampler::sample_count() of the whole render (0: the same)
-RenderParams make_params(const dtof_scene *sc, uint32_t seed, uint32_t spp, const float *offsets, int n_offsets, uint32_t sample_count = 0) {
+// offsets / n_offsets: batched hetero_offset values at the integrator's own frequency; variants / n_variants: batched (hetero_frequency, hetero_offset) pairs.
+// At most one of the two is given (n > 0); neither: the integrator's own pair.
+RenderParams make_params(const dtof_scene *sc, uint32_t seed, uint32_t spp, const float *offsets, int n_offsets, uint32_t sample_count = 0,
+                         const dtof_modulation *variants = nullptr, int n_variants = 0) {
     const HostSensor &se = sc->host.sensor; const PluginParams &pp = sc->pp;
     RenderParams rp; memset(&rp, 0, sizeof rp);
     sample_to_camera(se, rp.s2c);
@@ -233,21 +236,27 @@ RenderParams make_params(const dtof_scene *sc, uint32_t seed, uint32_t spp, cons
     // (they multiply JIT float32 arrays), dopplertofpath.cpp:62-69
     rp.T = pp.time;
     rp.w_g = (float) (2 * M_PI * (double) pp.w_g_mhz * 1e6);
-    rp.w_d = (float) (2 * M_PI / (double) pp.time * (double) pp.hetero_frequency);
+    const auto w_d_of = [&](float hetero_frequency) { return (float) (2 * M_PI / (double) pp.time * (double) hetero_frequency); };
+    const auto phase_of = [](float hetero_offset) { return (float) ((double) (hetero_offset * 2) * M_PI); };   // dopplertofpath.cpp:30-32
+    for (int k = 0; k < kMaxOffsets; ++k) rp.w_d[k] = w_d_of(pp.hetero_frequency);
     rp.phi_coef = (float) ((2 * M_PI * (double) pp.w_g_mhz) / 300);
     rp.amp = (float) (0.5 * (double) pp.g_1);
     rp.g_1 = pp.g_1; rp.g_0 = pp.g_0;
     rp.wave_type = pp.wave_type; rp.low_pass = pp.low_frequency_component_only;
-    if (n_offsets <= 0) { rp.n_offsets = 1; rp.phase[0] = pp.phase_offset; }
+    if (n_variants > 0) {   // film k: the render of an integrator with hetero_frequency = f_k, hetero_offset = o_k (constructor roundings, dopplertofpath.cpp:26-32)
+        if (n_variants > kMaxOffsets) throw std::runtime_error("at most 4 modulation variants can be batched per traversal");
+        rp.n_offsets = n_variants;
+        for (int k = 0; k < n_variants; ++k) { rp.w_d[k] = w_d_of(variants[k].hetero_frequency); rp.phase[k] = phase_of(variants[k].hetero_offset); }
+    } else if (n_offsets <= 0) { rp.n_offsets = 1; rp.phase[0] = pp.phase_offset; }
     else {
         if (n_offsets > kMaxOffsets) throw std::runtime_error("at most 4 modulation offsets can be batched per traversal");
         rp.n_offsets = n_offsets;
-        for (int k = 0; k < n_offsets; ++k) rp.phase[k] = (float) ((double) (offsets[k] * 2) * M_PI);   // dopplertofpath.cpp:30-32
+        for (int k = 0; k < n_offsets; ++k) rp.phase[k] = phase_of(offsets[k]);
     }
     rp.path_correlation_depth = pp.path_correlation_depth; rp.max_depth = pp.max_depth; rp.rr_depth = pp.rr_depth;
     rp.integrator = pp.integrator;
     rp.sampler_kind = pp.sampler_kind; rp.jitter = pp.jitter; rp.inv_spp = 1.0f / (float) sample_count;   // dr::rcp(ScalarFloat(m_sample_count))
-    if (pp.integrator != INTEGRATOR_DOPPLER && n_offsets > 0) throw std::runtime_error("modulation offsets only apply to the dopplertofpath integrator");
+    if (pp.integrator != INTEGRATOR_DOPPLER && (n_offsets > 0 || n_variants > 0)) throw std::runtime_error("modulation offsets only apply to the dopplertofpath integrator");
     return rp;
 }
 
@@ -329,7 +338,10 @@ struct RenderRequest {
     uint32_t seed = 0, spp = 0;                   // spp 0: the sampler's sample count
     int32_t row_begin = 0, row_end = 0;           // film rows [row_begin, row_end)
     bool stripes = false; int32_t stripe_rows = 0, stripe_period = 0;   // stripes: only the rows [row_begin + k * stripe_period, ... + stripe_rows) (interleaved shards)
-    const float *offsets = nullptr; int n_offsets = 0;
+    const float *offsets = nullptr; int n_offsets = 0;                // batched hetero_offset values, or
+    const dtof_modulation *variants = nullptr; int n_variants = 0;   // ... batched (hetero_frequency, hetero_offset) pairs (at most one of the two)
+    int films() const { return n_variants > 0 ? n_variants : n_offsets > 0 ? n_offsets : 1; }   // colour films the call writes
+    float4 *lane_planes = nullptr;                // lane dumps: [films()][dump_n] results of every film (q.res), besides film 0's in lane_dump
     float *film = nullptr; uint64_t film_stride = 0;   // K films (and the alpha film behind them) film_stride floats apart
     dtof_render_stats *stats = nullptr;
     LaneDebug *lane_dump = nullptr; uint64_t dump_begin = 0, dump_n = 0;   // lane_dump != nullptr: evaluate only lanes [dump_begin, dump_begin + dump_n) and copy their records out
@@ -442,7 +454,7 @@ void plan_lanes(FramePlan &p, const dtof_scene *sc, const RenderRequest &rq) {
         throw std::runtime_error("sample count must be at least time_correlate_number when per-interval stratification is on");
     if (sc->pp.integrator == 0 && sc->pp.sampler_kind == SAMPLER_CORRELATED && sc->pp.time_sampling == TIME_ANTITHETIC_MIRROR && sc->pp.time_correlate_number != 2)
         throw std::runtime_error("antithetic_mirror time sampling needs time_correlate_number == 2");   // Assert(m_time_correlate_number == 2), correlated.cpp:142
-    p.rp = make_params(sc, rq.seed, spp, rq.offsets, rq.n_offsets, sample_count);
+    p.rp = make_params(sc, rq.seed, spp, rq.offsets, rq.n_offsets, sample_count, rq.variants, rq.n_variants);
     p.rp.n_passes = p.n_passes;
     // lane dumps address (pass, lane) as pass * wavefront + lane and must stay inside one pass
     uint64_t dump_begin = rq.dump_begin;
@@ -665,6 +677,9 @@ void render_rows(dtof_scene *sc, const RenderRequest &rq) {
         if (dump_now) {
             launch_lane_dump(rp, q, sc->ws.dbg.p, s);
             HIP_CHECK(hipMemcpyAsync(rq.lane_dump + (b0 - p.first), sc->ws.dbg.p, (size_t) rp.n_lanes * sizeof(LaneDebug), hipMemcpyDeviceToHost, s));
+            if (rq.lane_planes)   // every film's record of the batch's lanes, as the splat kernels would read them
+                for (int k = 0; k < rp.n_offsets; ++k)
+                    HIP_CHECK(hipMemcpyAsync(rq.lane_planes + (size_t) k * rq.dump_n + (b0 - p.first), q.res + (size_t) k * q.capacity, (size_t) rp.n_lanes * sizeof(float4), hipMemcpyDeviceToHost, s));
             HIP_CHECK(hipStreamSynchronize(s));
         } else if (!rq.lane_dump && !fused_splat_done) {
             t = tm.begin(kStageSplat, s); launch_splat(rp, q, rq.film, rq.film_stride, p.launch, s);
@@ -731,11 +746,39 @@ void render_device_film(dtof_scene *sc, RenderRequest rq) {
     }
     sc->stop = false;
     const std::pair<int32_t, int32_t> rows = rq.stripes ? stripe_span(sc, rq.row_begin, rq.stripe_rows, rq.stripe_period) : std::make_pair(rq.row_begin, rq.row_end);
-    rq.film_stride = caller_film_stride(sc, rq.n_offsets, rows.first, rows.second);
+    rq.film_stride = caller_film_stride(sc, rq.films(), rows.first, rows.second);
     dtof_render_stats local;
     if (rq.deferred) rq.stats = &local;
     try { render_rows(sc, rq); }
     catch (...) { if (rq.deferred && sc->deferred.empty()) sc->events_used = 0; throw; }
+}
+
+// The variants arguments of the C ABI as a request carries them: NULL / 0 = the integrator's own pair; the count is checked here, before anything is enqueued
+void set_variants(RenderRequest &rq, const dtof_modulation *variants, int n_variants) {
+    if (!variants || n_variants <= 0) return;
+    if (n_variants > kMaxOffsets) throw std::runtime_error("at most 4 modulation variants can be batched per traversal");
+    rq.variants = variants; rq.n_variants = n_variants;
+}
+
+// The host-buffer renders (dtof_render_offsets / _variants): the library's own film of rq.films() colour planes (and the alpha plane), developed into out_rgb
+void render_host_films(dtof_scene *sc, RenderRequest rq, float *out_rgb) {
+    if (!sc || !out_rgb) throw std::runtime_error("null argument");
+    if (sc->pp.integrator != INTEGRATOR_DOPPLER && rq.n_variants > 0) throw std::runtime_error("modulation offsets only apply to the dopplertofpath integrator");   // before the film is cleared
+    ensure_device(sc);
+    sc->stop = false;
+    const int k = rq.films();
+    const HostSensor &se = sc->host.sensor;
+    size_t px = (size_t) se.crop_w * se.crop_h;
+    const int planes = k + (se.alpha ? 1 : 0), ch = se.alpha ? 4 : 3;   // rgba: one more film plane for the alpha channel, four channels out
+    sc->d_film.ensure(px * 4 * planes); sc->d_rgb.ensure(px * ch * k);
+    HIP_CHECK(hipMemsetAsync(sc->d_film.p, 0, px * 4 * planes * sizeof(float), sc->stream));
+    rq.row_begin = 0; rq.row_end = se.crop_h;
+    rq.film = sc->d_film.p; rq.film_stride = px * 4;   // the library's own film
+    render_rows(sc, rq);
+    if (se.alpha) for (int i = 0; i < k; ++i) launch_develop_rgba(sc->d_film.p + px * 4 * i, sc->d_film.p + px * 4 * k, sc->d_rgb.p + px * 4 * i, (int64_t) px, sc->stream);
+    else launch_develop(sc->d_film.p, sc->d_rgb.p, (int64_t) px * k, sc->stream);
+    HIP_CHECK(hipMemcpyAsync(out_rgb, sc->d_rgb.p, px * ch * k * sizeof(float), hipMemcpyDeviceToHost, sc->stream));
+    HIP_CHECK(hipStreamSynchronize(sc->stream));
 }
 
 std::map<std::string, std::string> to_map(const char *const *names, const char *const *values, int n) {
@@ -1057,22 +1100,44 @@ int dtof_develop(const float *d_film, float *d_rgb, int64_t n_pixels) {
 
 int dtof_render_offsets(dtof_scene *sc, uint32_t seed, uint32_t spp, const float *offsets, int n_offsets, float *out_rgb, dtof_render_stats *stats) {
     return guarded([&] {
-        if (!sc || !out_rgb) throw std::runtime_error("null argument");
-        ensure_device(sc);
-        sc->stop = false;
-        int k = n_offsets <= 0 ? 1 : n_offsets;
-        const HostSensor &se = sc->host.sensor;
-        size_t px = (size_t) se.crop_w * se.crop_h;
-        const int planes = k + (se.alpha ? 1 : 0), ch = se.alpha ? 4 : 3;   // rgba: one more film plane for the alpha channel, four channels out
-        sc->d_film.ensure(px * 4 * planes); sc->d_rgb.ensure(px * ch * k);
-        HIP_CHECK(hipMemsetAsync(sc->d_film.p, 0, px * 4 * planes * sizeof(float), sc->stream));
-        RenderRequest rq; rq.seed = seed; rq.spp = spp; rq.row_end = se.crop_h; rq.offsets = offsets; rq.n_offsets = n_offsets;
-        rq.film = sc->d_film.p; rq.film_stride = px * 4; rq.stats = stats;   // the library's own film
-        render_rows(sc, rq);
-        if (se.alpha) for (int i = 0; i < k; ++i) launch_develop_rgba(sc->d_film.p + px * 4 * i, sc->d_film.p + px * 4 * k, sc->d_rgb.p + px * 4 * i, (int64_t) px, sc->stream);
-        else launch_develop(sc->d_film.p, sc->d_rgb.p, (int64_t) px * k, sc->stream);
-        HIP_CHECK(hipMemcpyAsync(out_rgb, sc->d_rgb.p, px * ch * k * sizeof(float), hipMemcpyDeviceToHost, sc->stream));
-        HIP_CHECK(hipStreamSynchronize(sc->stream));
+        RenderRequest rq; rq.seed = seed; rq.spp = spp; rq.offsets = offsets; rq.n_offsets = n_offsets; rq.stats = stats;
+        render_host_films(sc, rq, out_rgb);
+    });
+}
+int dtof_render_variants(dtof_scene *sc, uint32_t seed, uint32_t spp, const dtof_modulation *variants, int n_variants, float *out_rgb, dtof_render_stats *stats) {
+    return guarded([&] {
+        RenderRequest rq; rq.seed = seed; rq.spp = spp; rq.stats = stats; set_variants(rq, variants, n_variants);
+        render_host_films(sc, rq, out_rgb);
+    });
+}
+int dtof_render_rows_variants(dtof_scene *sc, uint32_t seed, uint32_t spp, int32_t row_begin, int32_t row_end,
+                              const dtof_modulation *variants, int n_variants, float *d_film, dtof_render_stats *stats) {
+    return guarded([&] {
+        RenderRequest rq; rq.seed = seed; rq.spp = spp; rq.row_begin = row_begin; rq.row_end = row_end; rq.film = d_film; rq.stats = stats;
+        set_variants(rq, variants, n_variants); render_device_film(sc, rq);
+    });
+}
+int dtof_render_rows_variants_async(dtof_scene *sc, uint32_t seed, uint32_t spp, int32_t row_begin, int32_t row_end,
+                                    const dtof_modulation *variants, int n_variants, float *d_film) {
+    return guarded([&] {
+        RenderRequest rq; rq.seed = seed; rq.spp = spp; rq.row_begin = row_begin; rq.row_end = row_end; rq.film = d_film; rq.deferred = true;
+        set_variants(rq, variants, n_variants); render_device_film(sc, rq);
+    });
+}
+int dtof_render_stripes_variants(dtof_scene *sc, uint32_t seed, uint32_t spp, int32_t first_row, int32_t stripe_rows, int32_t stripe_period,
+                                 const dtof_modulation *variants, int n_variants, float *d_film, dtof_render_stats *stats) {
+    return guarded([&] {
+        RenderRequest rq; rq.seed = seed; rq.spp = spp; rq.row_begin = first_row; rq.stripes = true; rq.stripe_rows = stripe_rows; rq.stripe_period = stripe_period;
+        rq.film = d_film; rq.stats = stats;
+        set_variants(rq, variants, n_variants); render_device_film(sc, rq);
+    });
+}
+int dtof_render_stripes_variants_async(dtof_scene *sc, uint32_t seed, uint32_t spp, int32_t first_row, int32_t stripe_rows, int32_t stripe_period,
+                                       const dtof_modulation *variants, int n_variants, float *d_film) {
+    return guarded([&] {
+        RenderRequest rq; rq.seed = seed; rq.spp = spp; rq.row_begin = first_row; rq.stripes = true; rq.stripe_rows = stripe_rows; rq.stripe_period = stripe_period;
+        rq.film = d_film; rq.deferred = true;
+        set_variants(rq, variants, n_variants); render_device_film(sc, rq);
     });
 }
 
@@ -1093,6 +1158,23 @@ int dtof_sample_lanes_valid(dtof_scene *sc, uint32_t seed, uint32_t spp, uint64_
         RenderRequest rq; rq.seed = seed; rq.spp = spp; rq.lane_dump = lanes.data(); rq.dump_begin = lane_begin; rq.dump_n = n;
         render_rows(sc, rq);
         for (uint64_t i = 0; i < n; ++i) { memcpy(out + 12 * i, &lanes[i], 48); if (valid) valid[i] = lanes[i].valid != 0.f ? 1u : 0u; }
+    });
+}
+int dtof_sample_lanes_variants(dtof_scene *sc, uint32_t seed, uint32_t spp, const dtof_modulation *variants, int n_variants,
+                               uint64_t lane_begin, uint64_t n, float *out, uint32_t *valid, float *out_rgb) {
+    return guarded([&] {
+        if (!sc || !out || !out_rgb) throw std::runtime_error("null argument");
+        RenderRequest rq; rq.seed = seed; rq.spp = spp; rq.dump_begin = lane_begin; rq.dump_n = n;
+        set_variants(rq, variants, n_variants);
+        if (sc->pp.integrator != INTEGRATOR_DOPPLER && rq.n_variants > 0) throw std::runtime_error("modulation offsets only apply to the dopplertofpath integrator");
+        sc->stop = false;
+        if (n == 0) return;
+        std::vector<LaneDebug> lanes(n);
+        std::vector<float4> planes((size_t) rq.films() * n);
+        rq.lane_dump = lanes.data(); rq.lane_planes = planes.data();
+        render_rows(sc, rq);
+        for (uint64_t i = 0; i < n; ++i) { memcpy(out + 12 * i, &lanes[i], 48); if (valid) valid[i] = lanes[i].valid != 0.f ? 1u : 0u; }
+        for (size_t i = 0; i < planes.size(); ++i) { out_rgb[3 * i] = planes[i].x; out_rgb[3 * i + 1] = planes[i].y; out_rgb[3 * i + 2] = planes[i].z; }
     });
 }
 int dtof_sample_lanes(dtof_scene *sc, uint32_t seed, uint32_t spp, uint64_t lane_begin, uint64_t n, float *out) {

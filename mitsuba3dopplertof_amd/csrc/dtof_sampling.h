@@ -82,15 +82,15 @@ DTOF_D float waveform_low_pass(float _t, int type) {
     float r = 2.f - 4.f * c;
     return fmin_(fmax_(2.0f * r, -2.0f), 2.0f);
 }
-// eval_modulation_weight -- dopplertofpath.cpp:60-77
-DTOF_D float modulation_weight(const RenderParams &rp, float phase, float ray_time, float path_length) {
+// eval_modulation_weight -- dopplertofpath.cpp:60-77; w_d, phase: the film's (RenderParams::w_d[k], ::phase[k])
+DTOF_D float modulation_weight(const RenderParams &rp, float w_d, float phase, float ray_time, float path_length) {
     float phi = rp.phi_coef * path_length;
     if (rp.low_pass) {
-        float t = rp.w_d * ray_time + phase + phi;
+        float t = w_d * ray_time + phase + phi;
         return rp.amp * waveform_low_pass(t, rp.wave_type);
     }
     float t1 = rp.w_g * ray_time - phi;
-    float t2 = (rp.w_g + rp.w_d) * ray_time + phase;
+    float t2 = (rp.w_g + w_d) * ray_time + phase;
     float g_t = rp.g_1 * waveform(t1, rp.wave_type) + rp.g_0;
     float s_t = waveform(t2, rp.wave_type);
     return s_t * g_t;

@@ -314,7 +314,7 @@ void launch_bsdf_eval_spec(const uint8_t *scene, uint32_t shape_index, const flo
 //                 run inline, so neither the shadow queue nor a separate trace launch exists; the state streams
 //                 through HBM once per bounce (this is the default: the split kernels are latency-bound on small
 //                 scenes and the shadow records alone cost 96 B per path-bounce).
-// AREA: the scene has area emitters (emitter-hit term, prev_si state).  KMAX: compile-time bound of the batched offsets (1 or 4);
+// AREA: the scene has area emitters (emitter-hit term, prev_si state).  KMAX: compile-time bound of the batched modulation variants = films (1 or 4; RenderParams::w_d[k], ::phase[k]);
 // both keep the common case -- point lights, one offset -- free of the extra registers.
 // MODE 0 = split, 1 = fused, 2 = fused AND first bounce: the lane is generated (sampler seeding, camera ray) and its primary
 // ray traced right here, so the 96-byte primary state never makes the round trip through HBM and neither k_generate nor the
@@ -346,7 +346,7 @@ template <bool LDS, int MODE, bool AREA, int KMAX, bool MESH, int SPEC, int RESW
 // DTOF_K4_RES_MEM (default 1): the fused first-bounce kernels of SEVERAL films (KMAX > 1) keep neither the K running results nor the K NEE candidates in registers.
 // Round 4's four-film Domino kernel carried 12 + 12 of them across both traversals of every iteration, in scratch: 54 GB of HBM traffic per launch against 10.7 GB of
 // outputs, half its wave-cycles waiting (profiles/r04_pmc_c4_c5.txt).  What is pending across the shadow ray is K-INDEPENDENT -- the throughput, the unweighted
-// contribution bsdf_val * em_weight * mis_em and the path length to the emitter (dopplertofpath.cpp:214-226: only eval_modulation_weight, :60-77, depends on the offset)
+// contribution bsdf_val * em_weight * mis_em and the path length to the emitter (dopplertofpath.cpp:214-226: only eval_modulation_weight, :60-77, depends on the film's offset and frequency)
 // = 7 registers -- and the K weights are applied when the sample is committed, in the same fmaf order.  The running results live where they have to end up anyway, in
 // q.res: a commit is a read-modify-write of the lane's K records (the first one of a path writes without reading, `res_live`), lines the same wave wrote a few
 // microseconds earlier.  MEASURED (profiles/r05_k4_film_state.txt): on the four-film Domino frame that form is no faster than the registers (181.9 against 178.9 ms) --
@@ -624,7 +624,7 @@ __global__ __launch_bounds__(RESW ? RESW * 64 : kShadeBlock, RESW ? RESW / 4 : (
 #pragma unroll
             for (int k = 0; k < KMAX; ++k) if (KMAX == 1 || k < rp.n_offsets) {
                 V3 v = le * mis_bsdf;
-                if (rp.integrator == 0) v = v * modulation_weight(rp, rp.phase[k], time_, stv.w);
+                if (rp.integrator == 0) v = v * modulation_weight(rp, rp.w_d[k], rp.phase[k], time_, stv.w);
                 const float4 r = res_get(k);
                 res_put(k, make_float4(fmaf(stv.x, v.x, r.x), fmaf(stv.y, v.y, r.y), fmaf(stv.z, v.z, r.z), 0.f));
             }
@@ -686,7 +686,7 @@ __global__ __launch_bounds__(RESW ? RESW * 64 : kShadeBlock, RESW ? RESW / 4 : (
 #pragma unroll
                     for (int k = 0; k < KMAX; ++k) if (KMAX == 1 || k < rp.n_offsets) {
                         V3 v = le * mis_bsdf;
-                        if (!plain) v = v * modulation_weight(rp, rp.phase[k], time, path_length);
+                        if (!plain) v = v * modulation_weight(rp, rp.w_d[k], rp.phase[k], time, path_length);
                         const float4 r = RES_MEM ? res_get(k) : rcur[RES_MEM ? 0 : k];
                         const float4 acc = make_float4(fmaf(thr.x, v.x, r.x), fmaf(thr.y, v.y, r.y), fmaf(thr.z, v.z, r.z), 0.f);
                         if (RES_MEM) res_put(k, acc); else rcur[RES_MEM ? 0 : k] = acc;
@@ -832,7 +832,7 @@ __global__ __launch_bounds__(RESW ? RESW * 64 : kShadeBlock, RESW ? RESW / 4 : (
                 for (int k = 0; k < KMAX; ++k) if (KMAX == 1 || k < rp.n_offsets) {
                     float4 r = AREA ? rcur[RES_MEM ? 0 : k] : res_get(k);
                     V3 v = mk(bsdf_val.x * em_weight.x * mis_em, bsdf_val.y * em_weight.y * mis_em, bsdf_val.z * em_weight.z * mis_em);
-                    if (!plain) { float lw = modulation_weight(rp, rp.phase[k], time, path_length + ds_dist); v = v * lw; }
+                    if (!plain) { float lw = modulation_weight(rp, rp.w_d[k], rp.phase[k], time, path_length + ds_dist); v = v * lw; }
                     float3 c = make_float3(fmaf(thr.x, v.x, r.x), fmaf(thr.y, v.y, r.y), fmaf(thr.z, v.z, r.z));
                     cand[RES_MEM ? 0 : k] = c;
                     nonzero |= f2u(c.x) != f2u(r.x) || f2u(c.y) != f2u(r.y) || f2u(c.z) != f2u(r.z);
@@ -916,7 +916,7 @@ __global__ __launch_bounds__(RESW ? RESW * 64 : kShadeBlock, RESW ? RESW / 4 : (
 #pragma unroll
                 for (int k = 0; k < KMAX; ++k) if (k < rp.n_offsets) {
                     V3 v = pend_v;
-                    if (!plain_) v = v * modulation_weight(rp, rp.phase[k], shb.w, pend_len);   // shb.w: the ray time (the shadow ray carries it)
+                    if (!plain_) v = v * modulation_weight(rp, rp.w_d[k], rp.phase[k], shb.w, pend_len);   // shb.w: the ray time (the shadow ray carries it)
                     const float4 r = res_get(k);
                     res_put(k, make_float4(fmaf(pend_thr.x, v.x, r.x), fmaf(pend_thr.y, v.y, r.y), fmaf(pend_thr.z, v.z, r.z), 0.f));
                 }

@@ -65,6 +65,50 @@ def run_scene_doppler_tof_offsets(scene, hetero_offsets, total_spp=1024, output_
     return images
 
 
+def run_scene_doppler_tof_variants(scene, variants, total_spp=1024, output_files=None, **integrator_kwargs):
+    """run_scene_doppler_tof for SEVERAL (hetero_frequency, hetero_offset) pairs of one otherwise identical setting: neither property reaches anything but the
+    modulation weight, so every traversal evaluates up to four pairs at once (dtof_render_variants) and the images of one group share their paths.  Same passes and
+    seeds as run_scene_doppler_tof_offsets; returns the images in the order of `variants`."""
+    single, n_pass = _passes(total_spp)
+    integrator_kwargs = dict(integrator_kwargs)
+    integrator_kwargs.pop("hetero_offset", None)
+    integrator_kwargs.pop("hetero_frequency", None)
+    scene.set_integrator(doppler_integrator_dict(hetero_frequency=0.0, hetero_offset=0.0, **integrator_kwargs))
+    images, stats = [], []
+    for g in range(0, len(variants), 4):
+        group = [(float(f), float(o)) for f, o in variants[g:g + 4]]
+        acc = None
+        for i in range(n_pass):
+            img = scene.render(seed=i, spp=single, variants=group).astype(np.float32)
+            stats.append(scene.last_stats)
+            acc = img if acc is None else acc + img
+        images += list(acc / np.float32(n_pass))
+    scene.pass_stats = stats   # last_stats of every traversal, in order
+    if output_files:
+        for path, img in zip(output_files, images):
+            os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+            write_npy(path, img)
+    return images
+
+
+def run_scene_velocity_map(scene, total_spp=1024, offsets=(0.0, 0.25), **integrator_kwargs):
+    """The radial velocity map of image_utils.py:170-199 from ONE traversal per pass: the homodyne (hetero_frequency 0) and heterodyne (1) films of every offset are
+    variants of the same paths, so their ratio's noise is correlated instead of independent.  Two offsets are the four films of one traversal; more are grouped by
+    pairs of offsets.  Returns (velocity map (H, W), {"homodyne": [...], "heterodyne": [...]} ToF images in the order of `offsets`)."""
+    offsets = [float(o) for o in offsets]
+    variants = []
+    for g in range(0, len(offsets), 2):   # a homodyne / heterodyne pair never straddles two traversals
+        variants += [(0.0, o) for o in offsets[g:g + 2]] + [(1.0, o) for o in offsets[g:g + 2]]
+    images = run_scene_doppler_tof_variants(scene, variants, total_spp, **integrator_kwargs)
+    exposure_time, w_g = integrator_kwargs.get("exposure_time", 0.0015), integrator_kwargs.get("w_g", 30)
+    homo, hetero = [], []
+    for g in range(0, len(offsets), 2):
+        n = len(offsets[g:g + 2])
+        homo += [to_tof_image(im, exposure_time) for im in images[2 * g:2 * g + n]]
+        hetero += [to_tof_image(im, exposure_time) for im in images[2 * g + n:2 * g + 2 * n]]
+    return calc_velocity_from_homo_heteros(homo, hetero, exposure_time, w_g), {"homodyne": homo, "heterodyne": hetero}
+
+
 def run_scene_velocity(scene, total_spp=1024, output_file=None):
     single, _ = _passes(total_spp)
     img = render_multi_pass(scene, load_dict({"type": "velocity"}), total_spp, single)
