@@ -67,6 +67,11 @@ struct RenderParams {
     uint32_t flat_objects, flat_off;                        // fused pipeline, rectangle-only scenes of at most kFlatObjects objects: their number (trace_flat), else 0
     uint32_t memo_obj;                            // fused pipeline: the scene's only instance object (instance memo, dtof_traverse.h) or 0xffffffff
     int32_t want_valid;                           // the kernel that ends a path also writes its valid_ray flag to Queues::valid_out (alpha channel of an rgba film, lane dumps)
+    float emitter_pmf;                            // m_emitter_pmf (scene.cpp:96) = 1 / emitter count, 0 without emitters: launch-invariant, divided once on the host (plan_frame)
+    // The last iteration of this launch is TERMINAL: nothing continues any path after it (no further iteration runs, single pass, no null lobe that could still
+    // change valid_ray), so k_shade drops the half of the bounce nobody reads -- BSDF sampling, the draws behind the emitter sample, continuation ray, throughput /
+    // russian roulette, the advance of both streams -- and, where the iteration has no emitter sampling either (active_next false), everything behind the emitter-hit term
+    int32_t terminal;
 };
 
 // SoA wavefront state for one batch (device pointers; all arrays have `capacity` entries and are

@@ -358,6 +358,7 @@ struct SceneTraits {
     uint32_t n_nodes = 0, n_tlas_nodes = 0, n_objects = 0, stack_depth = 0, flat_off = 0;
     bool resident_layout = false; uint32_t small_off = 0, small_words = 0;   // the blob's record block can be the resident stage's
 };
+static uint32_t bh_emitters(const dtof_scene &sc) { return ((const BlobHeader *) sc.blob.data())->n_emitters; }   // the emitter count the kernels see (SceneView::n_emitters)
 SceneTraits scene_traits(const dtof_scene &sc) {
     const HostScene &hs = sc.host; const HostSensor &se = hs.sensor;
     const BlobHeader *bh = (const BlobHeader *) sc.blob.data();
@@ -401,7 +402,7 @@ SceneTraits scene_traits(const dtof_scene &sc) {
 }
 
 // What one launch of the bounce loop covers when it starts at an iteration
-struct LaunchSpan { uint32_t span, chunk_blocks, res_units; bool next_runs, splat_here; };
+struct LaunchSpan { uint32_t span, chunk_blocks, res_units; bool next_runs, splat_here, terminal; };
 
 // Every decision of a frame, taken before its first launch.  The batch loop reads it and sets only the per-batch and per-launch fields of its copy of rp.
 struct FramePlan {
@@ -410,7 +411,7 @@ struct FramePlan {
     uint32_t n_passes = 1, run_passes = 1, dump_pass = 0;
     uint64_t lanes_per_row = 0, first = 0, last = 0, batch = 1;   // every pass: lanes [first, last) in batches of `batch`
     int n_streams = 1;
-    bool fused = false, first_inline = false, skip_tail = false, fuse_splat_ok = false;
+    bool fused = false, first_inline = false, skip_tail = false, fuse_splat_ok = false, terminal_ok = false;
     uint32_t max_inline = 1, chunk_segs = 0, res_units = 1;
     ResidentStage resident;
     LaunchSwitches launch;                // launch.defer: the DEFER mode, 0 when the workspaces have no DEFER lists
@@ -422,6 +423,8 @@ struct FramePlan {
         LaunchSpan l; l.span = 1;
         if (first && n_passes == 1) while (l.span < max_inline && iteration_runs(it + l.span)) ++l.span;
         l.next_runs = iteration_runs(it + l.span);
+        // no iteration follows this launch's last one: it may run in its terminal form (RenderParams::terminal)
+        l.terminal = terminal_ok && !l.next_runs;
         // small frames whose whole path runs inline: one block per 64-lane chunk (8 x the waves); the count slots it adds into are zeroed first
         const bool whole_path = first && !l.next_runs;
         l.chunk_blocks = whole_path && n_seg <= chunk_segs ? kChunkBlocks : 1u;
@@ -502,6 +505,8 @@ void plan_lanes(FramePlan &p, const dtof_scene *sc, const RenderRequest &rq) {
 //   DTOF_TRACE_BLOCK    auto        64 | 128 | 256: block of the unstaged ray kernels
 //   DTOF_STAGE          1           0: never stage the scene into LDS
 //   DTOF_SPLAT          auto        dpp | generic: that splat kernel
+//   DTOF_TERMINAL_SKIP  1           0: the last iteration that runs keeps the half of the bounce nobody reads (BSDF sampling, continuation ray, throughput / RR,
+//                                   the advance of the streams) instead of its terminal form
 // Process-wide instead: DTOF_STAT_SLOTS (sizes the count slots), DTOF_ROCTX and DTOF_SYNC_LAUNCHES (debugging aids).
 FramePlan plan_frame(const dtof_scene *sc, const RenderRequest &rq) {
     const auto num = [](const char *name, int dflt) { const char *e = getenv(name); return e ? atoi(e) : dflt; };
@@ -586,6 +591,13 @@ FramePlan plan_frame(const dtof_scene *sc, const RenderRequest &rq) {
     // iteration sets it (dopplertofpath.cpp:252-253), which decides whether the path returns what it gathered or 0 (:279-282); the alpha channel / the lane dump's
     // `valid` likewise depend on the hit of that iteration when max_depth is 1
     p.skip_tail = !t.surface_emitters && p.n_passes == 1 && !t.null_lobe && !rp.want_valid;
+    // The terminal form of the last iteration that runs (k_shade: RenderParams::terminal) drops what only a continued path would read.  Eligible: a single pass (the
+    // streams of a finished path are carried into the next pass otherwise) and no null lobe in the scene -- a null sample of that iteration would leave valid_ray unset,
+    // which decides between the path's result and 0 and is what the alpha film / the lane dump's `valid` show; without one every vertex validates its path, so the
+    // terminal form writes valid_out = 1 where want_valid asks for it.  The survivor count of that iteration is not consumed either: the statistics read a count only
+    // as the input of the NEXT iteration, and no queue is compacted for a launch that does not happen.
+    p.terminal_ok = on("DTOF_TERMINAL_SKIP") && p.n_passes == 1 && !t.null_lobe;
+    rp.emitter_pmf = bh_emitters(*sc) ? 1.f / (float) bh_emitters(*sc) : 0.f;   // m_emitter_pmf (scene.cpp:96)
     // fused pipeline: the first bounce kernel generates the lanes and traces the primary rays itself
     p.first_inline = p.fused && rp.integrator != INTEGRATOR_VELOCITY && p.iteration_runs(0) && on("DTOF_FUSE_FIRST");
     // exactly one wave per pixel, one film: measured (profiles/r04_fused_splat_ab.txt) -- with more waves per pixel (C3: 256 spp) or four films (C5) the separate
@@ -654,7 +666,7 @@ void render_rows(dtof_scene *sc, const RenderRequest &rq) {
             }
             const bool first = p.first_inline && it == 0;
             const LaunchSpan l = p.launch_span(it, first, n_seg);
-            rp.inline_iters = l.span; rp.chunk_blocks = l.chunk_blocks; rp.res_units = l.res_units;
+            rp.inline_iters = l.span; rp.chunk_blocks = l.chunk_blocks; rp.res_units = l.res_units; rp.terminal = l.terminal ? 1 : 0;
             it += l.span - 1;   // `it` is now the last iteration this launch covers
             if (l.chunk_blocks > 1 || (l.res_units > 1 && p.resident.waves)) HIP_CHECK(hipMemsetAsync(q.counts, 0, (size_t) 2 * (it + 1) * n_seg * 4, s));
             if (!p.fused || (it == 0 && !first)) { t = tm.begin(kStageTrace, s); launch_trace(blob, blob_bytes, rp, q, qin, count_in, stack_depth, p.launch, s); tm.end(kStageTrace, t, s); if (stats) stats->n_launches_trace++; }

@@ -32,9 +32,11 @@ DTOF_D uint32_t block_append(bool pred, uint32_t *s_cnt, uint32_t &running) {
 // value and density for the emitter direction `wo` (local frame; only when active_em) and the sampled continuation.  SPEC = 0: the diffuse-only scenes' kernels
 // (diffuse under an optional twosided); 1: every BSDF / texture / adapter; 2: ... and blendbsdf / twosided with two BSDFs (the chain in a loop over two records).
 // One function for k_shade and for the known-answer entry dtof_bsdf_eval (the reference's BSDF unit tests run against it on the GPU).
+// The two halves can be asked for separately: active_em = value and density for `wo`, want_sample = the sampled continuation.  Without want_sample (uniform; the
+// terminal iteration of k_shade, whose paths nobody continues) the three samples are not read and weight / wo / bs_* come back as zero / false.
 struct BsdfOut { V3 val, weight, wo; float pdf, bs_pdf, bs_eta; bool bs_delta, bs_null; };   // bs_null: has_flag(bs.sampled_type, BSDFFlags::Null)
 template <int SPEC>
-DTOF_D void bsdf_eval_pdf_sample(const SceneView &sv, const DShape *sh, Surface &si, V3 wo, bool active_em, float sample_1, float s2x, float s2y, BsdfOut &out) {
+DTOF_D void bsdf_eval_pdf_sample(const SceneView &sv, const DShape *sh, Surface &si, V3 wo, bool active_em, float sample_1, float s2x, float s2y, BsdfOut &out, bool want_sample = true) {
     // ---- the shape's BSDF.  Outermost a `mask`, if any: MaskBSDF (src/bsdfs/mask.cpp:125-163) -- with probability 1 - opacity the path goes straight on (a null
     // interaction: wo = -wi, weight 1, pdf 1 - opacity), otherwise the nested BSDF is sampled with sample1 / opacity; eval and pdf of the nested BSDF are scaled by it.
     const bool masked = SPEC && (sh->flags & SF_MASK);
@@ -89,7 +91,7 @@ DTOF_D void bsdf_eval_pdf_sample(const SceneView &sv, const DShape *sh, Surface 
         if (SPEC && bsh->bsdf == BSDF_CONDUCTOR) {
             // SmoothConductor::sample (conductor.cpp:226-277) under TwoSidedBRDF::sample; eval / pdf of a delta lobe are zero
             const float cos_theta_i = twosided ? fabsf(si.wi.z) : si.wi.z;
-            if (cos_theta_i > 0.f) {
+            if (want_sample && cos_theta_i > 0.f) {
                 bs_wo = mk(-si.wi.x, -si.wi.y, si.wi.z);   // reflect(wi); the two-sided flips of wi.z and wo.z cancel
                 bs_eta = 1.f; bs_pdf = 1.f; bs_delta = true;
                 bsdf_weight = mk(hm.spec_refl[0] * fresnel_conductor(cos_theta_i, bsh->cond_eta[0], bsh->cond_k[0]),
@@ -98,6 +100,7 @@ DTOF_D void bsdf_eval_pdf_sample(const SceneView &sv, const DShape *sh, Surface 
             }
         } else if (SPEC && bsh->bsdf == BSDF_DIELECTRIC) {
             // SmoothDielectric::sample (dielectric.cpp:231-338), TransportMode::Radiance
+            if (want_sample) {
             float r_i, cos_theta_t, eta_it, eta_ti;
             fresnel_dielectric(si.wi.z, bsh->diel_eta, r_i, cos_theta_t, eta_it, eta_ti);
             const float t_i = 1.f - r_i;
@@ -108,11 +111,13 @@ DTOF_D void bsdf_eval_pdf_sample(const SceneView &sv, const DShape *sh, Surface 
             const float f2 = sqr(eta_ti);
             bsdf_weight = selected_r ? mk(hm.spec_refl[0], hm.spec_refl[1], hm.spec_refl[2])
                                      : mk(hm.spec_trans[0] * f2, hm.spec_trans[1] * f2, hm.spec_trans[2] * f2);
+            }
         } else if (SPEC && bsh->bsdf == BSDF_NULL) {
             // Null::sample (null.cpp:42-66): straight on, weight 1, pdf 1, a null (and with it a delta) lobe; eval and pdf are zero (:68-79)
-            bs_wo = mk(-si.wi.x, -si.wi.y, -si.wi.z); bs_eta = 1.f; bs_pdf = 1.f; bs_delta = true; bs_null = true; bsdf_weight = mk(1.f, 1.f, 1.f);
+            if (want_sample) { bs_wo = mk(-si.wi.x, -si.wi.y, -si.wi.z); bs_eta = 1.f; bs_pdf = 1.f; bs_delta = true; bs_null = true; bsdf_weight = mk(1.f, 1.f, 1.f); }
         } else if (SPEC && bsh->bsdf == BSDF_THINDIELECTRIC) {
             // ThinDielectric::sample (thindielectric.cpp:173-226): the reflectance of the slab with all internal bounces, wo = -wi
+            if (want_sample) {
             float r, t1, t2, t3;
             fresnel_dielectric(fabsf(si.wi.z), bsh->diel_eta, r, t1, t2, t3);
             r *= 2.f / (1.f + r);
@@ -121,12 +126,13 @@ DTOF_D void bsdf_eval_pdf_sample(const SceneView &sv, const DShape *sh, Surface 
             bs_null = !selected_r;   // bs.sampled_type = select(selected_r, DeltaReflection, Null) (:179)
             bs_wo = selected_r ? mk(-si.wi.x, -si.wi.y, si.wi.z) : mk(-si.wi.x, -si.wi.y, -si.wi.z);
             bsdf_weight = selected_r ? mk(hm.spec_refl[0], hm.spec_refl[1], hm.spec_refl[2]) : mk(hm.spec_trans[0], hm.spec_trans[1], hm.spec_trans[2]);
+            }
         } else if (SPEC && bsh->bsdf == BSDF_ROUGHDIELECTRIC) {
             // RoughDielectric::eval_pdf / sample (roughdielectric.cpp:240-346,503-611): glossy reflection and transmission lobes
             const Ggx g = mf_make((bsh->flags & SF_BECKMANN) ? MF_BECKMANN : MF_GGX, hm.alpha_u, hm.alpha_v, !(bsh->flags & SF_SAMPLE_ALL));
             const V3 wi = si.wi;
             if (active_em) rough_dielectric_eval_pdf(g, bsh, hm, wi, wo, bsdf_val, bsdf_pdf);
-            if (wi.z != 0.f) {
+            if (want_sample && wi.z != 0.f) {
                 float mpdf;
                 Ggx gs = g;   // sample_distr (:266-269)
                 if (!g.visible) { const float sc = 1.2f - .2f * sqrtf(fabsf(wi.z)); gs.au *= sc; gs.av *= sc; }
@@ -171,7 +177,7 @@ DTOF_D void bsdf_eval_pdf_sample(const SceneView &sv, const DShape *sh, Surface 
                 }
                 if (dot(wi, H) > 0.f && dot(wo_l, H) > 0.f) bsdf_pdf = g.visible ? ggx_eval(g, H) * ggx_smith_g1(g, wi, H) / (4.f * wi.z) : ggx_pdf(g, wi, H) / (4.f * dot(wo_l, H));   // :405-409
             }
-            if (wi.z > 0.f) {
+            if (want_sample && wi.z > 0.f) {
                 float mpdf;
                 const V3 m = ggx_sample(g, wi, s2x, s2y, mpdf);
                 const float dwm = dot(wi, m);
@@ -200,6 +206,7 @@ DTOF_D void bsdf_eval_pdf_sample(const SceneView &sv, const DShape *sh, Surface 
                 prob_specular = prob_specular / (prob_specular + prob_diffuse);
                 prob_diffuse = 1.f - prob_specular;
                 if (wo_l.z > 0.f) rough_plastic_eval_pdf(g, bsh, hm, table, diff, wi, wo_l, t_i, prob_specular, prob_diffuse, bsdf_val, bsdf_pdf);
+                if (want_sample) {
                 if (s1 < prob_specular) {
                     float mpdf; const V3 m = ggx_sample(g, wi, s2x, s2y, mpdf);
                     const float dwm = dot(wi, m);
@@ -210,6 +217,7 @@ DTOF_D void bsdf_eval_pdf_sample(const SceneView &sv, const DShape *sh, Surface 
                 if (bs_wo.z > 0.f) rough_plastic_eval_pdf(g, bsh, hm, table, diff, wi, bs_wo, t_i, prob_specular, prob_diffuse, value, bs_pdf);
                 if (bs_pdf > 0.f) bsdf_weight = value * rcp(bs_pdf);                  // Spectrum / Float = multiplication by the reciprocal
                 if (twosided && si.wi.z < 0.f) bs_wo.z = -bs_wo.z;
+                }
             }
         } else if (SPEC && bsh->bsdf == BSDF_PLASTIC) {
             // SmoothPlastic::eval / pdf / sample (plastic.cpp:219-360) under TwoSidedBRDF; wiz / woz are already flipped
@@ -226,7 +234,7 @@ DTOF_D void bsdf_eval_pdf_sample(const SceneView &sv, const DShape *sh, Surface 
                 prob_diffuse = prob_diffuse / (prob_specular + prob_diffuse);
                 bsdf_pdf = kInvPi * woz * prob_diffuse;
             }
-            if (wiz > 0.f) {
+            if (want_sample && wiz > 0.f) {
                 float prob_specular = f_i * w, prob_diffuse = (1.f - f_i) * (1.f - w);
                 prob_specular = prob_specular / (prob_specular + prob_diffuse);
                 prob_diffuse = 1.f - prob_specular;
@@ -247,7 +255,7 @@ DTOF_D void bsdf_eval_pdf_sample(const SceneView &sv, const DShape *sh, Surface 
             }
         } else {
             if (wiz > 0.f && woz > 0.f) { bsdf_val = mk(refl.x * kInvPi * woz, refl.y * kInvPi * woz, refl.z * kInvPi * woz); bsdf_pdf = kInvPi * woz; }
-            if (wiz > 0.f) {
+            if (want_sample && wiz > 0.f) {
                 bs_wo = cosine_hemisphere(s2x, s2y);
                 bs_pdf = kInvPi * bs_wo.z;
                 bs_eta = 1.f;
@@ -278,7 +286,7 @@ DTOF_D void bsdf_eval_pdf_sample(const SceneView &sv, const DShape *sh, Surface 
     si.wi = wi_plain;
     if (masked) {
         bsdf_val = bsdf_val * opacity; bsdf_pdf *= opacity;
-        if (null_pick) { bs_wo = mk(-si.wi.x, -si.wi.y, -si.wi.z); bs_eta = 1.f; bs_pdf = 1.f - opacity; bs_delta = true; bs_null = true; bsdf_weight = mk(1.f, 1.f, 1.f); }
+        if (want_sample && null_pick) { bs_wo = mk(-si.wi.x, -si.wi.y, -si.wi.z); bs_eta = 1.f; bs_pdf = 1.f - opacity; bs_delta = true; bs_null = true; bsdf_weight = mk(1.f, 1.f, 1.f); }
     }
     out.val = bsdf_val; out.pdf = bsdf_pdf; out.weight = bsdf_weight; out.wo = bs_wo; out.bs_pdf = bs_pdf; out.bs_eta = bs_eta; out.bs_delta = bs_delta; out.bs_null = bs_null;
 }
@@ -298,7 +306,7 @@ __global__ void k_bsdf_eval(const uint8_t *scene, uint32_t shape_index, const fl
     si.dp_du = mk(a[11], a[12], a[13]); si.dp_dv = mk(a[14], a[15], a[16]); si.n = mk(a[17], a[18], a[19]);
     si.sh_s = mk(a[20], a[21], a[22]); si.sh_t = mk(a[23], a[24], a[25]); si.sh_n = mk(a[26], a[27], a[28]);
     BsdfOut bo;
-    bsdf_eval_pdf_sample<SPEC>(sv, si.shape, si, mk(a[3], a[4], a[5]), true, a[6], a[7], a[8], bo);
+    bsdf_eval_pdf_sample<SPEC>(sv, si.shape, si, mk(a[3], a[4], a[5]), true, a[6], a[7], a[8], bo, true);   // both halves
     float *w = out + (size_t) i * 14;
     w[0] = bo.val.x; w[1] = bo.val.y; w[2] = bo.val.z; w[3] = bo.pdf; w[4] = bo.wo.x; w[5] = bo.wo.y; w[6] = bo.wo.z; w[7] = bo.bs_pdf; w[8] = bo.bs_eta;
     w[9] = bo.bs_delta ? 1.f : 0.f; w[10] = bo.weight.x; w[11] = bo.weight.y; w[12] = bo.weight.z; w[13] = bo.bs_null ? 1.f : 0.f;
@@ -569,6 +577,10 @@ __global__ __launch_bounds__(RESW ? RESW * 64 : kShadeBlock, RESW ? RESW / 4 : (
     const uint32_t depth = depth0 + it;
     const bool last = it + 1 >= n_inline;                 // uniform
     const uint32_t trace_next = last ? trace_next_last : 1u;
+    // the TERMINAL iteration (uniform; RenderParams::terminal): nothing continues a path after it and nobody reads what the second half of the bounce leaves behind.
+    // Where it still samples an emitter (active_next: the last iteration that runs in a scene without surface emitters) it keeps the emitter-hit term, the emitter
+    // sample with its two draws, the BSDF's value and density for it and the NEE candidate with its shadow ray; where it does not, only the emitter-hit term.
+    const bool terminal = last && rp.terminal != 0;
     alive = false; want_shadow = false;
     if (lane_on) {
         if (PARK) park_load();
@@ -618,7 +630,7 @@ __global__ __launch_bounds__(RESW ? RESW * 64 : kShadeBlock, RESW ? RESW / 4 : (
             const DEmitter &env = sv.emitters[rp.env_index];
             const bool is_map = env.kind == EMITTER_ENVMAP;   // EnvironmentMapEmitter::pdf_direction / eval (envmap.cpp:408-425,299-310) with ds.d = -si.wi = the ray direction
             const V3 rd = FIRST ? mk(rb.x, rb.y, rb.z) : [&] { const float4 b4 = q.ray_b[l]; return mk(b4.x, b4.y, b4.z); }();
-            const float em_pdf = pdelta ? 0.f : (is_map ? env_pdf_direction(sv.base, env, rd) : kInvFourPi) * (1.f / (float) sv.n_emitters);
+            const float em_pdf = pdelta ? 0.f : (is_map ? env_pdf_direction(sv.base, env, rd) : kInvFourPi) * rp.emitter_pmf;
             const float mis_bsdf = mis_weight(prev_pdf, em_pdf);
             const V3 le = prev_pdf > 0.f ? (is_map ? env_eval(sv.base, env, rd) : mk(env.intensity[0], env.intensity[1], env.intensity[2])) : mk(0, 0, 0);
 #pragma unroll
@@ -647,10 +659,12 @@ __global__ __launch_bounds__(RESW ? RESW * 64 : kShadeBlock, RESW ? RESW / 4 : (
             if (FIRST && it > 0 && have_memo && !sv.memo_m) {   // a ray's time does not change along its path: the inverse filled at generation still sits in the LDS column
                 instance_matrix(sv.objects[sv.memo_obj], time, memo_m); instance_memo_load(sv, memo_inv);
             }
-            compute_surface<MESH>(sv, hid & ((1u << q.id_shift) - 1u), hid >> q.id_shift, hh.w, t, u2f(hh.y), u2f(hh.z), o, d, time, si, have_memo, memo_m, memo_inv);
+            // the diffuse-only kernels' terminal iteration reads the cosines wi.z / wo.z and nothing else of the shading frame
+            const bool want_frame = SPEC != 0 || !terminal;
+            compute_surface<MESH>(sv, hid & ((1u << q.id_shift) - 1u), hid >> q.id_shift, hh.w, t, u2f(hh.y), u2f(hh.z), o, d, time, si, have_memo, memo_m, memo_inv, want_frame);
             const DShape *sh = si.shape;
 
-            const float pmf = sv.n_emitters ? 1.f / (float) sv.n_emitters : 0.f;   // m_emitter_pmf (scene.cpp:96)
+            const float pmf = rp.emitter_pmf;   // m_emitter_pmf (scene.cpp:96)
             // ---- direct emission (dopplertofpath.cpp:150-168 / path.cpp): the hit shape carries an area emitter
             bool res_dirty = false;
             float4 rcur[KREG];   // (RES_MEM: the emitter-hit term goes straight to q.res)
@@ -695,6 +709,15 @@ __global__ __launch_bounds__(RESW ? RESW * 64 : kShadeBlock, RESW ? RESW / 4 : (
                 }
             }
 
+            if (terminal && !active_next) {
+                // terminal, and no emitter is sampled at this depth: the iteration existed for the emitter-hit term alone.  valid_ray: terminal launches are those of
+                // scenes without a null lobe (plan_frame), where every vertex validates its path
+                if (res_dirty) {
+#pragma unroll
+                    for (int k = 0; k < KMAX; ++k) if (KMAX == 1 || k < rp.n_offsets) res_put(k, rcur[RES_MEM ? 0 : k]);
+                }
+                if (rp.want_valid) q.valid_out[l] = make_float4(1.f, 0.f, 0.f, 0.f);
+            } else {
             // ---- emitter sampling (scene.cpp:235-291; point.cpp:118-147; area.cpp:116-159 + shape.cpp:370-384 + rectangle.cpp:152-166)
             // The six draws of this iteration (App. A step 5) come from ONE stream: the main one (`path`, other samplers, correlate = false) or
             // the path-correlated one; next_1d_correlate advances both on every draw (correlated.cpp:156-161), so the stream that is not read
@@ -807,14 +830,14 @@ __global__ __launch_bounds__(RESW ? RESW * 64 : kShadeBlock, RESW ? RESW / 4 : (
                 sd = sd * rcp(sdist);
                 sha = make_float4(so.x, so.y, so.z, sdist * (1.f - kShadowEps));
                 shb = make_float4(sd.x, sd.y, sd.z, time);
-                wo = mk(dot(dd, si.sh_s), dot(dd, si.sh_t), dot(dd, si.sh_n));
+                wo = want_frame ? mk(dot(dd, si.sh_s), dot(dd, si.sh_t), dot(dd, si.sh_n)) : mk(0.f, 0.f, dot(dd, si.sh_n));
             }
-            float sample_1 = next_f32(sel); (void) sample_1;
-            float s2x = next_f32(sel), s2y = next_f32(sel);
+            float sample_1 = 0.f, s2x = 0.f, s2y = 0.f;   // terminal: the BSDF is not sampled, and the stream states are dropped with the path
+            if (!terminal) { sample_1 = next_f32(sel); s2x = next_f32(sel); s2y = next_f32(sel); }
 
             // ---- the shape's BSDF with its adapters (mask, blendbsdf, twosided, normalmap / bumpmap): bsdf_eval_pdf_sample above
             BsdfOut bo;
-            bsdf_eval_pdf_sample<SPEC>(sv, sh, si, wo, active_em, sample_1, s2x, s2y, bo);
+            bsdf_eval_pdf_sample<SPEC>(sv, sh, si, wo, active_em, sample_1, s2x, s2y, bo, !terminal);
             const V3 bsdf_val = bo.val, bs_wo = bo.wo; V3 bsdf_weight = bo.weight;
             const float bsdf_pdf = bo.pdf, bs_pdf = bo.bs_pdf, bs_eta = bo.bs_eta; const bool bs_delta = bo.bs_delta, bs_null = bo.bs_null;
             // ---- emitter contribution candidate (dopplertofpath.cpp:214-226); committed by k_shadow if unoccluded
@@ -844,6 +867,9 @@ __global__ __launch_bounds__(RESW ? RESW * 64 : kShadeBlock, RESW ? RESW / 4 : (
 #pragma unroll
                 for (int k = 0; k < KMAX; ++k) if (KMAX == 1 || k < rp.n_offsets) res_put(k, rcur[RES_MEM ? 0 : k]);
             }
+            if (terminal) {   // the path ends here whatever it sampled; valid_ray as above
+                if (rp.want_valid) q.valid_out[l] = make_float4(1.f, 0.f, 0.f, 0.f);
+            } else {
             // ---- continuation (dopplertofpath.cpp:232-276)
             V3 nd = vfma(si.sh_n, bs_wo.z, vfma(si.sh_t, bs_wo.y, si.sh_s * bs_wo.x));   // Frame::to_world
             V3 no = offset_p(si, nd);
@@ -888,6 +914,8 @@ __global__ __launch_bounds__(RESW ? RESW * 64 : kShadeBlock, RESW ? RESW / 4 : (
             }
             if ((alive && (!FIRST || last) && trace_next) || rp.n_passes > 1)   // several passes: the state of a finished path is what its lane starts the next pass with
                 q.rng_a[l] = make_uint4((uint32_t) main.state, (uint32_t) (main.state >> 32), (uint32_t) path.state, (uint32_t) (path.state >> 32));
+            }   // !terminal: continuation
+            }   // emitter sampling and what follows it
         }
     }
     if (last) {

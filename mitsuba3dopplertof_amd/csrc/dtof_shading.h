@@ -14,9 +14,11 @@ struct Surface { V3 p, n, sh_n, sh_s, sh_t, wi; float u, v; const DShape *shape;
 // Shape::compute_surface_interaction for rectangle (rectangle.cpp:250-323) / mesh (mesh.cpp:632-864),
 // Instance::compute_surface_interaction (instance.cpp:155-250), finalize (interaction.h:493-513)
 // memo_m / memo_inv: the instance matrix and its inverse of object sv.memo_obj at this ray time, if the caller has them (instance memo)
+// want_frame = false (uniform): the caller reads only the cosine wi.z of the shading frame -- no tangent frame (initialize_sh_frame: a normalize, a cross product,
+// the dp_du == 0 test) and no dp_du / dp_dv through the instance; sh_s, sh_t, dp_du, dp_dv and wi.x / wi.y come back as zero.  p, n, sh_n, wi.z, u, v are the same.
 template <bool MESH>
 DTOF_D void compute_surface(const SceneView &sv, uint32_t oi, uint32_t shape_k, uint32_t prim, float t, float b1, float b2,
-                            V3 o, V3 d, float time, Surface &si, bool use_memo, const float (&memo_m)[12], const float (&memo_inv)[12]) {
+                            V3 o, V3 d, float time, Surface &si, bool use_memo, const float (&memo_m)[12], const float (&memo_inv)[12], bool want_frame = true) {
     const DObject &ob = sv.objects[oi];
     bool inst = ob.kind == OBJ_INSTANCE;
     float m[12], inv[12];
@@ -106,14 +108,20 @@ DTOF_D void compute_surface(const SceneView &sv, uint32_t oi, uint32_t shape_k, 
         si.p = xf_point(m, si.p);
         si.n = normalize(xf_normal(inv, si.n));
         si.sh_n = normalize(xf_normal(inv, si.sh_n));
-        dp_du = xf_vector(m, dp_du); dp_dv = xf_vector(m, dp_dv);   // instance.cpp:201-202
+        if (want_frame) { dp_du = xf_vector(m, dp_du); dp_dv = xf_vector(m, dp_dv); }   // instance.cpp:201-202
+    }
+    V3 md = -d;
+    if (!want_frame) {
+        const V3 zero = mk(0.f, 0.f, 0.f);
+        si.sh_s = zero; si.sh_t = zero; si.dp_du = zero; si.dp_dv = zero;
+        si.wi = mk(0.f, 0.f, dot(md, si.sh_n));
+        return;
     }
     // initialize_sh_frame (interaction.h:258-268)
     V3 s = normalize(vfma(si.sh_n, -dot(si.sh_n, dp_du), dp_du));
     if (dp_du.x == 0.f && dp_du.y == 0.f && dp_du.z == 0.f) { V3 tt; coordinate_system(si.sh_n, s, tt); }
     si.sh_s = s; si.sh_t = cross(si.sh_n, s);
     si.dp_du = dp_du; si.dp_dv = dp_dv;
-    V3 md = -d;
     si.wi = mk(dot(md, si.sh_s), dot(md, si.sh_t), dot(md, si.sh_n));
 }
 template <bool MESH>
