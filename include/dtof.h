@@ -172,6 +172,9 @@ typedef struct {
      * film, radius-1 tent, the whole path inline).  The sums of a pixel's samples are then taken in another ORDER than the splat kernels': films of the two paths
      * differ in the last bits, so checksums compare only between runs with the same value here */
     uint32_t n_fused_splat_launches;
+    /* first-bounce launches that ran a kernel compiled with the frame plan's constants (single pass, Doppler integrator + correlated sampler, whole path inline, ...:
+     * every fact of the kernel's mask held) instead of the generic one; DTOF_PLAN_FACTS=0 keeps it at 0.  The results are the same bits either way */
+    uint32_t n_plan_facts_launches;
 } dtof_render_stats;
 
 /* out_rgb: caller-owned host buffer, crop_height*crop_width*3 float32, developed (RGB / W). */
@@ -269,6 +272,9 @@ int dtof_render_stripes_variants_async(dtof_scene *scene, uint32_t seed, uint32_
 
 /* Integrator::cancel / should_stop (include/mitsuba/render/integrator.h:96-109). */
 void dtof_cancel(dtof_scene *scene);
+/* First-bounce launches of this scene, since it was loaded, that ran a kernel compiled with the frame plan's constants (dtof_render_stats::n_plan_facts_launches): the
+ * same count for the calls that return no statistics block (the lane dumps). */
+uint64_t dtof_scene_plan_facts_launches(const dtof_scene *scene);
 
 /* Per-lane debugging entry (SURVEY 8b "dtof_sample_lanes"): evaluates wavefront lanes
  * [lane_begin, lane_begin+n) exactly as dtof_render would (multi-pass renders: index = pass * wavefront_size + lane, a range must stay

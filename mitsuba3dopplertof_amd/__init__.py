@@ -36,7 +36,8 @@ class _Stats(C.Structure):
                 ("ms_shade", C.c_double), ("ms_shadow", C.c_double), ("ms_splat", C.c_double),
                 ("n_launches_trace", C.c_uint32), ("n_launches_shade", C.c_uint32), ("n_launches_shadow", C.c_uint32),
                 ("n_batches", C.c_uint32), ("n_launches_first", C.c_uint32), ("ms_first", C.c_double),
-                ("n_inline_iterations", C.c_uint32), ("n_bounces_inline", C.c_uint64), ("n_fused_splat_launches", C.c_uint32)]
+                ("n_inline_iterations", C.c_uint32), ("n_bounces_inline", C.c_uint64), ("n_fused_splat_launches", C.c_uint32),
+                ("n_plan_facts_launches", C.c_uint32)]
 
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_}
@@ -100,6 +101,9 @@ def _lib():
     L.dtof_render_offsets.argtypes = [vp, C.c_uint32, C.c_uint32, vp, C.c_int, vp, C.POINTER(_Stats)]
     L.dtof_cancel.argtypes = [vp]
     L.dtof_cancel.restype = None
+    if hasattr(L, "dtof_scene_plan_facts_launches"):   # (an older build timed through DTOF_LIB has no such entry)
+        L.dtof_scene_plan_facts_launches.argtypes = [vp]
+        L.dtof_scene_plan_facts_launches.restype = C.c_uint64
     L.dtof_sample_lanes.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64, vp]
     L.dtof_sample_lanes_valid.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64, vp, vp]
     L.dtof_develop_rgba.argtypes = [vp, vp, vp, C.c_int64]
@@ -246,6 +250,11 @@ class Scene:
         out = np.zeros(n.value, np.float32)
         _check(_lib().dtof_scene_export(self._h, kind, out.ctypes.data, out.size, C.byref(n)))
         return out
+
+    @property
+    def plan_facts_launches(self):
+        """first-bounce launches since the scene was loaded that ran a kernel compiled with the frame plan's constants (lane dumps included)"""
+        return int(_lib().dtof_scene_plan_facts_launches(self._h))
 
     def set_integrator(self, props):
         _check(_lib().dtof_scene_set_integrator(self._h, *_plugin_args(props)))

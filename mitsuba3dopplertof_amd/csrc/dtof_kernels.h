@@ -130,15 +130,43 @@ constexpr uint32_t kParkState = 10, kParkRng = 6;   // one film: both streams + 
 // the stack columns of the resident kernels of several films hold 16-bit entries (dtof_traverse.h: encode_child16), the one-film kernels' 32-bit ones
 static inline uint32_t resident_stack_bytes(uint32_t depth, uint32_t waves, bool several_films) { return (depth < 2 ? 2 : depth) * waves * 64u * (several_films ? 2u : 4u); }
 
+// Plan facts (k_shade's FACTS template parameter): things the host fixed in the frame plan before a first-bounce launch, the same for every lane of it, that the kernel
+// otherwise re-decides inside its chunk and bounce loops -- each a scalar load from the kernarg segment at its point of use, a wait that also drains the LDS reads, a
+// branch, and registers kept alive for the side that is never taken.  A kernel instantiated with a mask reads the constant instead; render_rows (FramePlan::launch_facts)
+// works out which facts a launch satisfies, and a launcher picks a specialised instantiation only when every fact of its mask holds.
+enum : uint32_t {
+    kFactSinglePass     = 1u << 0,   // rp.n_passes == 1 (and with it rp.pass == 0): no stream state is carried between passes
+    kFactDopplerCorr    = 1u << 1,   // rp.integrator == 0 (dopplertofpath) and rp.sampler_kind == SAMPLER_CORRELATED
+    kFactNoLaneOutput   = 1u << 2,   // dbg == nullptr and rp.want_valid == 0: neither the lane dump's camera rays nor valid_out are written
+    kFactIdentityQueue  = 1u << 3,   // qin == nullptr and count_in == nullptr: lane j of segment S is lane S * kSeg + j, a segment's count follows from n_lanes
+    kFactNoRoulette     = 1u << 4,   // rp.rr_depth > depth + rp.inline_iters: russian roulette is not reached by any iteration (its draw still advances the stream)
+    kFactCorrelated     = 1u << 5,   // depth + rp.inline_iters < rp.path_correlation_depth: every iteration draws from the path-correlated stream
+    kFactWholePath      = 1u << 6,   // trace_next == 0 and rp.terminal != 0: nothing is queued behind the launch, its last iteration is the terminal one
+    kFactOneBlock       = 1u << 7,   // rp.chunk_blocks == 1: one block per 512-lane segment
+    kFactOneEmitter     = 1u << 8,   // the scene has exactly one emitter
+    kFactWavePixel      = 1u << 9,   // every chunk of every segment is a whole, 64-aligned wave of one pixel (k_shade: wave_pixel), proven from spp, lane_base and n_lanes
+};
+// the mask the headline kernel (dtof_shade_plain.hip) is compiled with; A/B of a subset: make variant NAME=x DEFS=-DDTOF_HEADLINE_FACTS=0x17
+#ifndef DTOF_HEADLINE_FACTS
+#define DTOF_HEADLINE_FACTS 0x3ff
+#endif
+constexpr uint32_t kHeadlineFacts = DTOF_HEADLINE_FACTS;
+// ... and the resident Domino kernel of one film at 16 waves (dtof_shade_res0.hip): every fact but kFactOneBlock, which describes the classic launch (0: not built)
+#ifndef DTOF_RESIDENT_FACTS
+#define DTOF_RESIDENT_FACTS 0x37f
+#endif
+constexpr uint32_t kResidentFacts = DTOF_RESIDENT_FACTS;
+
 // One launch of k_shade as launch_shade hands it to the translation unit that holds the instantiation (dtof_shade_*.hip: the ~100 instantiations of the
 // kernel compile in parallel, one group per file): staged = the scene blob is copied to LDS by every block; mode 0 split, 1 fused, 2 fused first bounce;
-// waves != 0: the resident form (`waves` waves per block, one block per CU).
-struct ShadeLaunch { bool staged; int mode; uint32_t waves, grid, lds; hipStream_t stream; ShadeArgs args; };
-void launch_shade_plain(bool area, bool k4, const ShadeLaunch &L);      // rectangle-only diffuse scenes          (dtof_shade_plain.hip)
+// waves != 0: the resident form (`waves` waves per block, one block per CU); facts: the plan facts this launch satisfies (0: take the generic kernels).
+// launch_shade_plain and launch_shade_resident0 return whether an instantiation specialised on plan facts ran.
+struct ShadeLaunch { bool staged; int mode; uint32_t waves, grid, lds; hipStream_t stream; ShadeArgs args; uint32_t facts; };
+bool launch_shade_plain(bool area, bool k4, const ShadeLaunch &L);      // rectangle-only diffuse scenes          (dtof_shade_plain.hip)
 void launch_shade_mesh(bool area, bool k4, const ShadeLaunch &L);       // + triangles / analytic shapes          (dtof_shade_mesh.hip)
 void launch_shade_spec1(bool k4, const ShadeLaunch &L);                 // every BSDF / emitter / texture         (dtof_shade_spec1.hip)
 void launch_shade_spec2(bool k4, const ShadeLaunch &L);                 // ... and blendbsdf                      (dtof_shade_spec2.hip)
-void launch_shade_resident0(bool area, bool k4, const ShadeLaunch &L);  // resident first bounce, diffuse scenes  (dtof_shade_res0.hip)
+bool launch_shade_resident0(bool area, bool k4, const ShadeLaunch &L);  // resident first bounce, diffuse scenes  (dtof_shade_res0.hip)
 void launch_shade_resident1(bool k4, const ShadeLaunch &L);             // resident first bounce, every BSDF      (dtof_shade_res1.hip)
 void launch_shade_resident2(bool k4, const ShadeLaunch &L);             // ... and blendbsdf                      (dtof_shade_res2.hip)
 
@@ -165,11 +193,12 @@ void launch_sum_counts(const uint32_t *counts, uint32_t n_seg, uint32_t n_rows, 
 uint32_t segments_for(uint32_t n_lanes);   // number of queue segments (count slots) for a batch
 void launch_trace(const uint8_t *scene, uint32_t scene_bytes, const RenderParams &rp, const Queues &q,
                   const uint32_t *qin, const uint32_t *count_in, uint32_t stack_depth, const LaunchSwitches &ls, hipStream_t s);
-void launch_shade(const uint8_t *scene, uint32_t scene_bytes, const RenderParams &rp, const Queues &q,
+bool launch_shade(const uint8_t *scene, uint32_t scene_bytes, const RenderParams &rp, const Queues &q,
                   const uint32_t *qin, const uint32_t *count_in, uint32_t *qout,
                   uint32_t *alive_out, uint32_t *shadow_out, uint32_t depth, bool fused, bool trace_next,
                   uint32_t stack_depth, const LaunchSwitches &ls, hipStream_t s, bool first = false, LaneDebug *dbg = nullptr,   // first: generate + primary trace inline (fused only)
-                  const ResidentStage *resident = nullptr, float *film = nullptr, uint64_t film_stride = 0);   // film: the launch covers the whole path and splats its lanes itself
+                  const ResidentStage *resident = nullptr, float *film = nullptr, uint64_t film_stride = 0,   // film: the launch covers the whole path and splats its lanes itself
+                  uint32_t facts = 0);   // facts: the plan facts the launch satisfies (kFact*); returns whether a kernel specialised on them ran
 void launch_shadow(const uint8_t *scene, uint32_t scene_bytes, const RenderParams &rp, const Queues &q,
                    const uint32_t *count_in, uint32_t stack_depth, const LaunchSwitches &ls, hipStream_t s);
 void launch_velocity(const uint8_t *scene, uint32_t scene_bytes, const RenderParams &rp, const Queues &q, uint32_t stack_depth, const LaunchSwitches &ls, hipStream_t s);

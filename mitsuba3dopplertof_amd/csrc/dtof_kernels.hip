@@ -656,11 +656,12 @@ uint32_t device_lds_limit() {
     if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&bytes, hipDeviceAttributeMaxSharedMemoryPerBlock, dev) != hipSuccess || bytes <= 0) return 64u * 1024u;
     return (uint32_t) bytes > 1024u ? (uint32_t) bytes - 1024u : 0u;   // k_shade's static LDS (count slots) comes on top of the dynamic size
 }
-void launch_shade(const uint8_t *scene, uint32_t scene_bytes, const RenderParams &rp, const Queues &q,
+bool launch_shade(const uint8_t *scene, uint32_t scene_bytes, const RenderParams &rp, const Queues &q,
                   const uint32_t *qin, const uint32_t *count_in, uint32_t *qout,
                   uint32_t *alive_out, uint32_t *shadow_out, uint32_t depth, bool fused, bool trace_next,
-                  uint32_t stack_depth, const LaunchSwitches &ls, hipStream_t s, bool first, LaneDebug *dbg, const ResidentStage *resident, float *film, uint64_t film_stride) {
-    if (rp.n_lanes == 0) return;
+                  uint32_t stack_depth, const LaunchSwitches &ls, hipStream_t s, bool first, LaneDebug *dbg, const ResidentStage *resident, float *film, uint64_t film_stride,
+                  uint32_t facts) {
+    if (rp.n_lanes == 0) return false;
     if (first && !fused) throw std::runtime_error("the first-bounce kernel exists in the fused pipeline only");
     const bool k4 = rp.n_offsets != 1;
     if (resident && resident->waves && first && fused && rp.has_tris && rp.chunk_blocks <= 1) {
@@ -674,12 +675,12 @@ void launch_shade(const uint8_t *scene, uint32_t scene_bytes, const RenderParams
             const uint32_t n_seg = nseg(rp.n_lanes), grid = std::min<uint32_t>((uint32_t) n_cu, (n_seg + waves - 1) / waves);
             const uint32_t memo = rp.memo_obj != 0xffffffffu ? 1u : 0u;
             const ShadeLaunch L = { false, 2, waves, grid, lds, s,
-                                    { scene, scene_bytes, 0u, rp, q, qin, count_in, qout, alive_out, shadow_out, depth, trace_next ? 1u : 0u, dbg, film, film_stride, n_seg, resident->small_off, resident->small_words, memo, resident_stack_bytes(stack_depth, waves, rp.n_offsets != 1) / 4u } };
+                                    { scene, scene_bytes, 0u, rp, q, qin, count_in, qout, alive_out, shadow_out, depth, trace_next ? 1u : 0u, dbg, film, film_stride, n_seg, resident->small_off, resident->small_words, memo, resident_stack_bytes(stack_depth, waves, rp.n_offsets != 1) / 4u }, facts };
             if (hipMemsetAsync(q.seg_counter, 0, 4, s) != hipSuccess) throw std::runtime_error("hipMemsetAsync(seg_counter) failed");
             if (rp.has_spec == 2) launch_shade_resident2(k4, L);
             else if (rp.has_spec) launch_shade_resident1(k4, L);
-            else launch_shade_resident0(rp.has_area != 0, k4, L);
-            return;
+            else return launch_shade_resident0(rp.has_area != 0, k4, L);
+            return false;
         }
     }
     // + the instance memo; a flat scene with one instance keeps the instance matrix there as well (k_shade: memo_m_lds) and needs no traversal stack beyond one entry
@@ -688,11 +689,12 @@ void launch_shade(const uint8_t *scene, uint32_t scene_bytes, const RenderParams
     const uint32_t sw = stage_words_for(scene_bytes, shade_stack, ls), grid = nseg(rp.n_lanes) * (first && rp.chunk_blocks > 1 ? rp.chunk_blocks : 1u), lds = sw * 16 + shade_stack;
     check_lds(lds);
     const ShadeLaunch L = { sw != 0, first ? 2 : fused ? 1 : 0, 0u, grid, lds, s,
-                            { scene, scene_bytes, sw, rp, q, qin, count_in, qout, alive_out, shadow_out, depth, trace_next ? 1u : 0u, dbg, film, film_stride, nseg(rp.n_lanes), 0u, 0u, 0u, 0u } };
+                            { scene, scene_bytes, sw, rp, q, qin, count_in, qout, alive_out, shadow_out, depth, trace_next ? 1u : 0u, dbg, film, film_stride, nseg(rp.n_lanes), 0u, 0u, 0u, 0u }, first ? facts : 0u };
     if (rp.has_spec == 2) launch_shade_spec2(k4, L);
     else if (rp.has_spec) launch_shade_spec1(k4, L);
     else if (rp.has_tris) launch_shade_mesh(rp.has_area != 0, k4, L);
-    else launch_shade_plain(rp.has_area != 0, k4, L);
+    else return launch_shade_plain(rp.has_area != 0, k4, L);
+    return false;
 }
 void launch_velocity(const uint8_t *scene, uint32_t scene_bytes, const RenderParams &rp, const Queues &q, uint32_t stack_depth, const LaunchSwitches &ls, hipStream_t s) {
     if (rp.n_lanes == 0) return;

@@ -106,6 +106,7 @@ struct dtof_scene {
     hipStream_t stream = nullptr, stream2 = nullptr;   // stream: the library's own, or the caller's (dtof_scene_set_stream)
     hipStream_t own_stream = nullptr;                    // what ensure_device created and the destructor destroys
     std::atomic<bool> stop { false };
+    uint64_t plan_facts_launches = 0;        // first-bounce launches that took a kernel compiled with plan facts, since the scene was loaded (dtof_scene_plan_facts_launches)
     // reusable statistics plumbing (creating events / pinned memory per call costs ~0.3 ms)
     std::vector<hipEvent_t> event_pool; size_t events_used = 0;
     // frames enqueued by dtof_render_rows_async and not collected yet: their events (frame, stages) and launch counters; no host synchronisation until dtof_async_collect
@@ -411,8 +412,8 @@ struct FramePlan {
     uint32_t n_passes = 1, run_passes = 1, dump_pass = 0;
     uint64_t lanes_per_row = 0, first = 0, last = 0, batch = 1;   // every pass: lanes [first, last) in batches of `batch`
     int n_streams = 1;
-    bool fused = false, first_inline = false, skip_tail = false, fuse_splat_ok = false, terminal_ok = false;
-    uint32_t max_inline = 1, chunk_segs = 0, res_units = 1;
+    bool fused = false, first_inline = false, skip_tail = false, fuse_splat_ok = false, terminal_ok = false, plan_facts = false;
+    uint32_t max_inline = 1, chunk_segs = 0, res_units = 1, n_emitters = 0;
     ResidentStage resident;
     LaunchSwitches launch;                // launch.defer: the DEFER mode, 0 when the workspaces have no DEFER lists
     // does iteration `it` of the bounce loop run?  (the reference's last iteration only looks for emitter hits, dopplertofpath.cpp:136-171: skip_tail drops it)
@@ -433,6 +434,28 @@ struct FramePlan {
         // fused splat: every wave of a whole-path launch holds the 64 samples of one pixel and adds their footprint to the film itself (no round trip through q.res)
         l.splat_here = whole_path && fuse_splat_ok;
         return l;
+    }
+    // The plan facts (dtof_kernels.h: kFact*) a first-bounce launch satisfies: `r` is the launch's RenderParams (batch and span fields set), depth0 its first iteration,
+    // identity_queue = it reads neither a lane queue nor segment counts, dump = it writes the lane dump's camera rays.  A launcher takes a kernel compiled with a mask of
+    // these only if every fact of the mask is set here; 0 (DTOF_PLAN_FACTS=0, or any launch but a first-bounce one) selects the generic kernels.
+    uint32_t launch_facts(const RenderParams &r, const LaunchSpan &l, uint32_t depth0, bool first, bool identity_queue, bool dump) const {
+        if (!plan_facts || !first) return 0u;
+        const uint32_t depth_end = depth0 + l.span;   // one past the deepest iteration the launch runs
+        uint32_t f = 0;
+        if (r.n_passes == 1 && r.pass == 0) f |= kFactSinglePass;
+        if (r.integrator == 0 && r.sampler_kind == SAMPLER_CORRELATED) f |= kFactDopplerCorr;
+        if (!dump && !r.want_valid) f |= kFactNoLaneOutput;
+        if (identity_queue) f |= kFactIdentityQueue;
+        if (r.rr_depth > depth_end) f |= kFactNoRoulette;                 // the deepest test is ndepth = depth_end >= rr_depth
+        if (depth_end < r.path_correlation_depth) f |= kFactCorrelated;   // the deepest test is depth_end - 1 + 1 < path_correlation_depth
+        if (!l.next_runs && l.terminal) f |= kFactWholePath;
+        if (l.chunk_blocks == 1) f |= kFactOneBlock;
+        if (n_emitters == 1) f |= kFactOneEmitter;
+        // every segment's count is min(512, n_lanes - 512 S), a multiple of 64 if n_lanes is one: each 64-lane chunk is then whole, and its lanes are the 64-aligned
+        // lanes [lane_base + 512 S + cbase, + 64), samples of one pixel when spp is a power of two >= 64.  (A striped shard -- a rank's share of a frame, virtual lanes --
+        // keeps the run-time test and with it the generic kernel.)
+        if (identity_queue && r.stripe_rows == 0 && r.spp_log2 != 0xffffffffu && r.spp_log2 >= 6 && (r.lane_base & 63u) == 0 && (r.n_lanes & 63u) == 0) f |= kFactWavePixel;
+        return f;
     }
 };
 
@@ -507,6 +530,7 @@ void plan_lanes(FramePlan &p, const dtof_scene *sc, const RenderRequest &rq) {
 //   DTOF_SPLAT          auto        dpp | generic: that splat kernel
 //   DTOF_TERMINAL_SKIP  1           0: the last iteration that runs keeps the half of the bounce nobody reads (BSDF sampling, continuation ray, throughput / RR,
 //                                   the advance of the streams) instead of its terminal form
+//   DTOF_PLAN_FACTS     1           0: a first-bounce launch always takes the generic kernel, never the one compiled with the frame plan's constants (kFact*)
 // Process-wide instead: DTOF_STAT_SLOTS (sizes the count slots), DTOF_ROCTX and DTOF_SYNC_LAUNCHES (debugging aids).
 FramePlan plan_frame(const dtof_scene *sc, const RenderRequest &rq) {
     const auto num = [](const char *name, int dflt) { const char *e = getenv(name); return e ? atoi(e) : dflt; };
@@ -597,6 +621,8 @@ FramePlan plan_frame(const dtof_scene *sc, const RenderRequest &rq) {
     // terminal form writes valid_out = 1 where want_valid asks for it.  The survivor count of that iteration is not consumed either: the statistics read a count only
     // as the input of the NEXT iteration, and no queue is compacted for a launch that does not happen.
     p.terminal_ok = on("DTOF_TERMINAL_SKIP") && p.n_passes == 1 && !t.null_lobe;
+    // kernels compiled with the plan's constants: which facts hold is decided per launch (FramePlan::launch_facts); no result depends on the switch
+    p.plan_facts = on("DTOF_PLAN_FACTS"); p.n_emitters = bh_emitters(*sc);
     rp.emitter_pmf = bh_emitters(*sc) ? 1.f / (float) bh_emitters(*sc) : 0.f;   // m_emitter_pmf (scene.cpp:96)
     // fused pipeline: the first bounce kernel generates the lanes and traces the primary rays itself
     p.first_inline = p.fused && rp.integrator != INTEGRATOR_VELOCITY && p.iteration_runs(0) && on("DTOF_FUSE_FIRST");
@@ -675,9 +701,12 @@ void render_rows(dtof_scene *sc, const RenderRequest &rq) {
             uint32_t *qout = q.q[it & 1], *alive_out = q.counts + (size_t) (2 * (it % kMaxIter)) * n_seg, *shadow_out = alive_out + n_seg;
             const Stage st_shade = first ? kStageFirst : kStageShade;
             t = tm.begin(st_shade, s);
+            const bool specialised =
             launch_shade(blob, blob_bytes, rp, q, qin, count_in, qout, alive_out, shadow_out, it + 1 - l.span, p.fused, l.next_runs, stack_depth, p.launch, s, first,
-                         first && dump_now ? sc->ws.dbg.p : nullptr, &p.resident, l.splat_here ? rq.film : nullptr, rq.film_stride);
+                         first && dump_now ? sc->ws.dbg.p : nullptr, &p.resident, l.splat_here ? rq.film : nullptr, rq.film_stride,
+                         p.launch_facts(rp, l, it + 1 - l.span, first, qin == nullptr && count_in == nullptr, dump_now));
             tm.end(st_shade, t, s);
+            if (specialised) { sc->plan_facts_launches++; if (stats) stats->n_plan_facts_launches++; }
             fused_splat_done |= l.splat_here;
             if (stats && l.splat_here) stats->n_fused_splat_launches++;
             if (stats && first) { stats->n_launches_first++; stats->n_inline_iterations += l.span; batch_inline.push_back(l.span); }
@@ -1089,7 +1118,7 @@ int dtof_async_collect(dtof_scene *sc, dtof_render_stats *sum, double *frame_ms,
             sum->ms_shade += stage_ms(f.ev[kStageShade]) + stage_ms(f.ev[kStageFirst]); sum->ms_shadow += stage_ms(f.ev[kStageShadow]); sum->ms_splat += stage_ms(f.ev[kStageSplat]);
             sum->n_paths += f.counters.n_paths; sum->n_batches += f.counters.n_batches;
             sum->n_launches_trace += f.counters.n_launches_trace; sum->n_launches_shade += f.counters.n_launches_shade; sum->n_launches_shadow += f.counters.n_launches_shadow;
-            sum->n_launches_first += f.counters.n_launches_first; sum->n_inline_iterations += f.counters.n_inline_iterations; sum->n_fused_splat_launches += f.counters.n_fused_splat_launches;
+            sum->n_launches_first += f.counters.n_launches_first; sum->n_inline_iterations += f.counters.n_inline_iterations; sum->n_fused_splat_launches += f.counters.n_fused_splat_launches; sum->n_plan_facts_launches += f.counters.n_plan_facts_launches;
         }
         sc->deferred.clear(); sc->events_used = 0;
     });
@@ -1159,6 +1188,7 @@ int dtof_render(dtof_scene *sc, uint32_t sensor_index, uint32_t seed, uint32_t s
 }
 
 void dtof_cancel(dtof_scene *sc) { if (sc) sc->stop = true; }
+uint64_t dtof_scene_plan_facts_launches(const dtof_scene *sc) { return sc ? sc->plan_facts_launches : 0; }
 
 int dtof_sample_lanes_valid(dtof_scene *sc, uint32_t seed, uint32_t spp, uint64_t lane_begin, uint64_t n, float *out, uint32_t *valid) {
     return guarded([&] {

@@ -159,13 +159,16 @@ DTOF_D void camera_ray(const RenderParams &rp, float ax, float ay, float apx, fl
 
 // PERSPECTIVE_ONLY: the sensor is known to be the plain perspective camera (the diffuse-only kernels: scenes with a thinlens / orthographic sensor run the every-BSDF
 // instantiations) -- the aperture draw and the two other ray constructions are not compiled in
-template <bool PERSPECTIVE_ONLY = false>
+// FACTS: plan facts taken as constants (dtof_kernels.h: kFact*; k_shade): a single pass, the Doppler integrator with the correlated sampler, `correlate` at every depth
+template <bool PERSPECTIVE_ONLY = false, uint32_t FACTS = 0>
 DTOF_D PrimaryLane generate_lane(const RenderParams &rp, uint32_t lane, bool wave_pixel = false, uint32_t vlane = 0) {
+    constexpr bool F_SINGLE_PASS = (FACTS & kFactSinglePass) != 0, F_DOPPLER_CORR = (FACTS & kFactDopplerCorr) != 0, F_CORRELATED = (FACTS & kFactCorrelated) != 0;
     // m_rng_time is drawn from by every strategy of the correlated sampler but uniform and stratified (correlated.cpp:96-106)
-    const bool needs_tm = rp.integrator == 0 && rp.sampler_kind == SAMPLER_CORRELATED && rp.time_sampling >= TIME_ANTITHETIC;   // every strategy but uniform / stratified (:103-107)
+    const bool needs_tm = (F_DOPPLER_CORR || (rp.integrator == 0 && rp.sampler_kind == SAMPLER_CORRELATED)) && rp.time_sampling >= TIME_ANTITHETIC;   // every strategy but uniform / stratified (:103-107)
     Rng main, tm, path; tm.state = 0; tm.inc = 1;
-    uint2 *const carried = rp.n_passes > 1 ? rp.pass_rng + (size_t) (vlane - rp.pass_first) * 3 : nullptr;
-    if (rp.pass == 0 && wave_pixel && needs_tm && rp.tcn == 2 && rp.pcn == 2) {
+    uint2 *const carried = !F_SINGLE_PASS && rp.n_passes > 1 ? rp.pass_rng + (size_t) (vlane - rp.pass_first) * 3 : nullptr;
+    const uint32_t pass = F_SINGLE_PASS ? 0u : rp.pass;
+    if (pass == 0 && wave_pixel && needs_tm && rp.tcn == 2 && rp.pcn == 2) {
         // Correlated pairs (the default time_correlate_number = path_correlate_number = 2): lanes 2k and 2k + 1 share their time stream
         // TEA(seed + 1, k) and their path stream TEA(seed + 2, k) (correlated.cpp:54-63).  The even lane evaluates the first, the odd lane the
         // second, and the two swap results (quad_perm [1, 0, 3, 2]): one TEA evaluation per lane instead of two, same integers.
@@ -176,7 +179,7 @@ DTOF_D PrimaryLane generate_lane(const RenderParams &rp, uint32_t lane, bool wav
         const uint32_t b0 = (uint32_t) __builtin_amdgcn_update_dpp(0, (int) a0, 0xb1, 0xf, 0xf, false), b1 = (uint32_t) __builtin_amdgcn_update_dpp(0, (int) a1, 0xb1, 0xf, 0xf, false);
         pcg_seed(odd ? b0 : a0, odd ? b1 : a1, tm.state, tm.inc);
         pcg_seed(odd ? a0 : b0, odd ? a1 : b1, path.state, path.inc);
-    } else if (rp.pass == 0) {
+    } else if (pass == 0) {
         main = seed_stream(rp.seed_value, lane);
         if (needs_tm) tm = seed_stream(rp.seed_value + 1, fdiv(lane, rp.d_tcn));
         path = seed_stream(rp.seed_value + 2, fdiv(lane, rp.d_pcn));
@@ -189,16 +192,16 @@ DTOF_D PrimaryLane generate_lane(const RenderParams &rp, uint32_t lane, bool wav
     const uint32_t pix = fdiv(lane, rp.d_spp);
     // current_sample_index = m_sample_index * samples_per_wavefront + lane % samples_per_wavefront (sampler.cpp:94-103); Sampler::advance
     // bumps m_sample_index once per pass (sampler.cpp:52-55)
-    uint32_t si = (rp.spp > 1 ? lane - pix * rp.spp : 0) + rp.pass * rp.spp;
+    uint32_t si = (rp.spp > 1 ? lane - pix * rp.spp : 0) + pass * rp.spp;
     const PixelInfo pi = wave_pixel ? pixel_info<true>(rp, pix) : pixel_info<false>(rp, pix);
     const uint32_t perm_seed = pi.perm_seed; const float posx = pi.posx, posy = pi.posy;
     uint32_t dim = 0;
 
-    bool cp = rp.path_correlation_depth > 0;
-    const bool doppler = rp.integrator == 0;
+    bool cp = F_CORRELATED || rp.path_correlation_depth > 0;
+    const bool doppler = F_DOPPLER_CORR || rp.integrator == 0;
     // one stream only: the plain branch of render_sample (integrator.cpp:416-431: next_2d / next_1d), and every sampler but
     // `correlated` (Sampler::next_*_correlate default to next_1d / next_2d, include/mitsuba/render/sampler.h:141-144)
-    const bool single = !doppler || rp.sampler_kind != SAMPLER_CORRELATED;
+    const bool single = !F_DOPPLER_CORR && (!doppler || rp.sampler_kind != SAMPLER_CORRELATED);
     float jx = single ? next_f32(main) : next_correlate(main, path, cp), jy = single ? next_f32(main) : next_correlate(main, path, cp);
     float spx = posx + jx, spy = posy + jy;
     float ax = fmaf(spx, rp.scale_x, rp.offset_x), ay = fmaf(spy, rp.scale_y, rp.offset_y);
@@ -209,8 +212,8 @@ DTOF_D PrimaryLane generate_lane(const RenderParams &rp, uint32_t lane, bool wav
     float time = rp.shutter_open;
     if (rp.shutter_open_time > 0.f) {
         float u;
-        if (!doppler || rp.sampler_kind == SAMPLER_INDEPENDENT) u = next_f32(main);   // Sampler::next_1d_time -> next_1d (sampler.h:131-132)
-        else if (rp.sampler_kind == SAMPLER_CORRELATED) u = next_time(rp, main, tm, si, perm_seed, dim);
+        if (!F_DOPPLER_CORR && (!doppler || rp.sampler_kind == SAMPLER_INDEPENDENT)) u = next_f32(main);   // Sampler::next_1d_time -> next_1d (sampler.h:131-132)
+        else if (F_DOPPLER_CORR || rp.sampler_kind == SAMPLER_CORRELATED) u = next_time(rp, main, tm, si, perm_seed, dim);
         else {   // TimeStratifiedSampler::next_1d_time (timestratified.cpp:117-129): the strategy arguments are ignored
             uint32_t p = permute_kensler(si, rp.sample_count, perm_seed + dim++, rp.d_sample_count);
             float j = rp.jitter ? next_f32(main) : .5f;

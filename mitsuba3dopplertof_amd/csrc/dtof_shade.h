@@ -340,7 +340,9 @@ void launch_bsdf_eval_spec(const uint8_t *scene, uint32_t shape_index, const flo
 // still comes through the vector L1 is the 128-byte instance record of a leaf visit and the queue traffic: the unstaged kernel keeps the CU's
 // vector memory path busy 75 - 85 % of the time (TA / TD busy counters, profiles/r03_pmc_domino_fused*.txt) with the four 16-byte node loads
 // per step per lane, and waits for it.
-template <bool LDS, int MODE, bool AREA, int KMAX, bool MESH, int SPEC, int RESW = 0, bool RH16 = false>   // RH16: the resident stage holds HALF-FLOAT node records (DNode16): a TLAS of up to 2 * kResNodes nodes in the LDS of kResNodes float ones; SPEC: 0 diffuse-only scenes, 1 every BSDF / emitter / texture, 2 = 1 + blendbsdf (the BSDF chain in a loop over two records)
+// FACTS: the plan facts (dtof_kernels.h: kFact*) this instantiation takes as constants instead of reading them, launch-uniform, from the kernarg segment where they
+// are used.  0 = none: every F_* below is then a compile-time `false` in front of the run-time read, and the kernel is the text it was without the parameter.
+template <bool LDS, int MODE, bool AREA, int KMAX, bool MESH, int SPEC, int RESW = 0, bool RH16 = false, uint32_t FACTS = 0>   // RH16: the resident stage holds HALF-FLOAT node records (DNode16): a TLAS of up to 2 * kResNodes nodes in the LDS of kResNodes float ones; SPEC: 0 diffuse-only scenes, 1 every BSDF / emitter / texture, 2 = 1 + blendbsdf (the BSDF chain in a loop over two records)
 #ifndef DTOF_MESH_WAVES
 #define DTOF_MESH_WAVES 3   // waves / SIMD the fused kernels with triangle code are compiled for (A/B: make variant DEFS=-DDTOF_MESH_WAVES=4)
 #endif
@@ -370,6 +372,13 @@ template <bool LDS, int MODE, bool AREA, int KMAX, bool MESH, int SPEC, int RESW
 #endif
 __global__ __launch_bounds__(RESW ? RESW * 64 : kShadeBlock, RESW ? RESW / 4 : (MODE == 2 && !MESH && !SPEC && KMAX == 1) ? 4 : (MODE != 0 && MESH) ? ((SPEC && KMAX > 1) ? 2 : DTOF_MESH_WAVES) : 1) void k_shade(ShadeArgs args_by_value) {
     constexpr bool FUSED = MODE != 0, FIRST = MODE == 2;
+    static_assert(FACTS == 0 || MODE == 2, "plan facts describe a first-bounce launch");
+    constexpr bool F_SINGLE_PASS = (FACTS & kFactSinglePass) != 0, F_DOPPLER_CORR = (FACTS & kFactDopplerCorr) != 0, F_NO_LANE_OUT = (FACTS & kFactNoLaneOutput) != 0;
+    constexpr bool F_IDENTITY = (FACTS & kFactIdentityQueue) != 0, F_NO_RR = (FACTS & kFactNoRoulette) != 0, F_CORRELATED = (FACTS & kFactCorrelated) != 0;
+    constexpr bool F_WHOLE_PATH = (FACTS & kFactWholePath) != 0, F_ONE_BLOCK = (FACTS & kFactOneBlock) != 0, F_ONE_EMITTER = (FACTS & kFactOneEmitter) != 0;
+    constexpr bool F_WAVE_PIXEL = (FACTS & kFactWavePixel) != 0;
+    static_assert(!F_WAVE_PIXEL || F_IDENTITY, "whole waves of one pixel are provable for an identity queue only");
+    static_assert(!F_ONE_BLOCK || RESW == 0, "blocks per segment belong to the classic launch");
     constexpr bool RES_LDS = RESW != 0 && KMAX > 1 && DTOF_K4_RES_LDS;   // several films, resident stage: running results in LDS columns
     constexpr bool S16 = RESW != 0 && KMAX > 1;                           // ... whose LDS comes from 16-bit traversal stacks (dtof_traverse.h: encode_child16)
     constexpr bool RES_MEM = FIRST && KMAX > 1 && (RES_LDS || DTOF_K4_RES_MEM);   // several films: running results outside the registers (LDS, else q.res), the pending NEE sample K-independent (see above)
@@ -400,7 +409,7 @@ __global__ __launch_bounds__(RESW ? RESW * 64 : kShadeBlock, RESW ? RESW / 4 : (
     // One block per 512-lane segment -- or, for a small frame whose whole path runs inline (rp.chunk_blocks = 8: nothing is compacted for a
     // later launch), one block per 64-lane chunk, so that a 1 M-lane frame is 16 384 waves instead of 2 048; the per-segment statistics are
     // then accumulated with atomics into slots the host has zeroed.
-    const uint32_t sub = FIRST ? (RESW ? A0.rp.res_units : A0.rp.chunk_blocks) : 1u;   // work units per segment: blocks (1 or kSeg / kShadeBlock), resident: what a wave takes from the counter at a time
+    const uint32_t sub = FIRST ? (RESW ? A0.rp.res_units : F_ONE_BLOCK ? 1u : A0.rp.chunk_blocks) : 1u;   // work units per segment: blocks (1 or kSeg / kShadeBlock), resident: what a wave takes from the counter at a time
     const uint32_t unit_lanes = kSeg / sub;
     SceneView sv_res;
     if (RESW) {   // the resident stage: every thread of the block copies, ONE barrier, then the waves go their own ways
@@ -448,7 +457,7 @@ __global__ __launch_bounds__(RESW ? RESW * 64 : kShadeBlock, RESW ? RESW / 4 : (
         seg = sub > 1 ? blockIdx.x / sub : blockIdx.x; sub_index = sub > 1 ? blockIdx.x - seg * sub : 0u;
     }
     (void) seg_first;
-    const uint32_t count = seg_count(A0.count_in, seg, A0.rp.n_lanes);
+    const uint32_t count = seg_count(F_IDENTITY ? nullptr : A0.count_in, seg, A0.rp.n_lanes);
     uint32_t n_alive = 0, n_shadow = 0;
     if (FIRST && lane_id < 2 * kMaxInline) s_inline[lane_id] = 0;   // a wave's own slots: no barrier needed
     if (count != 0) {
@@ -461,10 +470,11 @@ __global__ __launch_bounds__(RESW ? RESW * 64 : kShadeBlock, RESW ? RESW / 4 : (
     asm volatile("" : "+s"(rebase));
     const ShadeArgs &A = *(const ShadeArgs *) (kernarg + rebase);
     const RenderParams &rp = A.rp; const Queues &q = A.q;
-    const uint32_t *const qin = A.qin; uint32_t *const qout = A.qout; const uint32_t depth0 = A.depth, trace_next_last = A.trace_next; LaneDebug *const dbg = A.dbg;
+    const uint32_t *const qin = F_IDENTITY ? nullptr : A.qin; uint32_t *const qout = A.qout; const uint32_t depth0 = A.depth, trace_next_last = F_WHOLE_PATH ? 0u : A.trace_next;
+    LaneDebug *const dbg = F_NO_LANE_OUT ? nullptr : A.dbg;
     const uint32_t flat = FUSED && !MESH ? rp.flat_objects : 0u;   // != 0: the scene's object count, every ray tests them all (trace_flat)
     uint32_t j = cbase + lane_id;
-    bool in_range = j < count;
+    bool in_range = F_WAVE_PIXEL || j < count;   // (the fact: count - cbase >= 64 in every chunk)
     bool alive = false, want_shadow = false;
     uint32_t l = 0;
     // every register of the path state starts defined: a build of these kernels whose K = 4 every-BSDF instantiations ran at three waves per SIMD produced films that
@@ -544,7 +554,7 @@ __global__ __launch_bounds__(RESW ? RESW * 64 : kShadeBlock, RESW ? RESW / 4 : (
     // the wave's 64 lanes are the 64-aligned lanes [lane_base + seg * 512 + cbase, + 64): samples of one pixel if spp is a multiple of 64
     // ... AND the whole wave is in range: the pair swap of the correlated seeding (generate_lane) reads the partner lane, which a ragged tail
     // (dtof_sample_lanes with an odd count) would leave inactive
-    const bool wave_pixel = FIRST && rp.spp_log2 != 0xffffffffu && rp.spp_log2 >= 6 && (rp.lane_base & 63u) == 0 && count - cbase >= (uint32_t) kShadeBlock;
+    const bool wave_pixel = F_WAVE_PIXEL || (FIRST && rp.spp_log2 != 0xffffffffu && rp.spp_log2 >= 6 && (rp.lane_base & 63u) == 0 && count - cbase >= (uint32_t) kShadeBlock);
     // Fused splat (uniform): this launch runs the whole path of its lanes (nobody continues) and the host handed in the film -- the wave reduces the footprint
     // values of its 64 samples itself and issues the film atomics, the result never goes through q.res / q.pos and the splat kernel's round trip through HBM
     const bool fuse_splat = FIRST && A.film != nullptr;
@@ -552,7 +562,7 @@ __global__ __launch_bounds__(RESW ? RESW * 64 : kShadeBlock, RESW ? RESW / 4 : (
     if (in_range) {
         l = qin ? qin[seg * kSeg + j] : seg * kSeg + j;
         if (FIRST) {
-            const PrimaryLane pl = generate_lane<SPEC == 0>(rp, global_lane(rp, rp.lane_base + l), wave_pixel, rp.lane_base + l);
+            const PrimaryLane pl = generate_lane<SPEC == 0, FACTS>(rp, global_lane(rp, rp.lane_base + l), wave_pixel, rp.lane_base + l);
             ra = pl.ray_a; rb = pl.ray_b; main = pl.main; path = pl.path; st = make_float4(1.f, 1.f, 1.f, 0.f);
             if (PARK) park_store();
             pos_reg = pl.pos;
@@ -580,7 +590,7 @@ __global__ __launch_bounds__(RESW ? RESW * 64 : kShadeBlock, RESW ? RESW / 4 : (
     // the TERMINAL iteration (uniform; RenderParams::terminal): nothing continues a path after it and nobody reads what the second half of the bounce leaves behind.
     // Where it still samples an emitter (active_next: the last iteration that runs in a scene without surface emitters) it keeps the emitter-hit term, the emitter
     // sample with its two draws, the BSDF's value and density for it and the NEE candidate with its shadow ray; where it does not, only the emitter-hit term.
-    const bool terminal = last && rp.terminal != 0;
+    const bool terminal = last && (F_WHOLE_PATH || rp.terminal != 0);
     alive = false; want_shadow = false;
     if (lane_on) {
         if (PARK) park_load();
@@ -593,7 +603,7 @@ __global__ __launch_bounds__(RESW ? RESW * 64 : kShadeBlock, RESW ? RESW / 4 : (
                 path.state = (uint64_t) rs.z | ((uint64_t) rs.w << 32); path.inc = ((uint64_t) ri.y << 1) | 1u;
             }
         }
-        if (hid == 0xffffffffu && rp.n_passes > 1) {
+        if (!F_SINGLE_PASS && hid == 0xffffffffu && rp.n_passes > 1) {
             // several passes: the streams are carried into the next pass, so the six draws the reference makes for EVERY lane that is
             // active at the entry of an iteration (App. A step 5; both streams advance on each, correlated.cpp:156-161) also happen
             // for the lanes whose ray misses (single-pass renders drop the state of a finished path instead)
@@ -616,7 +626,7 @@ __global__ __launch_bounds__(RESW ? RESW * 64 : kShadeBlock, RESW ? RESW / 4 : (
                     for (int k = 0; k < KMAX; ++k) if (KMAX == 1 || k < rp.n_offsets) res_put(k, zero4);
                 }
             }
-            if (rp.want_valid) q.valid_out[l] = make_float4(valid_in ? 1.f : 0.f, 0.f, 0.f, 0.f);
+            if (!F_NO_LANE_OUT && rp.want_valid) q.valid_out[l] = make_float4(valid_in ? 1.f : 0.f, 0.f, 0.f, 0.f);
         }
         if (SPEC && hid == 0xffffffffu && rp.has_env && valid_in) {
             // The ray left the scene: si.emitter(scene) is the environment (dopplertofpath.cpp:150-168).  DirectionSample(scene, si, prev_si)
@@ -647,9 +657,9 @@ __global__ __launch_bounds__(RESW ? RESW * 64 : kShadeBlock, RESW ? RESW / 4 : (
             V3 thr = mk(st.x, st.y, st.z); float path_length = st.w;
             float eta_path = 1.f; bool prev_delta = depth == 0;   // dopplertofpath.cpp:103-108: eta = 1, prev_bsdf_delta = true
             if (SPEC && depth > 0) { const float2 sc = FIRST ? stc_reg : q.st_c[l]; eta_path = sc.x; prev_delta = FIRST ? sc.y != 0.f : ((uint32_t) sc.y & 1u) != 0u; }
-            bool correlate = (depth + 1) < rp.path_correlation_depth;
-            const bool plain = rp.integrator != 0;   // `path`: no modulation weight
-            const bool single = plain || rp.sampler_kind != SAMPLER_CORRELATED;   // main stream only (path.cpp:197,213-214,273; sampler.h:141-144)
+            bool correlate = F_CORRELATED || (depth + 1) < rp.path_correlation_depth;
+            const bool plain = !F_DOPPLER_CORR && rp.integrator != 0;   // `path`: no modulation weight
+            const bool single = !F_DOPPLER_CORR && (plain || rp.sampler_kind != SAMPLER_CORRELATED);   // main stream only (path.cpp:197,213-214,273; sampler.h:141-144)
             float t = u2f(hh.x);
             path_length += t * eta_path;   // dopplertofpath.cpp:141 (eta stays 1 without dielectrics)
             bool active_next = depth + 1 < rp.max_depth;
@@ -716,7 +726,7 @@ __global__ __launch_bounds__(RESW ? RESW * 64 : kShadeBlock, RESW ? RESW / 4 : (
 #pragma unroll
                     for (int k = 0; k < KMAX; ++k) if (KMAX == 1 || k < rp.n_offsets) res_put(k, rcur[RES_MEM ? 0 : k]);
                 }
-                if (rp.want_valid) q.valid_out[l] = make_float4(1.f, 0.f, 0.f, 0.f);
+                if (!F_NO_LANE_OUT && rp.want_valid) q.valid_out[l] = make_float4(1.f, 0.f, 0.f, 0.f);
             } else {
             // ---- emitter sampling (scene.cpp:235-291; point.cpp:118-147; area.cpp:116-159 + shape.cpp:370-384 + rectangle.cpp:152-166)
             // The six draws of this iteration (App. A step 5) come from ONE stream: the main one (`path`, other samplers, correlate = false) or
@@ -726,10 +736,10 @@ __global__ __launch_bounds__(RESW ? RESW * 64 : kShadeBlock, RESW ? RESW / 4 : (
             Rng sel = use_path ? path : main;
             float e1 = next_f32(sel), e2 = next_f32(sel);
             // has_flag(bsdf->flags(), BSDFFlags::Smooth) (:178): diffuse, (rough)plastic and roughconductor have a smooth lobe
-            bool active_em = active_next && sv.n_emitters > 0 && (!SPEC || bsdf_is_smooth(sh->bsdf) || ((sh->flags & (SF_BLEND | SF_TWOSIDED2)) && bsdf_is_smooth(sv.shapes[sh->blend_other].bsdf)));   // a blend (a twosided of two BSDFs) has the flags of both
+            bool active_em = active_next && (F_ONE_EMITTER || sv.n_emitters > 0) && (!SPEC || bsdf_is_smooth(sh->bsdf) || ((sh->flags & (SF_BLEND | SF_TWOSIDED2)) && bsdf_is_smooth(sv.shapes[sh->blend_other].bsdf)));   // a blend (a twosided of two BSDFs) has the flags of both
             V3 em_weight = mk(0, 0, 0), wo = mk(0, 0, 0); float ds_dist = 0.f, ds_pdf = 0.f; bool ds_delta = true;
             if (active_em) {
-                uint32_t ne = sv.n_emitters, idx = 0; float em_w = 1.f, sx = e1;
+                uint32_t ne = F_ONE_EMITTER ? 1u : sv.n_emitters, idx = 0; float em_w = 1.f, sx = e1;
                 if (ne > 1) { float scaled = e1 * (float) ne; idx = (uint32_t) scaled; if (idx > ne - 1) idx = ne - 1; em_w = (float) ne; sx = scaled - (float) idx; }
                 const DEmitter &em = sv.emitters[idx];
                 V3 dsp, dd; bool em_active = true;
@@ -868,7 +878,7 @@ __global__ __launch_bounds__(RESW ? RESW * 64 : kShadeBlock, RESW ? RESW / 4 : (
                 for (int k = 0; k < KMAX; ++k) if (KMAX == 1 || k < rp.n_offsets) res_put(k, rcur[RES_MEM ? 0 : k]);
             }
             if (terminal) {   // the path ends here whatever it sampled; valid_ray as above
-                if (rp.want_valid) q.valid_out[l] = make_float4(1.f, 0.f, 0.f, 0.f);
+                if (!F_NO_LANE_OUT && rp.want_valid) q.valid_out[l] = make_float4(1.f, 0.f, 0.f, 0.f);
             } else {
             // ---- continuation (dopplertofpath.cpp:232-276)
             V3 nd = vfma(si.sh_n, bs_wo.z, vfma(si.sh_t, bs_wo.y, si.sh_s * bs_wo.x));   // Frame::to_world
@@ -878,7 +888,7 @@ __global__ __launch_bounds__(RESW ? RESW * 64 : kShadeBlock, RESW ? RESW / 4 : (
             uint32_t ndepth = depth + 1;
             float thr_max = fmax_(fmax_(thr.x, thr.y), thr.z);
             float rr_prob = fmin_(thr_max * sqr(eta), .95f);
-            bool rr_active = ndepth >= rp.rr_depth;
+            bool rr_active = !F_NO_RR && ndepth >= rp.rr_depth;   // (the fact: the draw below still advances the stream, its value is not looked at)
             bool rr_continue = next_f32(sel) < rr_prob;
             if (use_path) { path.state = sel.state; main.state = pcg_jump6(main.state, main.inc); }
             else { main.state = sel.state; if (!single) path.state = pcg_jump6(path.state, path.inc); }
@@ -895,7 +905,7 @@ __global__ __launch_bounds__(RESW ? RESW * 64 : kShadeBlock, RESW ? RESW / 4 : (
                     for (int k = 0; k < KMAX; ++k) if (KMAX == 1 || k < rp.n_offsets) res_put(k, zero4);
                 }
             }
-            if (ends && rp.want_valid) q.valid_out[l] = make_float4(valid_now ? 1.f : 0.f, 0.f, 0.f, 0.f);
+            if (!F_NO_LANE_OUT && ends && rp.want_valid) q.valid_out[l] = make_float4(valid_now ? 1.f : 0.f, 0.f, 0.f, 0.f);
             if (FIRST) valid_reg = valid_now;
             if (alive) {
                 nra = make_float4(no.x, no.y, no.z, time); nrb = make_float4(nd.x, nd.y, nd.z, kLargest);
@@ -912,7 +922,7 @@ __global__ __launch_bounds__(RESW ? RESW * 64 : kShadeBlock, RESW ? RESW / 4 : (
                 if (PARK) park_store();
                 DTOF_POISON_CHECK();   // the state of a path that continues
             }
-            if ((alive && (!FIRST || last) && trace_next) || rp.n_passes > 1)   // several passes: the state of a finished path is what its lane starts the next pass with
+            if ((alive && (!FIRST || last) && trace_next) || (!F_SINGLE_PASS && rp.n_passes > 1))   // several passes: the state of a finished path is what its lane starts the next pass with
                 q.rng_a[l] = make_uint4((uint32_t) main.state, (uint32_t) (main.state >> 32), (uint32_t) path.state, (uint32_t) (path.state >> 32));
             }   // !terminal: continuation
             }   // emitter sampling and what follows it

@@ -3,9 +3,26 @@
 
 namespace dtof {
 
-void launch_shade_resident0(bool area, bool k4, const ShadeLaunch &L) {
+// the resident kernel of one film at 16 waves (Domino, C4) compiled with the frame plan's constants (dtof_kernels.h: kFact*); the LDS attribute as launch_resident_waves keeps it
+static void launch_resident_facts(const ShadeLaunch &L) {
+    static std::atomic<uint32_t> attr_lds[64];
+    int dev = 0; (void) hipGetDevice(&dev);
+    std::atomic<uint32_t> &mark = attr_lds[(unsigned) dev & 63u];
+    const auto kernel = k_shade<false, 2, false, 1, true, 0, 16, false, kResidentFacts>;
+    if (L.lds > mark.load()) {
+        if (hipFuncSetAttribute((const void *) kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int) L.lds) != hipSuccess)
+            throw std::runtime_error("hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed");
+        mark.store(L.lds);
+    }
+    hipLaunchKernelGGL(kernel, dim3(L.grid), dim3(16 * 64), L.lds, L.stream, L.args);
+}
+
+bool launch_shade_resident0(bool area, bool k4, const ShadeLaunch &L) {
+    // taken when the launch satisfies every fact of the mask, the generic instantiations below otherwise
+    if (kResidentFacts != 0 && !area && !k4 && L.waves == 16 && !L.args.rp.res_half && (L.facts & kResidentFacts) == kResidentFacts) { launch_resident_facts(L); return true; }
     if (area) { if (k4) launch_resident_variant<true, kMaxOffsets, 0>(L); else launch_resident_variant<true, 1, 0>(L); }
     else      { if (k4) launch_resident_variant<false, kMaxOffsets, 0>(L); else launch_resident_variant<false, 1, 0>(L); }
+    return false;
 }
 
 }  // namespace dtof
