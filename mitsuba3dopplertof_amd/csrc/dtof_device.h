@@ -80,9 +80,10 @@ DTOF_D float dpp_add(float v) {
 }
 
 // Generic per-lane splat (any filter radius / any spp): direct float atomics.
+template <int F = -1>   // F >= 0: the filter is known at compile time (no box branch, filter_weight<F>)
 DTOF_D void splat_lane(const RenderParams &rp, float *film, float spx, float spy, int pixel_x, int pixel_y, float r, float g, float b) {
     int W = rp.crop_w, H = rp.crop_h;
-    if (rp.filter == FILTER_BOX) {
+    if (F >= 0 ? F == FILTER_BOX : rp.filter == FILTER_BOX) {
         // block->put(box_filter ? pos : sample_pos) (integrator.cpp:540-541): the box filter splats at the lane's own pixel
         int x = pixel_x, y = pixel_y;
         if ((unsigned) x < (unsigned) W && (unsigned) y < (unsigned) H) {
@@ -96,9 +97,9 @@ DTOF_D void splat_lane(const RenderParams &rp, float *film, float spx, float spy
     float relx = (float) pix + .5f - spx, rely = (float) piy + .5f - spy;
     int lx = pix - rp.crop_x, ly = piy - rp.crop_y;
     for (int ys = 0; ys < cnt; ++ys) {
-        float wy = filter_weight(rp, rely + (float) ys);
+        float wy = filter_weight<F>(rp, rely + (float) ys);
         for (int xs = 0; xs < cnt; ++xs) {
-            float w = filter_weight(rp, relx + (float) xs) * wy;
+            float w = filter_weight<F>(rp, relx + (float) xs) * wy;
             int x = lx + xs, y = ly + ys;
             if ((unsigned) x < (unsigned) W && (unsigned) y < (unsigned) H) {
                 float *p = film + 4 * ((size_t) y * W + x);

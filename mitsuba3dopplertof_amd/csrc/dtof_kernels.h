@@ -145,12 +145,28 @@ enum : uint32_t {
     kFactOneBlock       = 1u << 7,   // rp.chunk_blocks == 1: one block per 512-lane segment
     kFactOneEmitter     = 1u << 8,   // the scene has exactly one emitter
     kFactWavePixel      = 1u << 9,   // every chunk of every segment is a whole, 64-aligned wave of one pixel (k_shade: wave_pixel), proven from spp, lane_base and n_lanes
+    // ... and facts of the scene the launch traces:
+    kFactFlat           = 1u << 10,  // rp.flat_objects != 0: every ray query is trace_flat; the kernel has no traversal stack and its launch no stack column in LDS
+    kFactOneWall        = 1u << 11,  // (with kFactFlat) the scene has exactly one instance object, it is rp.memo_obj and holds ONE rectangle (DFlatObject::instance == 2,
+                                     // DFlatKinds::general == 0, ::memo == 1u << memo_obj), and its matrix sits in the lane's LDS column (k_shade: memo_m_lds)
+    kFactFusedSplat     = 1u << 12,  // A.film != nullptr: the launch splats its lanes itself (plan_frame: fuse_splat_ok -- tent filter of radius in (0.5, 1], 64 spp, one film)
 };
 // the mask the headline kernel (dtof_shade_plain.hip) is compiled with; A/B of a subset: make variant NAME=x DEFS=-DDTOF_HEADLINE_FACTS=0x17
 #ifndef DTOF_HEADLINE_FACTS
-#define DTOF_HEADLINE_FACTS 0x3ff
+#define DTOF_HEADLINE_FACTS 0xfff
 #endif
 constexpr uint32_t kHeadlineFacts = DTOF_HEADLINE_FACTS;
+// ... and a second instantiation with kFactFusedSplat on top: C2's kernel (the mask above also serves C3 and every frame that leaves the splat to the splat kernels);
+// A/B without it: DEFS=-DDTOF_HEADLINE_FUSED=0
+#ifndef DTOF_HEADLINE_FUSED
+#define DTOF_HEADLINE_FUSED 1
+#endif
+constexpr uint32_t kHeadlineFusedFacts = DTOF_HEADLINE_FUSED ? (kHeadlineFacts | kFactFusedSplat) : 0u;
+// DTOF_WALL_FRAMES (default 1): under kFactOneWall the shading frames come precomputed -- the plain rectangles' from the DFlatFrame table of the blob, the moving wall's
+// normal and tangent from two registers filled once per path (k_shade) -- so that compute_surface runs no normalisation.  0 builds the facts without them (A/B).
+#ifndef DTOF_WALL_FRAMES
+#define DTOF_WALL_FRAMES 1
+#endif
 // ... and the resident Domino kernel of one film at 16 waves (dtof_shade_res0.hip): every fact but kFactOneBlock, which describes the classic launch (0: not built)
 #ifndef DTOF_RESIDENT_FACTS
 #define DTOF_RESIDENT_FACTS 0x37f
@@ -161,7 +177,8 @@ constexpr uint32_t kResidentFacts = DTOF_RESIDENT_FACTS;
 // kernel compile in parallel, one group per file): staged = the scene blob is copied to LDS by every block; mode 0 split, 1 fused, 2 fused first bounce;
 // waves != 0: the resident form (`waves` waves per block, one block per CU); facts: the plan facts this launch satisfies (0: take the generic kernels).
 // launch_shade_plain and launch_shade_resident0 return whether an instantiation specialised on plan facts ran.
-struct ShadeLaunch { bool staged; int mode; uint32_t waves, grid, lds; hipStream_t stream; ShadeArgs args; uint32_t facts; };
+// stack_lds: the bytes of `lds` that are the traversal-stack columns of a classic launch -- a kernel compiled with kFactFlat has no stack and is launched without them.
+struct ShadeLaunch { bool staged; int mode; uint32_t waves, grid, lds; hipStream_t stream; ShadeArgs args; uint32_t facts; uint32_t stack_lds; };
 bool launch_shade_plain(bool area, bool k4, const ShadeLaunch &L);      // rectangle-only diffuse scenes          (dtof_shade_plain.hip)
 void launch_shade_mesh(bool area, bool k4, const ShadeLaunch &L);       // + triangles / analytic shapes          (dtof_shade_mesh.hip)
 void launch_shade_spec1(bool k4, const ShadeLaunch &L);                 // every BSDF / emitter / texture         (dtof_shade_spec1.hip)

@@ -675,7 +675,7 @@ bool launch_shade(const uint8_t *scene, uint32_t scene_bytes, const RenderParams
             const uint32_t n_seg = nseg(rp.n_lanes), grid = std::min<uint32_t>((uint32_t) n_cu, (n_seg + waves - 1) / waves);
             const uint32_t memo = rp.memo_obj != 0xffffffffu ? 1u : 0u;
             const ShadeLaunch L = { false, 2, waves, grid, lds, s,
-                                    { scene, scene_bytes, 0u, rp, q, qin, count_in, qout, alive_out, shadow_out, depth, trace_next ? 1u : 0u, dbg, film, film_stride, n_seg, resident->small_off, resident->small_words, memo, resident_stack_bytes(stack_depth, waves, rp.n_offsets != 1) / 4u }, facts };
+                                    { scene, scene_bytes, 0u, rp, q, qin, count_in, qout, alive_out, shadow_out, depth, trace_next ? 1u : 0u, dbg, film, film_stride, n_seg, resident->small_off, resident->small_words, memo, resident_stack_bytes(stack_depth, waves, rp.n_offsets != 1) / 4u }, facts, 0u };
             if (hipMemsetAsync(q.seg_counter, 0, 4, s) != hipSuccess) throw std::runtime_error("hipMemsetAsync(seg_counter) failed");
             if (rp.has_spec == 2) launch_shade_resident2(k4, L);
             else if (rp.has_spec) launch_shade_resident1(k4, L);
@@ -685,11 +685,12 @@ bool launch_shade(const uint8_t *scene, uint32_t scene_bytes, const RenderParams
     }
     // + the instance memo; a flat scene with one instance keeps the instance matrix there as well (k_shade: memo_m_lds) and needs no traversal stack beyond one entry
     const bool memo_m = fused && !rp.has_tris && !rp.has_spec && rp.flat_objects != 0 && rp.memo_obj != 0xffffffffu;   // = the condition of k_shade's memo_m_lds in the instantiations launch_shade_plain picks
-    const uint32_t shade_stack = fused ? stack_bytes(memo_m ? 1u : stack_depth, kShadeBlock) + (memo_m ? 2u : 1u) * kMemoWords * kMemoStride * 4 : 0;
+    const uint32_t stack_lds = fused ? stack_bytes(memo_m ? 1u : stack_depth, kShadeBlock) : 0u;   // the stack columns: what a kernel compiled with kFactFlat is launched without
+    const uint32_t shade_stack = fused ? stack_lds + (memo_m ? 2u : 1u) * kMemoWords * kMemoStride * 4 : 0;
     const uint32_t sw = stage_words_for(scene_bytes, shade_stack, ls), grid = nseg(rp.n_lanes) * (first && rp.chunk_blocks > 1 ? rp.chunk_blocks : 1u), lds = sw * 16 + shade_stack;
     check_lds(lds);
     const ShadeLaunch L = { sw != 0, first ? 2 : fused ? 1 : 0, 0u, grid, lds, s,
-                            { scene, scene_bytes, sw, rp, q, qin, count_in, qout, alive_out, shadow_out, depth, trace_next ? 1u : 0u, dbg, film, film_stride, nseg(rp.n_lanes), 0u, 0u, 0u, 0u }, first ? facts : 0u };
+                            { scene, scene_bytes, sw, rp, q, qin, count_in, qout, alive_out, shadow_out, depth, trace_next ? 1u : 0u, dbg, film, film_stride, nseg(rp.n_lanes), 0u, 0u, 0u, 0u }, first ? facts : 0u, stack_lds };
     if (rp.has_spec == 2) launch_shade_spec2(k4, L);
     else if (rp.has_spec) launch_shade_spec1(k4, L);
     else if (rp.has_tris) launch_shade_mesh(rp.has_area != 0, k4, L);

@@ -357,6 +357,7 @@ struct SceneTraits {
     uint32_t env_index = 0, n_instances = 0, last_instance = 0;
     uint64_t blas_triangles = 0;          // triangles behind per-mesh BLASes
     uint32_t n_nodes = 0, n_tlas_nodes = 0, n_objects = 0, stack_depth = 0, flat_off = 0;
+    uint32_t flat_general = 0, flat_memo = 0;   // the flat table's DFlatKinds: objects that are general instances | instances of ONE rectangle
     bool resident_layout = false; uint32_t small_off = 0, small_words = 0;   // the blob's record block can be the resident stage's
 };
 static uint32_t bh_emitters(const dtof_scene &sc) { return ((const BlobHeader *) sc.blob.data())->n_emitters; }   // the emitter count the kernels see (SceneView::n_emitters)
@@ -394,6 +395,10 @@ SceneTraits scene_traits(const dtof_scene &sc) {
     for (uint32_t i = 0; i < bh->n_objects; ++i) if (dobj[i].kind == OBJ_INSTANCE) { ++t.n_instances; t.last_instance = i; }
     t.has_nodes16 = bh->off_nodes16 != 0; t.n_nodes = bh->n_nodes; t.n_tlas_nodes = bh->n_tlas_nodes; t.n_objects = bh->n_objects;
     t.stack_depth = bh->tlas_depth; t.flat_off = bh->off_flat;
+    if (bh->off_flat) {
+        const DFlatKinds *kinds = (const DFlatKinds *) (sc.blob.data() + bh->off_flat + (size_t) bh->n_objects * sizeof(DFlatObject));
+        t.flat_general = kinds->general; t.flat_memo = kinds->memo;
+    }
     // groups | shapes | emitters | triangles | shading data | intersection records: one block of at most 24 KiB in a blob too large to stage whole
     const uint32_t small_bytes = bh->off_tables - bh->off_groups;
     t.resident_layout = bh->n_nodes > 0 && sc.blob.size() > 16 * 1024 && bh->off_shapes > bh->off_groups && bh->off_emitters > bh->off_groups && bh->off_tris > bh->off_groups &&
@@ -412,7 +417,7 @@ struct FramePlan {
     uint32_t n_passes = 1, run_passes = 1, dump_pass = 0;
     uint64_t lanes_per_row = 0, first = 0, last = 0, batch = 1;   // every pass: lanes [first, last) in batches of `batch`
     int n_streams = 1;
-    bool fused = false, first_inline = false, skip_tail = false, fuse_splat_ok = false, terminal_ok = false, plan_facts = false;
+    bool fused = false, first_inline = false, skip_tail = false, fuse_splat_ok = false, terminal_ok = false, plan_facts = false, one_wall = false;
     uint32_t max_inline = 1, chunk_segs = 0, res_units = 1, n_emitters = 0;
     ResidentStage resident;
     LaunchSwitches launch;                // launch.defer: the DEFER mode, 0 when the workspaces have no DEFER lists
@@ -451,6 +456,9 @@ struct FramePlan {
         if (!l.next_runs && l.terminal) f |= kFactWholePath;
         if (l.chunk_blocks == 1) f |= kFactOneBlock;
         if (n_emitters == 1) f |= kFactOneEmitter;
+        if (r.flat_objects != 0) f |= kFactFlat;
+        if (one_wall) f |= kFactOneWall;
+        if (l.splat_here) f |= kFactFusedSplat;   // (the launcher hands in the film exactly then)
         // every segment's count is min(512, n_lanes - 512 S), a multiple of 64 if n_lanes is one: each 64-lane chunk is then whole, and its lanes are the 64-aligned
         // lanes [lane_base + 512 S + cbase, + 64), samples of one pixel when spp is a power of two >= 64.  (A striped shard -- a rank's share of a frame, virtual lanes --
         // keeps the run-time test and with it the generic kernel.)
@@ -593,6 +601,8 @@ FramePlan plan_frame(const dtof_scene *sc, const RenderRequest &rq) {
     // a handful of rectangles: test them all instead of walking a tree (trace_flat in dtof_traverse.h)
     rp.flat_objects = p.fused && !rp.has_tris && t.flat_off != 0 && on("DTOF_FLAT") ? t.n_objects : 0u;
     rp.flat_off = t.flat_off;
+    // ... whose only instance is the memo object and holds one rectangle (kFactOneWall; the launch of such a scene keeps the instance matrix in LDS, k_shade: memo_m_lds)
+    p.one_wall = rp.flat_objects != 0 && rp.memo_obj < 32u && t.flat_general == 0 && t.flat_memo == (1u << rp.memo_obj);
     // Resident stage of the fused first-bounce kernel (k_shade<..., RESW>): scenes whose blob is too large to stage whole but whose TLAS (at most kResidentNodes nodes,
     // twice that as half-float planes, no per-mesh BLAS) and small records fit one CU's LDS beside the stack columns -- Domino: 1 024 nodes, one shared 12-triangle cube.
     // Waves: 16 (128 VGPRs) beat 12 once the nodes come from LDS, K = 4 too (Domino 44.2 vs 47.8 ms, C5 181.0 vs 192.7; profiles/r03_resident_stage_ab.txt,
@@ -1002,6 +1012,21 @@ int dtof_scene_export(const dtof_scene *sc, int kind, float *out, size_t cap, si
         else if (kind == 21) for (auto &s : sc->host.shapes) v.push_back((float) s.tex_normal);   // normalmap / bumpmap: its texture, -1 = none
         else if (kind == 22) for (auto &s : sc->host.shapes) { v.push_back(s.bumpmap ? 1.f : 0.f); v.push_back(s.bump_scale); }   // bumpmap: is one, scale
         else if (kind == 24) for (auto &s : sc->host.shapes) v.push_back((float) s.tex_radiance);   // texture on the area emitter's radiance, -1 = a constant
+        else if (kind == 25) {   // the flat table's shading frames as packed into the blob, with the shape constants they were computed from
+            const BlobHeader *bh = (const BlobHeader *) sc->blob.data();
+            if (bh->off_flat) {
+                const DFlatObject *fo = (const DFlatObject *) (sc->blob.data() + bh->off_flat);
+                const DFlatFrame *fr = (const DFlatFrame *) ((const uint8_t *) (fo + bh->n_objects) + sizeof(DFlatKinds) + (size_t) bh->n_objects * sizeof(DFlatZ));
+                const DObject *ob = (const DObject *) (sc->blob.data() + bh->off_objects);
+                const DShape *shp = (const DShape *) (sc->blob.data() + bh->off_shapes);
+                const DGroup *grp = (const DGroup *) (sc->blob.data() + bh->off_groups);
+                for (uint32_t i = 0; i < bh->n_objects; ++i) {
+                    const DShape &d = shp[fo[i].instance ? grp[ob[i].index].first_shape : ob[i].index];   // an instance: the first shape of its group
+                    v.push_back((float) fo[i].instance); v.insert(v.end(), d.n, d.n + 3); v.insert(v.end(), d.dp_du, d.dp_du + 3);
+                    v.insert(v.end(), fr[i].s, fr[i].s + 3); v.insert(v.end(), fr[i].t, fr[i].t + 3);
+                }
+            }
+        }
         else if (kind == 23) for (auto &s : sc->host.shapes) {   // blendbsdf: is one, weight, its texture, kind and two-sidedness of bsdf_1
             v.push_back(s.blend_other ? (s.two_bsdfs ? 2.f : 1.f) : 0.f); v.push_back(s.blend_weight); v.push_back((float) s.tex_blend);   // 1 blendbsdf, 2 twosided with two BSDFs
             v.push_back(s.blend_other ? (float) s.blend_other->bsdf : -1.f); v.push_back(s.blend_other && s.blend_other->twosided ? 1.f : 0.f);

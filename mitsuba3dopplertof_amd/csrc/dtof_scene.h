@@ -34,7 +34,7 @@ struct BlobHeader {
     uint32_t off_nodes, off_objects, off_groups, off_shapes, off_tris, off_shading, off_emitters;
     uint32_t total_bytes, off_tables, tlas_depth, off_flat;      // off_tables: face distributions of mesh emitters (float / uint32 words)   // tlas_depth: stack entries a traversal can need (TLAS depth + deepest BLAS)
     uint32_t off_isect, n_tlas_nodes, off_nodes16;   // off_nodes16: DNode16[n_nodes] of scenes with a BLAS (0: none), see below;           // n_tlas_nodes: the first nodes of the array are the TLAS (the BLAS of the meshes follow)
-                           // off_isect: DTriIsect[n_tris], what the triangle test reads   // off_flat: DFlatObject[n_objects], DFlatKinds, DFlatZ[n_objects] of a rectangle-only scene of at most kFlatObjects objects, else 0
+                           // off_isect: DTriIsect[n_tris], what the triangle test reads   // off_flat: DFlatObject[n_objects], DFlatKinds, DFlatZ[n_objects], DFlatFrame[n_objects] of a rectangle-only scene of at most kFlatObjects objects, else 0
 };
 static_assert(sizeof(BlobHeader) == 80, "BlobHeader");
 // One top-level object of a small rectangle-only scene as trace_flat (dtof_traverse.h) reads it with ONE scalar load: a plain rectangle's
@@ -50,6 +50,11 @@ static_assert(sizeof(DFlatObject) == 64, "DFlatObject");
 struct DFlatKinds { uint32_t general, memo, pad[2]; };   // bit i: DFlatObject i has instance == 1 | instance == 2
 struct DFlatZ { float z[4]; };                            // c0[2], c1[2], c2[2], c3[2] of the same record
 static_assert(sizeof(DFlatKinds) == 16 && sizeof(DFlatZ) == 16, "DFlatZ");
+// ... and behind the DFlatZ table one DFlatFrame per object: the tangents sh_s / sh_t of a plain rectangle's shading frame (initialize_sh_frame, interaction.h:258-268),
+// which depend on nothing but the shape -- computed on the host (scene_build.cpp) with the functions of dtof_math.h in the order of compute_surface, which otherwise
+// repeats that normalisation at every path vertex.  Zeros for an instance (its frame depends on the ray time).  Read by the kernels compiled with kFactOneWall.
+struct DFlatFrame { float s[3], pad0, t[3], pad1; };
+static_assert(sizeof(DFlatFrame) == 32, "DFlatFrame");
 
 constexpr uint32_t kLeafFlag = 0x80000000u;
 // TLAS leaves only: the object behind this leaf holds a mesh with a BLAS of its own (bit 30; the object index is the 30 bits below).  The ray kernels of large meshes can

@@ -4,6 +4,7 @@
 #pragma once
 #include "dtof_device.h"
 #include <atomic>
+#include <type_traits>
 
 namespace dtof {
 
@@ -341,7 +342,7 @@ void launch_bsdf_eval_spec(const uint8_t *scene, uint32_t shape_index, const flo
 // vector memory path busy 75 - 85 % of the time (TA / TD busy counters, profiles/r03_pmc_domino_fused*.txt) with the four 16-byte node loads
 // per step per lane, and waits for it.
 // FACTS: the plan facts (dtof_kernels.h: kFact*) this instantiation takes as constants instead of reading them, launch-uniform, from the kernarg segment where they
-// are used.  0 = none: every F_* below is then a compile-time `false` in front of the run-time read, and the kernel is the text it was without the parameter.
+// are used; the scene facts among them (kFactFlat, kFactOneWall) also reach trace_flat and compute_surface, as a template argument of theirs.  0 = none: every F_* below is then a compile-time `false` in front of the run-time read, and the kernel is the text it was without the parameter.
 template <bool LDS, int MODE, bool AREA, int KMAX, bool MESH, int SPEC, int RESW = 0, bool RH16 = false, uint32_t FACTS = 0>   // RH16: the resident stage holds HALF-FLOAT node records (DNode16): a TLAS of up to 2 * kResNodes nodes in the LDS of kResNodes float ones; SPEC: 0 diffuse-only scenes, 1 every BSDF / emitter / texture, 2 = 1 + blendbsdf (the BSDF chain in a loop over two records)
 #ifndef DTOF_MESH_WAVES
 #define DTOF_MESH_WAVES 3   // waves / SIMD the fused kernels with triangle code are compiled for (A/B: make variant DEFS=-DDTOF_MESH_WAVES=4)
@@ -377,6 +378,11 @@ __global__ __launch_bounds__(RESW ? RESW * 64 : kShadeBlock, RESW ? RESW / 4 : (
     constexpr bool F_IDENTITY = (FACTS & kFactIdentityQueue) != 0, F_NO_RR = (FACTS & kFactNoRoulette) != 0, F_CORRELATED = (FACTS & kFactCorrelated) != 0;
     constexpr bool F_WHOLE_PATH = (FACTS & kFactWholePath) != 0, F_ONE_BLOCK = (FACTS & kFactOneBlock) != 0, F_ONE_EMITTER = (FACTS & kFactOneEmitter) != 0;
     constexpr bool F_WAVE_PIXEL = (FACTS & kFactWavePixel) != 0;
+    constexpr bool F_FLAT = (FACTS & kFactFlat) != 0, F_ONE_WALL = (FACTS & kFactOneWall) != 0, F_FUSED_SPLAT = (FACTS & kFactFusedSplat) != 0;
+    constexpr bool F_FRAMES = F_ONE_WALL && DTOF_WALL_FRAMES;   // shading frames precomputed: the wall's once per path, the plain rectangles' on the host (compute_surface)
+    static_assert(!F_FLAT || (!MESH && SPEC == 0 && RESW == 0), "trace_flat serves the staged rectangle-only diffuse kernels");
+    static_assert(!F_ONE_WALL || F_FLAT, "the one wall is an object of the flat table");
+    static_assert(!F_FUSED_SPLAT || KMAX == 1, "the fused splat is the one-film kernels'");
     static_assert(!F_WAVE_PIXEL || F_IDENTITY, "whole waves of one pixel are provable for an identity queue only");
     static_assert(!F_ONE_BLOCK || RESW == 0, "blocks per segment belong to the classic launch");
     constexpr bool RES_LDS = RESW != 0 && KMAX > 1 && DTOF_K4_RES_LDS;   // several films, resident stage: running results in LDS columns
@@ -402,10 +408,11 @@ __global__ __launch_bounds__(RESW ? RESW * 64 : kShadeBlock, RESW ? RESW / 4 : (
     // dynamic LDS: [staged scene | resident stage: node planes, record block][fused: instance memo, kMemoWords x 64 words per wave][traversal stack columns]
     // flat scenes with ONE instance (the moving wall of C2): the column holds the instance matrix as well (launch_shade sizes the LDS accordingly) -- re-deriving it per
     // iteration cost every lane 51 instructions, a hit on the wall now reads it back
-    const bool memo_m_lds = FUSED && !MESH && !RESW && A0.rp.flat_objects != 0u && A0.rp.memo_obj != 0xffffffffu;
+    const bool memo_m_lds = F_ONE_WALL || (FUSED && !MESH && !RESW && A0.rp.flat_objects != 0u && A0.rp.memo_obj != 0xffffffffu);
     const uint32_t memo_words = FUSED ? (RESW ? (A0.res_memo ? RESW * kMemoWords * kMemoStride : 0u) : (memo_m_lds ? 2u : 1u) * kMemoWords * kMemoStride) : 0u;
     // per-thread traversal stack column; the resident kernels' columns are 16-bit (halfword address in a uint32_t *: only trace_scene<SOA> / node_step<SOA> touch it)
-    uint32_t *stack = S16 ? (uint32_t *) ((uint16_t *) ((uint32_t *) (lds + stage_words) + memo_words) + threadIdx.x) : (uint32_t *) (lds + stage_words) + memo_words + threadIdx.x;
+    // (kFactFlat: no ray query walks a tree -- the launch has no stack columns, launch_shade_plain)
+    uint32_t *stack = F_FLAT ? nullptr : S16 ? (uint32_t *) ((uint16_t *) ((uint32_t *) (lds + stage_words) + memo_words) + threadIdx.x) : (uint32_t *) (lds + stage_words) + memo_words + threadIdx.x;
     // One block per 512-lane segment -- or, for a small frame whose whole path runs inline (rp.chunk_blocks = 8: nothing is compacted for a
     // later launch), one block per 64-lane chunk, so that a 1 M-lane frame is 16 384 waves instead of 2 048; the per-segment statistics are
     // then accumulated with atomics into slots the host has zeroed.
@@ -464,7 +471,7 @@ __global__ __launch_bounds__(RESW ? RESW * 64 : kShadeBlock, RESW ? RESW / 4 : (
     const uint8_t *base = LDS ? stage_scene(A0.scene, A0.scene_bytes, lds) : A0.scene;
     SceneView sv = RESW ? sv_res : make_view(base);
     if (FUSED) { sv.memo_obj = A0.rp.memo_obj; sv.memo = (float *) (lds + stage_words) + (RESW ? wave_id * kMemoWords * kMemoStride + lane_id : threadIdx.x); sv.memo_m = memo_m_lds; }
-    const bool have_memo = FUSED && sv.memo_obj != 0xffffffffu;
+    const bool have_memo = F_ONE_WALL || (FUSED && sv.memo_obj != 0xffffffffu);
     for (uint32_t cbase = sub > 1 ? sub_index * unit_lanes : 0u; cbase < (sub > 1 ? (sub_index + 1) * unit_lanes < count ? (sub_index + 1) * unit_lanes : count : count); cbase += kShadeBlock) {
     uint32_t rebase = 0;
     asm volatile("" : "+s"(rebase));
@@ -543,6 +550,12 @@ __global__ __launch_bounds__(RESW ? RESW * 64 : kShadeBlock, RESW ? RESW / 4 : (
     const bool valid_start = SPEC && rp.has_env && !rp.hide_emitters;
     bool valid_reg = valid_start;
     float memo_m[12], memo_inv[12];   // instance memo: the one instance's matrix and inverse at this lane's ray time
+    // kFactOneWall: the wall's unit normal and tangent at this lane's ray time, and the plain rectangles' frames (DFlatFrame[n] behind DFlatObject[n], DFlatKinds, DFlatZ[n])
+    typename std::conditional<F_FRAMES, WallFrames, NoFrames>::type wf;
+    if constexpr (F_FRAMES) {
+        wf.n = mk(0.f, 0.f, 1.f); wf.s = mk(1.f, 0.f, 0.f);
+        wf.table = (const DFlatFrame *) ((const uint4 *) ((const DFlatObject *) (sv.base + rp.flat_off) + rp.flat_objects) + 1 + rp.flat_objects);
+    }
     bool lane_on = in_range;
 #ifdef DTOF_TRAVERSAL_STATS   // development builds: lanes without a path carry a poison pattern; DTOF_POISON_CHECK counts it wherever path state is written out (statistic [14])
     constexpr uint64_t kPoisonState = 0xdeadbeefcafef00dull;
@@ -557,7 +570,7 @@ __global__ __launch_bounds__(RESW ? RESW * 64 : kShadeBlock, RESW ? RESW / 4 : (
     const bool wave_pixel = F_WAVE_PIXEL || (FIRST && rp.spp_log2 != 0xffffffffu && rp.spp_log2 >= 6 && (rp.lane_base & 63u) == 0 && count - cbase >= (uint32_t) kShadeBlock);
     // Fused splat (uniform): this launch runs the whole path of its lanes (nobody continues) and the host handed in the film -- the wave reduces the footprint
     // values of its 64 samples itself and issues the film atomics, the result never goes through q.res / q.pos and the splat kernel's round trip through HBM
-    const bool fuse_splat = FIRST && A.film != nullptr;
+    const bool fuse_splat = F_FUSED_SPLAT || (FIRST && A.film != nullptr);
     float2 pos_reg = make_float2(0.f, 0.f);
     if (in_range) {
         l = qin ? qin[seg * kSeg + j] : seg * kSeg + j;
@@ -575,8 +588,15 @@ __global__ __launch_bounds__(RESW ? RESW * 64 : kShadeBlock, RESW ? RESW / 4 : (
                 o.time = ra.w; o.ray_o[0] = ra.x; o.ray_o[1] = ra.y; o.ray_o[2] = ra.z; o.ray_d[0] = rb.x; o.ray_d[1] = rb.y; o.ray_d[2] = rb.z;
             }
             if (have_memo) instance_memo_fill(sv, ra.w, memo_m, memo_inv);
+            if constexpr (F_FRAMES) {   // what compute_surface evaluates for a hit on the wall, in its order: n = normalize(xf_normal(inv, n)), dp_du = xf_vector(m, dp_du), initialize_sh_frame
+                const DShape &ws = sv.shapes[sv.groups[sv.objects[sv.memo_obj].index].first_shape];
+                wf.n = normalize(xf_normal(memo_inv, mk(ws.n[0], ws.n[1], ws.n[2])));
+                const V3 du = xf_vector(memo_m, mk(ws.dp_du[0], ws.dp_du[1], ws.dp_du[2]));
+                wf.s = normalize(vfma(wf.n, -dot(wf.n, du), du));
+                if (du.x == 0.f && du.y == 0.f && du.z == 0.f) { V3 tt; coordinate_system(wf.n, wf.s, tt); }
+            }
             Hit h;
-            bool found = flat ? trace_flat<false, true>(sv, (ConstBytes) A.scene + rp.flat_off, rp.flat_off, flat, stack, mk(ra.x, ra.y, ra.z), mk(rb.x, rb.y, rb.z), ra.w, rb.w, h)
+            bool found = (F_FLAT || flat) ? trace_flat<false, true, FACTS & kFactOneWall>(sv, (ConstBytes) A.scene + rp.flat_off, rp.flat_off, flat, stack, mk(ra.x, ra.y, ra.z), mk(rb.x, rb.y, rb.z), ra.w, rb.w, h)
                               : trace_scene<false, MESH, FUSED, RESW != 0, kStackStride, S16, 0u, false, RH16>(sv, stack, mk(ra.x, ra.y, ra.z), mk(rb.x, rb.y, rb.z), ra.w, rb.w, h);
             hh = make_uint4(f2u(h.t), f2u(h.u), f2u(h.v), h.prim);
             hid = found ? (h.obj | (h.shape << q.id_shift)) : 0xffffffffu;
@@ -671,7 +691,8 @@ __global__ __launch_bounds__(RESW ? RESW * 64 : kShadeBlock, RESW ? RESW / 4 : (
             }
             // the diffuse-only kernels' terminal iteration reads the cosines wi.z / wo.z and nothing else of the shading frame
             const bool want_frame = SPEC != 0 || !terminal;
-            compute_surface<MESH>(sv, hid & ((1u << q.id_shift) - 1u), hid >> q.id_shift, hh.w, t, u2f(hh.y), u2f(hh.z), o, d, time, si, have_memo, memo_m, memo_inv, want_frame);
+            if constexpr (F_FRAMES) compute_surface<MESH, FACTS & kFactOneWall>(sv, hid & ((1u << q.id_shift) - 1u), hid >> q.id_shift, hh.w, t, u2f(hh.y), u2f(hh.z), o, d, time, si, have_memo, memo_m, memo_inv, want_frame, &wf);
+            else compute_surface<MESH, FACTS & kFactOneWall>(sv, hid & ((1u << q.id_shift) - 1u), hid >> q.id_shift, hh.w, t, u2f(hh.y), u2f(hh.z), o, d, time, si, have_memo, memo_m, memo_inv, want_frame);
             const DShape *sh = si.shape;
 
             const float pmf = rp.emitter_pmf;   // m_emitter_pmf (scene.cpp:96)
@@ -944,7 +965,7 @@ __global__ __launch_bounds__(RESW ? RESW * 64 : kShadeBlock, RESW ? RESW / 4 : (
 #if defined(DTOF_ABLATE) && (DTOF_ABLATE & 1)
             commit = sha.w > 0.f;
 #else
-            commit = flat ? !trace_flat<true, true>(sv, (ConstBytes) A.scene + rp.flat_off, rp.flat_off, flat, stack, mk(sha.x, sha.y, sha.z), mk(shb.x, shb.y, shb.z), shb.w, sha.w, hs)
+            commit = (F_FLAT || flat) ? !trace_flat<true, true, FACTS & kFactOneWall>(sv, (ConstBytes) A.scene + rp.flat_off, rp.flat_off, flat, stack, mk(sha.x, sha.y, sha.z), mk(shb.x, shb.y, shb.z), shb.w, sha.w, hs)
                           : !trace_scene<true, MESH, true, RESW != 0, kStackStride, S16, 0u, false, RH16>(sv, stack, mk(sha.x, sha.y, sha.z), mk(shb.x, shb.y, shb.z), shb.w, sha.w, hs);
 #endif
         }
@@ -984,7 +1005,7 @@ __global__ __launch_bounds__(RESW ? RESW * 64 : kShadeBlock, RESW ? RESW / 4 : (
 #if defined(DTOF_ABLATE) && (DTOF_ABLATE & 2)
             bool found = nra.x < 1e30f; h.t = 0.5f + 0.1f * nrb.x; h.u = nrb.y; h.v = nrb.z; h.obj = nrb.x > 0.3f ? 3 : nrb.y > 0.f ? 1 : 0; h.shape = 0; h.prim = 0;
 #else
-            bool found = flat ? trace_flat<false, true>(sv, (ConstBytes) A.scene + rp.flat_off, rp.flat_off, flat, stack, mk(nra.x, nra.y, nra.z), mk(nrb.x, nrb.y, nrb.z), nra.w, nrb.w, h)
+            bool found = (F_FLAT || flat) ? trace_flat<false, true, FACTS & kFactOneWall>(sv, (ConstBytes) A.scene + rp.flat_off, rp.flat_off, flat, stack, mk(nra.x, nra.y, nra.z), mk(nrb.x, nrb.y, nrb.z), nra.w, nrb.w, h)
                               : trace_scene<false, MESH, true, RESW != 0, kStackStride, S16, 0u, false, RH16>(sv, stack, mk(nra.x, nra.y, nra.z), mk(nrb.x, nrb.y, nrb.z), nra.w, nrb.w, h);
 #endif
             if (!FIRST || last) store_hit<MESH>(q, l, h, found);
@@ -1025,7 +1046,7 @@ __global__ __launch_bounds__(RESW ? RESW * 64 : kShadeBlock, RESW ? RESW / 4 : (
 #pragma unroll
             for (int k = 0; k < KMAX; ++k) if (KMAX == 1 || k < rp.n_offsets) {
                 float *fk = A.film + (size_t) k * A.film_stride;
-                if (in_range && !regular) splat_lane(rp, fk, sx, sy, px, py, rbase[k].x, rbase[k].y, rbase[k].z);
+                if (in_range && !regular) splat_lane<F_FUSED_SPLAT ? FILTER_TENT : -1>(rp, fk, sx, sy, px, py, rbase[k].x, rbase[k].y, rbase[k].z);
                 float v[36];
 #pragma unroll
                 for (int ys = 0; ys < 3; ++ys)
@@ -1040,7 +1061,7 @@ __global__ __launch_bounds__(RESW ? RESW * 64 : kShadeBlock, RESW ? RESW / 4 : (
         } else if (in_range) {   // a ragged chunk: every lane by itself
 #pragma unroll
             for (int k = 0; k < KMAX; ++k) if (KMAX == 1 || k < rp.n_offsets)
-                splat_lane(rp, A.film + (size_t) k * A.film_stride, sx, sy, px, py, rbase[k].x, rbase[k].y, rbase[k].z);
+                splat_lane<F_FUSED_SPLAT ? FILTER_TENT : -1>(rp, A.film + (size_t) k * A.film_stride, sx, sy, px, py, rbase[k].x, rbase[k].y, rbase[k].z);
         }
     }
     }   // chunk loop

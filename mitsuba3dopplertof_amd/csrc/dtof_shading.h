@@ -16,17 +16,25 @@ struct Surface { V3 p, n, sh_n, sh_s, sh_t, wi; float u, v; const DShape *shape;
 // memo_m / memo_inv: the instance matrix and its inverse of object sv.memo_obj at this ray time, if the caller has them (instance memo)
 // want_frame = false (uniform): the caller reads only the cosine wi.z of the shading frame -- no tangent frame (initialize_sh_frame: a normalize, a cross product,
 // the dp_du == 0 test) and no dp_du / dp_dv through the instance; sh_s, sh_t, dp_du, dp_dv and wi.x / wi.y come back as zero.  p, n, sh_n, wi.z, u, v are the same.
-template <bool MESH>
+// FACTS (k_shade's plan facts, dtof_kernels.h): under kFactOneWall every instance hit is the memo object's, its matrix and inverse in the lane's LDS column; with
+// DTOF_WALL_FRAMES the shading frames come precomputed through `wf` and no normalisation runs here: the wall's normal and tangent at this lane's ray time (a ray's time
+// does not change along its path: k_shade fills them once per path with the expressions below, in their order), a plain rectangle's tangents from the DFlatFrame table.
+struct WallFrames { V3 n, s; const DFlatFrame *table; };   // table: DFlatFrame[n_objects] of the staged blob
+struct NoFrames {};                                          // (what a kernel without the fact keeps in their place)
+template <bool MESH, uint32_t FACTS = 0>
 DTOF_D void compute_surface(const SceneView &sv, uint32_t oi, uint32_t shape_k, uint32_t prim, float t, float b1, float b2,
-                            V3 o, V3 d, float time, Surface &si, bool use_memo, const float (&memo_m)[12], const float (&memo_inv)[12], bool want_frame = true) {
+                            V3 o, V3 d, float time, Surface &si, bool use_memo, const float (&memo_m)[12], const float (&memo_inv)[12], bool want_frame = true,
+                            const WallFrames *wf = nullptr) {   // wf: only a kernel with the fact passes it
+    constexpr bool F_ONE_WALL = (FACTS & kFactOneWall) != 0, F_FRAMES = F_ONE_WALL && DTOF_WALL_FRAMES;
+    static_assert(!F_ONE_WALL || !MESH, "the one-wall fact describes a rectangle-only scene");
     const DObject &ob = sv.objects[oi];
-    bool inst = ob.kind == OBJ_INSTANCE;
+    bool inst = F_ONE_WALL ? oi == sv.memo_obj : ob.kind == OBJ_INSTANCE;   // (the fact: the memo object is the scene's only instance)
     float m[12], inv[12];
     V3 lo = o, ld = d;
     const DShape *sh;
     if (inst) {
-        if (use_memo && oi == sv.memo_obj) {
-            if (sv.memo_m) { instance_memo_load_matrix(sv, m); instance_memo_load(sv, inv); }   // both sit in the lane's LDS column since the lane was generated
+        if (F_ONE_WALL || (use_memo && oi == sv.memo_obj)) {
+            if (F_ONE_WALL || sv.memo_m) { instance_memo_load_matrix(sv, m); instance_memo_load(sv, inv); }   // both sit in the lane's LDS column since the lane was generated
             else {
 #pragma unroll
                 for (int i = 0; i < 12; ++i) { m[i] = memo_m[i]; inv[i] = memo_inv[i]; }
@@ -106,11 +114,23 @@ DTOF_D void compute_surface(const SceneView &sv, uint32_t oi, uint32_t shape_k, 
     }
     if (inst) {
         si.p = xf_point(m, si.p);
+        if constexpr (F_FRAMES) { si.n = wf->n; si.sh_n = si.n; }   // (a rectangle's n and sh_n are one vector: both lines below give the same value)
+        else {
         si.n = normalize(xf_normal(inv, si.n));
         si.sh_n = normalize(xf_normal(inv, si.sh_n));
         if (want_frame) { dp_du = xf_vector(m, dp_du); dp_dv = xf_vector(m, dp_dv); }   // instance.cpp:201-202
+        }
     }
     V3 md = -d;
+    if constexpr (F_FRAMES) if (want_frame) {   // dp_du / dp_dv: read by the normalmap / bumpmap frames of the every-BSDF kernels only, which carry no facts
+        const V3 zero = mk(0.f, 0.f, 0.f);
+        V3 s, tt;
+        if (inst) { s = wf->s; tt = cross(si.sh_n, s); }
+        else { const DFlatFrame &f = wf->table[oi]; s = mk(f.s[0], f.s[1], f.s[2]); tt = mk(f.t[0], f.t[1], f.t[2]); }
+        si.sh_s = s; si.sh_t = tt; si.dp_du = zero; si.dp_dv = zero;
+        si.wi = mk(dot(md, si.sh_s), dot(md, si.sh_t), dot(md, si.sh_n));
+        return;
+    }
     if (!want_frame) {
         const V3 zero = mk(0.f, 0.f, 0.f);
         si.sh_s = zero; si.sh_t = zero; si.dp_du = zero; si.dp_dv = zero;

@@ -505,7 +505,8 @@ DTOF_D F2 flat_zrow(float z0, float z1, float z2, float z3, V3 ro, V3 rd) {
     return F2{ fmaf(z2, ro.z, fmaf(z1, ro.y, fmaf(z0, ro.x, z3))), fmaf(z2, rd.z, fmaf(z1, rd.y, z0 * rd.x)) };
 #endif
 }
-template <bool ANY, bool MEMO>
+// FACTS (k_shade's plan facts, dtof_kernels.h): under kFactOneWall the one instance is the memo object of one rectangle -- no DFlatKinds loads, no instance loop.
+template <bool ANY, bool MEMO, uint32_t FACTS = 0>
 DTOF_D bool trace_flat(const SceneView &sv, ConstBytes flat_table, uint32_t flat_off, uint32_t n_objects, uint32_t *stack, V3 o, V3 d, float time, float maxt, Hit &best) {
     typedef const DFlatObject __attribute__((address_space(4))) *ConstFlat;
     const ConstFlat table = (ConstFlat) flat_table;
@@ -545,6 +546,8 @@ DTOF_D bool trace_flat(const SceneView &sv, ConstBytes flat_table, uint32_t flat
     // Instances are noted in a mask and intersected after the rectangles: the tie rule of intersect_object (equal t goes to the lower object index) does not depend on
     // the order of the visits.
     uint32_t instances = 0, oi = 0;
+    constexpr bool F_ONE_WALL = DTOF_FLAT_LDS && (FACTS & kFactOneWall) != 0;   // (the form without the cull keeps its instance marks)
+    static_assert(!F_ONE_WALL || MEMO, "the one wall is the memo object");
 #if DTOF_FLAT_LDS
     // The records come from the scene copy staged in LDS, every lane reading the same address (a broadcast): the matrix entries are then VGPR operands of the
     // multiply-adds, which issue at full rate -- as SGPR operands (scalar loads from the blob) each of the 21 costs two issue slots (profiles/r03_ubench_valu_rate.txt).
@@ -553,12 +556,12 @@ DTOF_D bool trace_flat(const SceneView &sv, ConstBytes flat_table, uint32_t flat
     const DFlatObject *lt = (const DFlatObject *) (sv.base + flat_off);
     const uint4 *zt = (const uint4 *) (lt + n_objects) + 1;   // DFlatZ[n_objects], behind the DFlatKinds record
     const DFlatKinds __attribute__((address_space(4))) *kinds = (const DFlatKinds __attribute__((address_space(4))) *) (table + n_objects);
-    const uint32_t memo_bit = MEMO && sv.memo_obj < 32u ? 1u << sv.memo_obj : 0u, memo_objs = kinds->memo & memo_bit;
-    instances = kinds->general | (kinds->memo & ~memo_bit);
+    const uint32_t memo_bit = F_ONE_WALL ? 1u << sv.memo_obj : MEMO && sv.memo_obj < 32u ? 1u << sv.memo_obj : 0u, memo_objs = F_ONE_WALL ? memo_bit : kinds->memo & memo_bit;
+    if (!F_ONE_WALL) instances = kinds->general | (kinds->memo & ~memo_bit);
     const float far = flat_cull_far(maxt);
     constexpr int kStat = ANY ? 16 : 20; (void) kStat;   // (stats builds)
     for (; oi < n_objects; ++oi) {
-        if ((instances >> oi) & 1u) continue;   // (uniform)
+        if (!F_ONE_WALL && ((instances >> oi) & 1u)) continue;   // (uniform)
         V3 ro, rd;
         to_object((memo_objs >> oi) & 1u, ro, rd);
         const uint4 zr = zt[oi];
@@ -597,7 +600,8 @@ DTOF_D bool trace_flat(const SceneView &sv, ConstBytes flat_table, uint32_t flat
         ++oi;
     }
 #endif
-    while (instances) {   // uniform
+    // (`stack` may be null here -- a kernel compiled with kFactFlat has none: intersect_object<ANY, MESH = false> tests rectangles only and never touches it)
+    if (!F_ONE_WALL) while (instances) {   // uniform
         const uint32_t k = (uint32_t) __builtin_ctz(instances); instances &= instances - 1u;
         const bool hit = intersect_object<ANY, false, MEMO>(sv, k, o, d, time, maxt, best, stack, 0, blockDim.x);
         if (ANY) occluded |= hit;

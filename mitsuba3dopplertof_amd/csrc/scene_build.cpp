@@ -550,7 +550,19 @@ std::vector<uint8_t> build_scene_blob(const HostScene &sc) {
         if (f.instance == 2) flat_kinds.memo |= 1u << i;
         flat_z.push_back(DFlatZ{ { f.c0[2], f.c1[2], f.c2[2], f.c3[2] } });
     }
-    const size_t flat_bytes = flat.size() * sizeof(DFlatObject) + (flat.empty() ? 0 : sizeof(DFlatKinds) + flat_z.size() * sizeof(DFlatZ));
+    // the shading frame of every plain rectangle: compute_surface's expressions (initialize_sh_frame with sh_n = n, the dp_du == 0 fallback included), evaluated once here
+    std::vector<DFlatFrame> flat_frames(flat.size());
+    for (size_t i = 0; i < flat.size(); ++i) {
+        DFlatFrame &fr = flat_frames[i]; memset(&fr, 0, sizeof fr);
+        if (flat[i].instance) continue;
+        const DShape &d = shapes[objects[i].index];
+        const V3 n = mk(d.n[0], d.n[1], d.n[2]), dp_du = mk(d.dp_du[0], d.dp_du[1], d.dp_du[2]);
+        V3 s = normalize(vfma(n, -dot(n, dp_du), dp_du));
+        if (dp_du.x == 0.f && dp_du.y == 0.f && dp_du.z == 0.f) { V3 tt; coordinate_system(n, s, tt); }
+        const V3 t = cross(n, s);
+        fr.s[0] = s.x; fr.s[1] = s.y; fr.s[2] = s.z; fr.t[0] = t.x; fr.t[1] = t.y; fr.t[2] = t.z;
+    }
+    const size_t flat_bytes = flat.size() * sizeof(DFlatObject) + (flat.empty() ? 0 : sizeof(DFlatKinds) + flat_z.size() * sizeof(DFlatZ) + flat_frames.size() * sizeof(DFlatFrame));
     { const uint32_t at = place(flat_bytes); h.off_flat = flat.empty() ? 0u : at; }
     h.total_bytes = (uint32_t) off;
     for (DShape &d : shapes) if (d.kind == SHAPE_MESH && (d.flags & SF_EMITTER)) d.emit_table += h.off_tables;
@@ -584,7 +596,8 @@ std::vector<uint8_t> build_scene_blob(const HostScene &sc) {
         uint8_t *p = blob.data() + h.off_flat;
         memcpy(p, flat.data(), flat.size() * sizeof(DFlatObject)); p += flat.size() * sizeof(DFlatObject);
         memcpy(p, &flat_kinds, sizeof flat_kinds); p += sizeof flat_kinds;
-        memcpy(p, flat_z.data(), flat_z.size() * sizeof(DFlatZ));
+        memcpy(p, flat_z.data(), flat_z.size() * sizeof(DFlatZ)); p += flat_z.size() * sizeof(DFlatZ);
+        memcpy(p, flat_frames.data(), flat_frames.size() * sizeof(DFlatFrame));
     }
     if (!nodes16.empty()) memcpy(blob.data() + h.off_nodes16, nodes16.data(), nodes16.size() * sizeof(DNode16));
     return blob;

@@ -26,7 +26,9 @@ code = ("import sys, numpy as np; sys.path.insert(0, %r); import mitsuba3doppler
 res = {n: [] for n, _ in variants}
 for r in range(3):
     for n, env in variants:
-        out = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, env=dict(os.environ, **env))
+        out = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, env=dict(os.environ, **env), timeout=300)   # a round is seconds
+        if out.returncode != 0:   # a child that failed ends the comparison: nothing more is started on that GPU
+            sys.exit("%s, round %d: exit status %d\n%s" % (n, r, out.returncode, out.stderr[-2000:]))
         res[n].append(out.stdout.strip() or out.stderr[-300:])
 print("variant: per round min/median of  total | first | bounce launch | trace | shadow | splat  (ms)")
 for n, _ in variants:

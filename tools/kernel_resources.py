@@ -11,6 +11,10 @@ FIELDS = [("vgpr", ".vgpr_count"), ("agpr", ".agpr_count"), ("sgpr", ".sgpr_coun
           ("scratch", ".private_segment_fixed_size"), ("lds", ".group_segment_fixed_size")]
 
 
+# (RESW, mask) of the specialised instantiations with the default -D values: the C2 / C3 kernels of dtof_shade_plain.hip and the resident Domino kernel of dtof_shade_res0.hip
+FACT_MASKS = {("0", 0x1fff): " = kHeadlineFusedFacts", ("0", 0xfff): " = kHeadlineFacts", ("16", 0x37f): " = kResidentFacts"}
+
+
 def run(*a):
     return subprocess.run(a, check=True, capture_output=True, text=True).stdout
 
@@ -37,7 +41,11 @@ def kernels(objdir, tmp, tag):
             res = {n: int(get(k).group(1)) if get(k) else 0 for n, k in FIELDS}
             res["occ"] = min(8, 512 // max(8, (res["vgpr"] + res["agpr"] + 7) // 8 * 8))
             name = run(shutil.which("c++filt") or LLVM + "/llvm-cxxfilt", sym).strip().replace("void dtof::", "").split("(")[0]
-            out[re.sub(r", 0u>$", ">", name)] = (res, text.get(sym, []))   # FACTS = 0 (k_shade's last template argument): the name the kernel had without it
+            name = re.sub(r", 0u>$", ">", name)   # FACTS = 0 (k_shade's last template argument): the name the kernel had without it
+            m = re.search(r", (\d+)u>$", name)      # ... and a kernel compiled with plan facts (dtof_kernels.h: kFact*): its mask in hex, with the name of the mask
+            if m and name.startswith("k_shade<"):
+                name = name[:m.start()] + ", FACTS 0x%x%s>" % (int(m.group(1)), FACT_MASKS.get((name.split(", ")[6], int(m.group(1))), ""))
+            out[name] = (res, text.get(sym, []))
     return out
 
 
