@@ -489,6 +489,16 @@ typedef const uint8_t __attribute__((address_space(4))) *ConstBytes;
 #ifndef DTOF_FLAT_LDS
 #define DTOF_FLAT_LDS 1
 #endif
+// DTOF_FLAT_PEEL=1: the kernels compiled with kFactOneWall visit the flat table as three segments around the wall instead of one loop that picks each object's ray
+// (the world ray, or the wall's) by copying it -- six v_mov_b32 per visit and six more for the wall, 7 % of the executed vector instructions of C2's kernel.  Same
+// visits, same order, same arithmetic (profiles/flat_peel_ab.txt).  0: the single loop, kept for A/B timing.
+#ifndef DTOF_FLAT_PEEL
+#define DTOF_FLAT_PEEL 1
+#endif
+// DTOF_FLAT_BEST_CULL=1 (with DTOF_FLAT_PEEL): a closest-hit query's certain-miss test is bounded by the nearest hit it holds instead of the ray's maxt.
+#ifndef DTOF_FLAT_BEST_CULL
+#define DTOF_FLAT_BEST_CULL 0
+#endif
 typedef float F2 __attribute__((ext_vector_type(2)));
 struct FlatRecord { uint32_t instance; F2 c0, c1, c2, c3; float z0, z1, z2, z3; };   // (x, y) entries of the four columns as pairs, the z row apart
 DTOF_D FlatRecord flat_load(const DFlatObject __attribute__((address_space(4))) *f) {
@@ -558,24 +568,60 @@ DTOF_D bool trace_flat(const SceneView &sv, ConstBytes flat_table, uint32_t flat
     const DFlatKinds __attribute__((address_space(4))) *kinds = (const DFlatKinds __attribute__((address_space(4))) *) (table + n_objects);
     const uint32_t memo_bit = F_ONE_WALL ? 1u << sv.memo_obj : MEMO && sv.memo_obj < 32u ? 1u << sv.memo_obj : 0u, memo_objs = F_ONE_WALL ? memo_bit : kinds->memo & memo_bit;
     if (!F_ONE_WALL) instances = kinds->general | (kinds->memo & ~memo_bit);
-    const float far = flat_cull_far(maxt);
     constexpr int kStat = ANY ? 16 : 20; (void) kStat;   // (stats builds)
-    for (; oi < n_objects; ++oi) {
-        if (!F_ONE_WALL && ((instances >> oi) & 1u)) continue;   // (uniform)
-        V3 ro, rd;
-        to_object((memo_objs >> oi) & 1u, ro, rd);
-        const uint4 zr = zt[oi];
-        const F2 z = flat_zrow(u2f(zr.x), u2f(zr.y), u2f(zr.z), u2f(zr.w), ro, rd);
-        const bool need = !flat_certain_miss(z.x, z.y, far);
-        DTOF_STAT(kStat); DTOF_STAT_WAVE(kStat + 2);
-        if (!need) DTOF_STAT(kStat + 1);
-        if (!__ballot(need)) continue;   // (uniform) no active lane can hit this rectangle
-        DTOF_STAT_WAVE(kStat + 3);
-        const uint4 *rp4 = (const uint4 *) (lt + oi);
-        const uint4 r0 = rp4[0], r1 = rp4[1], r2 = rp4[2], r3 = rp4[3];
-        FlatRecord a; a.instance = 0;
-        a.c0 = F2{ u2f(r0.x), u2f(r0.y) }; a.c1 = F2{ u2f(r1.x), u2f(r1.y) }; a.c2 = F2{ u2f(r2.x), u2f(r2.y) }; a.c3 = F2{ u2f(r3.x), u2f(r3.y) };
-        test(a, oi, ro, rd, z);
+    if constexpr (F_ONE_WALL && DTOF_FLAT_PEEL) {
+        // Three segments in ascending index order -- the rectangles below the wall, the wall, the rectangles above it: the plain rectangles read the world ray where
+        // it lies and the wall reads its own ray, so no iteration selects between the two by copying six registers.  One visit is the generic
+        // loop's body, operation for operation.
+        float far = flat_cull_far(maxt);
+        auto visit = [&](uint32_t k, const V3 &ro, const V3 &rd) {
+            const uint4 zr = zt[k];
+            const F2 z = flat_zrow(u2f(zr.x), u2f(zr.y), u2f(zr.z), u2f(zr.w), ro, rd);
+            const bool need = !flat_certain_miss(z.x, z.y, far);
+            DTOF_STAT(kStat); DTOF_STAT_WAVE(kStat + 2);
+            if (!need) DTOF_STAT(kStat + 1);
+            if (!__ballot(need)) return;   // (uniform) no active lane can hit this rectangle
+            DTOF_STAT_WAVE(kStat + 3);
+            const uint4 *rp4 = (const uint4 *) (lt + k);
+            const uint4 r0 = rp4[0], r1 = rp4[1], r2 = rp4[2], r3 = rp4[3];
+            FlatRecord a; a.instance = 0;
+            a.c0 = F2{ u2f(r0.x), u2f(r0.y) }; a.c1 = F2{ u2f(r1.x), u2f(r1.y) }; a.c2 = F2{ u2f(r2.x), u2f(r2.y) }; a.c3 = F2{ u2f(r3.x), u2f(r3.y) };
+            test(a, k, ro, rd, z);
+            // the closest hit so far bounds the rest of the query: a certain miss against best.t <= maxt could not have passed `t < best.t` (dtof_flat_cull.h)
+            if (!ANY && DTOF_FLAT_BEST_CULL) far = flat_cull_far(best.t);
+        };
+        const uint32_t wall = sv.memo_obj;   // < n_objects: a bit of the table's memo mask (kFactOneWall)
+        // ONE copy of the plain rectangles' body, run for both segments (two passes of an outer loop the compiler must keep: written out or unrolled, the three bodies
+        // of each of the three call sites take C2's kernel to its register cap and two values to scratch); the wall's body, with its ray, sits behind the first pass.
+#pragma unroll 1
+        for (uint32_t seg = 0; seg < 2u; ++seg) {
+            const uint32_t end = seg ? n_objects : wall;
+            for (; oi < end; ++oi) visit(oi, o, d);
+            if (seg == 0) {
+                float inv[12]; instance_memo_load(sv, inv);
+                const V3 wo = xf_point(inv, o), wd = xf_vector(inv, d);
+                visit(oi++, wo, wd);
+            }
+        }
+    } else {
+        const float far = flat_cull_far(maxt);
+        for (; oi < n_objects; ++oi) {
+            if (!F_ONE_WALL && ((instances >> oi) & 1u)) continue;   // (uniform)
+            V3 ro, rd;
+            to_object((memo_objs >> oi) & 1u, ro, rd);
+            const uint4 zr = zt[oi];
+            const F2 z = flat_zrow(u2f(zr.x), u2f(zr.y), u2f(zr.z), u2f(zr.w), ro, rd);
+            const bool need = !flat_certain_miss(z.x, z.y, far);
+            DTOF_STAT(kStat); DTOF_STAT_WAVE(kStat + 2);
+            if (!need) DTOF_STAT(kStat + 1);
+            if (!__ballot(need)) continue;   // (uniform) no active lane can hit this rectangle
+            DTOF_STAT_WAVE(kStat + 3);
+            const uint4 *rp4 = (const uint4 *) (lt + oi);
+            const uint4 r0 = rp4[0], r1 = rp4[1], r2 = rp4[2], r3 = rp4[3];
+            FlatRecord a; a.instance = 0;
+            a.c0 = F2{ u2f(r0.x), u2f(r0.y) }; a.c1 = F2{ u2f(r1.x), u2f(r1.y) }; a.c2 = F2{ u2f(r2.x), u2f(r2.y) }; a.c3 = F2{ u2f(r3.x), u2f(r3.y) };
+            test(a, oi, ro, rd, z);
+        }
     }
 #else
     // (without the cull) Two record buffers take turns (the loop is unrolled by two), so the next record's scalar load flies while the current one is tested and no
