@@ -26,6 +26,7 @@ namespace dtof {
 constexpr uint32_t kSeg = 512;
 static_assert(kSeg / 64 == kChunkBlocks, "chunks per segment");
 constexpr int kShadeBlock = 64;   // k_shade runs ONE wave per block: compaction is ballot+popcount only, no barrier in the chunk loop
+static_assert(kShadeBlock == 64, "k_shade's compaction (wave_append) and its per-wave statistics take the block for one wave");
 // The closest-hit record between the trace and the shade of a bounce: (t, u, v, primitive) + the object / shape id.  Rectangle-only
 // instantiations (MESH = false) keep the distance alone: a rectangle's surface interaction is rebuilt from the ray and t
 // (rectangle.cpp:250-323 recomputes the local hit point), its primitive index is 0 -- 12 bytes less to write and to read per path vertex.

@@ -654,7 +654,7 @@ uint32_t device_lds_limit() {
     if (const char *e = getenv("DTOF_LDS_LIMIT")) return (uint32_t) strtoul(e, nullptr, 10);   // tests: a smaller budget than the device's (the step-down / fallback paths)
     int dev = 0, bytes = 0;
     if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&bytes, hipDeviceAttributeMaxSharedMemoryPerBlock, dev) != hipSuccess || bytes <= 0) return 64u * 1024u;
-    return (uint32_t) bytes > 1024u ? (uint32_t) bytes - 1024u : 0u;   // k_shade's static LDS (count slots) comes on top of the dynamic size
+    return (uint32_t) bytes > 1024u ? (uint32_t) bytes - 1024u : 0u;   // k_shade's static LDS (s_inline_all: the inline iterations' statistics, at most 16 waves x 2 * kMaxInline words) comes on top of the dynamic size
 }
 bool launch_shade(const uint8_t *scene, uint32_t scene_bytes, const RenderParams &rp, const Queues &q,
                   const uint32_t *qin, const uint32_t *count_in, uint32_t *qout,

@@ -9,23 +9,12 @@
 namespace dtof {
 
 
-// Block-wide exclusive prefix of a predicate (ballot + popcount per wave, 4 wave totals through LDS).
-// Returns this lane's slot relative to `running` and advances `running` by the block total.
-DTOF_D uint32_t block_append(bool pred, uint32_t *s_cnt, uint32_t &running) {
-    uint64_t mask = __ballot(pred);
-    uint32_t lane = __lane_id(), wave = threadIdx.x >> 6;
-    if (kShadeBlock == 64) {   // single-wave block: the wave-level prefix is the block-level prefix
-        uint32_t slot1 = running + (uint32_t) __popcll(mask & ((1ull << lane) - 1ull));
-        running += (uint32_t) __popcll(mask);
-        return slot1;
-    }
-    if (lane == 0) s_cnt[wave] = (uint32_t) __popcll(mask);
-    __syncthreads();
-    uint32_t c0 = s_cnt[0], c1 = s_cnt[1], c2 = s_cnt[2], c3 = s_cnt[3];
-    __syncthreads();
-    uint32_t before = wave == 0 ? 0 : wave == 1 ? c0 : wave == 2 ? c0 + c1 : c0 + c1 + c2;
-    uint32_t slot = running + before + (uint32_t) __popcll(mask & ((1ull << lane) - 1ull));
-    running += c0 + c1 + c2 + c3;
+// Exclusive prefix of a predicate over the wave = the block (kShadeBlock is one wave; a resident wave owns its segment): ballot + popcount, no LDS, no barrier.
+// Returns this lane's slot relative to `running` and advances `running` by the wave's total.
+DTOF_D uint32_t wave_append(bool pred, uint32_t &running) {
+    const uint64_t mask = __ballot(pred);
+    const uint32_t slot = running + (uint32_t) __popcll(mask & ((1ull << __lane_id()) - 1ull));
+    running += (uint32_t) __popcll(mask);
     return slot;
 }
 
@@ -354,20 +343,17 @@ template <bool LDS, int MODE, bool AREA, int KMAX, bool MESH, int SPEC, int RESW
 // scenes each).  Two waves stay for these instantiations because they are FASTER there: with four films in registers the 168-VGPR build spills 240 - 390 registers, and
 // the K = 4 frames of the every-BSDF scenes take 1 - 10 % longer at three waves (cornell_specular 9.13 -> 9.60 ms, cornell_spot 7.80 -> 8.58; profiles/r03_k4_waves_ab.txt)
 // -- the opposite of the K = 1 kernels, which lose 20 - 27 % at two (profiles/r03_spec_waves_ab.txt).
-// DTOF_K4_RES_MEM (default 1): the fused first-bounce kernels of SEVERAL films (KMAX > 1) keep neither the K running results nor the K NEE candidates in registers.
-// Round 4's four-film Domino kernel carried 12 + 12 of them across both traversals of every iteration, in scratch: 54 GB of HBM traffic per launch against 10.7 GB of
-// outputs, half its wave-cycles waiting (profiles/r04_pmc_c4_c5.txt).  What is pending across the shadow ray is K-INDEPENDENT -- the throughput, the unweighted
-// contribution bsdf_val * em_weight * mis_em and the path length to the emitter (dopplertofpath.cpp:214-226: only eval_modulation_weight, :60-77, depends on the film's offset and frequency)
-// = 7 registers -- and the K weights are applied when the sample is committed, in the same fmaf order.  The running results live where they have to end up anyway, in
-// q.res: a commit is a read-modify-write of the lane's K records (the first one of a path writes without reading, `res_live`), lines the same wave wrote a few
-// microseconds earlier.  MEASURED (profiles/r05_k4_film_state.txt): on the four-film Domino frame that form is no faster than the registers (181.9 against 178.9 ms) --
-// the kernel's scratch stays above the L2 either way -- so it is OFF (=1 builds it for A/B).
-// DTOF_K4_RES_LDS (default 1): the RESIDENT several-film kernels keep the running results in LDS instead: Domino's stage leaves 44 KiB of the CU's 160 free at 16 waves,
-// kParkWords = 11 words per thread, which hold 11 of the 12 floats of four RGB results (the twelfth stays a register); the pending sample is the K-independent one
-// described above.  Film state then costs the K = 4 kernel ONE register more than the K = 1 kernel's, and a commit is 12 ds_read + 12 ds_write.
-#ifndef DTOF_K4_RES_MEM
-#define DTOF_K4_RES_MEM 0
-#endif
+// DTOF_K4_RES_LDS (default 1): the RESIDENT kernels of SEVERAL films (RESW != 0, KMAX > 1) keep neither the K running results nor the K NEE candidates in registers
+// (round 4's four-film Domino kernel carried 12 + 12 of them across both traversals of every iteration, in scratch: profiles/r04_pmc_c4_c5.txt).  What is pending across
+// the shadow ray is K-INDEPENDENT -- the throughput, the unweighted contribution bsdf_val * em_weight * mis_em and the path length to the emitter
+// (dopplertofpath.cpp:214-226: only eval_modulation_weight, :60-77, depends on the film's offset and frequency) = 7 registers -- and the K weights are applied when the
+// sample is committed, in the same fmaf order.  The running results live in LDS columns: Domino's stage leaves 44 KiB of the CU's 160 free at 16 waves, kParkWords = 11
+// words per thread, which hold 11 of the 12 floats of four RGB results (the twelfth stays a register).  Film state then costs the K = 4 kernel ONE register more than the
+// K = 1 kernel's, and a commit is 12 ds_read + 12 ds_write.  0: results and candidates stay in registers, as in every other kernel.
+// These kernels decide `want_shadow` from the pending sample (are its three products non-zero?) where every other form compares the candidate with the current result:
+// a few more shadow rays, same films -- their shadow-ray counters are NOT comparable with the other forms'.
+// (The same pending sample with the running results read-modify-written in q.res, for every several-film first-bounce kernel, was built behind a switch of its own and
+// measured no faster than the registers on the four-film Domino frame, 181.9 against 178.9 ms, profiles/r05_k4_film_state.txt.  Removed.)
 #ifndef DTOF_K4_RES_LDS
 #define DTOF_K4_RES_LDS 1
 #endif
@@ -385,19 +371,17 @@ __global__ __launch_bounds__(RESW ? RESW * 64 : kShadeBlock, RESW ? RESW / 4 : (
     static_assert(!F_FUSED_SPLAT || KMAX == 1, "the fused splat is the one-film kernels'");
     static_assert(!F_WAVE_PIXEL || F_IDENTITY, "whole waves of one pixel are provable for an identity queue only");
     static_assert(!F_ONE_BLOCK || RESW == 0, "blocks per segment belong to the classic launch");
-    constexpr bool RES_LDS = RESW != 0 && KMAX > 1 && DTOF_K4_RES_LDS;   // several films, resident stage: running results in LDS columns
+    constexpr bool RES_LDS = RESW != 0 && KMAX > 1 && DTOF_K4_RES_LDS;   // several films, resident stage: running results in LDS columns, the pending NEE sample K-independent (see above)
     constexpr bool S16 = RESW != 0 && KMAX > 1;                           // ... whose LDS comes from 16-bit traversal stacks (dtof_traverse.h: encode_child16)
-    constexpr bool RES_MEM = FIRST && KMAX > 1 && (RES_LDS || DTOF_K4_RES_MEM);   // several films: running results outside the registers (LDS, else q.res), the pending NEE sample K-independent (see above)
     static_assert(!RES_LDS || 3 * KMAX == (int) kParkWords + 1, "the film-state columns hold all but the last float of the K results");
     constexpr bool PARK_ST = DTOF_PARK && RESW == 16 && KMAX == 1;   // the path state no traversal reads waits in LDS columns while the rays are traced: throughput / path length (one film only) ...
     constexpr bool PARK = DTOF_PARK && RESW == 16 && (KMAX == 1 || RES_LDS);   // ... and both PCG streams (several films: behind the film words)
     constexpr uint32_t kRngAt = RES_LDS ? kParkWords : 0u;
-    constexpr int KREG = RES_MEM ? 1 : KMAX;                         // film-state registers the lane carries
+    constexpr int KREG = RES_LDS ? 1 : KMAX;                         // film-state registers the lane carries
     constexpr uint32_t kStackStride = RESW ? RESW * 64 : kShadeBlock;   // the block size = the stride of the traversal-stack columns
     static_assert(RESW == 0 || (MODE == 2 && !LDS && MESH), "the resident stage exists for the unstaged fused first-bounce kernel with mesh code");
     static_assert(!RH16 || RESW != 0, "half-float LDS planes belong to the resident stage");
     extern __shared__ uint4 lds[];
-    __shared__ uint32_t s_cnt[4];
     __shared__ uint32_t s_inline_all[(RESW ? RESW : 1) * 2 * kMaxInline];   // FIRST: lanes alive after / shadow rays of every inline iteration but the last (statistics), per wave
     typedef const char __attribute__((address_space(4))) *KernargBytes;
     const KernargBytes kernarg = (KernargBytes) __builtin_amdgcn_kernarg_segment_ptr();
@@ -449,7 +433,7 @@ __global__ __launch_bounds__(RESW ? RESW * 64 : kShadeBlock, RESW ? RESW / 4 : (
         sv_res.isect = (const DTriIsect *) (small + gh->off_isect);
         sv_res.emitters = (const DEmitter *) (small + gh->off_emitters);
     }
-    for (uint32_t seg_first = 1;; seg_first = 0) {   // resident: until the segment counter runs out; otherwise once
+    for (;;) {   // resident: until the segment counter runs out; otherwise once
     uint32_t seg, sub_index = 0;
     if (RESW) {
         uint32_t taken = 0;
@@ -463,7 +447,6 @@ __global__ __launch_bounds__(RESW ? RESW * 64 : kShadeBlock, RESW ? RESW / 4 : (
     } else {
         seg = sub > 1 ? blockIdx.x / sub : blockIdx.x; sub_index = sub > 1 ? blockIdx.x - seg * sub : 0u;
     }
-    (void) seg_first;
     const uint32_t count = seg_count(F_IDENTITY ? nullptr : A0.count_in, seg, A0.rp.n_lanes);
     uint32_t n_alive = 0, n_shadow = 0;
     if (FIRST && lane_id < 2 * kMaxInline) s_inline[lane_id] = 0;   // a wave's own slots: no barrier needed
@@ -493,39 +476,33 @@ __global__ __launch_bounds__(RESW ? RESW * 64 : kShadeBlock, RESW ? RESW / 4 : (
     float3 rbase[KREG];   // FIRST: the result a lane ends this launch with if its NEE candidate is not committed
 #pragma unroll
     for (int k = 0; k < KREG; ++k) rbase[k] = make_float3(0.f, 0.f, 0.f);
-    // RES_MEM: the pending emitter sample without its modulation weights -- throughput before the bounce, bsdf_val * em_weight * mis_em, path length to the emitter --
-    // and whether q.res holds the lane's running result yet (it is 0 until something was added: the first write needs no read, a path that adds nothing writes zeros at the end)
-    V3 pend_thr = mk(0, 0, 0), pend_v = mk(0, 0, 0); float pend_len = 0.f; bool res_live = false;
-    // the lane's running result of film k: a register (FIRST), its q.res record (the bounce kernels; RES_MEM once res_live -- before that it is 0 and nothing is read)
+    // RES_LDS: the pending emitter sample without its modulation weights -- throughput before the bounce, bsdf_val * em_weight * mis_em, path length to the emitter
+    V3 pend_thr = mk(0, 0, 0), pend_v = mk(0, 0, 0); float pend_len = 0.f;
     float *const park = RES_LDS || PARK ? (float *) (lds + stage_words) + memo_words + A0.res_park_off + threadIdx.x : nullptr;   // word f of this thread at park[f * kStackStride]
     float res_last = 0.f;   // RES_LDS: the one float of the K results that has no LDS word (film KMAX - 1, blue)
-    if (RES_LDS) {
-#pragma unroll
-        for (uint32_t f = 0; f < kParkWords; ++f) park[f * kStackStride] = 0.f;
-    }
+    // the lane's running result of film k: its LDS words (RES_LDS), a register (the other first-bounce kernels), its q.res record (the bounce kernels).  (Plain `if`s: under
+    // `if constexpr` the two closures capture other variables in the RES_LDS kernels than elsewhere, and the register allocation of every kernel moves with that.  Where
+    // KREG is 1, the [k] of the register form sits behind a return / an else of a constant.)
     auto res_get = [&](int k) -> float4 {
         if (RES_LDS) return make_float4(park[(3 * k) * kStackStride], park[(3 * k + 1) * kStackStride], 3 * k + 2 < (int) kParkWords ? park[(3 * k + 2) * kStackStride] : res_last, 0.f);
-        if (RES_MEM) return res_live ? q.res[(size_t) k * q.capacity + l] : make_float4(0.f, 0.f, 0.f, 0.f);
-        if (FIRST) { const float3 r = rbase[RES_MEM ? 0 : k]; return make_float4(r.x, r.y, r.z, 0.f); }
-        return q.res[(size_t) k * q.capacity + l];
+        if (!FIRST) return q.res[(size_t) k * q.capacity + l];
+        const float3 r = rbase[k]; return make_float4(r.x, r.y, r.z, 0.f);
     };
     auto res_put = [&](int k, float4 v) {
         if (RES_LDS) {
             park[(3 * k) * kStackStride] = v.x; park[(3 * k + 1) * kStackStride] = v.y;
             if (3 * k + 2 < (int) kParkWords) park[(3 * k + 2) * kStackStride] = v.z; else res_last = v.z;
         }
-        else if (FIRST && !RES_MEM) rbase[RES_MEM ? 0 : k] = make_float3(v.x, v.y, v.z);
+        else if (FIRST) rbase[k] = make_float3(v.x, v.y, v.z);
         else q.res[(size_t) k * q.capacity + l] = v;
     };
-    // "the lane's results are zero again" (a path of null interactions that ends invalid): RES_LDS rewrites its columns, the q.res form only drops its flag
+    // RES_LDS: the lane's results are zero (a new path; a path of null interactions that ends invalid)
     auto res_clear = [&]() {
-        if (RES_LDS) {
 #pragma unroll
-            for (uint32_t f = 0; f < kParkWords; ++f) park[f * kStackStride] = 0.f;
-            res_last = 0.f;
-        }
-        res_live = false;
+        for (uint32_t f = 0; f < kParkWords; ++f) park[f * kStackStride] = 0.f;
+        res_last = 0.f;
     };
+    if constexpr (RES_LDS) res_clear();
     const float4 zero4 = make_float4(0.f, 0.f, 0.f, 0.f);
     // Path state of the lane.  MODE 2 runs rp.inline_iters iterations of the bounce loop right here ("megakernel" head): between them the
     // state stays in these registers instead of making the round trip through the queues in HBM; after the last one the survivors are
@@ -640,7 +617,7 @@ __global__ __launch_bounds__(RESW ? RESW * 64 : kShadeBlock, RESW ? RESW / 4 : (
         const bool valid_in = FIRST ? valid_reg : (SPEC ? (depth > 0 ? q.st_c[l].y >= 2.f : valid_start) : depth > 0);
         if (hid == 0xffffffffu) {   // the path ends here: nothing validates it any more
             if (SPEC && !valid_in && depth > 0) {   // select(valid_ray, result, 0) (:279-282): what the path gathered behind null interactions does not count
-                if (RES_MEM) res_clear();
+                if constexpr (RES_LDS) res_clear();
                 else {
 #pragma unroll
                     for (int k = 0; k < KMAX; ++k) if (KMAX == 1 || k < rp.n_offsets) res_put(k, zero4);
@@ -670,7 +647,6 @@ __global__ __launch_bounds__(RESW ? RESW * 64 : kShadeBlock, RESW ? RESW / 4 : (
                 const float4 r = res_get(k);
                 res_put(k, make_float4(fmaf(stv.x, v.x, r.x), fmaf(stv.y, v.y, r.y), fmaf(stv.z, v.z, r.z), 0.f));
             }
-            if (RES_MEM) res_live = true;
         }
         if (hid != 0xffffffffu) {   // a miss ends the path (active_next = false, dopplertofpath.cpp:171)
             V3 o = mk(ra.x, ra.y, ra.z), d = mk(rb.x, rb.y, rb.z); float time = ra.w;
@@ -698,11 +674,11 @@ __global__ __launch_bounds__(RESW ? RESW * 64 : kShadeBlock, RESW ? RESW / 4 : (
             const float pmf = rp.emitter_pmf;   // m_emitter_pmf (scene.cpp:96)
             // ---- direct emission (dopplertofpath.cpp:150-168 / path.cpp): the hit shape carries an area emitter
             bool res_dirty = false;
-            float4 rcur[KREG];   // (RES_MEM: the emitter-hit term goes straight to q.res)
+            float4 rcur[KREG];   // (RES_LDS: the emitter-hit term goes straight to the LDS columns)
             if (AREA) {
-                if (!RES_MEM) {
+                if constexpr (!RES_LDS) {
 #pragma unroll
-                    for (int k = 0; k < KMAX; ++k) if (KMAX == 1 || k < rp.n_offsets) rcur[RES_MEM ? 0 : k] = res_get(k);
+                    for (int k = 0; k < KMAX; ++k) if (KMAX == 1 || k < rp.n_offsets) rcur[k] = res_get(k);
                 }
                 if (sh->flags & SF_EMITTER) {
                     float4 pb = depth > 0 ? (FIRST ? stb_reg : q.st_b[l]) : make_float4(0.f, 0.f, 0.f, 1.f);   // prev_si.p, prev_bsdf_pdf
@@ -732,20 +708,21 @@ __global__ __launch_bounds__(RESW ? RESW * 64 : kShadeBlock, RESW ? RESW / 4 : (
                     for (int k = 0; k < KMAX; ++k) if (KMAX == 1 || k < rp.n_offsets) {
                         V3 v = le * mis_bsdf;
                         if (!plain) v = v * modulation_weight(rp, rp.w_d[k], rp.phase[k], time, path_length);
-                        const float4 r = RES_MEM ? res_get(k) : rcur[RES_MEM ? 0 : k];
+                        float4 r;
+                        if constexpr (RES_LDS) r = res_get(k); else r = rcur[k];
                         const float4 acc = make_float4(fmaf(thr.x, v.x, r.x), fmaf(thr.y, v.y, r.y), fmaf(thr.z, v.z, r.z), 0.f);
-                        if (RES_MEM) res_put(k, acc); else rcur[RES_MEM ? 0 : k] = acc;
+                        if constexpr (RES_LDS) res_put(k, acc); else rcur[k] = acc;
                     }
-                    if (RES_MEM) res_live = true; else res_dirty = true;
+                    res_dirty = !RES_LDS;
                 }
             }
 
             if (terminal && !active_next) {
                 // terminal, and no emitter is sampled at this depth: the iteration existed for the emitter-hit term alone.  valid_ray: terminal launches are those of
                 // scenes without a null lobe (plan_frame), where every vertex validates its path
-                if (res_dirty) {
+                if constexpr (!RES_LDS) if (res_dirty) {
 #pragma unroll
-                    for (int k = 0; k < KMAX; ++k) if (KMAX == 1 || k < rp.n_offsets) res_put(k, rcur[RES_MEM ? 0 : k]);
+                    for (int k = 0; k < KMAX; ++k) if (KMAX == 1 || k < rp.n_offsets) res_put(k, rcur[k]);
                 }
                 if (!F_NO_LANE_OUT && rp.want_valid) q.valid_out[l] = make_float4(1.f, 0.f, 0.f, 0.f);
             } else {
@@ -875,7 +852,7 @@ __global__ __launch_bounds__(RESW ? RESW * 64 : kShadeBlock, RESW ? RESW / 4 : (
             if (active_em) {
                 const float mis_em = ds_delta ? 1.f : mis_weight(ds_pdf, bsdf_pdf);   // dopplertofpath.cpp:218-219
                 bool nonzero = false;
-                if (RES_MEM) {   // the sample waits for its visibility test WITHOUT the K modulation weights; they are applied at the commit (below), in the order of the loop that follows
+                if constexpr (RES_LDS) {   // the sample waits for its visibility test WITHOUT the K modulation weights; they are applied at the commit (below), in the order of the loop that follows
                     pend_thr = thr; pend_len = path_length + ds_dist;
                     pend_v = mk(bsdf_val.x * em_weight.x * mis_em, bsdf_val.y * em_weight.y * mis_em, bsdf_val.z * em_weight.z * mis_em);
                     // a sample whose three products are zero adds exactly zero to every film whatever its weights: no visibility test (the register form compares the
@@ -884,19 +861,19 @@ __global__ __launch_bounds__(RESW ? RESW * 64 : kShadeBlock, RESW ? RESW / 4 : (
                 } else {
 #pragma unroll
                 for (int k = 0; k < KMAX; ++k) if (KMAX == 1 || k < rp.n_offsets) {
-                    float4 r = AREA ? rcur[RES_MEM ? 0 : k] : res_get(k);
+                    float4 r = AREA ? rcur[k] : res_get(k);
                     V3 v = mk(bsdf_val.x * em_weight.x * mis_em, bsdf_val.y * em_weight.y * mis_em, bsdf_val.z * em_weight.z * mis_em);
                     if (!plain) { float lw = modulation_weight(rp, rp.w_d[k], rp.phase[k], time, path_length + ds_dist); v = v * lw; }
                     float3 c = make_float3(fmaf(thr.x, v.x, r.x), fmaf(thr.y, v.y, r.y), fmaf(thr.z, v.z, r.z));
-                    cand[RES_MEM ? 0 : k] = c;
+                    cand[k] = c;
                     nonzero |= f2u(c.x) != f2u(r.x) || f2u(c.y) != f2u(r.y) || f2u(c.z) != f2u(r.z);
                 }
                 }
                 want_shadow = nonzero;   // a candidate identical to the current result needs no visibility test
             }
-            if (res_dirty) {   // the emitter-hit term stands whether or not the NEE candidate is later committed
+            if constexpr (!RES_LDS) if (res_dirty) {   // the emitter-hit term stands whether or not the NEE candidate is later committed
 #pragma unroll
-                for (int k = 0; k < KMAX; ++k) if (KMAX == 1 || k < rp.n_offsets) res_put(k, rcur[RES_MEM ? 0 : k]);
+                for (int k = 0; k < KMAX; ++k) if (KMAX == 1 || k < rp.n_offsets) res_put(k, rcur[k]);
             }
             if (terminal) {   // the path ends here whatever it sampled; valid_ray as above
                 if (!F_NO_LANE_OUT && rp.want_valid) q.valid_out[l] = make_float4(1.f, 0.f, 0.f, 0.f);
@@ -920,7 +897,7 @@ __global__ __launch_bounds__(RESW ? RESW * 64 : kShadeBlock, RESW ? RESW / 4 : (
             const bool ends = !alive || (last && !trace_next);   // nobody continues this path: what it returns is decided here
             if (SPEC && ends && !valid_now) {   // select(valid_ray, result, 0) (:279-282): neither the emitter-hit term nor this vertex's NEE candidate survives
                 want_shadow = false;
-                if (RES_MEM) res_clear();
+                if constexpr (RES_LDS) res_clear();
                 else {
 #pragma unroll
                     for (int k = 0; k < KMAX; ++k) if (KMAX == 1 || k < rp.n_offsets) res_put(k, zero4);
@@ -950,26 +927,22 @@ __global__ __launch_bounds__(RESW ? RESW * 64 : kShadeBlock, RESW ? RESW / 4 : (
         }
     }
     if (last) {
-        uint32_t slot = block_append(alive, s_cnt, n_alive);
+        uint32_t slot = wave_append(alive, n_alive);
         if (alive && trace_next) qout[seg * kSeg + slot] = l;
     } else {   // FIRST, one wave per block
         const uint32_t n_on = (uint32_t) __popcll(__ballot(alive));
         if (lane_id == 0) s_inline[2 * it] += n_on;
     }
-    if (FUSED) {
+    if constexpr (FUSED) {
         bool commit = false;
         // (Both rays in ONE traversal loop -- a lane going on with its continuation ray while its neighbours are still in their shadow rays -- was built and measured in
         // round 5 and lost by a third: tools/experiments/r05_pair_traversal.patch, profiles/r05_pair_traversal.txt.)
         if (want_shadow) {   // test_visibility (scene.cpp:266-271): an unoccluded sample commits its candidate result
             Hit hs;
-#if defined(DTOF_ABLATE) && (DTOF_ABLATE & 1)
-            commit = sha.w > 0.f;
-#else
             commit = (F_FLAT || flat) ? !trace_flat<true, true, FACTS & kFactOneWall>(sv, (ConstBytes) A.scene + rp.flat_off, rp.flat_off, flat, stack, mk(sha.x, sha.y, sha.z), mk(shb.x, shb.y, shb.z), shb.w, sha.w, hs)
                           : !trace_scene<true, MESH, true, RESW != 0, kStackStride, S16, 0u, false, RH16>(sv, stack, mk(sha.x, sha.y, sha.z), mk(shb.x, shb.y, shb.z), shb.w, sha.w, hs);
-#endif
         }
-        if (RES_MEM) {   // the committed sample gets its K modulation weights now (dopplertofpath.cpp:221-226) and is added to the films' records in q.res
+        if constexpr (RES_LDS) {   // the committed sample gets its K modulation weights now (dopplertofpath.cpp:221-226) and is added to the films' running results
             if (commit) {
                 const bool plain_ = rp.integrator != 0;
 #pragma unroll
@@ -979,47 +952,37 @@ __global__ __launch_bounds__(RESW ? RESW * 64 : kShadeBlock, RESW ? RESW / 4 : (
                     const float4 r = res_get(k);
                     res_put(k, make_float4(fmaf(pend_thr.x, v.x, r.x), fmaf(pend_thr.y, v.y, r.y), fmaf(pend_thr.z, v.z, r.z), 0.f));
                 }
-                res_live = true;
             }
-            if (RES_LDS) {   // the results leave the LDS columns for q.res (what the splat kernels read)
-                if (last && in_range) {
+            if (last && in_range) {   // the results leave the LDS columns for q.res (what the splat kernels read)
 #pragma unroll
-                    for (int k = 0; k < KMAX; ++k) if (k < rp.n_offsets) q.res[(size_t) k * q.capacity + l] = res_get(k);
-                }
-            } else if (last && in_range && !res_live) {   // nothing was ever added (or a path of null interactions was zeroed): the records still hold an earlier batch's values
-#pragma unroll
-                for (int k = 0; k < KMAX; ++k) if (k < rp.n_offsets) res_put(k, zero4);
+                for (int k = 0; k < KMAX; ++k) if (k < rp.n_offsets) q.res[(size_t) k * q.capacity + l] = res_get(k);
             }
         } else if (FIRST) {   // the running result stays in rbase over the inline iterations; every lane's result is defined after the last (nothing zeroed it)
 #pragma unroll
             for (int k = 0; k < KMAX; ++k) if (KMAX == 1 || k < rp.n_offsets) {
-                if (commit) rbase[RES_MEM ? 0 : k] = cand[RES_MEM ? 0 : k];
-                if (last && in_range && !fuse_splat) q.res[(size_t) k * q.capacity + l] = make_float4(rbase[RES_MEM ? 0 : k].x, rbase[RES_MEM ? 0 : k].y, rbase[RES_MEM ? 0 : k].z, 0.f);
+                if (commit) rbase[k] = cand[k];
+                if (last && in_range && !fuse_splat) q.res[(size_t) k * q.capacity + l] = make_float4(rbase[k].x, rbase[k].y, rbase[k].z, 0.f);
             }
         } else if (commit) {
 #pragma unroll
-            for (int k = 0; k < KMAX; ++k) if (KMAX == 1 || k < rp.n_offsets) q.res[(size_t) k * q.capacity + l] = make_float4(cand[RES_MEM ? 0 : k].x, cand[RES_MEM ? 0 : k].y, cand[RES_MEM ? 0 : k].z, 0.f);
+            for (int k = 0; k < KMAX; ++k) if (KMAX == 1 || k < rp.n_offsets) q.res[(size_t) k * q.capacity + l] = make_float4(cand[k].x, cand[k].y, cand[k].z, 0.f);
         }
         if (alive && trace_next) {   // closest hit of the continuation ray, consumed by the next bounce (the Hit lives inside this block: no half-defined registers across the commit above)
             Hit h;
-#if defined(DTOF_ABLATE) && (DTOF_ABLATE & 2)
-            bool found = nra.x < 1e30f; h.t = 0.5f + 0.1f * nrb.x; h.u = nrb.y; h.v = nrb.z; h.obj = nrb.x > 0.3f ? 3 : nrb.y > 0.f ? 1 : 0; h.shape = 0; h.prim = 0;
-#else
             bool found = (F_FLAT || flat) ? trace_flat<false, true, FACTS & kFactOneWall>(sv, (ConstBytes) A.scene + rp.flat_off, rp.flat_off, flat, stack, mk(nra.x, nra.y, nra.z), mk(nrb.x, nrb.y, nrb.z), nra.w, nrb.w, h)
                               : trace_scene<false, MESH, true, RESW != 0, kStackStride, S16, 0u, false, RH16>(sv, stack, mk(nra.x, nra.y, nra.z), mk(nrb.x, nrb.y, nrb.z), nra.w, nrb.w, h);
-#endif
             if (!FIRST || last) store_hit<MESH>(q, l, h, found);
             if (FIRST) { hh = make_uint4(f2u(h.t), f2u(h.u), f2u(h.v), h.prim); hid = found ? (h.obj | (h.shape << q.id_shift)) : 0xffffffffu; }
         }
         const uint32_t n_sh = (uint32_t) __popcll(__ballot(want_shadow)) * ((threadIdx.x & 63) == 0 ? 1u : 0u);   // per-wave partial (stats only)
         if (last) n_shadow += n_sh; else if (lane_id == 0) s_inline[2 * it + 1] += n_sh;
     } else {
-        uint32_t sslot = seg * kSeg + block_append(want_shadow, s_cnt, n_shadow);
+        uint32_t sslot = seg * kSeg + wave_append(want_shadow, n_shadow);
         if (want_shadow) {
             q.sh_a[sslot] = sha; q.sh_b[sslot] = shb;
 #pragma unroll
             for (int k = 0; k < KMAX; ++k) if (KMAX == 1 || k < rp.n_offsets)
-                q.sh_c[(size_t) k * q.capacity + sslot] = make_float4(cand[RES_MEM ? 0 : k].x, cand[RES_MEM ? 0 : k].y, cand[RES_MEM ? 0 : k].z, u2f(l));
+                q.sh_c[(size_t) k * q.capacity + sslot] = make_float4(cand[k].x, cand[k].y, cand[k].z, u2f(l));
         }
     }
     if (last) break;
@@ -1028,7 +991,7 @@ __global__ __launch_bounds__(RESW ? RESW * 64 : kShadeBlock, RESW ? RESW / 4 : (
     lane_on = alive;
     if (alive) { ra = nra; rb = nrb; DTOF_POISON_CHECK(); }
     }   // inline iterations
-    if constexpr (!RES_MEM) if (FIRST && fuse_splat) {   // ---- ImageBlock::put (imageblock.cpp:414-531) of the wave's samples: tent filter of radius <= 1, a 3 x 3 footprint anchored at the sample's pixel
+    if constexpr (!RES_LDS) if (FIRST && fuse_splat) {   // ---- ImageBlock::put (imageblock.cpp:414-531) of the wave's samples: tent filter of radius <= 1, a 3 x 3 footprint anchored at the sample's pixel
         const uint32_t W = (uint32_t) rp.crop_w;
         const uint32_t pix = fdiv(global_lane(rp, rp.lane_base + l), rp.d_spp);
         const int py = (int) fdiv(pix, rp.d_w), px = (int) (pix - W * (uint32_t) py);
@@ -1066,12 +1029,6 @@ __global__ __launch_bounds__(RESW ? RESW * 64 : kShadeBlock, RESW ? RESW / 4 : (
     }
     }   // chunk loop
     }   // count != 0
-    if (FUSED && kShadeBlock > 64) {   // shadow-ray count for the statistics: sum the four per-wave partials
-        __syncthreads();
-        if ((threadIdx.x & 63) == 0) s_cnt[threadIdx.x >> 6] = n_shadow;
-        __syncthreads();
-        n_shadow = s_cnt[0] + s_cnt[1] + s_cnt[2] + s_cnt[3];
-    }
     if (lane_id == 0) {
         if (sub > 1) { atomicAdd(&A0.alive_out[seg], n_alive); atomicAdd(&A0.shadow_out[seg], n_shadow); }
         else { A0.alive_out[seg] = n_alive; A0.shadow_out[seg] = n_shadow; }

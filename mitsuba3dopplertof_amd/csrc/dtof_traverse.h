@@ -249,7 +249,7 @@ template <bool S16, uint32_t LDSN>
 DTOF_D uint32_t stack_get(const uint32_t *stack, const uint32_t *ovf, int sp, uint32_t stride) {
     if (LDSN != 0 && (uint32_t) sp >= LDSN) return ovf[(uint32_t) sp - LDSN];
     uint32_t x = S16 ? (uint32_t) ((const uint16_t *) stack)[sp * stride] : stack[sp * stride];
-    if (LDSN != 0) asm volatile("" : "+v"(x));   // (see stack_put: a ds_read in its own branch, not a flat_load)
+    if (LDSN != 0) asm volatile("" : "+v"(x));   // (see stack_put: a ds_read in its own branch, not a flat access)
     return x;
 }
 // One traversal step at inner node `cur` = four 16-byte loads issued together (no load depends on a field of the node): continue with the nearest child that is
@@ -435,7 +435,10 @@ DTOF_D bool trace_scene(const SceneView &sv, uint32_t *stack, V3 o, V3 d, float 
             if (cand->x == 0xffffffffu) cand->x = oi; else if (cand->y == 0xffffffffu) cand->y = oi; else if (cand->z == 0xffffffffu) cand->z = oi; else if (cand->w == 0xffffffffu) cand->w = oi;
             else put_aside = false;
         }
-        if (!put_aside && intersect_object<ANY, MESH, MEMO, STRIDE, S16, LDSN, H16>(sv, cur & ~kLeaf & (S16 ? 0xffffu : kLeafObjMask), o, d, time, maxt, best, stack, sp, stride, ovf) && ANY) return true;
+        // The kernels with 16-bit stack columns are the resident ones, whose scenes have no mesh behind a BLAS (render_rows throws otherwise): a BLAS walk would push
+        // 32-bit references onto those columns, so their instantiations carry none.
+        constexpr bool NOBLAS = S16;
+        if (!put_aside && intersect_object<ANY, MESH, MEMO, STRIDE, NOBLAS, LDSN, H16>(sv, cur & ~kLeaf & (S16 ? 0xffffu : kLeafObjMask), o, d, time, maxt, best, stack, sp, stride, ovf) && ANY) return true;
         if (sp == 0) break;
         --sp; cur = stack_get<S16, LDSN>(stack, ovf, sp, stride);
     }
@@ -469,9 +472,7 @@ DTOF_D bool trace_deferred(const SceneView &sv, uint32_t *stack, uint4 cand, V3 
 
 
 // Rectangle-only scenes of a handful of top-level objects (the five walls of the Cornell room of C2): no TLAS walk.  Every lane tests
-// every object in index order -- a loop whose trip count and addresses are wave-uniform, so the object and shape records come in by
-// SCALAR loads from the blob in global memory (constant address space; the copy staged in LDS serves the per-lane reads of
-// compute_surface) and their matrix entries are SGPR operands of the lane arithmetic.  No stack, no divergence: for <= 8 rectangles the
+// every object in index order -- a loop whose trip count and addresses are wave-uniform (the records' source: below).  No stack, no divergence: for <= 8 rectangles the
 // ~40 instructions per rectangle cost less than the ~55 per node step + ~60 per leaf visit of the binary tree at 0.5 lane utilisation.
 // Hits are those of trace_scene bit for bit: same rect_hit arithmetic, smallest t wins, ties go to the lowest object index
 // (ascending order + strict <).  Instances take intersect_object (one uniform branch).
@@ -479,70 +480,35 @@ DTOF_D bool trace_deferred(const SceneView &sv, uint32_t *stack, uint4 cand, V3 
 // of the wave can hit the rectangle, the wave branches over the rest of the test (the xy rows, the IEEE division, the u / v checks).  Shadow rays of a closed room never
 // cross a wall between two points inside it, and rays skip the walls behind them: of the ~37 instructions of a test, ~10 remain.
 typedef const uint8_t __attribute__((address_space(4))) *ConstBytes;
-// DTOF_FLAT_PK=1: the rectangle transform of trace_flat as packed multiply-adds (v_pk_fma_f32 with the matrix entries as SGPR-pair operands: two
-// multiply-adds in the 4 cycles ONE scalar-operand v_fma_f32 takes, profiles/r03_ubench_valu_rate.txt).  Bit-exact; measured on C2: 3 % fewer VALU
-// instructions but the pairs cost registers in a kernel at its cap -- spill loads / stores per wave 157 -> 580, frame 1.53 -> 1.65 ms
-// (profiles/r03_flat_packed_ab.txt).  Off.
-#ifndef DTOF_FLAT_PK
-#define DTOF_FLAT_PK 0
-#endif
-#ifndef DTOF_FLAT_LDS
-#define DTOF_FLAT_LDS 1
-#endif
-// DTOF_FLAT_PEEL=1: the kernels compiled with kFactOneWall visit the flat table as three segments around the wall instead of one loop that picks each object's ray
-// (the world ray, or the wall's) by copying it -- six v_mov_b32 per visit and six more for the wall, 7 % of the executed vector instructions of C2's kernel.  Same
-// visits, same order, same arithmetic (profiles/flat_peel_ab.txt).  0: the single loop, kept for A/B timing.
-#ifndef DTOF_FLAT_PEEL
-#define DTOF_FLAT_PEEL 1
-#endif
-// DTOF_FLAT_BEST_CULL=1 (with DTOF_FLAT_PEEL): a closest-hit query's certain-miss test is bounded by the nearest hit it holds instead of the ray's maxt.
-#ifndef DTOF_FLAT_BEST_CULL
-#define DTOF_FLAT_BEST_CULL 0
-#endif
+// (The rectangle transform as packed multiply-adds -- v_pk_fma_f32 with SGPR-pair operands -- was built behind a switch, bit-exact, and measured on C2: 3 % fewer VALU
+// instructions, but spill loads / stores per wave 157 -> 580 and the frame 1.53 -> 1.65 ms, profiles/r03_flat_packed_ab.txt.  Removed.)
 typedef float F2 __attribute__((ext_vector_type(2)));
-struct FlatRecord { uint32_t instance; F2 c0, c1, c2, c3; float z0, z1, z2, z3; };   // (x, y) entries of the four columns as pairs, the z row apart
-DTOF_D FlatRecord flat_load(const DFlatObject __attribute__((address_space(4))) *f) {
-    FlatRecord r; r.instance = f->instance;
-    r.c0 = F2{ f->c0[0], f->c0[1] }; r.c1 = F2{ f->c1[0], f->c1[1] }; r.c2 = F2{ f->c2[0], f->c2[1] }; r.c3 = F2{ f->c3[0], f->c3[1] };
-    r.z0 = f->c0[2]; r.z1 = f->c1[2]; r.z2 = f->c2[2]; r.z3 = f->c3[2];
-    return r;
-}
+struct FlatRecord { F2 c0, c1, c2, c3; };   // (x, y) entries of the four columns of a rectangle's matrix as pairs; the z row comes from the DFlatZ table
 // the z rows of the point and the direction (xf_point / xf_vector, z components): zrow.x = local z of the origin, zrow.y = that of the direction
 DTOF_D F2 flat_zrow(float z0, float z1, float z2, float z3, V3 ro, V3 rd) {
-#if DTOF_FLAT_PK   // (same entries, different vectors: one packed multiply-add per column; the direction's leading product becomes fma(m, d, -0), which equals m * d)
-    return __builtin_elementwise_fma(F2{ z2, z2 }, F2{ ro.z, rd.z }, __builtin_elementwise_fma(F2{ z1, z1 }, F2{ ro.y, rd.y }, __builtin_elementwise_fma(F2{ z0, z0 }, F2{ ro.x, rd.x }, F2{ z3, -0.f })));
-#else
     return F2{ fmaf(z2, ro.z, fmaf(z1, ro.y, fmaf(z0, ro.x, z3))), fmaf(z2, rd.z, fmaf(z1, rd.y, z0 * rd.x)) };
-#endif
 }
-// FACTS (k_shade's plan facts, dtof_kernels.h): under kFactOneWall the one instance is the memo object of one rectangle -- no DFlatKinds loads, no instance loop.
+// The records come from the scene copy staged in LDS, every lane reading the same address (a broadcast): the matrix entries are then VGPR operands of the
+// multiply-adds, which issue at full rate -- as SGPR operands (scalar loads from the blob in global memory, the first form of this loop, removed) each of the 21 costs two
+// issue slots (profiles/r03_ubench_valu_rate.txt).
+// First the object's z row (ONE ds_read_b128 from the DFlatZ table behind the records) and the certain-miss test; the rest of the record (four ds_read_b128) only
+// where a lane of the wave still needs the full test.
+// FACTS (k_shade's plan facts, dtof_kernels.h) selects one of two forms:
+//   kFactOneWall  the one instance is the memo object of one rectangle.  The table is visited as three segments in ascending index order -- the rectangles below the
+//                 wall, the wall, the rectangles above it: the plain rectangles read the world ray where it lies and the wall reads its own ray, so no iteration
+//                 selects between the two by copying six registers (profiles/flat_peel_ab.txt).  No DFlatKinds loads, no instance loop.
+//   otherwise     one loop that picks each object's ray; the instance marks are two scalar loads (DFlatKinds), the instances are intersected after the rectangles.
+// One visit is the same in both, operation for operation.  (Sharing its text as one lambda changes the generic kernels' code; the twelve lines are written twice.)
 template <bool ANY, bool MEMO, uint32_t FACTS = 0>
 DTOF_D bool trace_flat(const SceneView &sv, ConstBytes flat_table, uint32_t flat_off, uint32_t n_objects, uint32_t *stack, V3 o, V3 d, float time, float maxt, Hit &best) {
-    typedef const DFlatObject __attribute__((address_space(4))) *ConstFlat;
-    const ConstFlat table = (ConstFlat) flat_table;
     best.t = maxt; best.u = best.v = 0.f; best.obj = 0xffffffffu; best.shape = 0; best.prim = 0;
     bool occluded = false;
     DTOF_STAT(0);
-    // the ray in the space of object `oi`: the world ray, or -- the one memoised instance -- moved there first, as intersect_object does (instance.cpp:101-114)
-    auto to_object = [&](bool memo_instance, V3 &ro, V3 &rd) {
-        ro = o; rd = d;
-        if (memo_instance) {
-            float inv[12]; instance_memo_load(sv, inv);
-            ro = xf_point(inv, o); rd = xf_vector(inv, d);
-        }
-    };
     // rect_hit on a rectangle's record, the ray (ro, rd) in its space and z = flat_zrow of it
     auto test = [&](const FlatRecord &rec, uint32_t oi, V3 ro, V3 rd, F2 z) {
-        // xf_point / xf_vector with the matrix entries as scalar operands, two multiply-adds per instruction: the x and y rows of the point as one pair,
-        // those of the direction as another.  Each half is the IEEE operation of the scalar form, in its order; the direction's leading product becomes
-        // fma(m, d, -0), which equals m * d for every input.
-#if DTOF_FLAT_PK
-        const F2 lo_xy = __builtin_elementwise_fma(rec.c2, F2{ ro.z, ro.z }, __builtin_elementwise_fma(rec.c1, F2{ ro.y, ro.y }, __builtin_elementwise_fma(rec.c0, F2{ ro.x, ro.x }, rec.c3)));
-        const F2 ld_xy = __builtin_elementwise_fma(rec.c2, F2{ rd.z, rd.z }, __builtin_elementwise_fma(rec.c1, F2{ rd.y, rd.y }, rec.c0 * F2{ rd.x, rd.x }));
-#else   // the scalar form (one multiply-add per instruction, matrix entries as SGPR operands: 4 cycles each), kept for A/B timing
+        // xf_point / xf_vector, x and y rows: one multiply-add per instruction, in the order of the scalar form
         const F2 lo_xy = F2{ fmaf(rec.c2.x, ro.z, fmaf(rec.c1.x, ro.y, fmaf(rec.c0.x, ro.x, rec.c3.x))), fmaf(rec.c2.y, ro.z, fmaf(rec.c1.y, ro.y, fmaf(rec.c0.y, ro.x, rec.c3.y))) };
         const F2 ld_xy = F2{ fmaf(rec.c2.x, rd.z, fmaf(rec.c1.x, rd.y, rec.c0.x * rd.x)), fmaf(rec.c2.y, rd.z, fmaf(rec.c1.y, rd.y, rec.c0.y * rd.x)) };
-#endif
         const float t = -z.x / z.y;
         const float u = fmaf(ld_xy.x, t, lo_xy.x), v = fmaf(ld_xy.y, t, lo_xy.y);
         // no short-circuit: four compares and three mask ANDs instead of three exec-mask branches per rectangle (the scalar unit is as busy as the vector units here)
@@ -553,27 +519,16 @@ DTOF_D bool trace_flat(const SceneView &sv, ConstBytes flat_table, uint32_t flat
             best.t = take ? t : best.t; best.u = take ? u : best.u; best.v = take ? v : best.v; best.obj = take ? oi : best.obj;   // best.shape stays 0: the instances, which may set it, come after the rectangles
         }
     };
-    // Instances are noted in a mask and intersected after the rectangles: the tie rule of intersect_object (equal t goes to the lower object index) does not depend on
-    // the order of the visits.
-    uint32_t instances = 0, oi = 0;
-    constexpr bool F_ONE_WALL = DTOF_FLAT_LDS && (FACTS & kFactOneWall) != 0;   // (the form without the cull keeps its instance marks)
+    constexpr bool F_ONE_WALL = (FACTS & kFactOneWall) != 0;
     static_assert(!F_ONE_WALL || MEMO, "the one wall is the memo object");
-#if DTOF_FLAT_LDS
-    // The records come from the scene copy staged in LDS, every lane reading the same address (a broadcast): the matrix entries are then VGPR operands of the
-    // multiply-adds, which issue at full rate -- as SGPR operands (scalar loads from the blob) each of the 21 costs two issue slots (profiles/r03_ubench_valu_rate.txt).
-    // First the object's z row (ONE ds_read_b128 from the DFlatZ table behind the records) and the certain-miss test; the rest of the record (four ds_read_b128) only
-    // where a lane of the wave still needs the full test.  The instance marks are two scalar loads.
     const DFlatObject *lt = (const DFlatObject *) (sv.base + flat_off);
     const uint4 *zt = (const uint4 *) (lt + n_objects) + 1;   // DFlatZ[n_objects], behind the DFlatKinds record
-    const DFlatKinds __attribute__((address_space(4))) *kinds = (const DFlatKinds __attribute__((address_space(4))) *) (table + n_objects);
-    const uint32_t memo_bit = F_ONE_WALL ? 1u << sv.memo_obj : MEMO && sv.memo_obj < 32u ? 1u << sv.memo_obj : 0u, memo_objs = F_ONE_WALL ? memo_bit : kinds->memo & memo_bit;
-    if (!F_ONE_WALL) instances = kinds->general | (kinds->memo & ~memo_bit);
     constexpr int kStat = ANY ? 16 : 20; (void) kStat;   // (stats builds)
-    if constexpr (F_ONE_WALL && DTOF_FLAT_PEEL) {
-        // Three segments in ascending index order -- the rectangles below the wall, the wall, the rectangles above it: the plain rectangles read the world ray where
-        // it lies and the wall reads its own ray, so no iteration selects between the two by copying six registers.  One visit is the generic
-        // loop's body, operation for operation.
-        float far = flat_cull_far(maxt);
+    const float far = flat_cull_far(maxt);
+    // (Bounding a closest-hit query's certain-miss test by the nearest hit it holds instead of maxt was built behind a switch and failed the bar in its own
+    //  A/B, DESIGN 8.3 (g), profiles/flat_peel_ab.txt.  Removed.)
+    uint32_t oi = 0;
+    if constexpr (F_ONE_WALL) {
         auto visit = [&](uint32_t k, const V3 &ro, const V3 &rd) {
             const uint4 zr = zt[k];
             const F2 z = flat_zrow(u2f(zr.x), u2f(zr.y), u2f(zr.z), u2f(zr.w), ro, rd);
@@ -584,11 +539,9 @@ DTOF_D bool trace_flat(const SceneView &sv, ConstBytes flat_table, uint32_t flat
             DTOF_STAT_WAVE(kStat + 3);
             const uint4 *rp4 = (const uint4 *) (lt + k);
             const uint4 r0 = rp4[0], r1 = rp4[1], r2 = rp4[2], r3 = rp4[3];
-            FlatRecord a; a.instance = 0;
+            FlatRecord a;
             a.c0 = F2{ u2f(r0.x), u2f(r0.y) }; a.c1 = F2{ u2f(r1.x), u2f(r1.y) }; a.c2 = F2{ u2f(r2.x), u2f(r2.y) }; a.c3 = F2{ u2f(r3.x), u2f(r3.y) };
             test(a, k, ro, rd, z);
-            // the closest hit so far bounds the rest of the query: a certain miss against best.t <= maxt could not have passed `t < best.t` (dtof_flat_cull.h)
-            if (!ANY && DTOF_FLAT_BEST_CULL) far = flat_cull_far(best.t);
         };
         const uint32_t wall = sv.memo_obj;   // < n_objects: a bit of the table's memo mask (kFactOneWall)
         // ONE copy of the plain rectangles' body, run for both segments (two passes of an outer loop the compiler must keep: written out or unrolled, the three bodies
@@ -604,11 +557,19 @@ DTOF_D bool trace_flat(const SceneView &sv, ConstBytes flat_table, uint32_t flat
             }
         }
     } else {
-        const float far = flat_cull_far(maxt);
+        // Instances are noted in a mask and intersected after the rectangles: the tie rule of intersect_object (equal t goes to the lower object index) does not depend on
+        // the order of the visits.  The one memoised instance of one rectangle is visited in the loop, its ray moved there first as intersect_object does (instance.cpp:101-114).
+        typedef const DFlatObject __attribute__((address_space(4))) *ConstFlat;
+        const DFlatKinds __attribute__((address_space(4))) *kinds = (const DFlatKinds __attribute__((address_space(4))) *) ((ConstFlat) flat_table + n_objects);
+        const uint32_t memo_bit = MEMO && sv.memo_obj < 32u ? 1u << sv.memo_obj : 0u, memo_objs = kinds->memo & memo_bit;
+        uint32_t instances = kinds->general | (kinds->memo & ~memo_bit);
         for (; oi < n_objects; ++oi) {
-            if (!F_ONE_WALL && ((instances >> oi) & 1u)) continue;   // (uniform)
-            V3 ro, rd;
-            to_object((memo_objs >> oi) & 1u, ro, rd);
+            if ((instances >> oi) & 1u) continue;   // (uniform)
+            V3 ro = o, rd = d;
+            if ((memo_objs >> oi) & 1u) {
+                float inv[12]; instance_memo_load(sv, inv);
+                ro = xf_point(inv, o); rd = xf_vector(inv, d);
+            }
             const uint4 zr = zt[oi];
             const F2 z = flat_zrow(u2f(zr.x), u2f(zr.y), u2f(zr.z), u2f(zr.w), ro, rd);
             const bool need = !flat_certain_miss(z.x, z.y, far);
@@ -618,39 +579,16 @@ DTOF_D bool trace_flat(const SceneView &sv, ConstBytes flat_table, uint32_t flat
             DTOF_STAT_WAVE(kStat + 3);
             const uint4 *rp4 = (const uint4 *) (lt + oi);
             const uint4 r0 = rp4[0], r1 = rp4[1], r2 = rp4[2], r3 = rp4[3];
-            FlatRecord a; a.instance = 0;
+            FlatRecord a;
             a.c0 = F2{ u2f(r0.x), u2f(r0.y) }; a.c1 = F2{ u2f(r1.x), u2f(r1.y) }; a.c2 = F2{ u2f(r2.x), u2f(r2.y) }; a.c3 = F2{ u2f(r3.x), u2f(r3.y) };
             test(a, oi, ro, rd, z);
         }
-    }
-#else
-    // (without the cull) Two record buffers take turns (the loop is unrolled by two), so the next record's scalar load flies while the current one is tested and no
-    // register is copied from one iteration to the next.
-    auto test_record = [&](const FlatRecord &rec, uint32_t oi) {
-        V3 ro, rd;
-        to_object(rec.instance == 2, ro, rd);
-        test(rec, oi, ro, rd, flat_zrow(rec.z0, rec.z1, rec.z2, rec.z3, ro, rd));
-    };
-    FlatRecord a = flat_load(table);
-    for (;;) {
-        FlatRecord b;
-        const bool more_b = oi + 1 < n_objects;
-        if (more_b) b = flat_load(table + oi + 1);
-        if (a.instance == 1 || (a.instance == 2 && !(MEMO && sv.memo_obj == oi))) instances |= 1u << oi; else test_record(a, oi);
-        if (!more_b) break;
-        ++oi;
-        const bool more_a = oi + 1 < n_objects;
-        if (more_a) a = flat_load(table + oi + 1);
-        if (b.instance == 1 || (b.instance == 2 && !(MEMO && sv.memo_obj == oi))) instances |= 1u << oi; else test_record(b, oi);
-        if (!more_a) break;
-        ++oi;
-    }
-#endif
-    // (`stack` may be null here -- a kernel compiled with kFactFlat has none: intersect_object<ANY, MESH = false> tests rectangles only and never touches it)
-    if (!F_ONE_WALL) while (instances) {   // uniform
-        const uint32_t k = (uint32_t) __builtin_ctz(instances); instances &= instances - 1u;
-        const bool hit = intersect_object<ANY, false, MEMO>(sv, k, o, d, time, maxt, best, stack, 0, blockDim.x);
-        if (ANY) occluded |= hit;
+        // (`stack` may be null here -- a kernel compiled with kFactFlat has none: intersect_object<ANY, MESH = false> tests rectangles only and never touches it)
+        while (instances) {   // uniform
+            const uint32_t k = (uint32_t) __builtin_ctz(instances); instances &= instances - 1u;
+            const bool hit = intersect_object<ANY, false, MEMO>(sv, k, o, d, time, maxt, best, stack, 0, blockDim.x);
+            if (ANY) occluded |= hit;
+        }
     }
     return ANY ? occluded : best.obj != 0xffffffffu;
 }
