@@ -116,19 +116,48 @@ struct ShadeArgs {
     uint32_t n_seg, res_small_off, res_small_words, res_memo;   // resident stage (RESW != 0): segments of the batch; byte offset / uint4 count of the record block copied to LDS; 1 = the instance memo has LDS
     uint32_t res_park_off;   // resident stage with several films: word offset (behind the memo) of the film-state columns, kParkWords words per thread behind the stack columns
 };
+static_assert(sizeof(ShadeArgs) == 888, "ShadeArgs is k_shade's kernarg block: its layout, order and types do not change");
 // Resident kernels of several films keep the films' running results in LDS instead of registers (k_shade: RES_LDS): kParkWords of the 3 * kMaxOffsets floats per
 // thread -- what Domino's stage leaves free of the CU's 160 KiB at 16 waves (64 KiB node planes + 3 KiB records + 48 KiB stack columns) -- the last one stays a register
 constexpr uint32_t kParkWords = 11;
 // DTOF_PARK (default 1): the resident ONE-film kernels at 16 waves (128 VGPRs, ~150 spilled) park the path state no traversal reads -- both PCG states with their
 // stream selectors and throughput / path length, kParkState words -- in the same columns across the two traversals of an iteration instead of leaving them to the register
 // allocator's spill code: scratch 200 -> 168 B per lane, C4 33.69 -> 33.26 ms (profiles/r05_k4_film_state.txt).  A scene whose stage no longer fits the CU's LDS with
-// the columns at 16 waves takes 12 (resident_lds_bytes / render_rows' step-down), where the kernels have 168 VGPRs and park nothing.
+// the columns at 16 waves takes 12 (ShadeLds::resident / plan_frame's step-down), where the kernels have 168 VGPRs and park nothing.
 #ifndef DTOF_PARK
 #define DTOF_PARK 1
 #endif
 constexpr uint32_t kParkState = 10, kParkRng = 6;   // one film: both streams + throughput / path length; several films (behind the kParkWords film words): the streams only
-// the stack columns of the resident kernels of several films hold 16-bit entries (dtof_traverse.h: encode_child16), the one-film kernels' 32-bit ones
-static inline uint32_t resident_stack_bytes(uint32_t depth, uint32_t waves, bool several_films) { return (depth < 2 ? 2 : depth) * waves * 64u * (several_films ? 2u : 4u); }
+constexpr uint32_t kResidentNodes = 1024;   // TLAS nodes the resident stage holds (= kResNodes of dtof_traverse.h)
+// instance memo (SceneView::memo, dtof_traverse.h): 12 words per thread, word k of thread t at memo[k * kMemoStride + t]
+constexpr uint32_t kMemoStride = 64, kMemoWords = 12;
+
+// The dynamic LDS of ONE k_shade launch, part by part in the kernel's order (bytes).  Whatever sizes that LDS on the host -- the plan's choice of a wave count, the
+// launch, ShadeArgs::res_park_off -- reads it here; k_shade derives the same offsets from its template parameters and ShadeArgs (stage_words, memo_words, stack, park).
+struct ShadeLds {
+    uint32_t stage, memo;   // the staged scene blob, or the resident stage: four node planes + the record block; instance-memo columns of kMemoWords words per thread
+    uint32_t stack, park;   // traversal-stack columns, one entry per thread and level; resident kernels: film-state / path-state columns (kParkWords, kParkState, kParkRng)
+    constexpr uint32_t bytes() const { return stage + memo + stack + park; }
+    constexpr uint32_t without_stack() const { return stage + memo + park; }   // a kernel compiled with kFactFlat has no traversal stack and is launched without the columns
+    constexpr uint32_t park_off() const { return stack / 4u; }                 // ShadeArgs::res_park_off: the park columns lie this many words behind the memo
+    static constexpr ShadeLds columns(uint32_t stage_words, uint32_t waves, uint32_t memo_columns, uint32_t stack_depth, bool entries16, uint32_t park_words) {   // waves of 64 threads; at least two stack levels
+        return { stage_words * 16u, memo_columns * waves * kMemoWords * kMemoStride * 4u, (stack_depth < 2 ? 2u : stack_depth) * waves * 64u * (entries16 ? 2u : 4u), park_words * waves * 64u * 4u };
+    }
+    // The classic launch, one wave per block.  Split pipeline: the staged scene alone.  Fused: one memo column and the stack; a flat scene with ONE instance (one_instance:
+    // fused, rectangle-only diffuse, rp.flat_objects != 0, rp.memo_obj set = k_shade's memo_m_lds) keeps the instance matrix in a second column and needs one stack level.
+    static constexpr ShadeLds classic(uint32_t stage_words, bool fused, bool one_instance, uint32_t stack_depth) {
+        return fused ? columns(stage_words, 1u, one_instance ? 2u : 1u, one_instance ? 1u : stack_depth, false, 0u) : ShadeLds { stage_words * 16u, 0u, 0u, 0u };
+    }
+    // The resident launch, `waves` waves per block: a memo column per wave if the scene has a memo object; with several films 16-bit stack entries (dtof_traverse.h:
+    // encode_child16) and the film-state columns (k_shade: RES_LDS); at 16 waves the parked path state (PARK: one film kParkState words, several films the two streams)
+    static constexpr ShadeLds resident(uint32_t small_words, uint32_t waves, bool memo, bool several_films, uint32_t stack_depth) {
+        return columns(4u * kResidentNodes + small_words, waves, memo ? 1u : 0u, stack_depth, several_films, (several_films ? kParkWords : 0u) + (DTOF_PARK && waves == 16 ? (several_films ? kParkRng : kParkState) : 0u));
+    }
+};
+// known totals: Domino's stage (171 record words, 12 stack levels), one film at 16 waves without / with a memo column, four films at 8 waves; cornell_wall's classic one-wall launch (a 214-word blob) with and without its stack column
+static_assert(ShadeLds::resident(171, 16, false, false, 12).bytes() == 158384 && ShadeLds::resident(171, 16, true, false, 12).bytes() == 207536, "resident stage, one film");
+static_assert(ShadeLds::resident(171, 8, false, true, 12).bytes() == 103088 && ShadeLds::resident(171, 8, false, true, 12).park_off() == 3072, "resident stage, four films");
+static_assert(ShadeLds::classic(214, true, true, 5).bytes() == 10080 && ShadeLds::classic(214, true, true, 5).without_stack() == 9568, "classic one-wall launch");
 
 // Plan facts (k_shade's FACTS template parameter): things the host fixed in the frame plan before a first-bounce launch, the same for every lane of it, that the kernel
 // otherwise re-decides inside its chunk and bounce loops -- each a scalar load from the kernarg segment at its point of use, a wait that also drains the LDS reads, a
@@ -175,10 +204,9 @@ constexpr uint32_t kResidentFacts = DTOF_RESIDENT_FACTS;
 
 // One launch of k_shade as launch_shade hands it to the translation unit that holds the instantiation (dtof_shade_*.hip: the ~100 instantiations of the
 // kernel compile in parallel, one group per file): staged = the scene blob is copied to LDS by every block; mode 0 split, 1 fused, 2 fused first bounce;
-// waves != 0: the resident form (`waves` waves per block, one block per CU); facts: the plan facts this launch satisfies (0: take the generic kernels).
-// launch_shade_plain and launch_shade_resident0 return whether an instantiation specialised on plan facts ran.
-// stack_lds: the bytes of `lds` that are the traversal-stack columns of a classic launch -- a kernel compiled with kFactFlat has no stack and is launched without them.
-struct ShadeLaunch { bool staged; int mode; uint32_t waves, grid, lds; hipStream_t stream; ShadeArgs args; uint32_t facts; uint32_t stack_lds; };
+// waves != 0: the resident form (`waves` waves per block, one block per CU); lds: the launch's dynamic LDS (ShadeLds::bytes), lds_flat: the same without the stack columns, what a kernel compiled
+// with kFactFlat is launched with; facts: the plan facts this launch satisfies (0: take the generic kernels).  launch_shade_plain and launch_shade_resident0 return whether an instantiation specialised on plan facts ran.
+struct ShadeLaunch { bool staged; int mode; uint32_t waves, grid, lds, lds_flat; hipStream_t stream; ShadeArgs args; uint32_t facts; };
 bool launch_shade_plain(bool area, bool k4, const ShadeLaunch &L);      // rectangle-only diffuse scenes          (dtof_shade_plain.hip)
 void launch_shade_mesh(bool area, bool k4, const ShadeLaunch &L);       // + triangles / analytic shapes          (dtof_shade_mesh.hip)
 void launch_shade_spec1(bool k4, const ShadeLaunch &L);                 // every BSDF / emitter / texture         (dtof_shade_spec1.hip)
@@ -187,13 +215,12 @@ bool launch_shade_resident0(bool area, bool k4, const ShadeLaunch &L);  // resid
 void launch_shade_resident1(bool k4, const ShadeLaunch &L);             // resident first bounce, every BSDF      (dtof_shade_res1.hip)
 void launch_shade_resident2(bool k4, const ShadeLaunch &L);             // ... and blendbsdf                      (dtof_shade_res2.hip)
 
-// Resident stage of the fused first-bounce kernel (k_shade<..., RESW>, dtof_kernels.hip): `waves` waves per block (0 = off), one block per CU; the block
-// [small_off, small_off + 16 * small_words) of the blob (groups, shapes, emitters, triangles, shading data) and the TLAS nodes live in LDS.
-struct ResidentStage { uint32_t small_off = 0, small_words = 0, waves = 0; };
-constexpr uint32_t kResidentNodes = 1024;   // TLAS nodes the stage holds (= kResNodes of dtof_traverse.h)
-// dynamic LDS one block of the resident kernel needs with `waves` waves: node planes + record block + (instance memo) + stack columns
-uint32_t resident_lds_bytes(const RenderParams &rp, const ResidentStage &resident, uint32_t stack_depth, uint32_t waves);
-uint32_t device_lds_limit();   // hipDeviceAttributeMaxSharedMemoryPerBlock of the current device (160 KiB on gfx950), minus the kernels' static LDS
+// Resident stage of the fused first-bounce kernel (k_shade<..., RESW>, dtof_kernels.hip): `waves` waves per block (0 = off), one block per CU of the n_cu the
+// device has; the block [small_off, small_off + 16 * small_words) of the blob (groups, shapes, emitters, triangles, shading data) and the TLAS nodes live in LDS.
+struct ResidentStage { uint32_t small_off = 0, small_words = 0, waves = 0, n_cu = 0; };
+inline ShadeLds resident_lds(const RenderParams &rp, const ResidentStage &st, uint32_t stack_depth, uint32_t waves) { return ShadeLds::resident(st.small_words, waves, rp.memo_obj != 0xffffffffu, rp.n_offsets != 1, stack_depth); }
+uint32_t device_lds_limit();   // asked once per frame (plan_frame): hipDeviceAttributeMaxSharedMemoryPerBlock of the current device (160 KiB on gfx950), minus the kernels' static LDS
+uint32_t device_cu_count();    // ... and hipDeviceAttributeMultiprocessorCount
 
 // The launchers' development switches, read once per frame with the others (dtof_render.hip: read_switches, which lists them)
 struct LaunchSwitches {
@@ -210,12 +237,17 @@ void launch_sum_counts(const uint32_t *counts, uint32_t n_seg, uint32_t n_rows, 
 uint32_t segments_for(uint32_t n_lanes);   // number of queue segments (count slots) for a batch
 void launch_trace(const uint8_t *scene, uint32_t scene_bytes, const RenderParams &rp, const Queues &q,
                   const uint32_t *qin, const uint32_t *count_in, uint32_t stack_depth, const LaunchSwitches &ls, hipStream_t s);
-bool launch_shade(const uint8_t *scene, uint32_t scene_bytes, const RenderParams &rp, const Queues &q,
-                  const uint32_t *qin, const uint32_t *count_in, uint32_t *qout,
-                  uint32_t *alive_out, uint32_t *shadow_out, uint32_t depth, bool fused, bool trace_next,
-                  uint32_t stack_depth, const LaunchSwitches &ls, hipStream_t s, bool first = false, LaneDebug *dbg = nullptr,   // first: generate + primary trace inline (fused only)
-                  const ResidentStage *resident = nullptr, float *film = nullptr, uint64_t film_stride = 0,   // film: the launch covers the whole path and splats its lanes itself
-                  uint32_t facts = 0);   // facts: the plan facts the launch satisfies (kFact*); returns whether a kernel specialised on them ran
+// One launch of k_shade as render_rows asks for it
+struct ShadeRequest {
+    const uint8_t *scene = nullptr; uint32_t scene_bytes = 0, stack_depth = 0;   // the blob on the device; stack entries a traversal of it can need
+    const RenderParams *rp = nullptr; const Queues *q = nullptr; const LaunchSwitches *switches = nullptr; hipStream_t stream = nullptr;
+    const uint32_t *qin = nullptr, *count_in = nullptr;                       // the lane queue and segment counts it reads (nullptr: every lane of the batch)
+    uint32_t *qout = nullptr, *alive_out = nullptr, *shadow_out = nullptr;    // the lane queue it writes; the count slots of its last iteration
+    uint32_t depth = 0; int mode = 0; bool trace_next = false;                // its first iteration; 0 split, 1 fused, 2 fused first bounce (generate + primary trace inline); an iteration follows
+    LaneDebug *dbg = nullptr; float *film = nullptr; uint64_t film_stride = 0;   // first bounce of a lane dump: the camera rays; film: the launch covers the whole path and splats its lanes itself
+    uint32_t facts = 0; const ResidentStage *resident = nullptr;              // the plan facts it satisfies (kFact*); the plan made it a resident launch (LaunchSpan::resident) of this stage
+};
+bool launch_shade(const ShadeRequest &r);   // returns whether a kernel specialised on the facts ran
 void launch_shadow(const uint8_t *scene, uint32_t scene_bytes, const RenderParams &rp, const Queues &q,
                    const uint32_t *count_in, uint32_t stack_depth, const LaunchSwitches &ls, hipStream_t s);
 void launch_velocity(const uint8_t *scene, uint32_t scene_bytes, const RenderParams &rp, const Queues &q, uint32_t stack_depth, const LaunchSwitches &ls, hipStream_t s);

@@ -643,54 +643,45 @@ void launch_shadow(const uint8_t *scene, uint32_t scene_bytes, const RenderParam
     Queues qx = q; qx.xcd_remap = r.xcd;
     launch_rays(ShadowRays { scene, scene_bytes, rp, qx, count_in }, rp, q, r, s);
 }
-uint32_t resident_lds_bytes(const RenderParams &rp, const ResidentStage &resident, uint32_t stack_depth, uint32_t waves) {
-    static_assert(kResidentNodes == kResNodes, "resident stage size");
-    const uint32_t memo = rp.memo_obj != 0xffffffffu ? 1u : 0u;
-    // film-state columns of the several-film kernels (k_shade: RES_LDS) + parked path state (PARK: 16 waves only; the several-film kernels have room for the two streams)
-    const uint32_t park_words = rp.n_offsets != 1 ? kParkWords + (DTOF_PARK && waves == 16 ? kParkRng : 0u) : (DTOF_PARK && waves == 16 ? kParkState : 0u);
-    return (4u * kResNodes + resident.small_words) * 16u + memo * waves * kMemoWords * kMemoStride * 4u + resident_stack_bytes(stack_depth, waves, rp.n_offsets != 1) + park_words * waves * 64u * 4u;
-}
+static_assert(kResidentNodes == kResNodes, "resident stage size");
 uint32_t device_lds_limit() {
     if (const char *e = getenv("DTOF_LDS_LIMIT")) return (uint32_t) strtoul(e, nullptr, 10);   // tests: a smaller budget than the device's (the step-down / fallback paths)
     int dev = 0, bytes = 0;
     if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&bytes, hipDeviceAttributeMaxSharedMemoryPerBlock, dev) != hipSuccess || bytes <= 0) return 64u * 1024u;
     return (uint32_t) bytes > 1024u ? (uint32_t) bytes - 1024u : 0u;   // k_shade's static LDS (s_inline_all: the inline iterations' statistics, at most 16 waves x 2 * kMaxInline words) comes on top of the dynamic size
 }
-bool launch_shade(const uint8_t *scene, uint32_t scene_bytes, const RenderParams &rp, const Queues &q,
-                  const uint32_t *qin, const uint32_t *count_in, uint32_t *qout,
-                  uint32_t *alive_out, uint32_t *shadow_out, uint32_t depth, bool fused, bool trace_next,
-                  uint32_t stack_depth, const LaunchSwitches &ls, hipStream_t s, bool first, LaneDebug *dbg, const ResidentStage *resident, float *film, uint64_t film_stride,
-                  uint32_t facts) {
+uint32_t device_cu_count() {
+    int dev = 0, n_cu = 0; (void) hipGetDevice(&dev);
+    return hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n_cu <= 0 ? 256u : (uint32_t) n_cu;
+}
+// The plan decided what this launch is (FramePlan::launch_span); here it gets its argument block, its LDS (ShadeLds) and its grid, and goes to the file that holds its kernel.
+bool launch_shade(const ShadeRequest &r) {
+    const RenderParams &rp = *r.rp;
     if (rp.n_lanes == 0) return false;
-    if (first && !fused) throw std::runtime_error("the first-bounce kernel exists in the fused pipeline only");
-    const bool k4 = rp.n_offsets != 1;
-    if (resident && resident->waves && first && fused && rp.has_tris && rp.chunk_blocks <= 1) {
-        // one block of `waves` waves per CU; LDS = node planes + record block + (instance memo) + stack columns, well above the 64 KiB default limit.
-        // render_rows only offers the stage with a wave count that fits; a scene that still does not (a deeper stack than it assumed) takes the classic launch below.
-        const uint32_t waves = resident->waves, lds = resident_lds_bytes(rp, *resident, stack_depth, waves);
-        if (lds <= device_lds_limit()) {
-            int dev = 0, n_cu = 0;
-            (void) hipGetDevice(&dev);
-            if (hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n_cu <= 0) n_cu = 256;
-            const uint32_t n_seg = nseg(rp.n_lanes), grid = std::min<uint32_t>((uint32_t) n_cu, (n_seg + waves - 1) / waves);
-            const uint32_t memo = rp.memo_obj != 0xffffffffu ? 1u : 0u;
-            const ShadeLaunch L = { false, 2, waves, grid, lds, s,
-                                    { scene, scene_bytes, 0u, rp, q, qin, count_in, qout, alive_out, shadow_out, depth, trace_next ? 1u : 0u, dbg, film, film_stride, n_seg, resident->small_off, resident->small_words, memo, resident_stack_bytes(stack_depth, waves, rp.n_offsets != 1) / 4u }, facts, 0u };
-            if (hipMemsetAsync(q.seg_counter, 0, 4, s) != hipSuccess) throw std::runtime_error("hipMemsetAsync(seg_counter) failed");
-            if (rp.has_spec == 2) launch_shade_resident2(k4, L);
-            else if (rp.has_spec) launch_shade_resident1(k4, L);
-            else return launch_shade_resident0(rp.has_area != 0, k4, L);
-            return false;
-        }
+    const bool k4 = rp.n_offsets != 1, fused = r.mode != 0, first = r.mode == 2;
+    const uint32_t n_seg = nseg(rp.n_lanes);
+    ShadeLaunch L = {};
+    L.mode = r.mode; L.stream = r.stream; L.facts = r.facts;
+    ShadeArgs &A = L.args;
+    A.scene = r.scene; A.scene_bytes = r.scene_bytes; A.rp = rp; A.q = *r.q; A.qin = r.qin; A.count_in = r.count_in; A.qout = r.qout; A.alive_out = r.alive_out; A.shadow_out = r.shadow_out;
+    A.depth = r.depth; A.trace_next = r.trace_next ? 1u : 0u; A.dbg = r.dbg; A.film = r.film; A.film_stride = r.film_stride; A.n_seg = n_seg;
+    if (r.resident) {   // one block of `waves` waves per CU, the scene unstaged: its TLAS and records are the resident stage, well above the 64 KiB default limit
+        const ResidentStage &stage = *r.resident;
+        const ShadeLds lds = resident_lds(rp, stage, r.stack_depth, stage.waves);
+        L.waves = stage.waves; L.grid = std::min<uint32_t>(stage.n_cu, (n_seg + stage.waves - 1) / stage.waves); L.lds = lds.bytes();
+        A.res_small_off = stage.small_off; A.res_small_words = stage.small_words; A.res_memo = lds.memo ? 1u : 0u; A.res_park_off = lds.park_off();
+        if (hipMemsetAsync(r.q->seg_counter, 0, 4, r.stream) != hipSuccess) throw std::runtime_error("hipMemsetAsync(seg_counter) failed");
+        if (rp.has_spec == 2) launch_shade_resident2(k4, L);
+        else if (rp.has_spec) launch_shade_resident1(k4, L);
+        else return launch_shade_resident0(rp.has_area != 0, k4, L);
+        return false;
     }
-    // + the instance memo; a flat scene with one instance keeps the instance matrix there as well (k_shade: memo_m_lds) and needs no traversal stack beyond one entry
-    const bool memo_m = fused && !rp.has_tris && !rp.has_spec && rp.flat_objects != 0 && rp.memo_obj != 0xffffffffu;   // = the condition of k_shade's memo_m_lds in the instantiations launch_shade_plain picks
-    const uint32_t stack_lds = fused ? stack_bytes(memo_m ? 1u : stack_depth, kShadeBlock) : 0u;   // the stack columns: what a kernel compiled with kFactFlat is launched without
-    const uint32_t shade_stack = fused ? stack_lds + (memo_m ? 2u : 1u) * kMemoWords * kMemoStride * 4 : 0;
-    const uint32_t sw = stage_words_for(scene_bytes, shade_stack, ls), grid = nseg(rp.n_lanes) * (first && rp.chunk_blocks > 1 ? rp.chunk_blocks : 1u), lds = sw * 16 + shade_stack;
-    check_lds(lds);
-    const ShadeLaunch L = { sw != 0, first ? 2 : fused ? 1 : 0, 0u, grid, lds, s,
-                            { scene, scene_bytes, sw, rp, q, qin, count_in, qout, alive_out, shadow_out, depth, trace_next ? 1u : 0u, dbg, film, film_stride, nseg(rp.n_lanes), 0u, 0u, 0u, 0u }, first ? facts : 0u, stack_lds };
+    // a flat scene with one instance keeps the instance matrix in LDS as well (= the condition of k_shade's memo_m_lds in the instantiations launch_shade_plain picks)
+    const bool one_instance = fused && !rp.has_tris && !rp.has_spec && rp.flat_objects != 0 && rp.memo_obj != 0xffffffffu;
+    const uint32_t sw = stage_words_for(r.scene_bytes, ShadeLds::classic(0u, fused, one_instance, r.stack_depth).bytes(), *r.switches);
+    const ShadeLds lds = ShadeLds::classic(sw, fused, one_instance, r.stack_depth);
+    check_lds(lds.bytes());
+    L.staged = sw != 0; L.grid = n_seg * (first && rp.chunk_blocks > 1 ? rp.chunk_blocks : 1u); L.lds = lds.bytes(); L.lds_flat = lds.without_stack(); A.stage_words = sw;
     if (rp.has_spec == 2) launch_shade_spec2(k4, L);
     else if (rp.has_spec) launch_shade_spec1(k4, L);
     else if (rp.has_tris) launch_shade_mesh(rp.has_area != 0, k4, L);

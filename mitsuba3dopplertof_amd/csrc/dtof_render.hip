@@ -96,14 +96,14 @@ struct dtof_scene {
     PluginParams pp;
     std::vector<uint8_t> blob;
     DevBuf<uint8_t> d_blob; bool uploaded = false;
-    Workspace ws, ws2;                       // one per in-flight batch
+    Workspace ws;
     DevBuf<float> d_film, d_rgb;
     // the caller's device film as declared with dtof_scene_set_film_layout (0 = not declared: colour planes only, W * H * 4 apart)
     int32_t film_planes = 0; uint64_t film_plane_stride = 0;
     DevBuf<unsigned long long> d_sums;       // [batch][2*kMaxIter] per-iteration totals (survivors, shadow rays)
     DevBuf<uint2> d_pass_rng;                // multi-pass renders: [lane][3] stream states between the passes
     uint32_t id_shift = 24;                  // Queues::id_shift of this scene
-    hipStream_t stream = nullptr, stream2 = nullptr;   // stream: the library's own, or the caller's (dtof_scene_set_stream)
+    hipStream_t stream = nullptr;                        // the library's own, or the caller's (dtof_scene_set_stream)
     hipStream_t own_stream = nullptr;                    // what ensure_device created and the destructor destroys
     std::atomic<bool> stop { false };
     uint64_t plan_facts_launches = 0;        // first-bounce launches that took a kernel compiled with plan facts, since the scene was loaded (dtof_scene_plan_facts_launches)
@@ -127,7 +127,7 @@ struct dtof_scene {
         return pinned_counts;
     }
     ~dtof_scene() {
-        if (own_stream) (void) hipStreamDestroy(own_stream); if (stream2) (void) hipStreamDestroy(stream2);
+        if (own_stream) (void) hipStreamDestroy(own_stream);
         for (auto e : event_pool) (void) hipEventDestroy(e);
         if (pinned_counts) (void) hipHostFree(pinned_counts);
     }
@@ -144,7 +144,6 @@ namespace {
 void ensure_device(dtof_scene *sc) {
     if (!sc->own_stream) HIP_CHECK(hipStreamCreate(&sc->own_stream));
     if (!sc->stream) sc->stream = sc->own_stream;
-    if (!sc->stream2) HIP_CHECK(hipStreamCreate(&sc->stream2));
     if (!sc->uploaded) {
         sc->d_blob.ensure(sc->blob.size());
         HIP_CHECK(hipMemcpy(sc->d_blob.p, sc->blob.data(), sc->blob.size(), hipMemcpyHostToDevice));
@@ -408,7 +407,7 @@ SceneTraits scene_traits(const dtof_scene &sc) {
 }
 
 // What one launch of the bounce loop covers when it starts at an iteration
-struct LaunchSpan { uint32_t span, chunk_blocks, res_units; bool next_runs, splat_here, terminal; };
+struct LaunchSpan { uint32_t span, chunk_blocks, res_units; bool next_runs, splat_here, terminal, resident; };
 
 // Every decision of a frame, taken before its first launch.  The batch loop reads it and sets only the per-batch and per-launch fields of its copy of rp.
 struct FramePlan {
@@ -416,7 +415,6 @@ struct FramePlan {
     SceneTraits traits;
     uint32_t n_passes = 1, run_passes = 1, dump_pass = 0;
     uint64_t lanes_per_row = 0, first = 0, last = 0, batch = 1;   // every pass: lanes [first, last) in batches of `batch`
-    int n_streams = 1;
     bool fused = false, first_inline = false, skip_tail = false, fuse_splat_ok = false, terminal_ok = false, plan_facts = false, one_wall = false;
     uint32_t max_inline = 1, chunk_segs = 0, res_units = 1, n_emitters = 0;
     ResidentStage resident;
@@ -434,6 +432,8 @@ struct FramePlan {
         // small frames whose whole path runs inline: one block per 64-lane chunk (8 x the waves); the count slots it adds into are zeroed first
         const bool whole_path = first && !l.next_runs;
         l.chunk_blocks = whole_path && n_seg <= chunk_segs ? kChunkBlocks : 1u;
+        // the resident kernel's launch: the plan offers a stage (fused pipeline, mesh code, a wave count that fits: plan_frame) and there is one block per segment
+        l.resident = first && resident.waves != 0 && l.chunk_blocks == 1;
         // parts of a segment as the resident kernel's work units shorten the launch's tail (kept for a frame sharded over many GPUs); their count slots are added into
         l.res_units = whole_path ? res_units : 1u;
         // fused splat: every wave of a whole-path launch holds the 64 samples of one pixel and adds their footprint to the film itself (no round trip through q.res)
@@ -516,7 +516,6 @@ void plan_lanes(FramePlan &p, const dtof_scene *sc, const RenderRequest &rq) {
 // Every decision of the frame.  The development switches of the frame path are read here, once per frame, and nowhere else:
 //   switch              default     selects
 //   DTOF_PIPELINE       auto        split | fused: the pipeline
-//   DTOF_STREAMS        1           2: two batches in flight on two streams (measured gain 0 % Cornell .. 7 % Domino; it blurs per-stage timing)
 //   DTOF_FUSE_FIRST     1           0: separate k_generate + k_trace launches instead of the fused first-bounce kernel
 //   DTOF_INSTANCE_MEMO  1           0: no instance memo
 //   DTOF_FLAT           1           0: fused rectangle-only scenes keep the TLAS instead of testing every object (trace_flat)
@@ -545,7 +544,7 @@ FramePlan plan_frame(const dtof_scene *sc, const RenderRequest &rq) {
     const auto on = [](const char *name) { const char *e = getenv(name); return !(e && e[0] == '0'); };
     const auto str = [](const char *name) { const char *e = getenv(name); return std::string(e ? e : ""); };
     const std::string env_pipeline = str("DTOF_PIPELINE"), env_splat = str("DTOF_SPLAT");
-    const int env_streams = num("DTOF_STREAMS", 1), env_inline = num("DTOF_INLINE_ITERS", (int) kMaxInline), env_units = num("DTOF_RES_UNITS", 1), env_block = num("DTOF_TRACE_BLOCK", 0);
+    const int env_inline = num("DTOF_INLINE_ITERS", (int) kMaxInline), env_units = num("DTOF_RES_UNITS", 1), env_block = num("DTOF_TRACE_BLOCK", 0);
     const char *env_resident = getenv("DTOF_RESIDENT"), *env_batch = getenv("DTOF_BATCH_LANES");
     const uint64_t batch_lanes = env_batch && strtoull(env_batch, nullptr, 10) ? strtoull(env_batch, nullptr, 10) : (1ull << 27);
     FramePlan p;
@@ -567,15 +566,13 @@ FramePlan plan_frame(const dtof_scene *sc, const RenderRequest &rq) {
     // frame instead of two is another 2 % (34.86 -> 34.14 ms, profiles/r04_domino_waves_batch.txt)
     p.batch = rq.lane_dump ? std::min<uint64_t>(batch_lanes, std::max<uint64_t>(rq.dump_n, 1)) : std::max<uint64_t>(1, batch_lanes / p.lanes_per_row) * p.lanes_per_row;
     p.batch = std::min<uint64_t>(p.batch, std::max<uint64_t>(p.last - p.first, 1));
-    if (p.batch > sc->ws.capacity) {   // a workspace that has to grow: keep it within the free device memory (168 B + 32 B per offset film per lane, two copies with two streams)
+    if (p.batch > sc->ws.capacity) {   // a workspace that has to grow: keep it within the free device memory (168 B + 32 B per offset film per lane, and as much again left free)
         size_t free_b = 0, total_b = 0;
         if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) {
             const uint64_t per_lane = 168 + 32ull * (uint64_t) std::max<int32_t>(rp.n_offsets, 1);
             while (p.batch > (1ull << 22) && p.batch * per_lane * 2 > (uint64_t) free_b + (uint64_t) sc->ws.capacity * per_lane) p.batch = std::max<uint64_t>(1, (p.batch / 2) / p.lanes_per_row) * p.lanes_per_row;
         }
     }
-    // Two streams: the VALU-bound trace/shadow kernels of one batch overlap the HBM-bound shade kernel of the other.  The passes of a lane follow each other on one stream.
-    p.n_streams = (rq.lane_dump || p.n_passes > 1 || env_streams != 2) ? 1 : 2;
     // Pipeline.  "fused" runs occlusion + continuation traversal inside the shade kernel (one kernel per bounce, and the first-bounce kernel running up to four
     // iterations with the path state in registers), "split" runs k_trace -> k_shade -> k_shadow per bounce.  Automatic: fused unless large meshes sit behind their own
     // BLAS -- deep per-mesh traversals diverge inside the fat shade kernel (mesh room, 522 k triangles: 19.8 ms fused vs 16.1 ms split; 18 k triangles still run faster
@@ -583,10 +580,6 @@ FramePlan plan_frame(const dtof_scene *sc, const RenderRequest &rq) {
     // kernels were capped at 168 VGPRs = 3 waves / SIMD (512 x 512 x 64: Cornell boxes 5.26 -> 4.60 ms, area light 7.12 -> 6.13, sphere light 6.42 -> 4.83,
     // disk 5.30 -> 3.90, Domino 1024 x 1024 x 128 with its 1 025 instances 69.5 -> 62.2 ms; profiles/r02_pipeline_choice.txt).
     p.fused = env_pipeline == "split" ? false : env_pipeline == "fused" ? true : t.blas_triangles <= 32768 && sc->host.textures.empty();
-    if (p.n_streams == 2 && !rq.lane_dump && p.last - p.first <= p.batch && p.last - p.first >= 2 * p.lanes_per_row) {
-        const uint64_t rows = (p.last - p.first) / p.lanes_per_row;
-        p.batch = ((rows + 1) / 2) * p.lanes_per_row;   // one batch would serialise: cut it in two row bands
-    }
     rp.has_area = t.surface_emitters;   // area emitters make the emitter-hit term (and the last iteration) live
     rp.has_spec = t.has_spec; rp.has_tris = t.has_tris; rp.has_analytic = t.has_analytic ? 1 : 0;
     if (t.has_env) { rp.has_env = 1; rp.env_index = t.env_index; }
@@ -614,7 +607,8 @@ FramePlan plan_frame(const dtof_scene *sc, const RenderRequest &rq) {
         rp.res_half = t.n_nodes > kResidentNodes ? 1u : 0u;
         // the stage must fit the CU's LDS beside the stack columns (a deep TLAS needs many): fewer waves per block while it does not, none if 8 do not either
         const uint32_t limit = device_lds_limit();
-        while (p.resident.waves && resident_lds_bytes(rp, p.resident, t.stack_depth, p.resident.waves) > limit) p.resident.waves = p.resident.waves > 8 ? p.resident.waves - 4 : 0;
+        while (p.resident.waves && resident_lds(rp, p.resident, t.stack_depth, p.resident.waves).bytes() > limit) p.resident.waves = p.resident.waves > 8 ? p.resident.waves - 4 : 0;
+        p.resident.n_cu = device_cu_count();
     }
     // the 16-bit traversal of the resident kernels (dtof_traverse.h: NOBLAS, encode_child16) holds for these scenes only
     if (p.resident.waves && rp.has_blas) throw std::runtime_error("internal error: the resident stage was chosen for a scene with a per-mesh BLAS");
@@ -650,18 +644,13 @@ void render_rows(dtof_scene *sc, const RenderRequest &rq) {
     const FramePlan p = plan_frame(sc, rq);
     RenderParams rp = p.rp;
     dtof_render_stats *const stats = rq.stats;
-    Queues qs[2];   // one workspace per in-flight batch
-    qs[0] = sc->ws.prepare((uint32_t) p.batch, rp.n_offsets, rp.want_valid, p.launch.defer != 0, sc->id_shift);
-    qs[1] = p.n_streams == 2 ? sc->ws2.prepare((uint32_t) p.batch, rp.n_offsets, rp.want_valid, p.launch.defer != 0, sc->id_shift) : qs[0];
+    const Queues q = sc->ws.prepare((uint32_t) p.batch, rp.n_offsets, rp.want_valid, p.launch.defer != 0, sc->id_shift);
     if (rq.lane_dump) sc->ws.dbg.ensure(p.batch);
-    hipStream_t ss[2] = { sc->stream, p.n_streams == 2 ? sc->stream2 : sc->stream };
+    const hipStream_t s = sc->stream;
     const uint8_t *blob = sc->d_blob.p; const uint32_t blob_bytes = (uint32_t) sc->blob.size(), stack_depth = p.traits.stack_depth;
     StageTimer tm(stats != nullptr, sc);
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    struct EventGuard { hipEvent_t e = nullptr; ~EventGuard() { if (e) (void) hipEventDestroy(e); } } g_fork, g_join;   // released on every exit path
-    if (p.n_streams == 2) { HIP_CHECK(hipEventCreateWithFlags(&g_fork.e, hipEventDisableTiming)); HIP_CHECK(hipEventCreateWithFlags(&g_join.e, hipEventDisableTiming)); }
-    if (stats) { memset(stats, 0, sizeof *stats); ev0 = sc->take_event(); ev1 = sc->take_event(); HIP_CHECK(hipEventRecord(ev0, ss[0])); }
-    if (p.n_streams == 2) { HIP_CHECK(hipEventRecord(g_fork.e, ss[0])); HIP_CHECK(hipStreamWaitEvent(ss[1], g_fork.e, 0)); }
+    if (stats) { memset(stats, 0, sizeof *stats); ev0 = sc->take_event(); ev1 = sc->take_event(); HIP_CHECK(hipEventRecord(ev0, s)); }
     std::vector<uint32_t> batch_lanes, batch_iters, batch_inline;   // batch_inline: iterations the first-bounce launch of the batch covered (fused pipeline)
     // per-iteration totals of every batch: sized ONCE (DevBuf::ensure reallocates without copying, and a hipFree in the middle of the frame would also synchronise the device)
     if (stats && !rq.deferred && p.last > p.first) sc->d_sums.ensure((size_t) ((p.last - p.first + p.batch - 1) / p.batch) * p.run_passes * 2 * kMaxIter);
@@ -680,7 +669,6 @@ void render_rows(dtof_scene *sc, const RenderRequest &rq) {
         const bool dump_now = rq.lane_dump && pass == p.dump_pass;
         if (batch_index >= 2) HIP_CHECK(hipEventSynchronize(batch_done[batch_index & 1]));
         if (sc->stop.load()) break;
-        const Queues &q = qs[batch_index & 1]; hipStream_t s = ss[batch_index & 1];
         rp.lane_base = (uint32_t) b0; rp.n_lanes = (uint32_t) std::min<uint64_t>(p.batch, p.last - b0);
         const uint32_t n_seg = segments_for(rp.n_lanes);
         int t = -1;
@@ -704,17 +692,20 @@ void render_rows(dtof_scene *sc, const RenderRequest &rq) {
             const LaunchSpan l = p.launch_span(it, first, n_seg);
             rp.inline_iters = l.span; rp.chunk_blocks = l.chunk_blocks; rp.res_units = l.res_units; rp.terminal = l.terminal ? 1 : 0;
             it += l.span - 1;   // `it` is now the last iteration this launch covers
-            if (l.chunk_blocks > 1 || (l.res_units > 1 && p.resident.waves)) HIP_CHECK(hipMemsetAsync(q.counts, 0, (size_t) 2 * (it + 1) * n_seg * 4, s));
+            if (l.chunk_blocks > 1 || (l.res_units > 1 && l.resident)) HIP_CHECK(hipMemsetAsync(q.counts, 0, (size_t) 2 * (it + 1) * n_seg * 4, s));
             if (!p.fused || (it == 0 && !first)) { t = tm.begin(kStageTrace, s); launch_trace(blob, blob_bytes, rp, q, qin, count_in, stack_depth, p.launch, s); tm.end(kStageTrace, t, s); if (stats) stats->n_launches_trace++; }
             // per-iteration count slots; beyond kMaxIter iterations (unbounded depth, paths that russian roulette keeps alive that long)
             // the slots are reused -- only the statistics lose those iterations, no path is cut short
             uint32_t *qout = q.q[it & 1], *alive_out = q.counts + (size_t) (2 * (it % kMaxIter)) * n_seg, *shadow_out = alive_out + n_seg;
             const Stage st_shade = first ? kStageFirst : kStageShade;
             t = tm.begin(st_shade, s);
-            const bool specialised =
-            launch_shade(blob, blob_bytes, rp, q, qin, count_in, qout, alive_out, shadow_out, it + 1 - l.span, p.fused, l.next_runs, stack_depth, p.launch, s, first,
-                         first && dump_now ? sc->ws.dbg.p : nullptr, &p.resident, l.splat_here ? rq.film : nullptr, rq.film_stride,
-                         p.launch_facts(rp, l, it + 1 - l.span, first, qin == nullptr && count_in == nullptr, dump_now));
+            ShadeRequest sr;
+            sr.scene = blob; sr.scene_bytes = blob_bytes; sr.stack_depth = stack_depth; sr.rp = &rp; sr.q = &q; sr.switches = &p.launch; sr.stream = s;
+            sr.qin = qin; sr.count_in = count_in; sr.qout = qout; sr.alive_out = alive_out; sr.shadow_out = shadow_out;
+            sr.depth = it + 1 - l.span; sr.mode = first ? 2 : p.fused ? 1 : 0; sr.trace_next = l.next_runs; sr.resident = l.resident ? &p.resident : nullptr;
+            sr.dbg = first && dump_now ? sc->ws.dbg.p : nullptr; sr.film = l.splat_here ? rq.film : nullptr; sr.film_stride = rq.film_stride;
+            sr.facts = p.launch_facts(rp, l, sr.depth, first, qin == nullptr && count_in == nullptr, dump_now);
+            const bool specialised = launch_shade(sr);
             tm.end(st_shade, t, s);
             if (specialised) { sc->plan_facts_launches++; if (stats) stats->n_plan_facts_launches++; }
             fused_splat_done |= l.splat_here;
@@ -750,8 +741,6 @@ void render_rows(dtof_scene *sc, const RenderRequest &rq) {
             stats->n_batches++;
         }
     }
-    if (p.n_streams == 2) { HIP_CHECK(hipEventRecord(g_join.e, ss[1])); HIP_CHECK(hipStreamWaitEvent(ss[0], g_join.e, 0)); }
-    hipStream_t s = ss[0];
     if (stats && rq.deferred) {
         HIP_CHECK(hipEventRecord(ev1, s));
         dtof_scene::DeferredFrame f; f.ev0 = ev0; f.ev1 = ev1; f.counters = *stats;

@@ -4,6 +4,7 @@
 #pragma once
 #include "dtof_device.h"
 #include <atomic>
+#include <initializer_list>
 #include <type_traits>
 
 namespace dtof {
@@ -389,8 +390,9 @@ __global__ __launch_bounds__(RESW ? RESW * 64 : kShadeBlock, RESW ? RESW / 4 : (
     const uint32_t lane_id = RESW ? threadIdx.x & 63u : threadIdx.x, wave_id = RESW ? threadIdx.x >> 6 : 0u;   // one wave per block otherwise
     uint32_t *const s_inline = s_inline_all + wave_id * 2 * kMaxInline;
     const uint32_t stage_words = RESW ? 4u * kResNodes + A0.res_small_words : A0.stage_words;
-    // dynamic LDS: [staged scene | resident stage: node planes, record block][fused: instance memo, kMemoWords x 64 words per wave][traversal stack columns]
-    // flat scenes with ONE instance (the moving wall of C2): the column holds the instance matrix as well (launch_shade sizes the LDS accordingly) -- re-deriving it per
+    // dynamic LDS: [staged scene | resident stage: node planes, record block][fused: instance memo, kMemoWords x 64 words per wave][traversal stack columns][park columns]
+    // -- the host sizes every launch with ShadeLds (dtof_kernels.h), the mirror of the offsets derived here (stage_words, memo_words, stack, park)
+    // flat scenes with ONE instance (the moving wall of C2): the column holds the instance matrix as well (ShadeLds::classic sizes the LDS accordingly) -- re-deriving it per
     // iteration cost every lane 51 instructions, a hit on the wall now reads it back
     const bool memo_m_lds = F_ONE_WALL || (FUSED && !MESH && !RESW && A0.rp.flat_objects != 0u && A0.rp.memo_obj != 0xffffffffu);
     const uint32_t memo_words = FUSED ? (RESW ? (A0.res_memo ? RESW * kMemoWords * kMemoStride : 0u) : (memo_m_lds ? 2u : 1u) * kMemoWords * kMemoStride) : 0u;
@@ -1055,20 +1057,20 @@ static void launch_shade_variant(const ShadeLaunch &L) {
     else          { if (L.mode == 2) DTOF_LAUNCH_ONE(false, 2); else if (L.mode == 1) DTOF_LAUNCH_ONE(false, 1); else DTOF_LAUNCH_ONE(false, 0); }
 #undef DTOF_LAUNCH_ONE
 }
-// the resident form of the fused first-bounce kernel: `waves` waves per block, one block per CU.  Its dynamic LDS lies above the 64 KiB a kernel gets
-// without asking: hipFuncSetAttribute(MaxDynamicSharedMemorySize) is per DEVICE, so the high-water mark is kept per device ordinal (dtof-render drives
-// one host thread per GPU in one process).
+// The dynamic LDS of a resident launch lies above the 64 KiB a kernel gets without asking: hipFuncSetAttribute(MaxDynamicSharedMemorySize) is per DEVICE, so the
+// high-water mark of a kernel (or of kernels raised together) is kept per device ordinal (dtof-render drives one host thread per GPU in one process).
+static inline void raise_dynamic_lds(std::atomic<uint32_t> (&marks)[64], std::initializer_list<const void *> kernels, uint32_t lds) {
+    int dev = 0; (void) hipGetDevice(&dev);
+    std::atomic<uint32_t> &mark = marks[(unsigned) dev & 63u]; if (lds <= mark.load()) return;
+    for (const void *kernel : kernels)
+        if (hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds) != hipSuccess) throw std::runtime_error("hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed");
+    mark.store(lds);
+}
+// the resident form of the fused first-bounce kernel: `waves` waves per block, one block per CU
 template <bool A, int K, int S, int W>
 static void launch_resident_waves(const ShadeLaunch &L) {
     static std::atomic<uint32_t> attr_lds[64];
-    int dev = 0; (void) hipGetDevice(&dev);
-    std::atomic<uint32_t> &mark = attr_lds[(unsigned) dev & 63u];
-    if (L.lds > mark.load()) {
-        if (hipFuncSetAttribute((const void *) k_shade<false, 2, A, K, true, S, W>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) L.lds) != hipSuccess ||
-            hipFuncSetAttribute((const void *) k_shade<false, 2, A, K, true, S, W, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) L.lds) != hipSuccess)
-            throw std::runtime_error("hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed");
-        mark.store(L.lds);
-    }
+    raise_dynamic_lds(attr_lds, { (const void *) k_shade<false, 2, A, K, true, S, W>, (const void *) k_shade<false, 2, A, K, true, S, W, true> }, L.lds);
     if (L.args.rp.res_half) hipLaunchKernelGGL((k_shade<false, 2, A, K, true, S, W, true>), dim3(L.grid), dim3(W * 64), L.lds, L.stream, L.args);   // a TLAS of 1 025 .. 2 048 nodes: half-float planes
     else hipLaunchKernelGGL((k_shade<false, 2, A, K, true, S, W>), dim3(L.grid), dim3(W * 64), L.lds, L.stream, L.args);
 }

@@ -3,17 +3,11 @@
 
 namespace dtof {
 
-// the resident kernel of one film at 16 waves (Domino, C4) compiled with the frame plan's constants (dtof_kernels.h: kFact*); the LDS attribute as launch_resident_waves keeps it
+// the resident kernel of one film at 16 waves (Domino, C4) compiled with the frame plan's constants (dtof_kernels.h: kFact*)
 static void launch_resident_facts(const ShadeLaunch &L) {
     static std::atomic<uint32_t> attr_lds[64];
-    int dev = 0; (void) hipGetDevice(&dev);
-    std::atomic<uint32_t> &mark = attr_lds[(unsigned) dev & 63u];
     const auto kernel = k_shade<false, 2, false, 1, true, 0, 16, false, kResidentFacts>;
-    if (L.lds > mark.load()) {
-        if (hipFuncSetAttribute((const void *) kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int) L.lds) != hipSuccess)
-            throw std::runtime_error("hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed");
-        mark.store(L.lds);
-    }
+    raise_dynamic_lds(attr_lds, { (const void *) kernel }, L.lds);
     hipLaunchKernelGGL(kernel, dim3(L.grid), dim3(16 * 64), L.lds, L.stream, L.args);
 }
 

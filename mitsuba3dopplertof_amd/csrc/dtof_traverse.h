@@ -191,8 +191,7 @@ DTOF_D void instance_matrix(const DObject &ob, float time, float *m) {
     for (int i = 0; i < 12; ++i) m[i] = ob.key0[i] * omt + ob.key1[i] * t;
 }
 
-// instance memo (see SceneView): 12 words per thread, word k of thread t at memo[k * kMemoStride + t]
-constexpr uint32_t kMemoStride = 64, kMemoWords = 12;
+// instance memo (see SceneView): kMemoWords words per thread, word k of thread t at memo[k * kMemoStride + t] (dtof_kernels.h)
 DTOF_D void instance_memo_fill(const SceneView &sv, float time, float *m, float *inv) {
     instance_matrix(sv.objects[sv.memo_obj], time, m);
     affine_inverse(m, inv);
