@@ -278,6 +278,9 @@ void dtof_cancel(dtof_scene *scene);
 /* First-bounce launches of this scene, since it was loaded, that ran a kernel compiled with the frame plan's constants (dtof_render_stats::n_plan_facts_launches): the
  * same count for the calls that return no statistics block (the lane dumps). */
 uint64_t dtof_scene_plan_facts_launches(const dtof_scene *scene);
+/* The FACTS mask (dtof_kernels.h: kFact*) of the first-bounce kernel compiled with plan facts that the scene's last frame launched, 0 if it launched none: tells the
+ * instantiations apart, which the count above cannot. */
+uint32_t dtof_scene_last_plan_facts(const dtof_scene *scene);
 
 /* Per-lane debugging entry (SURVEY 8b "dtof_sample_lanes"): evaluates wavefront lanes
  * [lane_begin, lane_begin+n) exactly as dtof_render would (multi-pass renders: index = pass * wavefront_size + lane, a range must stay

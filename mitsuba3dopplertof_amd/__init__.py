@@ -104,6 +104,9 @@ def _lib():
     if hasattr(L, "dtof_scene_plan_facts_launches"):   # (an older build timed through DTOF_LIB has no such entry)
         L.dtof_scene_plan_facts_launches.argtypes = [vp]
         L.dtof_scene_plan_facts_launches.restype = C.c_uint64
+    if hasattr(L, "dtof_scene_last_plan_facts"):
+        L.dtof_scene_last_plan_facts.argtypes = [vp]
+        L.dtof_scene_last_plan_facts.restype = C.c_uint32
     L.dtof_sample_lanes.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64, vp]
     L.dtof_sample_lanes_valid.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64, vp, vp]
     L.dtof_develop_rgba.argtypes = [vp, vp, vp, C.c_int64]
@@ -255,6 +258,11 @@ class Scene:
     def plan_facts_launches(self):
         """first-bounce launches since the scene was loaded that ran a kernel compiled with the frame plan's constants (lane dumps included)"""
         return int(_lib().dtof_scene_plan_facts_launches(self._h))
+
+    @property
+    def last_plan_facts(self):
+        """the FACTS mask of the first-bounce kernel compiled with the frame plan's constants that the last frame launched, 0 if it launched none"""
+        return int(_lib().dtof_scene_last_plan_facts(self._h))
 
     def set_integrator(self, props):
         _check(_lib().dtof_scene_set_integrator(self._h, *_plugin_args(props)))

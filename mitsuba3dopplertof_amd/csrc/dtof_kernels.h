@@ -179,7 +179,18 @@ enum : uint32_t {
     kFactOneWall        = 1u << 11,  // (with kFactFlat) the scene has exactly one instance object, it is rp.memo_obj and holds ONE rectangle (DFlatObject::instance == 2,
                                      // DFlatKinds::general == 0, ::memo == 1u << memo_obj), and its matrix sits in the lane's LDS column (k_shade: memo_m_lds)
     kFactFusedSplat     = 1u << 12,  // A.film != nullptr: the launch splats its lanes itself (plan_frame: fuse_splat_ok -- tent filter of radius in (0.5, 1], 64 spp, one film)
+    // ... and the sampler's and the integrator's choices of a route: which VALUES the route reads (n_stratum, inv_tcn, amp, w_d, ...) stays run-time
+    kFactStratifiedPairs = 1u << 13, // rp.time_sampling == TIME_STRATIFIED, rp.stratify != 0, rp.tcn == 2 and rp.pcn == 2, rp.shutter_open_time > 0, rp.spp > 1: no time stream,
+                                     // next_time is its stratified route, pair and member of a sample are a shift and a mask
+    kFactPow2Strata     = 1u << 14,  // rp.n_stratum is a power of two >= 2: permute_kensler_pow2 (dtof_math.h), no cycle-walking loop and no division
+    kFactSineLowPass    = 1u << 15,  // rp.low_pass != 0 and rp.wave_type == WAVE_SIN: modulation_weight is amp * cos_(fmod_pos(w_d * t + phase + phi))
+    kFactEmitterSampled = 1u << 16,  // depth + rp.inline_iters < rp.max_depth: every iteration of the launch samples an emitter (k_shade: active_next)
+    kFactIdShift24      = 1u << 17,  // q.id_shift == 24
 };
+// The facts of (h).  A kernel that carries any of them AND kFactWavePixel also takes the lane mappings kFactWavePixel proves -- global lane = virtual lane (no stripes), the
+// pixel a shift of the wave's first lane by rp.spp_log2, the sample index a mask -- which the kernels compiled before (h) keep reading: their machine code does not move.
+constexpr uint32_t kFactsSampling = kFactStratifiedPairs | kFactPow2Strata | kFactSineLowPass | kFactEmitterSampled | kFactIdShift24;
+constexpr bool facts_lane_shifts(uint32_t facts) { return (facts & kFactWavePixel) != 0 && (facts & kFactsSampling) != 0; }
 // the mask the headline kernel (dtof_shade_plain.hip) is compiled with; A/B of a subset: make variant NAME=x DEFS=-DDTOF_HEADLINE_FACTS=0x17
 #ifndef DTOF_HEADLINE_FACTS
 #define DTOF_HEADLINE_FACTS 0xfff
@@ -191,6 +202,13 @@ constexpr uint32_t kHeadlineFacts = DTOF_HEADLINE_FACTS;
 #define DTOF_HEADLINE_FUSED 1
 #endif
 constexpr uint32_t kHeadlineFusedFacts = DTOF_HEADLINE_FUSED ? (kHeadlineFacts | kFactFusedSplat) : 0u;
+// ... and a third with the route facts of (h) on top of that: C2 again (stratified pairs, 32 strata, the sinusoidal low-pass weight), tried first; C3 (antithetic_mirror)
+// and whatever else breaks one of them keep the kernels above.  0: not built; A/B of a subset: DEFS=-DDTOF_HEADLINE_C2=0x6000
+#ifndef DTOF_HEADLINE_C2
+#define DTOF_HEADLINE_C2 0x3e000
+#endif
+constexpr uint32_t kHeadlineC2Facts = (DTOF_HEADLINE_C2) != 0 && kHeadlineFusedFacts != 0 ? (kHeadlineFusedFacts | (DTOF_HEADLINE_C2)) : 0u;
+static_assert(((DTOF_HEADLINE_C2) & ~kFactsSampling) == 0, "DTOF_HEADLINE_C2 names route facts only (bits 13 and up)");
 // DTOF_WALL_FRAMES (default 1): under kFactOneWall the shading frames come precomputed -- the plain rectangles' from the DFlatFrame table of the blob, the moving wall's
 // normal and tangent from two registers filled once per path (k_shade) -- so that compute_surface runs no normalisation.  0 builds the facts without them (A/B).
 #ifndef DTOF_WALL_FRAMES
@@ -205,13 +223,13 @@ constexpr uint32_t kResidentFacts = DTOF_RESIDENT_FACTS;
 // One launch of k_shade as launch_shade hands it to the translation unit that holds the instantiation (dtof_shade_*.hip: the ~100 instantiations of the
 // kernel compile in parallel, one group per file): staged = the scene blob is copied to LDS by every block; mode 0 split, 1 fused, 2 fused first bounce;
 // waves != 0: the resident form (`waves` waves per block, one block per CU); lds: the launch's dynamic LDS (ShadeLds::bytes), lds_flat: the same without the stack columns, what a kernel compiled
-// with kFactFlat is launched with; facts: the plan facts this launch satisfies (0: take the generic kernels).  launch_shade_plain and launch_shade_resident0 return whether an instantiation specialised on plan facts ran.
+// with kFactFlat is launched with; facts: the plan facts this launch satisfies (0: take the generic kernels).  launch_shade_plain and launch_shade_resident0 return the mask of the instantiation specialised on plan facts that ran, 0 if a generic one did.
 struct ShadeLaunch { bool staged; int mode; uint32_t waves, grid, lds, lds_flat; hipStream_t stream; ShadeArgs args; uint32_t facts; };
-bool launch_shade_plain(bool area, bool k4, const ShadeLaunch &L);      // rectangle-only diffuse scenes          (dtof_shade_plain.hip)
+uint32_t launch_shade_plain(bool area, bool k4, const ShadeLaunch &L);  // rectangle-only diffuse scenes          (dtof_shade_plain.hip)
 void launch_shade_mesh(bool area, bool k4, const ShadeLaunch &L);       // + triangles / analytic shapes          (dtof_shade_mesh.hip)
 void launch_shade_spec1(bool k4, const ShadeLaunch &L);                 // every BSDF / emitter / texture         (dtof_shade_spec1.hip)
 void launch_shade_spec2(bool k4, const ShadeLaunch &L);                 // ... and blendbsdf                      (dtof_shade_spec2.hip)
-bool launch_shade_resident0(bool area, bool k4, const ShadeLaunch &L);  // resident first bounce, diffuse scenes  (dtof_shade_res0.hip)
+uint32_t launch_shade_resident0(bool area, bool k4, const ShadeLaunch &L);  // resident first bounce, diffuse scenes  (dtof_shade_res0.hip)
 void launch_shade_resident1(bool k4, const ShadeLaunch &L);             // resident first bounce, every BSDF      (dtof_shade_res1.hip)
 void launch_shade_resident2(bool k4, const ShadeLaunch &L);             // ... and blendbsdf                      (dtof_shade_res2.hip)
 
@@ -247,7 +265,7 @@ struct ShadeRequest {
     LaneDebug *dbg = nullptr; float *film = nullptr; uint64_t film_stride = 0;   // first bounce of a lane dump: the camera rays; film: the launch covers the whole path and splats its lanes itself
     uint32_t facts = 0; const ResidentStage *resident = nullptr;              // the plan facts it satisfies (kFact*); the plan made it a resident launch (LaunchSpan::resident) of this stage
 };
-bool launch_shade(const ShadeRequest &r);   // returns whether a kernel specialised on the facts ran
+uint32_t launch_shade(const ShadeRequest &r);   // returns the FACTS mask of the kernel that ran (0: a generic one)
 void launch_shadow(const uint8_t *scene, uint32_t scene_bytes, const RenderParams &rp, const Queues &q,
                    const uint32_t *count_in, uint32_t stack_depth, const LaunchSwitches &ls, hipStream_t s);
 void launch_velocity(const uint8_t *scene, uint32_t scene_bytes, const RenderParams &rp, const Queues &q, uint32_t stack_depth, const LaunchSwitches &ls, hipStream_t s);

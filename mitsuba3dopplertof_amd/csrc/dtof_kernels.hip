@@ -655,9 +655,9 @@ uint32_t device_cu_count() {
     return hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n_cu <= 0 ? 256u : (uint32_t) n_cu;
 }
 // The plan decided what this launch is (FramePlan::launch_span); here it gets its argument block, its LDS (ShadeLds) and its grid, and goes to the file that holds its kernel.
-bool launch_shade(const ShadeRequest &r) {
+uint32_t launch_shade(const ShadeRequest &r) {
     const RenderParams &rp = *r.rp;
-    if (rp.n_lanes == 0) return false;
+    if (rp.n_lanes == 0) return 0u;
     const bool k4 = rp.n_offsets != 1, fused = r.mode != 0, first = r.mode == 2;
     const uint32_t n_seg = nseg(rp.n_lanes);
     ShadeLaunch L = {};
@@ -674,7 +674,7 @@ bool launch_shade(const ShadeRequest &r) {
         if (rp.has_spec == 2) launch_shade_resident2(k4, L);
         else if (rp.has_spec) launch_shade_resident1(k4, L);
         else return launch_shade_resident0(rp.has_area != 0, k4, L);
-        return false;
+        return 0u;
     }
     // a flat scene with one instance keeps the instance matrix in LDS as well (= the condition of k_shade's memo_m_lds in the instantiations launch_shade_plain picks)
     const bool one_instance = fused && !rp.has_tris && !rp.has_spec && rp.flat_objects != 0 && rp.memo_obj != 0xffffffffu;
@@ -686,7 +686,7 @@ bool launch_shade(const ShadeRequest &r) {
     else if (rp.has_spec) launch_shade_spec1(k4, L);
     else if (rp.has_tris) launch_shade_mesh(rp.has_area != 0, k4, L);
     else return launch_shade_plain(rp.has_area != 0, k4, L);
-    return false;
+    return 0u;
 }
 void launch_velocity(const uint8_t *scene, uint32_t scene_bytes, const RenderParams &rp, const Queues &q, uint32_t stack_depth, const LaunchSwitches &ls, hipStream_t s) {
     if (rp.n_lanes == 0) return;

@@ -510,5 +510,23 @@ DTOF_HD uint32_t permute_kensler(uint32_t index, uint32_t n, uint32_t seed, Fast
     const uint32_t v = index + seed;
     return v - n * fdiv(v, dn);
 }
+// ... for n a power of two >= 2 and index < n (kFactPow2Strata): the same integers in a straight line.  w = n - 1 is already the mask of all bits below n, so the
+// smear leaves it as it is.  The cycle-walking loop runs exactly once: its last two steps are `tmp &= w`, which leaves tmp <= w, and `tmp ^= tmp >> 5`, the XOR of two
+// values that both fit the mask w and therefore fits it too -- index <= w = n - 1 < n whatever came before.  And v - n * (v / n) = v mod n = v & (n - 1), with v the same
+// wrapped 32-bit sum in both forms.  (tests/sampling_facts_check.cpp sweeps the two against each other.)
+DTOF_HD uint32_t permute_kensler_pow2(uint32_t index, uint32_t n, uint32_t seed) {
+    const uint32_t w = n - 1;
+    uint32_t tmp = index;
+    tmp ^= seed;            tmp *= 0xe170893du;
+    tmp ^= seed >> 16;      tmp ^= (tmp & w) >> 4;
+    tmp ^= seed >> 8;       tmp *= 0x0929eb3fu;
+    tmp ^= seed >> 23;      tmp ^= (tmp & w) >> 1;
+    tmp *= 1 | seed >> 27;  tmp *= 0x6935fa69u;
+    tmp ^= (tmp & w) >> 11; tmp *= 0x74dcb303u;
+    tmp ^= (tmp & w) >> 2;  tmp *= 0x9e501cc3u;
+    tmp ^= (tmp & w) >> 2;  tmp *= 0xc860a3dfu;
+    tmp &= w;               tmp ^= tmp >> 5;
+    return (tmp + seed) & w;
+}
 
 }  // namespace dtof

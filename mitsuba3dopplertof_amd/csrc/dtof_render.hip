@@ -107,6 +107,7 @@ struct dtof_scene {
     hipStream_t own_stream = nullptr;                    // what ensure_device created and the destructor destroys
     std::atomic<bool> stop { false };
     uint64_t plan_facts_launches = 0;        // first-bounce launches that took a kernel compiled with plan facts, since the scene was loaded (dtof_scene_plan_facts_launches)
+    uint32_t last_plan_facts = 0;            // ... and the FACTS mask of the one the last frame launched, 0 if it launched none (dtof_scene_last_plan_facts)
     // reusable statistics plumbing (creating events / pinned memory per call costs ~0.3 ms)
     std::vector<hipEvent_t> event_pool; size_t events_used = 0;
     // frames enqueued by dtof_render_rows_async and not collected yet: their events (frame, stages) and launch counters; no host synchronisation until dtof_async_collect
@@ -416,7 +417,7 @@ struct FramePlan {
     uint32_t n_passes = 1, run_passes = 1, dump_pass = 0;
     uint64_t lanes_per_row = 0, first = 0, last = 0, batch = 1;   // every pass: lanes [first, last) in batches of `batch`
     bool fused = false, first_inline = false, skip_tail = false, fuse_splat_ok = false, terminal_ok = false, plan_facts = false, one_wall = false;
-    uint32_t max_inline = 1, chunk_segs = 0, res_units = 1, n_emitters = 0;
+    uint32_t max_inline = 1, chunk_segs = 0, res_units = 1, n_emitters = 0, id_shift = 0;   // id_shift: Queues::id_shift of the frame's launches
     ResidentStage resident;
     LaunchSwitches launch;                // launch.defer: the DEFER mode, 0 when the workspaces have no DEFER lists
     // does iteration `it` of the bounce loop run?  (the reference's last iteration only looks for emitter hits, dopplertofpath.cpp:136-171: skip_tail drops it)
@@ -458,6 +459,12 @@ struct FramePlan {
         if (n_emitters == 1) f |= kFactOneEmitter;
         if (r.flat_objects != 0) f |= kFactFlat;
         if (one_wall) f |= kFactOneWall;
+        // the routes of the correlated sampler's time draw and of the modulation weight; n_stratum & (n_stratum - 1): a power of two has one bit
+        if ((f & kFactDopplerCorr) && r.time_sampling == TIME_STRATIFIED && r.stratify != 0 && r.tcn == 2 && r.pcn == 2 && r.shutter_open_time > 0.f && r.spp > 1) f |= kFactStratifiedPairs;
+        if (r.n_stratum >= 2 && (r.n_stratum & (r.n_stratum - 1u)) == 0) f |= kFactPow2Strata;
+        if (r.low_pass != 0 && r.wave_type == WAVE_SIN) f |= kFactSineLowPass;
+        if (depth_end < r.max_depth) f |= kFactEmitterSampled;            // the deepest test is depth_end - 1 + 1 < max_depth
+        if (id_shift == 24) f |= kFactIdShift24;
         if (l.splat_here) f |= kFactFusedSplat;   // (the launcher hands in the film exactly then)
         // every segment's count is min(512, n_lanes - 512 S), a multiple of 64 if n_lanes is one: each 64-lane chunk is then whole, and its lanes are the 64-aligned
         // lanes [lane_base + 512 S + cbase, + 64), samples of one pixel when spp is a power of two >= 64.  (A striped shard -- a rank's share of a frame, virtual lanes --
@@ -626,7 +633,7 @@ FramePlan plan_frame(const dtof_scene *sc, const RenderRequest &rq) {
     // as the input of the NEXT iteration, and no queue is compacted for a launch that does not happen.
     p.terminal_ok = on("DTOF_TERMINAL_SKIP") && p.n_passes == 1 && !t.null_lobe;
     // kernels compiled with the plan's constants: which facts hold is decided per launch (FramePlan::launch_facts); no result depends on the switch
-    p.plan_facts = on("DTOF_PLAN_FACTS"); p.n_emitters = bh_emitters(*sc);
+    p.plan_facts = on("DTOF_PLAN_FACTS"); p.n_emitters = bh_emitters(*sc); p.id_shift = sc->id_shift;
     rp.emitter_pmf = bh_emitters(*sc) ? 1.f / (float) bh_emitters(*sc) : 0.f;   // m_emitter_pmf (scene.cpp:96)
     // fused pipeline: the first bounce kernel generates the lanes and traces the primary rays itself
     p.first_inline = p.fused && rp.integrator != INTEGRATOR_VELOCITY && p.iteration_runs(0) && on("DTOF_FUSE_FIRST");
@@ -642,6 +649,7 @@ void render_rows(dtof_scene *sc, const RenderRequest &rq) {
     if (!sc->host.has_sensor) throw std::runtime_error("the scene does not contain a sensor");
     ensure_device(sc);
     const FramePlan p = plan_frame(sc, rq);
+    sc->last_plan_facts = 0;
     RenderParams rp = p.rp;
     dtof_render_stats *const stats = rq.stats;
     const Queues q = sc->ws.prepare((uint32_t) p.batch, rp.n_offsets, rp.want_valid, p.launch.defer != 0, sc->id_shift);
@@ -705,9 +713,9 @@ void render_rows(dtof_scene *sc, const RenderRequest &rq) {
             sr.depth = it + 1 - l.span; sr.mode = first ? 2 : p.fused ? 1 : 0; sr.trace_next = l.next_runs; sr.resident = l.resident ? &p.resident : nullptr;
             sr.dbg = first && dump_now ? sc->ws.dbg.p : nullptr; sr.film = l.splat_here ? rq.film : nullptr; sr.film_stride = rq.film_stride;
             sr.facts = p.launch_facts(rp, l, sr.depth, first, qin == nullptr && count_in == nullptr, dump_now);
-            const bool specialised = launch_shade(sr);
+            const uint32_t specialised = launch_shade(sr);   // the mask of the kernel compiled with plan facts that ran, if one did
             tm.end(st_shade, t, s);
-            if (specialised) { sc->plan_facts_launches++; if (stats) stats->n_plan_facts_launches++; }
+            if (specialised) { sc->plan_facts_launches++; sc->last_plan_facts = specialised; if (stats) stats->n_plan_facts_launches++; }
             fused_splat_done |= l.splat_here;
             if (stats && l.splat_here) stats->n_fused_splat_launches++;
             if (stats && first) { stats->n_launches_first++; stats->n_inline_iterations += l.span; batch_inline.push_back(l.span); }
@@ -1203,6 +1211,7 @@ int dtof_render(dtof_scene *sc, uint32_t sensor_index, uint32_t seed, uint32_t s
 
 void dtof_cancel(dtof_scene *sc) { if (sc) sc->stop = true; }
 uint64_t dtof_scene_plan_facts_launches(const dtof_scene *sc) { return sc ? sc->plan_facts_launches : 0; }
+uint32_t dtof_scene_last_plan_facts(const dtof_scene *sc) { return sc ? sc->last_plan_facts : 0; }
 
 int dtof_sample_lanes_valid(dtof_scene *sc, uint32_t seed, uint32_t spp, uint64_t lane_begin, uint64_t n, float *out, uint32_t *valid) {
     return guarded([&] {

@@ -33,18 +33,22 @@ DTOF_D float next_correlate(Rng &main, Rng &path, bool correlate) {
     return pcg_output_f32(old);
 }
 // next_1d_time -- correlated.cpp:92-153; si = current_sample_index (sampler.cpp:94-103)
+// FACTS (dtof_kernels.h): kFactStratifiedPairs -- the stratified strategy with per-interval stratification and pairs (tcn == 2): the route below is the only one compiled,
+// si / 2 and si % 2 a shift and a mask; kFactPow2Strata -- the permutation of a power-of-two stratum count.  The values the route reads stay run-time.
+template <uint32_t FACTS = 0>
 DTOF_D float next_time(const RenderParams &rp, Rng &main, Rng &tm, uint32_t si, uint32_t perm_seed, uint32_t &dim) {
-    int strategy = rp.time_sampling; uint32_t tcn = rp.tcn;
+    constexpr bool F_STRAT = (FACTS & kFactStratifiedPairs) != 0, F_POW2 = (FACTS & kFactPow2Strata) != 0;
+    int strategy = F_STRAT ? (int) TIME_STRATIFIED : rp.time_sampling; uint32_t tcn = F_STRAT ? 2u : rp.tcn;
     if (strategy == TIME_UNIFORM) return next_f32(main);
     float r = strategy == TIME_STRATIFIED ? next_f32(main) : next_f32(tm);
-    const uint32_t quo = fdiv(si, rp.d_tcn), rem = si - quo * tcn;   // si / tcn, si % tcn
-    if (rp.stratify) {
+    const uint32_t quo = F_STRAT ? si >> 1 : fdiv(si, rp.d_tcn), rem = F_STRAT ? si & 1u : si - quo * tcn;   // si / tcn, si % tcn
+    if (F_STRAT || rp.stratify) {
         if (strategy == TIME_STRATIFIED) {
             // the reference evaluates p1 (seed + dim) and p2 (seed + dim + 1) and selects; the permutation is a pure function,
             // so only the selected one is computed
             const uint32_t ps = perm_seed + dim + ((rem != 0) ? 0u : 1u);
             dim += 2;
-            const uint32_t p = permute_kensler(quo, rp.n_stratum, ps, rp.d_stratum);
+            const uint32_t p = F_POW2 ? permute_kensler_pow2(quo, rp.n_stratum, ps) : permute_kensler(quo, rp.n_stratum, ps, rp.d_stratum);
             r = ((float) p + r) * rp.inv_n_stratum;
         } else {
             r = ((float) quo + r) * rp.inv_n_stratum;
@@ -83,11 +87,14 @@ DTOF_D float waveform_low_pass(float _t, int type) {
     return fmin_(fmax_(2.0f * r, -2.0f), 2.0f);
 }
 // eval_modulation_weight -- dopplertofpath.cpp:60-77; w_d, phase: the film's (RenderParams::w_d[k], ::phase[k])
+// FACTS: kFactSineLowPass -- the low-pass weight of the sinusoidal wave is the only form compiled: amp * cos_(fmod_pos(w_d * t + phase + phi))
+template <uint32_t FACTS = 0>
 DTOF_D float modulation_weight(const RenderParams &rp, float w_d, float phase, float ray_time, float path_length) {
+    constexpr bool F_SINE_LP = (FACTS & kFactSineLowPass) != 0;
     float phi = rp.phi_coef * path_length;
-    if (rp.low_pass) {
+    if (F_SINE_LP || rp.low_pass) {
         float t = w_d * ray_time + phase + phi;
-        return rp.amp * waveform_low_pass(t, rp.wave_type);
+        return rp.amp * waveform_low_pass(t, F_SINE_LP ? (int) WAVE_SIN : rp.wave_type);
     }
     float t1 = rp.w_g * ray_time - phi;
     float t2 = (rp.w_g + w_d) * ray_time + phase;
@@ -100,8 +107,10 @@ DTOF_D float modulation_weight(const RenderParams &rp, float w_d, float phase, f
 // One lane of render_sample's head (integrator.cpp:476-495 / :416-431): sampler seeding, pixel jitter, time sample, camera ray.
 struct PrimaryLane { float4 ray_a, ray_b; Rng main, path; float2 pos; };
 // global lane index (pixel-major, the index every stream of the sampler is seeded with) of a lane of this launch
+// FACTS: kFactWavePixel holds for launches without stripes only (facts_lane_shifts, dtof_kernels.h)
+template <uint32_t FACTS = 0>
 DTOF_D uint32_t global_lane(const RenderParams &rp, uint32_t virtual_lane) {
-    if (rp.stripe_rows == 0) return virtual_lane;
+    if (facts_lane_shifts(FACTS) || rp.stripe_rows == 0) return virtual_lane;
     const uint32_t v = fdiv(virtual_lane, rp.d_lanes_per_row), in_row = virtual_lane - v * rp.lanes_per_row;
     const uint32_t s = fdiv(v, rp.d_stripe_rows), y = rp.stripe_first + s * rp.stripe_period + (v - s * rp.stripe_rows);
     return y * rp.lanes_per_row + in_row;
@@ -163,8 +172,11 @@ DTOF_D void camera_ray(const RenderParams &rp, float ax, float ay, float apx, fl
 template <bool PERSPECTIVE_ONLY = false, uint32_t FACTS = 0>
 DTOF_D PrimaryLane generate_lane(const RenderParams &rp, uint32_t lane, bool wave_pixel = false, uint32_t vlane = 0) {
     constexpr bool F_SINGLE_PASS = (FACTS & kFactSinglePass) != 0, F_DOPPLER_CORR = (FACTS & kFactDopplerCorr) != 0, F_CORRELATED = (FACTS & kFactCorrelated) != 0;
+    // kFactStratifiedPairs: the stratified strategy never draws from the time stream (it is not seeded), pairs share their path stream (lane / 2), the shutter is open
+    // for a time and a pixel has several samples; lane shifts (kFactWavePixel in a kernel of DESIGN 8.3 (h)): spp is a power of two >= 64 and the wave's lanes are one pixel's
+    constexpr bool F_STRAT = (FACTS & kFactStratifiedPairs) != 0 && F_DOPPLER_CORR, F_SHIFTS = facts_lane_shifts(FACTS);
     // m_rng_time is drawn from by every strategy of the correlated sampler but uniform and stratified (correlated.cpp:96-106)
-    const bool needs_tm = (F_DOPPLER_CORR || (rp.integrator == 0 && rp.sampler_kind == SAMPLER_CORRELATED)) && rp.time_sampling >= TIME_ANTITHETIC;   // every strategy but uniform / stratified (:103-107)
+    const bool needs_tm = !F_STRAT && (F_DOPPLER_CORR || (rp.integrator == 0 && rp.sampler_kind == SAMPLER_CORRELATED)) && rp.time_sampling >= TIME_ANTITHETIC;   // every strategy but uniform / stratified (:103-107)
     Rng main, tm, path; tm.state = 0; tm.inc = 1;
     uint2 *const carried = !F_SINGLE_PASS && rp.n_passes > 1 ? rp.pass_rng + (size_t) (vlane - rp.pass_first) * 3 : nullptr;
     const uint32_t pass = F_SINGLE_PASS ? 0u : rp.pass;
@@ -182,17 +194,18 @@ DTOF_D PrimaryLane generate_lane(const RenderParams &rp, uint32_t lane, bool wav
     } else if (pass == 0) {
         main = seed_stream(rp.seed_value, lane);
         if (needs_tm) tm = seed_stream(rp.seed_value + 1, fdiv(lane, rp.d_tcn));
-        path = seed_stream(rp.seed_value + 2, fdiv(lane, rp.d_pcn));
+        path = seed_stream(rp.seed_value + 2, F_STRAT ? lane >> 1 : fdiv(lane, rp.d_pcn));
     } else {   // later passes: the sampler was seeded once (integrator.cpp:265); its streams run on where the previous pass left them
         const uint2 a = carried[0], b = carried[1], c = carried[2];
         main.state = (uint64_t) a.x | ((uint64_t) a.y << 32); main.inc = stream_inc(rp.seed_value, lane);
         if (needs_tm) { tm.state = (uint64_t) b.x | ((uint64_t) b.y << 32); tm.inc = stream_inc(rp.seed_value + 1, fdiv(lane, rp.d_tcn)); }
         path.state = (uint64_t) c.x | ((uint64_t) c.y << 32); path.inc = stream_inc(rp.seed_value + 2, fdiv(lane, rp.d_pcn));
     }
-    const uint32_t pix = fdiv(lane, rp.d_spp);
+    // (lane shifts: the pixel of the wave's first lane is every lane's, so the index stays on the scalar unit, where pixel_info<true> wants it)
+    const uint32_t pix = F_SHIFTS ? (uint32_t) __builtin_amdgcn_readfirstlane((int) lane) >> rp.spp_log2 : fdiv(lane, rp.d_spp);
     // current_sample_index = m_sample_index * samples_per_wavefront + lane % samples_per_wavefront (sampler.cpp:94-103); Sampler::advance
     // bumps m_sample_index once per pass (sampler.cpp:52-55)
-    uint32_t si = (rp.spp > 1 ? lane - pix * rp.spp : 0) + pass * rp.spp;
+    uint32_t si = (F_SHIFTS ? lane & (rp.spp - 1u) : (F_STRAT || rp.spp > 1) ? lane - pix * rp.spp : 0) + pass * rp.spp;
     const PixelInfo pi = wave_pixel ? pixel_info<true>(rp, pix) : pixel_info<false>(rp, pix);
     const uint32_t perm_seed = pi.perm_seed; const float posx = pi.posx, posy = pi.posy;
     uint32_t dim = 0;
@@ -210,10 +223,10 @@ DTOF_D PrimaryLane generate_lane(const RenderParams &rp, uint32_t lane, bool wav
     float apx = .5f, apy = .5f;
     if (lens) { apx = single ? next_f32(main) : next_correlate(main, path, cp); apy = single ? next_f32(main) : next_correlate(main, path, cp); }
     float time = rp.shutter_open;
-    if (rp.shutter_open_time > 0.f) {
+    if (F_STRAT || rp.shutter_open_time > 0.f) {
         float u;
         if (!F_DOPPLER_CORR && (!doppler || rp.sampler_kind == SAMPLER_INDEPENDENT)) u = next_f32(main);   // Sampler::next_1d_time -> next_1d (sampler.h:131-132)
-        else if (F_DOPPLER_CORR || rp.sampler_kind == SAMPLER_CORRELATED) u = next_time(rp, main, tm, si, perm_seed, dim);
+        else if (F_DOPPLER_CORR || rp.sampler_kind == SAMPLER_CORRELATED) u = next_time<FACTS>(rp, main, tm, si, perm_seed, dim);
         else {   // TimeStratifiedSampler::next_1d_time (timestratified.cpp:117-129): the strategy arguments are ignored
             uint32_t p = permute_kensler(si, rp.sample_count, perm_seed + dim++, rp.d_sample_count);
             float j = rp.jitter ? next_f32(main) : .5f;

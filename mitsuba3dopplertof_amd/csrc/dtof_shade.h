@@ -366,6 +366,8 @@ __global__ __launch_bounds__(RESW ? RESW * 64 : kShadeBlock, RESW ? RESW / 4 : (
     constexpr bool F_WHOLE_PATH = (FACTS & kFactWholePath) != 0, F_ONE_BLOCK = (FACTS & kFactOneBlock) != 0, F_ONE_EMITTER = (FACTS & kFactOneEmitter) != 0;
     constexpr bool F_WAVE_PIXEL = (FACTS & kFactWavePixel) != 0;
     constexpr bool F_FLAT = (FACTS & kFactFlat) != 0, F_ONE_WALL = (FACTS & kFactOneWall) != 0, F_FUSED_SPLAT = (FACTS & kFactFusedSplat) != 0;
+    // the routes of the sampler and of the modulation weight are taken inside generate_lane / next_time / modulation_weight, which get FACTS; here:
+    constexpr bool F_EMITTER_SAMPLED = (FACTS & kFactEmitterSampled) != 0, F_ID24 = (FACTS & kFactIdShift24) != 0, F_SHIFTS = facts_lane_shifts(FACTS);
     constexpr bool F_FRAMES = F_ONE_WALL && DTOF_WALL_FRAMES;   // shading frames precomputed: the wall's once per path, the plain rectangles' on the host (compute_surface)
     static_assert(!F_FLAT || (!MESH && SPEC == 0 && RESW == 0), "trace_flat serves the staged rectangle-only diffuse kernels");
     static_assert(!F_ONE_WALL || F_FLAT, "the one wall is an object of the flat table");
@@ -554,7 +556,7 @@ __global__ __launch_bounds__(RESW ? RESW * 64 : kShadeBlock, RESW ? RESW / 4 : (
     if (in_range) {
         l = qin ? qin[seg * kSeg + j] : seg * kSeg + j;
         if (FIRST) {
-            const PrimaryLane pl = generate_lane<SPEC == 0, FACTS>(rp, global_lane(rp, rp.lane_base + l), wave_pixel, rp.lane_base + l);
+            const PrimaryLane pl = generate_lane<SPEC == 0, FACTS>(rp, global_lane<FACTS>(rp, rp.lane_base + l), wave_pixel, rp.lane_base + l);
             ra = pl.ray_a; rb = pl.ray_b; main = pl.main; path = pl.path; st = make_float4(1.f, 1.f, 1.f, 0.f);
             if (PARK) park_store();
             pos_reg = pl.pos;
@@ -578,7 +580,7 @@ __global__ __launch_bounds__(RESW ? RESW * 64 : kShadeBlock, RESW ? RESW / 4 : (
             bool found = (F_FLAT || flat) ? trace_flat<false, true, FACTS & kFactOneWall>(sv, (ConstBytes) A.scene + rp.flat_off, rp.flat_off, flat, stack, mk(ra.x, ra.y, ra.z), mk(rb.x, rb.y, rb.z), ra.w, rb.w, h)
                               : trace_scene<false, MESH, FUSED, RESW != 0, kStackStride, S16, 0u, false, RH16>(sv, stack, mk(ra.x, ra.y, ra.z), mk(rb.x, rb.y, rb.z), ra.w, rb.w, h);
             hh = make_uint4(f2u(h.t), f2u(h.u), f2u(h.v), h.prim);
-            hid = found ? (h.obj | (h.shape << q.id_shift)) : 0xffffffffu;
+            hid = found ? (h.obj | (h.shape << (F_ID24 ? 24u : q.id_shift))) : 0xffffffffu;
         }
     }
     const uint32_t n_inline = FIRST ? rp.inline_iters : 1u;
@@ -645,7 +647,7 @@ __global__ __launch_bounds__(RESW ? RESW * 64 : kShadeBlock, RESW ? RESW / 4 : (
 #pragma unroll
             for (int k = 0; k < KMAX; ++k) if (KMAX == 1 || k < rp.n_offsets) {
                 V3 v = le * mis_bsdf;
-                if (rp.integrator == 0) v = v * modulation_weight(rp, rp.w_d[k], rp.phase[k], time_, stv.w);
+                if (rp.integrator == 0) v = v * modulation_weight<FACTS>(rp, rp.w_d[k], rp.phase[k], time_, stv.w);
                 const float4 r = res_get(k);
                 res_put(k, make_float4(fmaf(stv.x, v.x, r.x), fmaf(stv.y, v.y, r.y), fmaf(stv.z, v.z, r.z), 0.f));
             }
@@ -660,7 +662,7 @@ __global__ __launch_bounds__(RESW ? RESW * 64 : kShadeBlock, RESW ? RESW / 4 : (
             const bool single = !F_DOPPLER_CORR && (plain || rp.sampler_kind != SAMPLER_CORRELATED);   // main stream only (path.cpp:197,213-214,273; sampler.h:141-144)
             float t = u2f(hh.x);
             path_length += t * eta_path;   // dopplertofpath.cpp:141 (eta stays 1 without dielectrics)
-            bool active_next = depth + 1 < rp.max_depth;
+            bool active_next = F_EMITTER_SAMPLED || depth + 1 < rp.max_depth;   // (the fact: true in every iteration of the launch)
 
             Surface si;
             if (!FIRST && have_memo) instance_memo_fill(sv, time, memo_m, memo_inv);
@@ -669,8 +671,8 @@ __global__ __launch_bounds__(RESW ? RESW * 64 : kShadeBlock, RESW ? RESW / 4 : (
             }
             // the diffuse-only kernels' terminal iteration reads the cosines wi.z / wo.z and nothing else of the shading frame
             const bool want_frame = SPEC != 0 || !terminal;
-            if constexpr (F_FRAMES) compute_surface<MESH, FACTS & kFactOneWall>(sv, hid & ((1u << q.id_shift) - 1u), hid >> q.id_shift, hh.w, t, u2f(hh.y), u2f(hh.z), o, d, time, si, have_memo, memo_m, memo_inv, want_frame, &wf);
-            else compute_surface<MESH, FACTS & kFactOneWall>(sv, hid & ((1u << q.id_shift) - 1u), hid >> q.id_shift, hh.w, t, u2f(hh.y), u2f(hh.z), o, d, time, si, have_memo, memo_m, memo_inv, want_frame);
+            if constexpr (F_FRAMES) compute_surface<MESH, FACTS & kFactOneWall>(sv, hid & ((1u << (F_ID24 ? 24u : q.id_shift)) - 1u), hid >> (F_ID24 ? 24u : q.id_shift), hh.w, t, u2f(hh.y), u2f(hh.z), o, d, time, si, have_memo, memo_m, memo_inv, want_frame, &wf);
+            else compute_surface<MESH, FACTS & kFactOneWall>(sv, hid & ((1u << (F_ID24 ? 24u : q.id_shift)) - 1u), hid >> (F_ID24 ? 24u : q.id_shift), hh.w, t, u2f(hh.y), u2f(hh.z), o, d, time, si, have_memo, memo_m, memo_inv, want_frame);
             const DShape *sh = si.shape;
 
             const float pmf = rp.emitter_pmf;   // m_emitter_pmf (scene.cpp:96)
@@ -709,7 +711,7 @@ __global__ __launch_bounds__(RESW ? RESW * 64 : kShadeBlock, RESW ? RESW / 4 : (
 #pragma unroll
                     for (int k = 0; k < KMAX; ++k) if (KMAX == 1 || k < rp.n_offsets) {
                         V3 v = le * mis_bsdf;
-                        if (!plain) v = v * modulation_weight(rp, rp.w_d[k], rp.phase[k], time, path_length);
+                        if (!plain) v = v * modulation_weight<FACTS>(rp, rp.w_d[k], rp.phase[k], time, path_length);
                         float4 r;
                         if constexpr (RES_LDS) r = res_get(k); else r = rcur[k];
                         const float4 acc = make_float4(fmaf(thr.x, v.x, r.x), fmaf(thr.y, v.y, r.y), fmaf(thr.z, v.z, r.z), 0.f);
@@ -865,7 +867,7 @@ __global__ __launch_bounds__(RESW ? RESW * 64 : kShadeBlock, RESW ? RESW / 4 : (
                 for (int k = 0; k < KMAX; ++k) if (KMAX == 1 || k < rp.n_offsets) {
                     float4 r = AREA ? rcur[k] : res_get(k);
                     V3 v = mk(bsdf_val.x * em_weight.x * mis_em, bsdf_val.y * em_weight.y * mis_em, bsdf_val.z * em_weight.z * mis_em);
-                    if (!plain) { float lw = modulation_weight(rp, rp.w_d[k], rp.phase[k], time, path_length + ds_dist); v = v * lw; }
+                    if (!plain) { float lw = modulation_weight<FACTS>(rp, rp.w_d[k], rp.phase[k], time, path_length + ds_dist); v = v * lw; }
                     float3 c = make_float3(fmaf(thr.x, v.x, r.x), fmaf(thr.y, v.y, r.y), fmaf(thr.z, v.z, r.z));
                     cand[k] = c;
                     nonzero |= f2u(c.x) != f2u(r.x) || f2u(c.y) != f2u(r.y) || f2u(c.z) != f2u(r.z);
@@ -950,7 +952,7 @@ __global__ __launch_bounds__(RESW ? RESW * 64 : kShadeBlock, RESW ? RESW / 4 : (
 #pragma unroll
                 for (int k = 0; k < KMAX; ++k) if (k < rp.n_offsets) {
                     V3 v = pend_v;
-                    if (!plain_) v = v * modulation_weight(rp, rp.w_d[k], rp.phase[k], shb.w, pend_len);   // shb.w: the ray time (the shadow ray carries it)
+                    if (!plain_) v = v * modulation_weight<FACTS>(rp, rp.w_d[k], rp.phase[k], shb.w, pend_len);   // shb.w: the ray time (the shadow ray carries it)
                     const float4 r = res_get(k);
                     res_put(k, make_float4(fmaf(pend_thr.x, v.x, r.x), fmaf(pend_thr.y, v.y, r.y), fmaf(pend_thr.z, v.z, r.z), 0.f));
                 }
@@ -974,7 +976,7 @@ __global__ __launch_bounds__(RESW ? RESW * 64 : kShadeBlock, RESW ? RESW / 4 : (
             bool found = (F_FLAT || flat) ? trace_flat<false, true, FACTS & kFactOneWall>(sv, (ConstBytes) A.scene + rp.flat_off, rp.flat_off, flat, stack, mk(nra.x, nra.y, nra.z), mk(nrb.x, nrb.y, nrb.z), nra.w, nrb.w, h)
                               : trace_scene<false, MESH, true, RESW != 0, kStackStride, S16, 0u, false, RH16>(sv, stack, mk(nra.x, nra.y, nra.z), mk(nrb.x, nrb.y, nrb.z), nra.w, nrb.w, h);
             if (!FIRST || last) store_hit<MESH>(q, l, h, found);
-            if (FIRST) { hh = make_uint4(f2u(h.t), f2u(h.u), f2u(h.v), h.prim); hid = found ? (h.obj | (h.shape << q.id_shift)) : 0xffffffffu; }
+            if (FIRST) { hh = make_uint4(f2u(h.t), f2u(h.u), f2u(h.v), h.prim); hid = found ? (h.obj | (h.shape << (F_ID24 ? 24u : q.id_shift))) : 0xffffffffu; }
         }
         const uint32_t n_sh = (uint32_t) __popcll(__ballot(want_shadow)) * ((threadIdx.x & 63) == 0 ? 1u : 0u);   // per-wave partial (stats only)
         if (last) n_shadow += n_sh; else if (lane_id == 0) s_inline[2 * it + 1] += n_sh;
@@ -995,7 +997,7 @@ __global__ __launch_bounds__(RESW ? RESW * 64 : kShadeBlock, RESW ? RESW / 4 : (
     }   // inline iterations
     if constexpr (!RES_LDS) if (FIRST && fuse_splat) {   // ---- ImageBlock::put (imageblock.cpp:414-531) of the wave's samples: tent filter of radius <= 1, a 3 x 3 footprint anchored at the sample's pixel
         const uint32_t W = (uint32_t) rp.crop_w;
-        const uint32_t pix = fdiv(global_lane(rp, rp.lane_base + l), rp.d_spp);
+        const uint32_t pix = F_SHIFTS ? (uint32_t) __builtin_amdgcn_readfirstlane((int) (rp.lane_base + l)) >> rp.spp_log2 : fdiv(global_lane(rp, rp.lane_base + l), rp.d_spp);   // (as in generate_lane)
         const int py = (int) fdiv(pix, rp.d_w), px = (int) (pix - W * (uint32_t) py);
         const float sx = pos_reg.x, sy = pos_reg.y;
         const bool regular = in_range && (int) floorf(sx) - rp.crop_x == px && (int) floorf(sy) - rp.crop_y == py;   // (rarely a float position rounds up into the next pixel)

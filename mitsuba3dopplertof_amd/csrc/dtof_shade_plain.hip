@@ -6,18 +6,22 @@ namespace dtof {
 // The headline kernel (cornell_wall, C2 / C3: the staged first-bounce kernel of one film without area emitters) compiled with the frame plan's constants
 // (dtof_kernels.h: kFact*): taken when the launch satisfies every fact of its mask.  A kernel compiled with kFactFlat has no traversal stack: its launch carries
 // no stack column (ShadeLaunch::lds_flat).
-template <uint32_t FACTS> static bool launch_headline(const ShadeLaunch &L) {
-    if (FACTS == 0 || (L.facts & FACTS) != FACTS) return false;
+template <uint32_t FACTS> static uint32_t launch_headline(const ShadeLaunch &L) {
+    if (FACTS == 0 || (L.facts & FACTS) != FACTS) return 0u;
     hipLaunchKernelGGL((k_shade<true, 2, false, 1, false, 0, 0, false, FACTS>), dim3(L.grid), dim3(kShadeBlock), (FACTS & kFactFlat) ? L.lds_flat : L.lds, L.stream, L.args);
-    return true;
+    return FACTS;
 }
-bool launch_shade_plain(bool area, bool k4, const ShadeLaunch &L) {
-    // The most specific kernel whose mask holds: C2's, which also splats (kFactFusedSplat), before the one that leaves the film to the splat kernels (C3, box filters);
-    // the generic instantiation below otherwise
-    if (!area && !k4 && L.staged && L.mode == 2 && (launch_headline<kHeadlineFusedFacts>(L) || launch_headline<kHeadlineFacts>(L))) return true;
+uint32_t launch_shade_plain(bool area, bool k4, const ShadeLaunch &L) {
+    // The most specific kernel whose mask holds: C2's with its sampling and modulation routes compiled in (kHeadlineC2Facts), then the one that splats whatever the routes
+    // (kFactFusedSplat), then the one that leaves the film to the splat kernels (C3, box filters); the generic instantiation below otherwise
+    if (!area && !k4 && L.staged && L.mode == 2) {
+        if (uint32_t ran = launch_headline<kHeadlineC2Facts>(L)) return ran;
+        if (uint32_t ran = launch_headline<kHeadlineFusedFacts>(L)) return ran;
+        if (uint32_t ran = launch_headline<kHeadlineFacts>(L)) return ran;
+    }
     if (area) { if (k4) launch_shade_variant<true, kMaxOffsets, false, 0>(L); else launch_shade_variant<true, 1, false, 0>(L); }
     else      { if (k4) launch_shade_variant<false, kMaxOffsets, false, 0>(L); else launch_shade_variant<false, 1, false, 0>(L); }
-    return false;
+    return 0u;
 }
 
 // dtof_bsdf_eval_ex, spec = 0 (k_bsdf_eval in dtof_shade.h)

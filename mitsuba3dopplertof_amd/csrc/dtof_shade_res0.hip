@@ -11,12 +11,12 @@ static void launch_resident_facts(const ShadeLaunch &L) {
     hipLaunchKernelGGL(kernel, dim3(L.grid), dim3(16 * 64), L.lds, L.stream, L.args);
 }
 
-bool launch_shade_resident0(bool area, bool k4, const ShadeLaunch &L) {
+uint32_t launch_shade_resident0(bool area, bool k4, const ShadeLaunch &L) {
     // taken when the launch satisfies every fact of the mask, the generic instantiations below otherwise
-    if (kResidentFacts != 0 && !area && !k4 && L.waves == 16 && !L.args.rp.res_half && (L.facts & kResidentFacts) == kResidentFacts) { launch_resident_facts(L); return true; }
+    if (kResidentFacts != 0 && !area && !k4 && L.waves == 16 && !L.args.rp.res_half && (L.facts & kResidentFacts) == kResidentFacts) { launch_resident_facts(L); return kResidentFacts; }
     if (area) { if (k4) launch_resident_variant<true, kMaxOffsets, 0>(L); else launch_resident_variant<true, 1, 0>(L); }
     else      { if (k4) launch_resident_variant<false, kMaxOffsets, 0>(L); else launch_resident_variant<false, 1, 0>(L); }
-    return false;
+    return 0u;
 }
 
 }  // namespace dtof
