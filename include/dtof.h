@@ -147,6 +147,25 @@ int dtof_bsdf_eval(dtof_scene *scene, uint32_t shape_index, uint32_t n, const fl
  * -1 = the one a render of this scene runs.  A `spec` the render path could never run on that shape fails with DTOF_ERR_INVALID and writes nothing: 0 on anything but
  * an untextured diffuse (plain or twosided), 1 on a blendbsdf or a two-BSDF twosided.  dtof_bsdf_eval is spec = 2 with the flat frame. */
 int dtof_bsdf_eval_ex(dtof_scene *scene, uint32_t shape_index, int spec, uint32_t n, const float *in29, float *out14);
+/* The emitter side of a path vertex over arrays, through the very device functions the shade kernels call (next-event estimation and the two densities that feed MIS).
+ * mode 0: Scene::sample_emitter_direction without its visibility test (src/render/scene.cpp:171-189,235-291; src/emitters/{point,spot,directional,constant,envmap,
+ *         area}.cpp; Shape / Sphere::sample_direction; Mesh::sample_position; Texture::sample_position).  Per query 5 floats: the reference point p[3] and the two
+ *         draws e1 (emitter pick, reused) and e2 -> 14 floats: sampled point[3], direction[3], distance, density (times the pick's probability), 1 for a delta
+ *         emitter, weight[3] (times the reciprocal of the pick's probability), 1 if the sample is usable (density != 0 and the emitter faces p), the picked emitter.
+ * mode 1: the emitter-hit density, DirectionSample(scene, si, prev_si) + Scene::pdf_emitter_direction (area.cpp:161-180, sphere.cpp:298-310) behind a lobe that is
+ *         not a delta.  Per query 11 floats: the previous vertex[3], the hit point[3], its shading normal[3], its uv[2], on shape `shape_or_minus1` -> 5 floats:
+ *         distance, direction[3], density.
+ * mode 2: the environment seen by a ray that left the scene (constant.cpp:150-155, envmap.cpp:299-310,408-425).  Per query the ray's direction[3] -> 4 floats:
+ *         density, value[3].
+ * `level` names the (AREA, MESH, SPEC) instantiation of the shade kernels whose code runs: 0 (no, no, 0), 1 (yes, no, 0), 2 (no, yes, 0), 3 (yes, yes, 0),
+ * 4 (yes, yes, 1), 5 (yes, yes, 2), 6 = level 0 as the kernels compiled for scenes with exactly one emitter take it; -1 = the one a render of this scene runs.
+ * The call fails with DTOF_ERR_INVALID and writes nothing
+ *   - for a level the render path could never run on this scene: levels 0, 2 and 6 need point emitters only (6: exactly one), level 1 point emitters and untextured
+ *     rectangle lights only, levels 0 - 3 and 6 no spot, directional, constant or envmap emitter and no textured radiance;
+ *   - for a scene without emitters (mode 0), a shape without an emitter (mode 1), a scene without an environment (mode 2), an index out of range;
+ *   - if ANY float of a query is not finite, or a draw lies outside [0, 1).  The table searches of the mesh, texture and environment-map samplers index by their
+ *     sample, and the samplers produce [0, 1 - 2^-24] only: no other value reaches the device. */
+int dtof_emitter_eval(dtof_scene *scene, int mode, int level, int32_t shape_or_minus1, uint32_t n, const float *in, float *out);
 
 /* ---------------------------------------------------------------- rendering
  * Replaces Integrator::render(Scene*, uint32_t sensor_index, uint32_t seed, uint32_t spp, bool develop,

@@ -150,7 +150,8 @@ def _lib():
     for name, args in (("dtof_render_variants", [vp, C.c_uint32, C.c_uint32, vp, C.c_int, vp, C.POINTER(_Stats)]),
                        ("dtof_render_rows_variants", rows + [C.POINTER(_Stats)]), ("dtof_render_rows_variants_async", rows),
                        ("dtof_render_stripes_variants", stripes + [C.POINTER(_Stats)]), ("dtof_render_stripes_variants_async", stripes),
-                       ("dtof_sample_lanes_variants", [vp, C.c_uint32, C.c_uint32, vp, C.c_int, C.c_uint64, C.c_uint64, vp, vp, vp])):
+                       ("dtof_sample_lanes_variants", [vp, C.c_uint32, C.c_uint32, vp, C.c_int, C.c_uint64, C.c_uint64, vp, vp, vp]),
+                       ("dtof_emitter_eval", [vp, C.c_int, C.c_int, C.c_int32, C.c_uint32, vp, vp])):
         if hasattr(L, name):   # a DTOF_LIB build from before the variants (A/B timing against an older commit) loads; calling what it lacks still raises
             getattr(L, name).argtypes = args
     _LIB = L
@@ -390,6 +391,17 @@ class Scene:
             q = np.ascontiguousarray(np.concatenate([q, np.broadcast_to(g, (len(q), 18))], axis=1))
         out = np.zeros((len(q), 14), np.float32)
         _check(_lib().dtof_bsdf_eval_ex(self._h, shape_index, spec, len(q), q.ctypes.data, out.ctypes.data))
+        return out
+
+    def emitter_eval(self, mode, queries, level=-1, shape_index=-1):
+        """The emitter side of a path vertex over arrays, through the shade kernels' own device functions (dtof_emitter_eval).  mode 0: (n, 5) reference point and the
+        draws e1, e2 -> (n, 14) sampled point[3], direction[3], distance, density, delta, weight[3], usable, picked emitter; mode 1: (n, 11) previous vertex, hit point,
+        shading normal, uv on shape `shape_index` -> (n, 5) distance, direction[3], density; mode 2: (n, 3) directions -> (n, 4) density and value of the environment.
+        `level`: the (AREA, MESH, SPEC) instantiation (0 .. 6; -1 = the one a render of this scene runs).  Floats that are not finite and draws outside [0, 1) are refused."""
+        n_in, n_out = {0: (5, 14), 1: (11, 5), 2: (3, 4)}[mode]
+        q = np.ascontiguousarray(queries, np.float32).reshape(-1, n_in)
+        out = np.zeros((len(q), n_out), np.float32)
+        _check(_lib().dtof_emitter_eval(self._h, mode, level, shape_index, len(q), q.ctypes.data, out.ctypes.data))
         return out
 
     def camera_rays(self, samples):

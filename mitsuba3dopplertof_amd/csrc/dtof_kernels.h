@@ -297,6 +297,12 @@ void launch_component(const ComponentArgs &a, const RenderParams &rp, hipStream_
 void launch_bsdf_eval_0(const uint8_t *scene, uint32_t shape_index, const float *in, float *out, uint32_t n, hipStream_t s);
 void launch_bsdf_eval_1(const uint8_t *scene, uint32_t shape_index, const float *in, float *out, uint32_t n, hipStream_t s);
 void launch_bsdf_eval_2(const uint8_t *scene, uint32_t shape_index, const float *in, float *out, uint32_t n, hipStream_t s);
+// The emitter side of a path vertex over arrays (dtof_emitter_eval; k_emitter_eval, dtof_shade.h), one launcher per file of shade kernels for the (AREA, MESH, SPEC)
+// levels of that file: 0 (F,F,0), 1 (T,F,0) and 6 (level 0 under kFactOneEmitter) plain; 2 (F,T,0), 3 (T,T,0) mesh; 4 (T,T,1) spec1; 5 (T,T,2) spec2
+void launch_emitter_eval_plain(const uint8_t *scene, int level, int mode, uint32_t index, float pmf, const float *in, float *out, uint32_t n, hipStream_t s);
+void launch_emitter_eval_mesh(const uint8_t *scene, int level, int mode, uint32_t index, float pmf, const float *in, float *out, uint32_t n, hipStream_t s);
+void launch_emitter_eval_spec1(const uint8_t *scene, int level, int mode, uint32_t index, float pmf, const float *in, float *out, uint32_t n, hipStream_t s);
+void launch_emitter_eval_spec2(const uint8_t *scene, int level, int mode, uint32_t index, float pmf, const float *in, float *out, uint32_t n, hipStream_t s);
 void launch_camera_rays(const RenderParams &rp, const float *in, float *out, uint32_t n, hipStream_t s);   // Sensor::sample_ray over arrays (known-answer entry)
 // Scene::ray_intersect / ray_test over arrays
 void launch_ray_query(const uint8_t *scene, const float *rays, float *out, int32_t *ids, float *uv4, uint32_t n, bool any, uint32_t stack_depth, hipStream_t s);

@@ -1471,6 +1471,58 @@ int dtof_bsdf_eval(dtof_scene *sc, uint32_t shape_index, uint32_t n, const float
     }
     return dtof_bsdf_eval_ex(sc, shape_index, 2, n, in29.empty() ? nullptr : in29.data(), out14);
 }
+int dtof_emitter_eval(dtof_scene *sc, int mode, int level, int32_t shape_or_minus1, uint32_t n, const float *in, float *out) {
+    return guarded([&] {
+        if (!sc || (n && (!in || !out))) throw std::runtime_error("null argument");
+        if (mode < 0 || mode > 2) throw std::runtime_error("dtof_emitter_eval: mode must be 0 (sample), 1 (hit) or 2 (miss)");
+        const BlobHeader *bh = (const BlobHeader *) sc->blob.data();
+        const DShape *shapes = (const DShape *) (sc->blob.data() + bh->off_shapes);
+        const DEmitter *emitters = (const DEmitter *) (sc->blob.data() + bh->off_emitters);
+        const SceneTraits t = scene_traits(*sc);
+        if (level == -1) level = t.has_spec ? 3 + t.has_spec : t.has_tris ? (t.surface_emitters ? 3 : 2) : (t.surface_emitters ? 1 : 0);   // what render_rows launches
+        if (level < 0 || level > 6) throw std::runtime_error("dtof_emitter_eval: level must be -1 or 0 .. 6");
+        const bool area = level == 1 || (level >= 3 && level != 6), mesh = level >= 2 && level != 6, spec = level == 4 || level == 5;
+        // the levels the render path could run on this scene (scene_traits, render_rows)
+        bool points_only = true, points_and_plain_rects = true, plain = true;
+        for (uint32_t i = 0; i < bh->n_emitters; ++i) {
+            const DEmitter &em = emitters[i];
+            points_only &= em.kind == EMITTER_POINT;
+            if (em.kind == EMITTER_AREA) {
+                if (em.shape >= bh->n_shapes) throw std::runtime_error("dtof_emitter_eval: an emitter's shape index is out of range");
+                points_and_plain_rects &= shapes[em.shape].kind == SHAPE_RECT && !shapes[em.shape].tex_radiance;
+                plain &= !shapes[em.shape].tex_radiance;
+            } else if (em.kind != EMITTER_POINT) points_and_plain_rects = plain = false;
+        }
+        if (!area && !spec && !points_only) throw std::runtime_error("dtof_emitter_eval: the kernels without area emitters run on scenes with point emitters only");
+        if (area && !mesh && !spec && !points_and_plain_rects) throw std::runtime_error("dtof_emitter_eval: the rectangle-only kernels run on point emitters and untextured rectangle lights only");
+        if (!spec && !plain) throw std::runtime_error("dtof_emitter_eval: spot, directional and environment emitters and textured radiance run in the SPEC kernels only");
+        if (level == 6 && bh->n_emitters != 1) throw std::runtime_error("dtof_emitter_eval: the one-emitter fact holds on scenes with exactly one emitter");
+        uint32_t index = 0;
+        if (mode == 0) {
+            if (bh->n_emitters == 0) throw std::runtime_error("dtof_emitter_eval: the scene has no emitter");
+        } else if (mode == 1) {
+            if (shape_or_minus1 < 0 || (uint32_t) shape_or_minus1 >= bh->n_shapes) throw std::runtime_error("dtof_emitter_eval: shape index out of range");
+            if (!(shapes[shape_or_minus1].flags & SF_EMITTER) || !area) throw std::runtime_error("dtof_emitter_eval: the shape carries no emitter");
+            index = (uint32_t) shape_or_minus1;
+        } else {
+            if (!t.has_env || !spec) throw std::runtime_error("dtof_emitter_eval: the scene has no environment");
+            index = t.env_index;
+        }
+        // the table searches index by their sample, and the sampler produces [0, 1 - 2^-24] only: nothing else reaches the device
+        const uint32_t n_in = mode == 0 ? 5 : mode == 1 ? 11 : 3, n_out = mode == 0 ? 14 : mode == 1 ? 5 : 4;
+        for (size_t i = 0; i < (size_t) n * n_in; ++i) if (!std::isfinite(in[i])) throw std::runtime_error("dtof_emitter_eval: a query holds a float that is not finite");
+        if (mode == 0) for (size_t i = 0; i < n; ++i) for (int k = 3; k < 5; ++k)
+            if (!(in[i * 5 + k] >= 0.f && in[i * 5 + k] < 1.f)) throw std::runtime_error("dtof_emitter_eval: a draw lies outside [0, 1)");
+        ensure_device(sc);
+        const float pmf = bh_emitters(*sc) ? 1.f / (float) bh_emitters(*sc) : 0.f;   // m_emitter_pmf, as make_params sets it
+        DevBuf<float> din, dout; din.ensure((size_t) n * n_in); dout.ensure((size_t) n * n_out);
+        HIP_CHECK(hipMemcpy(din.p, in, (size_t) n * n_in * 4, hipMemcpyHostToDevice));
+        (level == 4 ? launch_emitter_eval_spec1 : level == 5 ? launch_emitter_eval_spec2 : mesh ? launch_emitter_eval_mesh : launch_emitter_eval_plain)
+            (sc->d_blob.p, level, mode, index, pmf, din.p, dout.p, n, nullptr);
+        HIP_CHECK(hipGetLastError());
+        HIP_CHECK(hipMemcpy(out, dout.p, (size_t) n * n_out * 4, hipMemcpyDeviceToHost));
+    });
+}
 int dtof_camera_rays(dtof_scene *sc, uint32_t n, const float *samples4, float *out7) {
     return guarded([&] {
         if (!sc || (n && (!samples4 || !out7))) throw std::runtime_error("null argument");

@@ -307,6 +307,48 @@ void launch_bsdf_eval_spec(const uint8_t *scene, uint32_t shape_index, const flo
     if (n) hipLaunchKernelGGL(k_bsdf_eval<SPEC>, dim3(nblk(n)), dim3(kBlock), 0, s, scene, shape_index, in, out, n);
 }
 
+// The emitter side of a path vertex over arrays (dtof_emitter_eval): the functions of dtof_shading.h that k_shade<.., AREA, .., MESH, SPEC, .., FACTS> calls, as that
+// instantiation calls them (ONE_EMITTER = its kFactOneEmitter fact).  One thread per query, no LDS.  Each dtof_shade_*.hip file instantiates the launcher for the
+// (AREA, MESH, SPEC) combinations of its own shade kernels.
+//   mode 0  in 5: ref[3], e1, e2                          out 14: p[3], d[3], dist, pdf (* pmf), delta, weight[3] (* the pick's 1 / probability), usable, picked index
+//   mode 1  in 11: prev[3], hit[3], sh_n[3], u, v          out 5: dist, d[3], em_pdf                      (`index` = the hit shape; the previous lobe is not a delta)
+//   mode 2  in 3: the direction of the ray that left       out 4: em_pdf, value[3]                        (`index` = the environment emitter; SPEC only)
+template <bool AREA, bool MESH, int SPEC, bool ONE_EMITTER>
+__global__ void k_emitter_eval(const uint8_t *scene, int mode, uint32_t index, float pmf, const float *in, float *out, uint32_t n) {
+    uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const SceneView sv = make_view(scene);
+    if (mode == 0) {
+        const float *a = in + (size_t) i * 5;
+        const EmitterSample es = sample_emitter_direction<AREA, MESH, SPEC, ONE_EMITTER>(sv, mk(a[0], a[1], a[2]), a[3], a[4], pmf);
+        float *w = out + (size_t) i * 14;
+        w[0] = es.p.x; w[1] = es.p.y; w[2] = es.p.z; w[3] = es.d.x; w[4] = es.d.y; w[5] = es.d.z; w[6] = es.dist; w[7] = es.pdf; w[8] = es.delta ? 1.f : 0.f;
+        w[9] = es.weight.x; w[10] = es.weight.y; w[11] = es.weight.z; w[12] = es.usable ? 1.f : 0.f; w[13] = (float) es.index;
+    } else if (mode == 1) {
+        if constexpr (AREA) {
+            const float *a = in + (size_t) i * 11;
+            const EmitterHit eh = emitter_pdf_direction<MESH, SPEC>(sv, &sv.shapes[index], mk(a[3], a[4], a[5]), mk(a[6], a[7], a[8]), a[9], a[10], mk(a[0], a[1], a[2]), false, pmf);
+            float *w = out + (size_t) i * 5;
+            w[0] = eh.dist; w[1] = eh.d.x; w[2] = eh.d.y; w[3] = eh.d.z; w[4] = eh.pdf;
+        }
+    } else {
+        if constexpr (SPEC != 0) {   // the miss term of k_shade
+            const float *a = in + (size_t) i * 3;
+            const DEmitter &env = sv.emitters[index];
+            const bool is_map = env.kind == EMITTER_ENVMAP;
+            const V3 rd = mk(a[0], a[1], a[2]);
+            const float em_pdf = (is_map ? env_pdf_direction(sv.base, env, rd) : kInvFourPi) * pmf;
+            const V3 le = is_map ? env_eval(sv.base, env, rd) : mk(env.intensity[0], env.intensity[1], env.intensity[2]);
+            float *w = out + (size_t) i * 4;
+            w[0] = em_pdf; w[1] = le.x; w[2] = le.y; w[3] = le.z;
+        }
+    }
+}
+template <bool AREA, bool MESH, int SPEC, bool ONE_EMITTER = false>
+void launch_emitter_eval_level(const uint8_t *scene, int mode, uint32_t index, float pmf, const float *in, float *out, uint32_t n, hipStream_t s) {
+    if (n) hipLaunchKernelGGL((k_emitter_eval<AREA, MESH, SPEC, ONE_EMITTER>), dim3(nblk(n)), dim3(kBlock), 0, s, scene, mode, index, pmf, in, out, n);
+}
+
 // FUSED = false: the "split" pipeline -- shadow rays go to the shadow queue (k_shadow commits them) and the
 //                 continuation ray is traced by the next k_trace launch.
 // FUSED = true : one kernel per bounce -- the occlusion query and the closest-hit query of the continuation ray
@@ -686,24 +728,8 @@ __global__ __launch_bounds__(RESW ? RESW * 64 : kShadeBlock, RESW ? RESW / 4 : (
                 }
                 if (sh->flags & SF_EMITTER) {
                     float4 pb = depth > 0 ? (FIRST ? stb_reg : q.st_b[l]) : make_float4(0.f, 0.f, 0.f, 1.f);   // prev_si.p, prev_bsdf_pdf
-                    V3 rel = si.p - mk(pb.x, pb.y, pb.z);                      // DirectionSample(scene, si, prev_si), records.h:173-180
-                    float dist = norm(rel);
-                    V3 dsd = rel * rcp(dist);
-                    float em_pdf = 0.f;
-                    if (!prev_delta) {                                          // !prev_bsdf_delta: AreaLight::pdf_direction (area.cpp:161-180)
-                        float dp = dot(dsd, si.sh_n);   // ds.n = si.sh_frame.n (PositionSample(si), records.h:63-65)
-                        if (SPEC && dp < 0.f && sh->tex_radiance) {   // area.cpp:170-176: pdf_position of the texture at ds.uv = si.uv, through the parameterisation's |dp_du x dp_dv|
-                            V3 pp, pn; float su, sv_, area_norm;
-                            if (rect_eval_parameterization(*sh, si.u, si.v, pp, pn, su, sv_, area_norm))
-                                em_pdf = texture_pdf_position(sv, sh->tex_radiance << 4, si.u, si.v) * sqr(dist) / (area_norm * -dp) * pmf;
-                        } else
-                        if (dp < 0.f) {
-                            const float adp = fabsf(dp);
-                            const float pdf = MESH && sh->kind == SHAPE_SPHERE ? sphere_pdf_direction(*sh, mk(pb.x, pb.y, pb.z), dsd, si.sh_n, dist)
-                                                                               : sh->inv_area * (adp != 0.f ? (dist * dist) / adp : 0.f);
-                            em_pdf = pdf * pmf;
-                        }
-                    }
+                    // DirectionSample(scene, si, prev_si), records.h:173-180; !prev_bsdf_delta: AreaLight::pdf_direction (area.cpp:161-180)
+                    const float em_pdf = emitter_pdf_direction<MESH, SPEC>(sv, sh, si.p, si.sh_n, si.u, si.v, mk(pb.x, pb.y, pb.z), prev_delta, pmf).pdf;
                     float mis_bsdf = mis_weight(pb.w, em_pdf);
                     bool on = si.wi.z > 0.f && pb.w > 0.f;                       // AreaLight::eval (area.cpp:82-89), mask prev_bsdf_pdf > 0
                     V3 le = on ? mk(sh->radiance[0], sh->radiance[1], sh->radiance[2]) : mk(0, 0, 0);
@@ -741,100 +767,9 @@ __global__ __launch_bounds__(RESW ? RESW * 64 : kShadeBlock, RESW ? RESW / 4 : (
             bool active_em = active_next && (F_ONE_EMITTER || sv.n_emitters > 0) && (!SPEC || bsdf_is_smooth(sh->bsdf) || ((sh->flags & (SF_BLEND | SF_TWOSIDED2)) && bsdf_is_smooth(sv.shapes[sh->blend_other].bsdf)));   // a blend (a twosided of two BSDFs) has the flags of both
             V3 em_weight = mk(0, 0, 0), wo = mk(0, 0, 0); float ds_dist = 0.f, ds_pdf = 0.f; bool ds_delta = true;
             if (active_em) {
-                uint32_t ne = F_ONE_EMITTER ? 1u : sv.n_emitters, idx = 0; float em_w = 1.f, sx = e1;
-                if (ne > 1) { float scaled = e1 * (float) ne; idx = (uint32_t) scaled; if (idx > ne - 1) idx = ne - 1; em_w = (float) ne; sx = scaled - (float) idx; }
-                const DEmitter &em = sv.emitters[idx];
-                V3 dsp, dd; bool em_active = true;
-                if ((!AREA && !SPEC) || em.kind == EMITTER_POINT) {   // scenes without surface emitters that run the diffuse-only kernels have point lights only (render_rows)
-                    dsp = mk(em.pos[0], em.pos[1], em.pos[2]);
-                    dd = dsp - si.p;
-                    float dist2 = dot(dd, dd), inv_dist = rsqrt_(dist2);
-                    ds_dist = sqrtf(dist2);
-                    dd = dd * inv_dist;
-                    float id2 = sqr(inv_dist);
-                    em_weight = mk(em.intensity[0] * id2, em.intensity[1] * id2, em.intensity[2] * id2);
-                    ds_pdf = 1.f;
-                } else if (SPEC && em.kind == EMITTER_CONSTANT) {   // ConstantBackgroundEmitter::sample_direction (constant.cpp:118-148)
-                    dd = uniform_sphere(sx, e2);
-                    const float radius = fmax_(em.cutoff_angle, norm(si.p - mk(em.pos[0], em.pos[1], em.pos[2])));   // m_bsphere, enlarged to hold the reference point
-                    ds_dist = 2.f * radius;
-                    dsp = vfma(dd, ds_dist, si.p);
-                    ds_pdf = kInvFourPi; ds_delta = false;
-                    const float ip = rcp(ds_pdf);
-                    em_weight = mk(em.intensity[0] * ip, em.intensity[1] * ip, em.intensity[2] * ip);
-                } else if (SPEC && em.kind == EMITTER_DIRECTIONAL) {   // DirectionalEmitter::sample_direction (directional.cpp:148-176)
-                    const V3 dir = mk(em.to_local[0], em.to_local[1], em.to_local[2]);
-                    const float radius = fmax_(em.cutoff_angle, norm(si.p - mk(em.pos[0], em.pos[1], em.pos[2])));
-                    ds_dist = 2.f * radius;
-                    dsp = si.p - dir * ds_dist;
-                    dd = -dir;
-                    ds_pdf = 1.f;
-                    em_weight = mk(em.intensity[0], em.intensity[1], em.intensity[2]);
-                } else if (SPEC && em.kind == EMITTER_ENVMAP) {   // EnvironmentMapEmitter::sample_direction (envmap.cpp:363-406)
-                    env_sample_direction(sv.base, em, si.p, sx, e2, dd, ds_dist, ds_pdf, em_weight, em_active);
-                    dsp = si.p + dd * ds_dist;
-                    ds_delta = false;
-                } else if (SPEC && em.kind == EMITTER_SPOT) {   // SpotLight::sample_direction (spot.cpp:152-187), falloff_curve (:116-126)
-                    dsp = mk(em.pos[0], em.pos[1], em.pos[2]);
-                    dd = dsp - si.p;
-                    ds_dist = norm(dd);
-                    const float inv_dist = rcp(ds_dist);
-                    dd = dd * inv_dist;
-                    const V3 local = normalize(xf_vector(em.to_local, -dd));
-                    const float cos_theta = local.z;
-                    const float beam = cos_theta >= em.cos_beam ? 1.f : (em.cutoff_angle - acos_(cos_theta)) * em.inv_transition;
-                    const float falloff = cos_theta > em.cos_cutoff ? beam : 0.f;
-                    const float k = falloff * sqr(inv_dist);
-                    em_weight = falloff > 0.f ? mk(em.intensity[0] * k, em.intensity[1] * k, em.intensity[2] * k) : mk(0, 0, 0);
-                    ds_pdf = 1.f;
-                } else {
-                    const DShape &es = sv.shapes[em.shape];
-                    V3 en;
-                    if (SPEC && es.tex_radiance) {
-                        // AreaLight::sample_direction with a spatially varying radiance (area.cpp:129-153): the TEXTURE is sampled (Texture::sample_position), the shape maps the
-                        // uv to a point (Rectangle::eval_parameterization), the density goes from uv space to solid angle with |dp_du x dp_dv|
-                        float tu, tv, tpdf, su = 0.f, sv_ = 0.f, area_norm = 1.f;
-                        texture_sample_position(sv, es.tex_radiance << 4, sx, e2, tu, tv, tpdf);
-                        V3 pp = si.p; en = mk(0.f, 0.f, 1.f);
-                        const bool valid = tpdf != 0.f && rect_eval_parameterization(es, tu, tv, pp, en, su, sv_, area_norm);
-                        dsp = valid ? pp : si.p;
-                        dd = dsp - si.p;
-                        const float dist2 = dot(dd, dd);
-                        ds_dist = sqrtf(dist2);
-                        dd = dd * rcp(ds_dist);
-                        const float dp = dot(dd, en);
-                        em_active = valid && dp < 0.f;
-                        ds_pdf = em_active ? tpdf / area_norm * dist2 / -dp : 0.f;
-                        ds_delta = false;
-                        const V3 c = em_active ? texture_eval(sv, es.tex_radiance << 4, su, sv_) : mk(0, 0, 0);   // m_radiance->eval(si) / ds.pdf
-                        em_weight = em_active ? mk(c.x / ds_pdf, c.y / ds_pdf, c.z / ds_pdf) : mk(0, 0, 0);
-                    } else {
-                    if (MESH && es.kind == SHAPE_SPHERE) {   // Sphere overrides Shape::sample_direction
-                        sphere_sample_direction(es, si.p, sx, e2, dsp, en, dd, ds_dist, ds_pdf);
-                    } else {
-                        if (!MESH || es.kind == SHAPE_RECT) {
-                            dsp = xf_point(es.to_world, mk(sx * 2.f - 1.f, e2 * 2.f - 1.f, 0.f));
-                            en = mk(es.n[0], es.n[1], es.n[2]);
-                        } else if (es.kind == SHAPE_DISK) {   // Disk::sample_position (disk.cpp:158-177)
-                            float px, py; concentric_disk(sx, e2, px, py);
-                            dsp = xf_point(es.to_world, mk(px, py, 0.f));
-                            en = mk(es.n[0], es.n[1], es.n[2]);
-                        } else mesh_sample_position(sv, es, sx, e2, dsp, en);
-                        dd = dsp - si.p;
-                        float dist2 = dot(dd, dd);
-                        ds_dist = sqrtf(dist2);
-                        dd = dd * rcp(ds_dist);
-                        float dp = fabsf(dot(dd, en)), x = dist2 / dp;
-                        ds_pdf = es.inv_area * (isfinite(x) ? x : 0.f);
-                    }
-                    ds_delta = false;
-                    em_active = dot(dd, en) < 0.f && ds_pdf != 0.f;
-                    float ip = rcp(ds_pdf);
-                    em_weight = em_active ? mk(em.intensity[0] * ip, em.intensity[1] * ip, em.intensity[2] * ip) : mk(0, 0, 0);
-                    }
-                }
-                ds_pdf *= pmf; em_weight = em_weight * em_w;
-                active_em = ds_pdf != 0.f && em_active;
+                const EmitterSample es = sample_emitter_direction<AREA, MESH, SPEC, F_ONE_EMITTER>(sv, si.p, e1, e2, pmf);
+                const V3 dsp = es.p, dd = es.d;
+                em_weight = es.weight; ds_dist = es.dist; ds_pdf = es.pdf; ds_delta = es.delta; active_em = es.usable;
                 // Interaction::spawn_ray_to (interaction.h:141-149)
                 V3 so = offset_p(si, dsp - si.p);
                 V3 sd = dsp - so;

@@ -29,4 +29,11 @@ void launch_bsdf_eval_0(const uint8_t *scene, uint32_t shape_index, const float 
     launch_bsdf_eval_spec<0>(scene, shape_index, in, out, n, s);
 }
 
+// dtof_emitter_eval, levels 0 (no area emitters), 1 (area emitters) and 6 (level 0 under the kFactOneEmitter fact of the headline kernels) (k_emitter_eval in dtof_shade.h)
+void launch_emitter_eval_plain(const uint8_t *scene, int level, int mode, uint32_t index, float pmf, const float *in, float *out, uint32_t n, hipStream_t s) {
+    if (level == 1) launch_emitter_eval_level<true, false, 0>(scene, mode, index, pmf, in, out, n, s);
+    else if (level == 6) launch_emitter_eval_level<false, false, 0, true>(scene, mode, index, pmf, in, out, n, s);
+    else launch_emitter_eval_level<false, false, 0>(scene, mode, index, pmf, in, out, n, s);
+}
+
 }  // namespace dtof

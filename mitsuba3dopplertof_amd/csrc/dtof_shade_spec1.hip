@@ -12,4 +12,9 @@ void launch_bsdf_eval_1(const uint8_t *scene, uint32_t shape_index, const float 
     launch_bsdf_eval_spec<1>(scene, shape_index, in, out, n, s);
 }
 
+// dtof_emitter_eval, level 4 (k_emitter_eval in dtof_shade.h)
+void launch_emitter_eval_spec1(const uint8_t *scene, int level, int mode, uint32_t index, float pmf, const float *in, float *out, uint32_t n, hipStream_t s) {
+    launch_emitter_eval_level<true, true, 1>(scene, mode, index, pmf, in, out, n, s);
+}
+
 }  // namespace dtof

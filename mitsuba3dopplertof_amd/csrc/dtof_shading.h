@@ -613,4 +613,135 @@ DTOF_D void env_sample_direction(const uint8_t *base, const DEmitter &em, V3 ref
     weight = active ? mk(rad.x * ip, rad.y * ip, rad.z * ip) : mk(0, 0, 0);
 }
 
+// ---- the emitter side of a path vertex, as k_shade runs it and as dtof_emitter_eval runs it over arrays (k_emitter_eval, dtof_shade.h).  AREA, MESH, SPEC are the
+// kernel's own template arguments; ONE_EMITTER is its kFactOneEmitter fact (the scene has exactly one emitter: no pick).
+// Scene::sample_emitter_direction without the visibility test (scene.cpp:235-291 with sample_emitter :171-189; point.cpp:118-147; area.cpp:116-159 + shape.cpp:370-384 +
+// rectangle.cpp:152-166): the emitter pick from e1 with the reused sample, Emitter::sample_direction of the picked emitter for the reference point `ref`, then the
+// pick's probability in the density and its reciprocal in the weight.  `usable`: ds_pdf != 0 and the emitter faces `ref`.
+struct EmitterSample { V3 p, d, weight; float dist, pdf; bool delta, usable; uint32_t index; };
+template <bool AREA, bool MESH, int SPEC, bool ONE_EMITTER>
+DTOF_D EmitterSample sample_emitter_direction(const SceneView &sv, V3 ref, float e1, float e2, float pmf) {
+    V3 em_weight = mk(0, 0, 0); float ds_dist = 0.f, ds_pdf = 0.f; bool ds_delta = true;
+    uint32_t ne = ONE_EMITTER ? 1u : sv.n_emitters, idx = 0; float em_w = 1.f, sx = e1;
+    if (ne > 1) { float scaled = e1 * (float) ne; idx = (uint32_t) scaled; if (idx > ne - 1) idx = ne - 1; em_w = (float) ne; sx = scaled - (float) idx; }
+    const DEmitter &em = sv.emitters[idx];
+    V3 dsp, dd; bool em_active = true;
+    if ((!AREA && !SPEC) || em.kind == EMITTER_POINT) {   // scenes without surface emitters that run the diffuse-only kernels have point lights only (render_rows)
+        dsp = mk(em.pos[0], em.pos[1], em.pos[2]);
+        dd = dsp - ref;
+        float dist2 = dot(dd, dd), inv_dist = rsqrt_(dist2);
+        ds_dist = sqrtf(dist2);
+        dd = dd * inv_dist;
+        float id2 = sqr(inv_dist);
+        em_weight = mk(em.intensity[0] * id2, em.intensity[1] * id2, em.intensity[2] * id2);
+        ds_pdf = 1.f;
+    } else if (SPEC && em.kind == EMITTER_CONSTANT) {   // ConstantBackgroundEmitter::sample_direction (constant.cpp:118-148)
+        dd = uniform_sphere(sx, e2);
+        const float radius = fmax_(em.cutoff_angle, norm(ref - mk(em.pos[0], em.pos[1], em.pos[2])));   // m_bsphere, enlarged to hold the reference point
+        ds_dist = 2.f * radius;
+        dsp = vfma(dd, ds_dist, ref);
+        ds_pdf = kInvFourPi; ds_delta = false;
+        const float ip = rcp(ds_pdf);
+        em_weight = mk(em.intensity[0] * ip, em.intensity[1] * ip, em.intensity[2] * ip);
+    } else if (SPEC && em.kind == EMITTER_DIRECTIONAL) {   // DirectionalEmitter::sample_direction (directional.cpp:148-176)
+        const V3 dir = mk(em.to_local[0], em.to_local[1], em.to_local[2]);
+        const float radius = fmax_(em.cutoff_angle, norm(ref - mk(em.pos[0], em.pos[1], em.pos[2])));
+        ds_dist = 2.f * radius;
+        dsp = ref - dir * ds_dist;
+        dd = -dir;
+        ds_pdf = 1.f;
+        em_weight = mk(em.intensity[0], em.intensity[1], em.intensity[2]);
+    } else if (SPEC && em.kind == EMITTER_ENVMAP) {   // EnvironmentMapEmitter::sample_direction (envmap.cpp:363-406)
+        env_sample_direction(sv.base, em, ref, sx, e2, dd, ds_dist, ds_pdf, em_weight, em_active);
+        dsp = ref + dd * ds_dist;
+        ds_delta = false;
+    } else if (SPEC && em.kind == EMITTER_SPOT) {   // SpotLight::sample_direction (spot.cpp:152-187), falloff_curve (:116-126)
+        dsp = mk(em.pos[0], em.pos[1], em.pos[2]);
+        dd = dsp - ref;
+        ds_dist = norm(dd);
+        const float inv_dist = rcp(ds_dist);
+        dd = dd * inv_dist;
+        const V3 local = normalize(xf_vector(em.to_local, -dd));
+        const float cos_theta = local.z;
+        const float beam = cos_theta >= em.cos_beam ? 1.f : (em.cutoff_angle - acos_(cos_theta)) * em.inv_transition;
+        const float falloff = cos_theta > em.cos_cutoff ? beam : 0.f;
+        const float k = falloff * sqr(inv_dist);
+        em_weight = falloff > 0.f ? mk(em.intensity[0] * k, em.intensity[1] * k, em.intensity[2] * k) : mk(0, 0, 0);
+        ds_pdf = 1.f;
+    } else {
+        const DShape &es = sv.shapes[em.shape];
+        V3 en;
+        if (SPEC && es.tex_radiance) {
+            // AreaLight::sample_direction with a spatially varying radiance (area.cpp:129-153): the TEXTURE is sampled (Texture::sample_position), the shape maps the
+            // uv to a point (Rectangle::eval_parameterization), the density goes from uv space to solid angle with |dp_du x dp_dv|
+            float tu, tv, tpdf, su = 0.f, sv_ = 0.f, area_norm = 1.f;
+            texture_sample_position(sv, es.tex_radiance << 4, sx, e2, tu, tv, tpdf);
+            V3 pp = ref; en = mk(0.f, 0.f, 1.f);
+            const bool valid = tpdf != 0.f && rect_eval_parameterization(es, tu, tv, pp, en, su, sv_, area_norm);
+            dsp = valid ? pp : ref;
+            dd = dsp - ref;
+            const float dist2 = dot(dd, dd);
+            ds_dist = sqrtf(dist2);
+            dd = dd * rcp(ds_dist);
+            const float dp = dot(dd, en);
+            em_active = valid && dp < 0.f;
+            ds_pdf = em_active ? tpdf / area_norm * dist2 / -dp : 0.f;
+            ds_delta = false;
+            const V3 c = em_active ? texture_eval(sv, es.tex_radiance << 4, su, sv_) : mk(0, 0, 0);   // m_radiance->eval(si) / ds.pdf
+            em_weight = em_active ? mk(c.x / ds_pdf, c.y / ds_pdf, c.z / ds_pdf) : mk(0, 0, 0);
+        } else {
+        if (MESH && es.kind == SHAPE_SPHERE) {   // Sphere overrides Shape::sample_direction
+            sphere_sample_direction(es, ref, sx, e2, dsp, en, dd, ds_dist, ds_pdf);
+        } else {
+            if (!MESH || es.kind == SHAPE_RECT) {
+                dsp = xf_point(es.to_world, mk(sx * 2.f - 1.f, e2 * 2.f - 1.f, 0.f));
+                en = mk(es.n[0], es.n[1], es.n[2]);
+            } else if (es.kind == SHAPE_DISK) {   // Disk::sample_position (disk.cpp:158-177)
+                float px, py; concentric_disk(sx, e2, px, py);
+                dsp = xf_point(es.to_world, mk(px, py, 0.f));
+                en = mk(es.n[0], es.n[1], es.n[2]);
+            } else mesh_sample_position(sv, es, sx, e2, dsp, en);
+            dd = dsp - ref;
+            float dist2 = dot(dd, dd);
+            ds_dist = sqrtf(dist2);
+            dd = dd * rcp(ds_dist);
+            float dp = fabsf(dot(dd, en)), x = dist2 / dp;
+            ds_pdf = es.inv_area * (isfinite(x) ? x : 0.f);
+        }
+        ds_delta = false;
+        em_active = dot(dd, en) < 0.f && ds_pdf != 0.f;
+        float ip = rcp(ds_pdf);
+        em_weight = em_active ? mk(em.intensity[0] * ip, em.intensity[1] * ip, em.intensity[2] * ip) : mk(0, 0, 0);
+        }
+    }
+    ds_pdf *= pmf; em_weight = em_weight * em_w;
+    return EmitterSample{ dsp, dd, em_weight, ds_dist, ds_pdf, ds_delta, ds_pdf != 0.f && em_active, idx };
+}
+
+// The density of the emitter-hit term: DirectionSample(scene, si, prev_si) (records.h:173-180) of a hit at `p` on the emitting shape `sh` seen from the previous vertex
+// `prev`, and Scene::pdf_emitter_direction = AreaLight::pdf_direction (area.cpp:161-180) * pmf for it; 0 behind a delta lobe (!prev_bsdf_delta masks the call).
+struct EmitterHit { V3 d; float dist, pdf; };
+template <bool MESH, int SPEC>
+DTOF_D EmitterHit emitter_pdf_direction(const SceneView &sv, const DShape *sh, V3 p, V3 sh_n, float u, float v, V3 prev, bool prev_delta, float pmf) {
+    V3 rel = p - prev;
+    float dist = norm(rel);
+    V3 dsd = rel * rcp(dist);
+    float em_pdf = 0.f;
+    if (!prev_delta) {
+        float dp = dot(dsd, sh_n);   // ds.n = si.sh_frame.n (PositionSample(si), records.h:63-65)
+        if (SPEC && dp < 0.f && sh->tex_radiance) {   // area.cpp:170-176: pdf_position of the texture at ds.uv = si.uv, through the parameterisation's |dp_du x dp_dv|
+            V3 pp, pn; float su, sv_, area_norm;
+            if (rect_eval_parameterization(*sh, u, v, pp, pn, su, sv_, area_norm))
+                em_pdf = texture_pdf_position(sv, sh->tex_radiance << 4, u, v) * sqr(dist) / (area_norm * -dp) * pmf;
+        } else
+        if (dp < 0.f) {
+            const float adp = fabsf(dp);
+            const float pdf = MESH && sh->kind == SHAPE_SPHERE ? sphere_pdf_direction(*sh, prev, dsd, sh_n, dist)
+                                                               : sh->inv_area * (adp != 0.f ? (dist * dist) / adp : 0.f);
+            em_pdf = pdf * pmf;
+        }
+    }
+    return EmitterHit{ dsd, dist, em_pdf };
+}
+
 }  // namespace dtof

@@ -335,6 +335,25 @@ void     orc_kat_frame(const float *n, float *out6);
 int      orc_kat_ray_intersect(const orc_scene *sc, const float *o, const float *d, float time, float maxt, float *out25, int32_t *ids);
 void     orc_kat_bsdf(const orc_shape *sh, const float *wi, const float *wo, const float *s3, float *out13);
 void     orc_kat_bsdf_n(const orc_shape *sh, uint32_t n, const float *in29, float *out17);   /* ... over arrays, general uv and frame, with the lobe-choice thresholds */
+/* The emitter side of a path vertex over arrays: see dtof_oracle.c.  Behind the 14 / 5 output words of modes 0 / 1 come the values the chain compared (NaN: that
+ * compare did not run): */
+enum {
+    ORC_EMT_SCALED = 14,                        /* the pick: e1 * n_emitters, truncated to the index */
+    ORC_EMT_FACE = 15, ORC_EMT_FACE_V = 16,     /* mesh light: the picked face and s_y * area_sum, which the search compared with ... */
+    ORC_EMT_CDF_LO = 17, ORC_EMT_CDF_HI = 18,   /* ... cdf[face - 1] (< v) and cdf[face] (>= v); */
+    ORC_EMT_SY_LO = 19, ORC_EMT_SY_HI = 20,     /* the same two bounds divided by area_sum: in units of s_y */
+    ORC_EMT_ROW = 21, ORC_EMT_ROW_V = 22, ORC_EMT_ROW_LO = 23, ORC_EMT_ROW_HI = 24,   /* DiscreteDistribution2D: row, the scaled sample, marg_cdf[row - 1], marg_cdf[row] */
+    ORC_EMT_COL = 25, ORC_EMT_COL_V = 26, ORC_EMT_COL_LO = 27, ORC_EMT_COL_HI = 28,   /* ... column, the scaled sample, cond_cdf[col - 1], cond_cdf[col] */
+    ORC_EMT_HIER = 29,                          /* Hierarchical2D, levels 1 .. 3 (4 words each): sy * (r0 + r1), r0, sx * (c0 + c1), c0 (`>` picks the second half) */
+    ORC_EMT_COS_THETA = 41, ORC_EMT_COS_BEAM = 42, ORC_EMT_COS_CUTOFF = 43,             /* spot */
+    ORC_EMT_DC2 = 44, ORC_EMT_RADJ2 = 45, ORC_EMT_STM2 = 46,                          /* sphere: dc_2, sqr(radius_adj), sin_theta_max_2 (compared with 0.00068523) */
+    ORC_EMT_CELL = 47,                          /* Hierarchical2D: the index of the chosen cell in level 0 */
+    ORC_EMT_SAMPLE_DP = 48,                     /* area lights: dot(d, n) at the sampled point (`< 0` makes the sample usable) */
+    ORC_EMT_N0 = 49,
+    ORC_EMT_DP = 5, ORC_EMT_SIN_ALPHA = 6,      /* mode 1: dot(d, sh_n); the sphere's sin_alpha (compared with 0.99999994) */
+    ORC_EMT_N1 = 7, ORC_EMT_N2 = 4
+};
+void     orc_kat_emitter_n(const orc_scene *sc, int mode, int32_t index, uint32_t n, const float *in, float *out);
 void     orc_texture_eval(const orc_texture *tex, float u, float v, float *out3);
 float    orc_texture_eval_1(const orc_texture *tex, float u, float v);   /* Texture::eval_1: a 1-channel texel, the luminance of an RGB texel, the mean of a checkerboard colour */
 void     orc_kat_sphere_sample_direction(const orc_shape *sh, const float *ref, float s_x, float s_y, float *out11);

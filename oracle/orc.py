@@ -199,6 +199,8 @@ def lib():
         L.orc_kat_ray_intersect.argtypes = [C.POINTER(OrcScene), C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_void_p, C.c_void_p]
         L.orc_kat_bsdf.argtypes = [C.POINTER(OrcShape), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.orc_kat_bsdf_n.argtypes = [C.POINTER(OrcShape), C.c_uint32, C.c_void_p, C.c_void_p]
+        L.orc_kat_emitter_n.argtypes = [C.POINTER(OrcScene), C.c_int, C.c_int32, C.c_uint32, C.c_void_p, C.c_void_p]
+        L.orc_kat_emitter_sample.argtypes = [C.POINTER(OrcScene), C.c_int, C.c_void_p, C.c_float, C.c_float, C.c_void_p]
         L.orc_kat_sphere_sample_direction.argtypes = [C.POINTER(OrcShape), C.c_void_p, C.c_float, C.c_float, C.c_void_p]
         L.orc_kat_shape_area.restype = C.c_float
         L.orc_kat_shape_area.argtypes = [C.POINTER(OrcShape)]
