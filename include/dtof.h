@@ -292,6 +292,49 @@ int dtof_render_stripes_variants(dtof_scene *scene, uint32_t seed, uint32_t spp,
 int dtof_render_stripes_variants_async(dtof_scene *scene, uint32_t seed, uint32_t spp, int32_t first_row, int32_t stripe_rows, int32_t stripe_period,
                                        const dtof_modulation *variants, int n_variants, float *d_film_rgbw);
 
+/* ---------------------------------------------------------------- radial-velocity map
+ * The tail of a Doppler time-of-flight render -- the passes' mean, the ToF images and the velocity map of the homodyne / heterodyne ratio -- on the device, from films
+ * that never leave it.  The results are, bit for bit, what numpy computes on the host from the same films (NaNs are NaNs there and here; payloads are not specified):
+ *   sum     acc = img if acc is None else acc + img over the developed passes, float32 (render_multi_pass, doppler_tutorials/src/program_runner.py:11-31)
+ *   ToF     mean = sum / (float) n_passes; ((0.2126f r + 0.7152f g) + 0.0722f b) * (float) exposure_time, no fused multiply-add
+ *           (to_tof_image on a float32 image, doppler_tutorials/src/utils/image_utils.py:20-31)
+ *   map     in double: ratio = |hom| > 0 ? het / hom : 0; conf = |hom| + 1e-5 * 0.0015 (that exposure time is hard-coded there); the ratios' conf-weighted mean,
+ *           summed from 0.0 in pair order; clipped to [-1, 0.999] (a NaN stays a NaN, as with np.clip); dw = (ratio * (1 / T)) / (ratio - 1);
+ *           v = -(((0.5 dw) 3e8) / (w_g 1e6))   (calc_velocity_from_homo_hetero / _heteros, image_utils.py:140-199)
+ * exposure_time (seconds) and w_g_mhz are the DOUBLES the tutorials hand to those functions; they are not read from the integrator, whose `time` is rounded to float32.
+ * Every entry below fails with DTOF_ERR_INVALID before anything is enqueued or written: null arguments, n_pairs / n_offsets outside [1, 16], a plane index outside the
+ * sum, n_passes = 0, an exposure_time or w_g_mhz that is not finite or not > 0, negative sizes, film or sum pointers that are not 16- / 4-byte aligned. */
+
+/* HDRFilm::develop (src/films/hdrfilm.cpp:305-406) of `planes` RGBW film planes of n_pixels * 4 floats, `plane_stride_floats` apart (0 = dense; else a multiple of 4
+ * and >= n_pixels * 4), stored into (first != 0: the first pass assigns, so that a -0.0 survives) or added to (first == 0) the dense running sum
+ * d_rgb_sum[planes][n_pixels][3] (render_multi_pass, doppler_tutorials/src/program_runner.py:11-31), the input of dtof_velocity_map_async
+ * (doppler_tutorials/src/utils/image_utils.py:20-31,140-199).  Enqueued on the scene's stream without a host wait. */
+int dtof_develop_accumulate_async(dtof_scene *scene, const float *d_film_rgbw, int32_t planes, uint64_t plane_stride_floats, float *d_rgb_sum, int64_t n_pixels,
+                                  int first);
+/* The mean of render_multi_pass (doppler_tutorials/src/program_runner.py:11-31: acc / n_passes), then to_tof_image + calc_velocity_from_homo_heteros
+ * (doppler_tutorials/src/utils/image_utils.py:20-31,140-199) over the sum of n_passes passes.  d_rgb_sum holds 2 * n_pairs planes
+ * [2 * n_pairs][n_pixels][3]; pair k is (homodyne_planes[k], heterodyne_planes[k]), indices into those planes (host arrays, read before the call returns).
+ * d_velocity[n_pixels] double: the combined map; d_velocity_pairs_or_null[n_pairs][n_pixels] double: the map of every pair alone (calc_velocity_from_homo_hetero,
+ * image_utils.py:140-168); d_tof_or_null[2 * n_pairs][n_pixels] float32: the ToF image of every plane.  Enqueued on the scene's stream without a host wait. */
+int dtof_velocity_map_async(dtof_scene *scene, const float *d_rgb_sum, int n_pairs, const int32_t *homodyne_planes, const int32_t *heterodyne_planes,
+                            uint32_t n_passes, double exposure_time, double w_g_mhz, int64_t n_pixels, float *d_tof_or_null, double *d_velocity_pairs_or_null,
+                            double *d_velocity);
+/* The films one traversal renders for a velocity map: offsets are grouped two per traversal, group (o0, o1) as the variants (0, o0), (0, o1), (1, o0), (1, o1) -- the
+ * homodyne films (hetero_frequency 0), then the heterodyne ones (1) -- so a pair never straddles two traversals; an odd last offset is the group (0, o), (1, o).
+ * Writes the 2 * n_offsets variants of all groups in order (no device needed). */
+int dtof_velocity_map_variants(const float *offsets, int n_offsets, dtof_modulation *out_variants);
+/* The whole loop of the tutorials' velocity-map experiment (render_multi_pass, doppler_tutorials/src/program_runner.py:11-31, per film;
+ * doppler_tutorials/src/utils/image_utils.py:20-31,140-199) into host buffers:
+ * per group of two offsets (dtof_velocity_map_variants) and pass i = 0 .. n_passes - 1, the library's own film is cleared, rendered with seed i and `spp` samples per
+ * pixel (0 = the sampler's sample count) like dtof_render_rows_variants_async, and accumulated; then one reconstruction, one copy per requested output and ONE host
+ * synchronisation (pipelines that need a host wait inside a frame keep theirs).  out_velocity[H * W] double; out_velocity_pairs_or_null[n_offsets][H * W] double, in
+ * the order of `offsets`; out_tof_or_null[2 * n_offsets][H * W] float32, plane k the ToF image of variant k of dtof_velocity_map_variants.  `stats` (may be NULL)
+ * sums the traversals like dtof_async_collect: n_paths = W * H * spp * n_passes * ceil(n_offsets / 2), n_bounces and n_shadow_rays stay 0.  The alpha film of an
+ * rgba scene is rendered and ignored.  The caller's dtof_scene_set_film_layout state is neither read nor changed.  An integrator other than `dopplertofpath` fails
+ * with DTOF_ERR_INVALID. */
+int dtof_render_velocity_map(dtof_scene *scene, uint32_t n_passes, uint32_t spp, const float *offsets, int n_offsets, double exposure_time, double w_g_mhz,
+                             double *out_velocity, double *out_velocity_pairs_or_null, float *out_tof_or_null, dtof_render_stats *stats);
+
 /* Integrator::cancel / should_stop (include/mitsuba/render/integrator.h:96-109). */
 void dtof_cancel(dtof_scene *scene);
 /* First-bounce launches of this scene, since it was loaded, that ran a kernel compiled with the frame plan's constants (dtof_render_stats::n_plan_facts_launches): the

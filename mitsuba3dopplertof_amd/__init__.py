@@ -16,7 +16,7 @@ import os
 import numpy as np
 
 __all__ = ["load_file", "load_string", "load_dict", "Scene", "Integrator", "Sampler", "DtofError", "render",
-           "render_multi_pass", "to_tof_image", "lib_path", "ETimeSampling"]
+           "render_multi_pass", "to_tof_image", "lib_path", "ETimeSampling", "velocity_map_variants"]
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB = None
@@ -151,7 +151,11 @@ def _lib():
                        ("dtof_render_rows_variants", rows + [C.POINTER(_Stats)]), ("dtof_render_rows_variants_async", rows),
                        ("dtof_render_stripes_variants", stripes + [C.POINTER(_Stats)]), ("dtof_render_stripes_variants_async", stripes),
                        ("dtof_sample_lanes_variants", [vp, C.c_uint32, C.c_uint32, vp, C.c_int, C.c_uint64, C.c_uint64, vp, vp, vp]),
-                       ("dtof_emitter_eval", [vp, C.c_int, C.c_int, C.c_int32, C.c_uint32, vp, vp])):
+                       ("dtof_emitter_eval", [vp, C.c_int, C.c_int, C.c_int32, C.c_uint32, vp, vp]),
+                       ("dtof_develop_accumulate_async", [vp, vp, C.c_int32, C.c_uint64, vp, C.c_int64, C.c_int]),
+                       ("dtof_velocity_map_async", [vp, vp, C.c_int, vp, vp, C.c_uint32, C.c_double, C.c_double, C.c_int64, vp, vp, vp]),
+                       ("dtof_velocity_map_variants", [vp, C.c_int, vp]),
+                       ("dtof_render_velocity_map", [vp, C.c_uint32, C.c_uint32, vp, C.c_int, C.c_double, C.c_double, vp, vp, vp, C.POINTER(_Stats)])):
         if hasattr(L, name):   # a DTOF_LIB build from before the variants (A/B timing against an older commit) loads; calling what it lacks still raises
             getattr(L, name).argtypes = args
     _LIB = L
@@ -220,6 +224,18 @@ def _batch_args(offsets, variants):
         o = np.ascontiguousarray(offsets, dtype=np.float32)
         return o, o.ctypes.data, len(o), False
     return None, None, 0, False
+
+
+MAX_VELOCITY_OFFSETS = 16   # offsets one velocity map combines (kMaxVelocityPairs)
+
+
+def velocity_map_variants(offsets):
+    """The (hetero_frequency, hetero_offset) films of a velocity map in the order they are rendered (dtof_velocity_map_variants): offsets are grouped two per
+    traversal, group (o0, o1) as (0, o0), (0, o1), (1, o0), (1, o1), so a homodyne / heterodyne pair never straddles two traversals -> (2 * len(offsets), 2) float32"""
+    o = np.ascontiguousarray(offsets, dtype=np.float32).reshape(-1)
+    out = np.zeros((2 * len(o), 2), np.float32)
+    _check(_lib().dtof_velocity_map_variants(o.ctypes.data, len(o), out.ctypes.data))
+    return out
 
 
 class Scene:
@@ -348,6 +364,42 @@ class Scene:
 
     def develop_async(self, d_film_ptr, d_rgb_ptr, n_pixels):
         _check(_lib().dtof_develop_async(self._h, d_film_ptr, d_rgb_ptr, n_pixels))
+
+    def develop_accumulate_async(self, d_film_ptr, planes, d_rgb_sum_ptr, n_pixels, first, plane_stride_floats=0):
+        """enqueue rgb / W of `planes` RGBW film planes into (first) or onto the dense float32 sum [planes][n_pixels][3] of a multi-pass render (dtof_develop_accumulate_async)"""
+        _check(_lib().dtof_develop_accumulate_async(self._h, d_film_ptr, int(planes), int(plane_stride_floats), d_rgb_sum_ptr, int(n_pixels), int(bool(first))))
+
+    def velocity_map_async(self, d_rgb_sum_ptr, homodyne_planes, heterodyne_planes, n_passes, n_pixels, d_velocity_ptr, exposure_time=0.0015, w_g=30,
+                           d_tof_ptr=None, d_velocity_pairs_ptr=None):
+        """enqueue the velocity map of the sum of `n_passes` passes (dtof_velocity_map_async): pair k is planes (homodyne_planes[k], heterodyne_planes[k]) of the 2 * n_pairs
+        planes of the sum; d_velocity [n_pixels] float64, optionally d_velocity_pairs [n_pairs][n_pixels] float64 and d_tof [2 * n_pairs][n_pixels] float32"""
+        hom, het = np.ascontiguousarray(homodyne_planes, dtype=np.int32).reshape(-1), np.ascontiguousarray(heterodyne_planes, dtype=np.int32).reshape(-1)
+        if len(hom) != len(het):
+            raise DtofError("as many homodyne as heterodyne planes make the pairs")
+        _check(_lib().dtof_velocity_map_async(self._h, d_rgb_sum_ptr, len(hom), hom.ctypes.data, het.ctypes.data, int(n_passes), float(exposure_time), float(w_g),
+                                              int(n_pixels), d_tof_ptr, d_velocity_pairs_ptr, d_velocity_ptr))
+
+    def render_velocity_map(self, n_passes, spp, offsets=(0.0, 0.25), exposure_time=0.0015, w_g=30, pairs=False):
+        """The radial-velocity map of `n_passes` passes (seeds 0 .. n_passes - 1) of `spp` samples, reconstructed on the device (dtof_render_velocity_map): every two
+        offsets share one traversal per pass, their films never leave the GPU.  Returns (velocity (H, W) float64, {"homodyne": [...], "heterodyne": [...]} float32 ToF
+        images in the order of `offsets`) and, with pairs=True, the maps of every offset alone (len(offsets), H, W) float64 -- the values numpy computes from the same
+        films with harness.calc_velocity_from_homo_heteros / _hetero.  last_stats sums the traversals."""
+        off = np.ascontiguousarray([float(o) for o in offsets], dtype=np.float32)
+        n = len(off)
+        w, h = self.size
+        st = _Stats()
+        v, tof = np.zeros((h, w), np.float64), np.zeros((2 * n, h, w), np.float32)
+        per_pair = np.zeros((n, h, w), np.float64) if pairs else None
+        _check(_lib().dtof_render_velocity_map(self._h, int(n_passes), int(spp), off.ctypes.data, n, float(exposure_time), float(w_g), v.ctypes.data,
+                                               per_pair.ctypes.data if pairs else None, tof.ctypes.data, C.byref(st)))
+        self.last_stats = st.as_dict()
+        homo, hetero = [], []
+        for g in range(0, n, 2):   # the planes of a group: its homodyne films, then its heterodyne films (velocity_map_variants)
+            k = min(2, n - g)
+            homo += [tof[2 * g + j] for j in range(k)]
+            hetero += [tof[2 * g + k + j] for j in range(k)]
+        films = {"homodyne": homo, "heterodyne": hetero}
+        return (v, films, per_pair) if pairs else (v, films)
 
     def collect(self, max_frames=4096):
         """wait for the frames enqueued by render_rows_async -> (summed stats dict, per-frame GPU milliseconds)"""

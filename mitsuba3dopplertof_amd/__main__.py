@@ -3,6 +3,8 @@ plugins this library implements:
 
     python -m mitsuba3dopplertof_amd scene.xml [-D key=value ...] [-o out.exr|.npy|.pfm] [--spp N] [--seed S]
                                                [--offsets 0,0.25,0.5,0.75] [-v]
+    python -m mitsuba3dopplertof_amd scene.xml --velocity-map 0,0.25 [--w-g 30 --exposure-time 0.0015] [--spp N] [-o out.npy]
+        the radial-velocity map of the scene's dopplertofpath integrator (float64 .npy), reconstructed on the GPU: passes of min(1024, N) samples, seeds 0, 1, ...
     python -m torch.distributed.run --nproc-per-node G --master-addr 127.0.0.1 -m mitsuba3dopplertof_amd scene.xml ...
         one process per GPU: the pixel rows are sharded across the G ranks, rank 0 gathers and writes the image
 """
@@ -14,7 +16,7 @@ import time
 import numpy as np
 
 
-def main(argv=None):
+def parser():
     ap = argparse.ArgumentParser(prog="python -m mitsuba3dopplertof_amd", description=__doc__.split("\n\n")[0])
     ap.add_argument("scene")
     ap.add_argument("-D", "--define", action="append", default=[], metavar="key=value",
@@ -26,8 +28,53 @@ def main(argv=None):
     ap.add_argument("--stripes", type=int, default=0, metavar="ROWS",
                     help="multi-GPU runs: interleave stripes of ROWS pixel rows across the ranks (load balance) instead of one contiguous band per rank")
     ap.add_argument("-m", "--mode", default="hip_rgb", help="accepted for command-line compatibility (only hip_rgb exists)")
+    ap.add_argument("--velocity-map", default=None, metavar="OFFSETS",
+                    help="comma separated hetero_offset values: write the radial-velocity map of their homodyne / heterodyne films (float64 .npy) instead of an image")
+    ap.add_argument("--w-g", type=float, default=30.0, help="--velocity-map: illumination frequency in MHz")
+    ap.add_argument("--exposure-time", type=float, default=0.0015, help="--velocity-map: exposure time in seconds")
     ap.add_argument("-v", "--verbose", action="store_true")
+    return ap
+
+
+def check_velocity_map_args(ap, args):
+    """what --velocity-map cannot be combined with, refused before the scene is loaded"""
+    if int(os.environ.get("WORLD_SIZE", "1")) > 1:
+        ap.error("--velocity-map is a single-GPU feature")
+    if args.offsets is not None:
+        ap.error("--velocity-map takes its own offsets: do not combine it with --offsets")
+    if args.seed != 0:
+        ap.error("--velocity-map renders the seeds 0, 1, ... of its passes: --seed does not apply")
+    if args.output is not None and not args.output.lower().endswith(".npy"):
+        ap.error("--velocity-map writes a float64 .npy file")
+    try:
+        [float(x) for x in args.velocity_map.split(",")]
+    except ValueError:
+        ap.error("--velocity-map expects comma separated numbers")
+
+
+def velocity_map(args, scene):
+    """--velocity-map: the passes of harness._passes (the sampler's sample count when --spp is 0), one traversal per two offsets and pass, everything behind the film
+    splat on the GPU (Scene.render_velocity_map)"""
+    from mitsuba3dopplertof_amd.harness import _passes
+    offsets = [float(x) for x in args.velocity_map.split(",")]
+    out = args.output or os.path.splitext(args.scene)[0] + "_velocity.npy"
+    single, n_pass = _passes(args.spp or scene.info()["sample_count"])
+    t0 = time.time()
+    v, _films = scene.render_velocity_map(n_pass, single, offsets, exposure_time=args.exposure_time, w_g=args.w_g)
+    dt = time.time() - t0
+    os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+    np.save(out, v)
+    if args.verbose:
+        st = scene.last_stats
+        print("Velocity map finished. (took %.1f ms, %d passes of %d spp, %s)" % (dt * 1e3, n_pass, single, st))
+    return 0
+
+
+def main(argv=None):
+    ap = parser()
     args = ap.parse_args(argv)
+    if args.velocity_map is not None:
+        check_velocity_map_args(ap, args)
     import mitsuba3dopplertof_amd as mi
     from mitsuba3dopplertof_amd.io import write_image
     defines = {}
@@ -38,6 +85,8 @@ def main(argv=None):
         defines[k] = v
     try:
         scene = mi.load_file(args.scene, **defines)
+        if args.velocity_map is not None:
+            return velocity_map(args, scene)
         t0 = time.time()
         offsets = [float(x) for x in args.offsets.split(",")] if args.offsets else None
         world = int(os.environ.get("WORLD_SIZE", "1"))

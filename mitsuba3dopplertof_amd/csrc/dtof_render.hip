@@ -8,6 +8,7 @@
 // sampler.cpp:115-134 / correlated.cpp:38-64).
 #include "../../include/dtof.h"
 #include "dtof_kernels.h"
+#include "dtof_reconstruct.h"
 #include "dtof_scene.h"
 #include "dtof_math.h"
 #include <atomic>
@@ -98,6 +99,7 @@ struct dtof_scene {
     DevBuf<uint8_t> d_blob; bool uploaded = false;
     Workspace ws;
     DevBuf<float> d_film, d_rgb;
+    DevBuf<float> d_vm_sum, d_vm_tof; DevBuf<double> d_vm_maps;   // dtof_render_velocity_map: the passes' sum, the ToF images, the per-pair maps and the combined map
     // the caller's device film as declared with dtof_scene_set_film_layout (0 = not declared: colour planes only, W * H * 4 apart)
     int32_t film_planes = 0; uint64_t film_plane_stride = 0;
     DevBuf<unsigned long long> d_sums;       // [batch][2*kMaxIter] per-iteration totals (survivors, shadow rays)
@@ -1123,6 +1125,17 @@ int dtof_develop_async(dtof_scene *sc, const float *d_film, float *d_rgb, int64_
         HIP_CHECK(hipGetLastError());
     });
 }
+// one finished deferred frame added to a statistics block (its stream has been waited for); returns the frame's duration
+static float add_deferred_frame(dtof_render_stats *sum, const dtof_scene::DeferredFrame &f) {
+    float t = 0; HIP_CHECK(hipEventElapsedTime(&t, f.ev0, f.ev1));
+    sum->ms_total += t;
+    sum->ms_generate += stage_ms(f.ev[kStageGenerate]); sum->ms_trace += stage_ms(f.ev[kStageTrace]); sum->ms_first += stage_ms(f.ev[kStageFirst]);
+    sum->ms_shade += stage_ms(f.ev[kStageShade]) + stage_ms(f.ev[kStageFirst]); sum->ms_shadow += stage_ms(f.ev[kStageShadow]); sum->ms_splat += stage_ms(f.ev[kStageSplat]);
+    sum->n_paths += f.counters.n_paths; sum->n_batches += f.counters.n_batches;
+    sum->n_launches_trace += f.counters.n_launches_trace; sum->n_launches_shade += f.counters.n_launches_shade; sum->n_launches_shadow += f.counters.n_launches_shadow;
+    sum->n_launches_first += f.counters.n_launches_first; sum->n_inline_iterations += f.counters.n_inline_iterations; sum->n_fused_splat_launches += f.counters.n_fused_splat_launches; sum->n_plan_facts_launches += f.counters.n_plan_facts_launches;
+    return t;
+}
 int dtof_async_collect(dtof_scene *sc, dtof_render_stats *sum, double *frame_ms, uint32_t capacity, uint32_t *n_frames) {
     return guarded([&] {
         if (!sc || !sum || !n_frames) throw std::runtime_error("null argument");
@@ -1132,17 +1145,134 @@ int dtof_async_collect(dtof_scene *sc, dtof_render_stats *sum, double *frame_ms,
         *n_frames = (uint32_t) sc->deferred.size();
         uint32_t i = 0;
         for (auto &f : sc->deferred) {
-            float t = 0; HIP_CHECK(hipEventElapsedTime(&t, f.ev0, f.ev1));
+            const float t = add_deferred_frame(sum, f);
             if (frame_ms && i < capacity) frame_ms[i] = t;
             ++i;
-            sum->ms_total += t;
-            sum->ms_generate += stage_ms(f.ev[kStageGenerate]); sum->ms_trace += stage_ms(f.ev[kStageTrace]); sum->ms_first += stage_ms(f.ev[kStageFirst]);
-            sum->ms_shade += stage_ms(f.ev[kStageShade]) + stage_ms(f.ev[kStageFirst]); sum->ms_shadow += stage_ms(f.ev[kStageShadow]); sum->ms_splat += stage_ms(f.ev[kStageSplat]);
-            sum->n_paths += f.counters.n_paths; sum->n_batches += f.counters.n_batches;
-            sum->n_launches_trace += f.counters.n_launches_trace; sum->n_launches_shade += f.counters.n_launches_shade; sum->n_launches_shadow += f.counters.n_launches_shadow;
-            sum->n_launches_first += f.counters.n_launches_first; sum->n_inline_iterations += f.counters.n_inline_iterations; sum->n_fused_splat_launches += f.counters.n_fused_splat_launches; sum->n_plan_facts_launches += f.counters.n_plan_facts_launches;
         }
         sc->deferred.clear(); sc->events_used = 0;
+    });
+}
+
+// ---------------------------------------------------------------- radial-velocity map (dtof_reconstruct.hip)
+// The checks the three entries share, made before a device is touched: a refused call enqueues and writes nothing.
+static void check_velocity_scalars(uint32_t n_passes, double exposure_time, double w_g_mhz) {
+    if (n_passes == 0) throw std::runtime_error("n_passes must be at least 1");
+    if (!std::isfinite(exposure_time) || !(exposure_time > 0)) throw std::runtime_error("exposure_time must be finite and > 0");
+    if (!std::isfinite(w_g_mhz) || !(w_g_mhz > 0)) throw std::runtime_error("w_g_mhz must be finite and > 0");
+}
+static void check_grid(int64_t n_pixels) {   // one lane per pixel in blocks of 256: the block count is a 32-bit grid dimension
+    if (n_pixels < 0) throw std::runtime_error("negative pixel count");
+    if (n_pixels > (int64_t) 0x7fffffff * 256) throw std::runtime_error("too many pixels for one launch");
+}
+static VelocityMapArgs velocity_args(int n_pairs, const int32_t *hom, const int32_t *het, uint32_t n_passes, double exposure_time, double w_g_mhz) {
+    VelocityMapArgs a; memset(&a, 0, sizeof a);
+    a.n_pairs = n_pairs;
+    for (int k = 0; k < n_pairs; ++k) {
+        if (hom[k] < 0 || hom[k] >= 2 * n_pairs || het[k] < 0 || het[k] >= 2 * n_pairs)
+            throw std::runtime_error("pair " + std::to_string(k) + ": plane index outside the " + std::to_string(2 * n_pairs) + " planes of the sum");
+        a.hom[k] = hom[k]; a.het[k] = het[k];
+    }
+    a.n_passes = (float) n_passes; a.exposure_time = (float) exposure_time;
+    a.inv_time = 1.0 / exposure_time; a.w_g_hz = w_g_mhz * 1e6; a.conf_floor = 1e-5 * 0.0015;   // in double, once, as Python forms them
+    return a;
+}
+
+int dtof_develop_accumulate_async(dtof_scene *sc, const float *d_film, int32_t planes, uint64_t plane_stride_floats, float *d_rgb_sum, int64_t n_pixels, int first) {
+    return guarded([&] {
+        if (!sc || !d_film || !d_rgb_sum) throw std::runtime_error("null argument");
+        if (planes < 1 || planes > 65535) throw std::runtime_error("the film must have between 1 and 65535 planes");
+        check_grid(n_pixels);
+        if (plane_stride_floats != 0 && (plane_stride_floats % 4 != 0 || plane_stride_floats < (uint64_t) n_pixels * 4))
+            throw std::runtime_error("plane stride must be a multiple of 4 floats and at least n_pixels * 4");
+        if ((uintptr_t) d_film % 16 != 0 || (uintptr_t) d_rgb_sum % 4 != 0) throw std::runtime_error("the film must be 16-byte aligned, the sum 4-byte aligned");
+        ensure_device(sc);
+        launch_develop_accumulate(d_film, planes, plane_stride_floats, d_rgb_sum, n_pixels, first != 0, sc->stream);
+        HIP_CHECK(hipGetLastError());
+    });
+}
+int dtof_velocity_map_async(dtof_scene *sc, const float *d_rgb_sum, int n_pairs, const int32_t *homodyne_planes, const int32_t *heterodyne_planes, uint32_t n_passes,
+                            double exposure_time, double w_g_mhz, int64_t n_pixels, float *d_tof, double *d_velocity_pairs, double *d_velocity) {
+    return guarded([&] {
+        if (!sc || !d_rgb_sum || !homodyne_planes || !heterodyne_planes || !d_velocity) throw std::runtime_error("null argument");
+        if (n_pairs < 1 || n_pairs > kMaxVelocityPairs) throw std::runtime_error("between 1 and 16 (homodyne, heterodyne) pairs can be combined");
+        check_velocity_scalars(n_passes, exposure_time, w_g_mhz);
+        check_grid(n_pixels);
+        if ((uintptr_t) d_rgb_sum % 4 != 0 || (uintptr_t) d_tof % 4 != 0 || (uintptr_t) d_velocity_pairs % 8 != 0 || (uintptr_t) d_velocity % 8 != 0)
+            throw std::runtime_error("misaligned buffer");
+        const VelocityMapArgs a = velocity_args(n_pairs, homodyne_planes, heterodyne_planes, n_passes, exposure_time, w_g_mhz);
+        ensure_device(sc);
+        launch_velocity_map(d_rgb_sum, a, n_pixels, d_tof, d_velocity_pairs, d_velocity, sc->stream);
+        HIP_CHECK(hipGetLastError());
+    });
+}
+int dtof_velocity_map_variants(const float *offsets, int n_offsets, dtof_modulation *out_variants) {
+    return guarded([&] {
+        if (!offsets || !out_variants) throw std::runtime_error("null argument");
+        if (n_offsets < 1 || n_offsets > kMaxVelocityPairs) throw std::runtime_error("between 1 and 16 offsets make a velocity map");
+        for (int g = 0; g < n_offsets; g += 2) {   // a homodyne / heterodyne pair never straddles two traversals
+            const int n = std::min(2, n_offsets - g);
+            for (int j = 0; j < n; ++j) {
+                out_variants[2 * g + j] = dtof_modulation { 0.f, offsets[g + j] };
+                out_variants[2 * g + n + j] = dtof_modulation { 1.f, offsets[g + j] };
+            }
+        }
+    });
+}
+int dtof_render_velocity_map(dtof_scene *sc, uint32_t n_passes, uint32_t spp, const float *offsets, int n_offsets, double exposure_time, double w_g_mhz,
+                             double *out_velocity, double *out_velocity_pairs, float *out_tof, dtof_render_stats *stats) {
+    return guarded([&] {
+        if (!sc || !offsets || !out_velocity) throw std::runtime_error("null argument");
+        if (n_offsets < 1 || n_offsets > kMaxVelocityPairs) throw std::runtime_error("between 1 and 16 offsets make a velocity map");
+        check_velocity_scalars(n_passes, exposure_time, w_g_mhz);
+        if (sc->pp.integrator != INTEGRATOR_DOPPLER) throw std::runtime_error("modulation offsets only apply to the dopplertofpath integrator");
+        if (!sc->host.has_sensor) throw std::runtime_error("the scene does not contain a sensor");
+        dtof_modulation variants[2 * kMaxVelocityPairs];
+        if (dtof_velocity_map_variants(offsets, n_offsets, variants) != DTOF_OK) throw std::runtime_error(g_last_error);
+        int32_t hom[kMaxVelocityPairs], het[kMaxVelocityPairs];   // offset j of group g = j / 2: its films lie behind the 4 * g planes of the full groups before it
+        for (int j = 0; j < n_offsets; ++j) {
+            const int g = j / 2, n = std::min(2, n_offsets - 2 * g);
+            hom[j] = 4 * g + j % 2; het[j] = 4 * g + n + j % 2;
+        }
+        const VelocityMapArgs a = velocity_args(n_offsets, hom, het, n_passes, exposure_time, w_g_mhz);
+        ensure_device(sc);
+        sc->stop = false;
+        const HostSensor &se = sc->host.sensor;
+        const size_t px = (size_t) se.crop_w * se.crop_h;
+        const int alpha = se.alpha ? 1 : 0;
+        sc->d_film.ensure(px * 4 * (kMaxOffsets + alpha));   // the library's own film: the caller's declared layout is not consulted
+        sc->d_vm_sum.ensure(px * 3 * 2 * n_offsets); sc->d_vm_tof.ensure(px * 2 * n_offsets); sc->d_vm_maps.ensure(px * (n_offsets + 1));
+        const hipStream_t s = sc->stream;
+        const size_t first_frame = sc->deferred.size();   // frames the caller has not collected yet stay his
+        try {
+            for (int g = 0; g < n_offsets; g += 2) {
+                const int films = 2 * std::min(2, n_offsets - g);
+                for (uint32_t pass = 0; pass < n_passes; ++pass) {
+                    HIP_CHECK(hipMemsetAsync(sc->d_film.p, 0, px * 4 * (films + alpha) * sizeof(float), s));
+                    dtof_render_stats frame;
+                    RenderRequest rq; rq.seed = pass; rq.spp = spp; rq.row_begin = 0; rq.row_end = se.crop_h; rq.film = sc->d_film.p; rq.film_stride = px * 4;
+                    rq.deferred = true; rq.stats = &frame;
+                    set_variants(rq, variants + 2 * g, films);
+                    render_rows(sc, rq);
+                    launch_develop_accumulate(sc->d_film.p, films, 0, sc->d_vm_sum.p + px * 3 * 2 * g, (int64_t) px, pass == 0, s);   // the alpha plane behind them is left out
+                }
+            }
+            double *d_pairs = sc->d_vm_maps.p + px;
+            launch_velocity_map(sc->d_vm_sum.p, a, (int64_t) px, out_tof ? sc->d_vm_tof.p : nullptr, out_velocity_pairs ? d_pairs : nullptr, sc->d_vm_maps.p, s);
+            HIP_CHECK(hipGetLastError());
+            HIP_CHECK(hipMemcpyAsync(out_velocity, sc->d_vm_maps.p, px * sizeof(double), hipMemcpyDeviceToHost, s));
+            if (out_velocity_pairs) HIP_CHECK(hipMemcpyAsync(out_velocity_pairs, d_pairs, px * n_offsets * sizeof(double), hipMemcpyDeviceToHost, s));
+            if (out_tof) HIP_CHECK(hipMemcpyAsync(out_tof, sc->d_vm_tof.p, px * 2 * n_offsets * sizeof(float), hipMemcpyDeviceToHost, s));
+            HIP_CHECK(hipStreamSynchronize(s));
+            dtof_render_stats sum; memset(&sum, 0, sizeof sum);
+            for (size_t i = first_frame; i < sc->deferred.size(); ++i) add_deferred_frame(&sum, sc->deferred[i]);
+            if (stats) *stats = sum;
+        } catch (...) {   // the frames of this call leave the list either way (their events go back to the pool once no frame is in flight)
+            if (sc->deferred.size() > first_frame) { (void) hipStreamSynchronize(s); sc->deferred.resize(first_frame); }
+            if (sc->deferred.empty()) sc->events_used = 0;
+            throw;
+        }
+        sc->deferred.resize(first_frame);
+        if (sc->deferred.empty()) sc->events_used = 0;
     });
 }
 

@@ -109,6 +109,19 @@ def run_scene_velocity_map(scene, total_spp=1024, offsets=(0.0, 0.25), **integra
     return calc_velocity_from_homo_heteros(homo, hetero, exposure_time, w_g), {"homodyne": homo, "heterodyne": hetero}
 
 
+def run_scene_velocity_map_device(scene, total_spp=1024, offsets=(0.0, 0.25), **integrator_kwargs):
+    """run_scene_velocity_map with everything behind the film splat on the GPU (Scene.render_velocity_map): the same integrator, passes, seeds and traversals, but the
+    films are developed, averaged and turned into the map by two kernels and only the results cross to the host.  Same return value; the map is bit for bit what
+    calc_velocity_from_homo_heteros makes of the returned ToF images."""
+    single, n_pass = _passes(total_spp)
+    integrator_kwargs = dict(integrator_kwargs)
+    integrator_kwargs.pop("hetero_offset", None)
+    integrator_kwargs.pop("hetero_frequency", None)
+    scene.set_integrator(doppler_integrator_dict(hetero_frequency=0.0, hetero_offset=0.0, **integrator_kwargs))
+    exposure_time, w_g = integrator_kwargs.get("exposure_time", 0.0015), integrator_kwargs.get("w_g", 30)
+    return scene.render_velocity_map(n_pass, single, [float(o) for o in offsets], exposure_time, w_g)
+
+
 def run_scene_velocity(scene, total_spp=1024, output_file=None):
     single, _ = _passes(total_spp)
     img = render_multi_pass(scene, load_dict({"type": "velocity"}), total_spp, single)
