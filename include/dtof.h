@@ -335,6 +335,41 @@ int dtof_velocity_map_variants(const float *offsets, int n_offsets, dtof_modulat
 int dtof_render_velocity_map(dtof_scene *scene, uint32_t n_passes, uint32_t spp, const float *offsets, int n_offsets, double exposure_time, double w_g_mhz,
                              double *out_velocity, double *out_velocity_pairs_or_null, float *out_tof_or_null, dtof_render_stats *stats);
 
+/* ---------------------------------------------------------------- float64 film (opt-in)
+ * A Doppler ToF image is a sum of large terms of both signs, and a float32 film adds them in whatever order the atomics arrive: pixels that cancel to a small fraction
+ * of their terms differ from run to run and from the order-independent value of the film.  The entries below render into a film of DOUBLES.  Every splat
+ * term is still the float32 product ImageBlock::put forms (src/render/imageblock.cpp:414-531: value * (wx * wy), wx * wy for the weight channel; the box filter adds
+ * the value itself and 1) -- it is converted to double and only double additions follow; HDRFilm::develop (src/films/hdrfilm.cpp:305-406) is
+ * (float) (sum / (W == 0 ? 1 : W)) with the division in double.  Nothing else differs from the float32 entries: same lanes, same samplers, same kernels up to the splat
+ * (the first-bounce kernel never splats into this film: dtof_render_stats::n_fused_splat_launches stays 0).  A film plane is crop_height * crop_width * 4 doubles
+ * (R, G, B, W); plane k is variant k, the alpha film of an rgba scene lies behind the colour planes.  Refusals are those of the float32 entries (null arguments, more
+ * than four variants, variants under an integrator other than `dopplertofpath`, a film layout too small for the call): DTOF_ERR_INVALID before any device call. */
+
+/* dtof_render_variants with the library's own float64 film (ImageBlock::put, src/render/imageblock.cpp:414-531, and HDRFilm::develop, src/films/hdrfilm.cpp:305-406,
+ * with a double accumulator -- the accumulator type is all that differs).  n_variants == 0: the integrator's own pair, one plane.  out_images: n_variants developed
+ * images (rgb, or rgba for an rgba film); out_films_or_null: the raw film, n_variants (+ 1 for rgba: the alpha film) planes of crop_height * crop_width * 4 doubles. */
+int dtof_render_variants_f64(dtof_scene *scene, uint32_t seed, uint32_t spp, const dtof_modulation *variants, int n_variants,
+                             float *out_images, double *out_films_or_null, dtof_render_stats *stats);
+/* dtof_render_rows_variants into the caller's float64 DEVICE film (ImageBlock::put, src/render/imageblock.cpp:414-531; develop it with dtof_develop_f64_async,
+ * src/films/hdrfilm.cpp:305-406 -- the accumulator type is all that differs).  The layout is an argument of the call, not state of the scene: `planes` planes,
+ * `plane_stride_doubles` apart (0 = dense; else a multiple of 4 and at least one film row).  Fewer planes than the call writes (n_variants, + 1 for an rgba scene),
+ * or -- when it writes more than one -- a stride smaller than the film rows it can reach (its rows and the filter's halo, see dtof_scene_set_film_layout) fails with
+ * DTOF_ERR_INVALID before anything is launched.  The film must be 8-byte aligned and zeroed by the caller; the call accumulates and waits for the stream. */
+int dtof_render_rows_variants_f64(dtof_scene *scene, uint32_t seed, uint32_t spp, int32_t row_begin, int32_t row_end,
+                                  const dtof_modulation *variants, int n_variants, double *d_film64_rgbw, int32_t planes, uint64_t plane_stride_doubles,
+                                  dtof_render_stats *stats);
+/* dtof_develop_async of a float64 film plane (HDRFilm::develop, src/films/hdrfilm.cpp:305-406, of what ImageBlock::put, src/render/imageblock.cpp:414-531, summed in
+ * double -- the accumulator type is all that differs): d_rgb[n_pixels][3] = (float) (RGB / (W == 0 ? 1 : W)), the division in double.  Enqueued on the scene's stream. */
+int dtof_develop_f64_async(dtof_scene *scene, const double *d_film64_rgbw, float *d_rgb, int64_t n_pixels);
+/* ... of an rgba film (dtof_develop_rgba; src/films/hdrfilm.cpp:305-406 over the sums of src/render/imageblock.cpp:414-531 in double -- the accumulator type is all
+ * that differs): (R, G, B) / W of the colour plane and A / W of the alpha plane.  d_rgba is 16-byte aligned. */
+int dtof_develop_rgba_f64_async(dtof_scene *scene, const double *d_film64_rgbw, const double *d_alpha_film64, float *d_rgba, int64_t n_pixels);
+/* dtof_render_velocity_map over the library's own float64 film: the same groups, passes, seeds and outputs, but every pass is splatted in double
+ * (src/render/imageblock.cpp:414-531) and developed in double, rounded to float once (src/films/hdrfilm.cpp:305-406), before it enters the same float32 running sum --
+ * the accumulator type is all that differs.  The map is, bit for bit, what numpy computes from the images of dtof_render_variants_f64 with the same seeds. */
+int dtof_render_velocity_map_f64(dtof_scene *scene, uint32_t n_passes, uint32_t spp, const float *offsets, int n_offsets, double exposure_time, double w_g_mhz,
+                                 double *out_velocity, double *out_velocity_pairs_or_null, float *out_tof_or_null, dtof_render_stats *stats);
+
 /* Integrator::cancel / should_stop (include/mitsuba/render/integrator.h:96-109). */
 void dtof_cancel(dtof_scene *scene);
 /* First-bounce launches of this scene, since it was loaded, that ran a kernel compiled with the frame plan's constants (dtof_render_stats::n_plan_facts_launches): the

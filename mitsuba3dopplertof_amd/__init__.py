@@ -155,7 +155,11 @@ def _lib():
                        ("dtof_develop_accumulate_async", [vp, vp, C.c_int32, C.c_uint64, vp, C.c_int64, C.c_int]),
                        ("dtof_velocity_map_async", [vp, vp, C.c_int, vp, vp, C.c_uint32, C.c_double, C.c_double, C.c_int64, vp, vp, vp]),
                        ("dtof_velocity_map_variants", [vp, C.c_int, vp]),
-                       ("dtof_render_velocity_map", [vp, C.c_uint32, C.c_uint32, vp, C.c_int, C.c_double, C.c_double, vp, vp, vp, C.POINTER(_Stats)])):
+                       ("dtof_render_velocity_map", [vp, C.c_uint32, C.c_uint32, vp, C.c_int, C.c_double, C.c_double, vp, vp, vp, C.POINTER(_Stats)]),
+                       ("dtof_render_velocity_map_f64", [vp, C.c_uint32, C.c_uint32, vp, C.c_int, C.c_double, C.c_double, vp, vp, vp, C.POINTER(_Stats)]),
+                       ("dtof_render_variants_f64", [vp, C.c_uint32, C.c_uint32, vp, C.c_int, vp, vp, C.POINTER(_Stats)]),
+                       ("dtof_render_rows_variants_f64", rows[:-1] + [vp, C.c_int32, C.c_uint64, C.POINTER(_Stats)]),
+                       ("dtof_develop_f64_async", [vp, vp, vp, C.c_int64]), ("dtof_develop_rgba_f64_async", [vp, vp, vp, vp, C.c_int64])):
         if hasattr(L, name):   # a DTOF_LIB build from before the variants (A/B timing against an older commit) loads; calling what it lacks still raises
             getattr(L, name).argtypes = args
     _LIB = L
@@ -226,6 +230,16 @@ def _batch_args(offsets, variants):
     return None, None, 0, False
 
 
+FILMS = ("float32", "float64")   # the film's accumulator: float32 atomics (the default), or the opt-in float64 film (dtof_film64.hip)
+
+
+def _film64(film):
+    """the `film=` argument of the render calls -> whether it names the float64 film; anything but the two names is refused"""
+    if film not in FILMS:
+        raise DtofError('film must be "float32" or "float64", not %r' % (film,))
+    return film == "float64"
+
+
 MAX_VELOCITY_OFFSETS = 16   # offsets one velocity map combines (kMaxVelocityPairs)
 
 
@@ -287,12 +301,22 @@ class Scene:
     def set_sampler(self, props):
         _check(_lib().dtof_scene_set_sampler(self._h, *_plugin_args(props)))
 
-    def render(self, seed=0, spp=0, offsets=None, sensor=0, variants=None):
+    def render(self, seed=0, spp=0, offsets=None, sensor=0, variants=None, film="float32"):
         """Developed image (H, W, 3) float32 -- (H, W, 4) for an rgba film; with `offsets` (list of hetero_offset values) -> (K, H, W, 3 | 4).
         `variants`: list of (hetero_frequency, hetero_offset) pairs -> (K, H, W, 3 | 4), image k that of an integrator carrying pair k; every four of them
-        share one traversal (dtof_render_variants), last_stats then sums the traversals."""
+        share one traversal (dtof_render_variants), last_stats then sums the traversals.
+        film="float64": the same images from a film accumulated and developed in double (dtof_render_variants_f64); offsets are then variants at the integrator's
+        own frequency, every four of them one traversal."""
         if offsets is not None and variants is not None:
             raise DtofError("pass either offsets or variants, not both")
+        if _film64(film):
+            if sensor != 0:
+                raise DtofError("Scene::render(): sensor index %d is out of bounds!" % sensor)
+            if offsets is not None:
+                f = self.info()["hetero_frequency"]
+                variants = [(f, float(o)) for o in np.ascontiguousarray(offsets, dtype=np.float32).reshape(-1)]
+            images, _ = self._render_f64(seed, spp, variants, False)
+            return images[0] if variants is None else images
         w, h = self.size
         st = _Stats()
         ch = 4 if self.info()["has_alpha"] else 3
@@ -316,6 +340,33 @@ class Scene:
             _check(_lib().dtof_render_offsets(self._h, seed, spp, off.ctypes.data, len(off), out.ctypes.data, C.byref(st)))
         self.last_stats = st.as_dict()
         return out
+
+    def _render_f64(self, seed, spp, variants, want_films):
+        """(images (K, H, W, 3 | 4), films (planes, H, W, 4) float64 or None) through dtof_render_variants_f64, four variants per traversal; None: the integrator's own pair"""
+        w, h = self.size
+        alpha = 1 if self.info()["has_alpha"] else 0
+        var = None if variants is None else _variant_array(variants)
+        k = 1 if var is None else len(var)
+        if want_films and k > MAX_VARIANTS:
+            raise DtofError("at most 4 modulation variants can be batched per traversal")
+        images = np.zeros((k, h, w, 3 + alpha), np.float32)
+        films = np.zeros((k + alpha, h, w, 4), np.float64) if want_films else None
+        st, total = _Stats(), None
+        for g in range(0, k, MAX_VARIANTS):
+            group = None if var is None else np.ascontiguousarray(var[g:g + MAX_VARIANTS])
+            part = images[g:g + MAX_VARIANTS]
+            _check(_lib().dtof_render_variants_f64(self._h, seed, spp, None if group is None else group.ctypes.data, 0 if group is None else len(group),
+                                                   part.ctypes.data, films.ctypes.data if want_films else None, C.byref(st)))
+            d = st.as_dict()
+            total = d if total is None else {key: total[key] + d[key] for key in d}
+        self.last_stats = total
+        return images, films
+
+    def render_film64(self, seed=0, spp=0, variants=None):
+        """One traversal into the float64 film (dtof_render_variants_f64) -> (images (K, H, W, 3 | 4) float32, films (K, H, W, 4) float64 -- one more plane, the alpha
+        film, behind the K colour planes of an rgba scene).  The images are the films developed in double: (float) (RGB / (W == 0 ? 1 : W)).  `variants`: up to four
+        (hetero_frequency, hetero_offset) pairs; None: the integrator's own pair (K = 1)."""
+        return self._render_f64(seed, spp, variants, True)
 
     def set_film_layout(self, planes, plane_stride_floats=0):
         """Declare the caller's device film for render_rows / render_stripes (dtof_scene_set_film_layout): `planes` RGBW planes, `plane_stride_floats` apart (0 = dense
@@ -343,6 +394,23 @@ class Scene:
         _check(fn(self._h, seed, spp, row_begin, row_end, ptr, n, d_film_ptr, C.byref(st)))
         self.last_stats = st.as_dict()
         return self.last_stats
+
+    def render_rows_f64(self, d_film_ptr, seed, spp, row_begin, row_end, variants=None, planes=None, plane_stride_doubles=0):
+        """render_rows into a float64 DEVICE film (dtof_render_rows_variants_f64): `planes` RGBW planes of doubles (default: film_planes() of the call), `plane_stride_doubles`
+        apart (0 = dense H * W * 4).  The layout belongs to the call: set_film_layout is neither read nor changed."""
+        st = _Stats()
+        keep, ptr, n, _ = _batch_args(None, variants)
+        planes = self.film_planes(n) if planes is None else int(planes)
+        _check(_lib().dtof_render_rows_variants_f64(self._h, seed, spp, row_begin, row_end, ptr, n, d_film_ptr, planes, int(plane_stride_doubles), C.byref(st)))
+        self.last_stats = st.as_dict()
+        return self.last_stats
+
+    def develop_f64_async(self, d_film_ptr, d_rgb_ptr, n_pixels, d_alpha_film_ptr=None):
+        """enqueue the develop of one float64 film plane (dtof_develop_f64_async); with the alpha plane of an rgba film: rgba (dtof_develop_rgba_f64_async)"""
+        if d_alpha_film_ptr is None:
+            _check(_lib().dtof_develop_f64_async(self._h, d_film_ptr, d_rgb_ptr, n_pixels))
+        else:
+            _check(_lib().dtof_develop_rgba_f64_async(self._h, d_film_ptr, d_alpha_film_ptr, d_rgb_ptr, n_pixels))
 
     def render_rows_async(self, d_film_ptr, seed, spp, row_begin, row_end, offsets=None, variants=None):
         """enqueue one frame on the scene's stream without waiting for it (dtof_render_rows_async / _variants_async); collect() waits and returns the timings"""
@@ -379,19 +447,21 @@ class Scene:
         _check(_lib().dtof_velocity_map_async(self._h, d_rgb_sum_ptr, len(hom), hom.ctypes.data, het.ctypes.data, int(n_passes), float(exposure_time), float(w_g),
                                               int(n_pixels), d_tof_ptr, d_velocity_pairs_ptr, d_velocity_ptr))
 
-    def render_velocity_map(self, n_passes, spp, offsets=(0.0, 0.25), exposure_time=0.0015, w_g=30, pairs=False):
+    def render_velocity_map(self, n_passes, spp, offsets=(0.0, 0.25), exposure_time=0.0015, w_g=30, pairs=False, film="float32"):
         """The radial-velocity map of `n_passes` passes (seeds 0 .. n_passes - 1) of `spp` samples, reconstructed on the device (dtof_render_velocity_map): every two
         offsets share one traversal per pass, their films never leave the GPU.  Returns (velocity (H, W) float64, {"homodyne": [...], "heterodyne": [...]} float32 ToF
         images in the order of `offsets`) and, with pairs=True, the maps of every offset alone (len(offsets), H, W) float64 -- the values numpy computes from the same
-        films with harness.calc_velocity_from_homo_heteros / _hetero.  last_stats sums the traversals."""
+        films with harness.calc_velocity_from_homo_heteros / _hetero.  last_stats sums the traversals.  film="float64": every pass is splatted and developed in double
+        (dtof_render_velocity_map_f64) -- the films numpy has to be given are then those of render(..., film="float64")."""
+        entry = _lib().dtof_render_velocity_map_f64 if _film64(film) else _lib().dtof_render_velocity_map
         off = np.ascontiguousarray([float(o) for o in offsets], dtype=np.float32)
         n = len(off)
         w, h = self.size
         st = _Stats()
         v, tof = np.zeros((h, w), np.float64), np.zeros((2 * n, h, w), np.float32)
         per_pair = np.zeros((n, h, w), np.float64) if pairs else None
-        _check(_lib().dtof_render_velocity_map(self._h, int(n_passes), int(spp), off.ctypes.data, n, float(exposure_time), float(w_g), v.ctypes.data,
-                                               per_pair.ctypes.data if pairs else None, tof.ctypes.data, C.byref(st)))
+        _check(entry(self._h, int(n_passes), int(spp), off.ctypes.data, n, float(exposure_time), float(w_g), v.ctypes.data,
+                     per_pair.ctypes.data if pairs else None, tof.ctypes.data, C.byref(st)))
         self.last_stats = st.as_dict()
         homo, hetero = [], []
         for g in range(0, n, 2):   # the planes of a group: its homodyne films, then its heterodyne films (velocity_map_variants)
@@ -529,12 +599,13 @@ class Integrator:
             _LIB.dtof_integrator_destroy(self._h)
             self._h = C.c_void_p()
 
-    def render(self, scene, seed=0, spp=0, sensor=0, offsets=None, variants=None):
+    def render(self, scene, seed=0, spp=0, sensor=0, offsets=None, variants=None, film="float32"):
+        """film="float64": the float64 film of Scene.render; like the batched forms it makes this integrator the scene's"""
         if offsets is not None and variants is not None:
             raise DtofError("pass either offsets or variants, not both")
-        if offsets is not None or variants is not None:
+        if offsets is not None or variants is not None or _film64(film):
             scene.set_integrator(self.props)
-            return scene.render(seed=seed, spp=spp, sensor=sensor, offsets=offsets, variants=variants)
+            return scene.render(seed=seed, spp=spp, sensor=sensor, offsets=offsets, variants=variants, film=film)
         w, h = scene.size
         st, out = _Stats(), np.zeros((h, w, 4 if scene.info()["has_alpha"] else 3), np.float32)
         _check(_lib().dtof_integrator_render(self._h, None, scene._h, sensor, seed, spp, out.ctypes.data, C.byref(st)))
@@ -570,14 +641,15 @@ def render(scene, spp=0, seed=0, integrator=None, sensor=0):
     return scene.render(seed=seed, spp=spp, sensor=sensor)
 
 
-def render_multi_pass(scene, integrator, total_spp, single_pass_spp=1024, show_progress=False):
+def render_multi_pass(scene, integrator, total_spp, single_pass_spp=1024, show_progress=False, film="float32"):
     """doppler_tutorials/src/program_runner.py:11-31: mean of renders with seeds 0..n-1, each of
-    min(single_pass_spp, total_spp) samples per pixel."""
+    min(single_pass_spp, total_spp) samples per pixel.  film="float64": every pass through the float64 film."""
     single = min(single_pass_spp, total_spp)
     n_pass = max(total_spp // single, 1)
+    film_kw = dict(film=film) if _film64(film) else {}
     acc = None
     for i in range(n_pass):
-        img = integrator.render(scene, seed=i, spp=single).astype(np.float32)
+        img = integrator.render(scene, seed=i, spp=single, **film_kw).astype(np.float32)
         acc = img if acc is None else acc + img
     return acc / np.float32(n_pass)
 

@@ -2,7 +2,7 @@
 plugins this library implements:
 
     python -m mitsuba3dopplertof_amd scene.xml [-D key=value ...] [-o out.exr|.npy|.pfm] [--spp N] [--seed S]
-                                               [--offsets 0,0.25,0.5,0.75] [-v]
+                                               [--offsets 0,0.25,0.5,0.75] [--film float64] [-v]
     python -m mitsuba3dopplertof_amd scene.xml --velocity-map 0,0.25 [--w-g 30 --exposure-time 0.0015] [--spp N] [-o out.npy]
         the radial-velocity map of the scene's dopplertofpath integrator (float64 .npy), reconstructed on the GPU: passes of min(1024, N) samples, seeds 0, 1, ...
     python -m torch.distributed.run --nproc-per-node G --master-addr 127.0.0.1 -m mitsuba3dopplertof_amd scene.xml ...
@@ -32,8 +32,16 @@ def parser():
                     help="comma separated hetero_offset values: write the radial-velocity map of their homodyne / heterodyne films (float64 .npy) instead of an image")
     ap.add_argument("--w-g", type=float, default=30.0, help="--velocity-map: illumination frequency in MHz")
     ap.add_argument("--exposure-time", type=float, default=0.0015, help="--velocity-map: exposure time in seconds")
+    ap.add_argument("--film", default="float32", choices=("float32", "float64"),
+                    help="the film's accumulator: float64 sums the splat in double on the GPU (order-independent images and velocity maps; single GPU)")
     ap.add_argument("-v", "--verbose", action="store_true")
     return ap
+
+
+def check_film_args(ap, args):
+    """what --film float64 cannot be combined with, refused before the scene is loaded: the multi-GPU film exchange (and dtof-render --gpus) is float32"""
+    if args.film == "float64" and (int(os.environ.get("WORLD_SIZE", "1")) > 1 or args.stripes > 0):
+        ap.error("--film float64 is a single-GPU feature: the sharded and striped multi-GPU renders (and dtof-render --gpus) keep the float32 film")
 
 
 def check_velocity_map_args(ap, args):
@@ -60,7 +68,7 @@ def velocity_map(args, scene):
     out = args.output or os.path.splitext(args.scene)[0] + "_velocity.npy"
     single, n_pass = _passes(args.spp or scene.info()["sample_count"])
     t0 = time.time()
-    v, _films = scene.render_velocity_map(n_pass, single, offsets, exposure_time=args.exposure_time, w_g=args.w_g)
+    v, _films = scene.render_velocity_map(n_pass, single, offsets, exposure_time=args.exposure_time, w_g=args.w_g, film=args.film)
     dt = time.time() - t0
     os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
     np.save(out, v)
@@ -73,6 +81,7 @@ def velocity_map(args, scene):
 def main(argv=None):
     ap = parser()
     args = ap.parse_args(argv)
+    check_film_args(ap, args)
     if args.velocity_map is not None:
         check_velocity_map_args(ap, args)
     import mitsuba3dopplertof_amd as mi
@@ -106,7 +115,7 @@ def main(argv=None):
             if img is None:
                 return 0
         else:
-            img = scene.render(seed=args.seed, spp=args.spp, offsets=offsets)
+            img = scene.render(seed=args.seed, spp=args.spp, offsets=offsets, film=args.film)
         dt = time.time() - t0
     except mi.DtofError as e:
         print("Error: %s" % e, file=sys.stderr)

@@ -1,0 +1,176 @@
+// dtof_film64.hip -- the float64 film: the splat of ImageBlock::put (src/render/imageblock.cpp:414-531) with a double accumulator, and HDRFilm::develop
+// (src/films/hdrfilm.cpp:305-406) taken in double.
+//   splat_f64              : every term is the float32 product the float32 film adds (w = wx * wy, value * w, w for the weight channel; the box filter adds the value
+//                            itself and 1.f -- splat_lane, dtof_device.h); the term is converted to double and from there on only double additions happen.  A double
+//                            sum of a few thousand float32 terms carries ~29 spare bits, so the order of the additions no longer reaches the developed float.
+//   develop_f64 / rgba_f64 : (float) (sum / (w == 0 ? 1 : w)), the division in double
+//   develop_accumulate_f64 : the same develop, then the float32 running sum of k_develop_accumulate (dtof_reconstruct.hip)
+// Compiled with -ffp-contract=off like every kernel here.
+#include "dtof_device.h"
+#include "dtof_film64.h"
+
+namespace dtof {
+
+namespace {
+constexpr int kFilm64Block = 256;
+constexpr int kRunCells = 5;   // footprints up to 5 x 5 pixels (radius <= 2.5) are reduced per run of lanes; wider ones take one atomic per lane and cell
+
+// The lanes of a wave are cut into RUNS of consecutive lanes that share a footprint anchor (the samples of a pixel are consecutive lanes and almost always share it;
+// a run ends at the wave's end, at a lane of another pixel, or at a sample whose position rounded into the next pixel).  dist: the lane's distance from the head of
+// its run; steps: bit s set = some lane of the wave has dist >= 2^s (wave-uniform).  -> in the LAST lane of every run the sum of v over the run, added up as a
+// Hillis-Steele tree: after step s a lane holds the sum of the min(2^(s+1), dist + 1) values that end at it.
+DTOF_D double run_sum(double v, uint32_t dist, uint32_t steps) {
+#pragma unroll
+    for (uint32_t s = 0; s < 6; ++s)
+        if ((steps >> s) & 1u) {
+            const double up = __shfl_up(v, 1u << s);
+            if (dist >= (1u << s)) v = v + up;
+        }
+    return v;
+}
+
+// a[j] of a small register array for a wave-uniform j, without indexing the registers
+template <int N> DTOF_D float pick(const float (&a)[N], int j) {
+    float v = a[0];
+#pragma unroll
+    for (int m = 1; m < N; ++m) v = j == m ? a[m] : v;
+    return v;
+}
+
+DTOF_D void add_f64(double *p, double v) { if (v != 0.0) atomicAdd(p, v); }   // x + (+-0) = x, and the film starts at +0: skipping a zero changes no bit
+
+// q.pos, q.res plane k at k * q.capacity and the pixel from global_lane, as k_splat_generic reads them.  Every thread of the block stays in the kernel (the shuffles
+// of run_sum are wave-wide); a thread without a lane is a run of its own that adds nothing.
+__global__ __launch_bounds__(kFilm64Block) void k_splat_f64(RenderParams rp, Queues q, double *film, size_t film_stride) {
+    const uint32_t i = blockIdx.x * kFilm64Block + threadIdx.x;
+    const bool valid = i < rp.n_lanes;
+    const int W = rp.crop_w, H = rp.crop_h, K = rp.n_offsets;
+    const bool box = rp.filter == FILTER_BOX;
+    const int n = box ? 0 : (int) ceilf(rp.filter_radius - .5f), cnt = 2 * n + 1;
+    const float2 p = valid ? q.pos[i] : make_float2(0.f, 0.f);
+    // the footprint's anchor in film coordinates (splat_lane): the box filter splats at the lane's own pixel, every other at floor(position) - n
+    int ax, ay; float relx = 0.f, rely = 0.f;
+    if (box) {
+        const uint32_t pix = fdiv(global_lane(rp, rp.lane_base + (valid ? i : 0u)), rp.d_spp);
+        ay = (int) fdiv(pix, rp.d_w); ax = (int) (pix - (uint32_t) W * (uint32_t) ay);
+    } else {
+        const int pix = (int) floorf(p.x) - n, piy = (int) floorf(p.y) - n;
+        relx = (float) pix + .5f - p.x; rely = (float) piy + .5f - p.y;
+        ax = pix - rp.crop_x; ay = piy - rp.crop_y;
+    }
+    if (cnt > kRunCells) {   // wide footprints (the Lanczos filter's 7 x 7): one atomic per lane, cell and channel
+        if (!valid) return;
+        for (int ys = 0; ys < cnt; ++ys) {
+            const float wy = filter_weight(rp, rely + (float) ys);
+            for (int xs = 0; xs < cnt; ++xs) {
+                const float w = filter_weight(rp, relx + (float) xs) * wy;
+                const int x = ax + xs, y = ay + ys;
+                if ((unsigned) x >= (unsigned) W || (unsigned) y >= (unsigned) H) continue;
+                for (int k = 0; k < K; ++k) {
+                    const float4 r = q.res[(size_t) k * q.capacity + i];
+                    double *c = film + (size_t) k * film_stride + 4 * ((size_t) y * W + x);
+                    add_f64(c, (double) (r.x * w)); add_f64(c + 1, (double) (r.y * w)); add_f64(c + 2, (double) (r.z * w)); add_f64(c + 3, (double) w);
+                }
+            }
+        }
+        return;
+    }
+    // runs: a lane heads one if it is the wave's first, has no sample, follows a lane without one or a lane with another anchor
+    const uint32_t wl = __lane_id();
+    const int pax = __shfl_up(ax, 1), pay = __shfl_up(ay, 1), pvalid = __shfl_up((int) valid, 1);
+    const bool head = wl == 0 || !valid || !pvalid || pax != ax || pay != ay;
+    const unsigned long long heads = __ballot(head);   // bit 0 is always set
+    const uint32_t run_first = 63u - (uint32_t) __builtin_clzll(heads & (~0ull >> (63u - wl)));
+    const uint32_t dist = wl - run_first;
+    const bool last = wl == 63u || ((heads >> (wl + 1u)) & 1ull);
+    uint32_t steps = 0;
+#pragma unroll
+    for (uint32_t s = 0; s < 6; ++s) steps |= __ballot(dist >= (1u << s)) != 0ull ? 1u << s : 0u;
+    float wx[kRunCells];
+#pragma unroll
+    for (int a = 0; a < kRunCells; ++a) wx[a] = a < cnt && !box ? filter_weight(rp, relx + (float) a) : 0.f;
+    float rr[kMaxOffsets], rg[kMaxOffsets], rb[kMaxOffsets];
+#pragma unroll
+    for (int k = 0; k < kMaxOffsets; ++k) {
+        const float4 v = valid && k < K ? q.res[(size_t) k * q.capacity + i] : make_float4(0.f, 0.f, 0.f, 0.f);
+        rr[k] = v.x; rg[k] = v.y; rb[k] = v.z;
+    }
+    // The cell and film loops stay rolled (25 cells x 13 sums unrolled would be ~60 KiB of code): their counters are scalars, pick() turns into selects on them.
+#pragma unroll 1
+    for (int ys = 0; ys < cnt; ++ys) {
+        const float wys = box ? 1.f : filter_weight(rp, rely + (float) ys);
+#pragma unroll 1
+        for (int xs = 0; xs < cnt; ++xs) {
+            const int x = ax + xs, y = ay + ys;
+            const bool write = valid && last && (unsigned) x < (unsigned) W && (unsigned) y < (unsigned) H;   // the same cell for every lane of the run
+            double *cell = film + 4 * ((size_t) (write ? y : 0) * W + (write ? x : 0));
+            const float w = box ? 1.f : pick(wx, xs) * wys;
+            const double ws = run_sum(valid ? (double) w : 0.0, dist, steps);
+#pragma unroll 1
+            for (int k = 0; k < K; ++k) {
+                const float vr = pick(rr, k), vg = pick(rg, k), vb = pick(rb, k);
+                // the box filter adds the value itself (value * 1.f is the same float)
+                const double sr = run_sum((double) (box ? vr : vr * w), dist, steps);
+                const double sg = run_sum((double) (box ? vg : vg * w), dist, steps);
+                const double sb = run_sum((double) (box ? vb : vb * w), dist, steps);
+                if (write) {
+                    double *c = cell + (size_t) k * film_stride;
+                    add_f64(c, sr); add_f64(c + 1, sg); add_f64(c + 2, sb); add_f64(c + 3, ws);
+                }
+            }
+        }
+    }
+}
+
+__global__ __launch_bounds__(kFilm64Block) void k_develop_f64(const double *film, uint64_t plane_stride, float *rgb, int64_t n) {
+    const int64_t i = (int64_t) blockIdx.x * kFilm64Block + threadIdx.x;
+    if (i >= n) return;
+    const double *f = film + (uint64_t) blockIdx.y * plane_stride + 4 * i;
+    const double w = f[3] == 0.0 ? 1.0 : f[3];
+    float *o = rgb + ((int64_t) blockIdx.y * n + i) * 3;
+    o[0] = (float) (f[0] / w); o[1] = (float) (f[1] / w); o[2] = (float) (f[2] / w);
+}
+
+// pixel_format = rgba (hdrfilm.cpp:339-400): the alpha channel was accumulated into a film of its own, (A, 0, 0, W) with the same weights
+__global__ __launch_bounds__(kFilm64Block) void k_develop_rgba_f64(const double *film, const double *alpha_film, float *rgba, int64_t n) {
+    const int64_t i = (int64_t) blockIdx.x * kFilm64Block + threadIdx.x;
+    if (i >= n) return;
+    const double *f = film + 4 * i, *a = alpha_film + 4 * i;
+    const double w = f[3] == 0.0 ? 1.0 : f[3], wa = a[3] == 0.0 ? 1.0 : a[3];
+    ((float4 *) rgba)[i] = make_float4((float) (f[0] / w), (float) (f[1] / w), (float) (f[2] / w), (float) (a[0] / wa));
+}
+
+__global__ __launch_bounds__(kFilm64Block) void k_develop_accumulate_f64(const double *film, uint64_t plane_stride, float *rgb_sum, int64_t n, int first) {
+    const int64_t i = (int64_t) blockIdx.x * kFilm64Block + threadIdx.x;
+    if (i >= n) return;
+    const double *f = film + (uint64_t) blockIdx.y * plane_stride + 4 * i;
+    const double w = f[3] == 0.0 ? 1.0 : f[3];   // k_develop_f64's expression
+    const float r = (float) (f[0] / w), g = (float) (f[1] / w), b = (float) (f[2] / w);
+    float *o = rgb_sum + ((int64_t) blockIdx.y * n + i) * 3;
+    if (first) { o[0] = r; o[1] = g; o[2] = b; }   // the first pass ASSIGNS (acc = img), as k_develop_accumulate does
+    else { o[0] = o[0] + r; o[1] = o[1] + g; o[2] = o[2] + b; }
+}
+
+dim3 pixel_grid(int64_t n_pixels, int32_t planes) { return dim3((uint32_t) ((n_pixels + kFilm64Block - 1) / kFilm64Block), (uint32_t) planes); }
+}  // namespace
+
+void launch_splat_f64(const RenderParams &rp, const Queues &q, double *film64, uint64_t plane_stride_doubles, hipStream_t s) {
+    if (rp.n_lanes == 0) return;
+    hipLaunchKernelGGL(k_splat_f64, dim3((rp.n_lanes + kFilm64Block - 1) / kFilm64Block), dim3(kFilm64Block), 0, s, rp, q, film64, (size_t) plane_stride_doubles);
+}
+void launch_develop_f64(const double *film64, int32_t planes, uint64_t plane_stride_doubles, float *rgb, int64_t n_pixels, hipStream_t s) {
+    if (n_pixels <= 0 || planes <= 0) return;
+    const uint64_t stride = plane_stride_doubles ? plane_stride_doubles : (uint64_t) n_pixels * 4;
+    hipLaunchKernelGGL(k_develop_f64, pixel_grid(n_pixels, planes), dim3(kFilm64Block), 0, s, film64, stride, rgb, n_pixels);
+}
+void launch_develop_rgba_f64(const double *film64, const double *alpha_film64, float *rgba, int64_t n_pixels, hipStream_t s) {
+    if (n_pixels <= 0) return;
+    hipLaunchKernelGGL(k_develop_rgba_f64, pixel_grid(n_pixels, 1), dim3(kFilm64Block), 0, s, film64, alpha_film64, rgba, n_pixels);
+}
+void launch_develop_accumulate_f64(const double *film64, int32_t planes, uint64_t plane_stride_doubles, float *rgb_sum, int64_t n_pixels, bool first, hipStream_t s) {
+    if (n_pixels <= 0 || planes <= 0) return;
+    const uint64_t stride = plane_stride_doubles ? plane_stride_doubles : (uint64_t) n_pixels * 4;
+    hipLaunchKernelGGL(k_develop_accumulate_f64, pixel_grid(n_pixels, planes), dim3(kFilm64Block), 0, s, film64, stride, rgb_sum, n_pixels, first ? 1 : 0);
+}
+
+}  // namespace dtof

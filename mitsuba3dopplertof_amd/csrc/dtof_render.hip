@@ -9,6 +9,7 @@
 #include "../../include/dtof.h"
 #include "dtof_kernels.h"
 #include "dtof_reconstruct.h"
+#include "dtof_film64.h"
 #include "dtof_scene.h"
 #include "dtof_math.h"
 #include <atomic>
@@ -99,6 +100,7 @@ struct dtof_scene {
     DevBuf<uint8_t> d_blob; bool uploaded = false;
     Workspace ws;
     DevBuf<float> d_film, d_rgb;
+    DevBuf<double> d_film64;   // the library's own float64 film (dtof_render_variants_f64, dtof_render_velocity_map_f64)
     DevBuf<float> d_vm_sum, d_vm_tof; DevBuf<double> d_vm_maps;   // dtof_render_velocity_map: the passes' sum, the ToF images, the per-pair maps and the combined map
     // the caller's device film as declared with dtof_scene_set_film_layout (0 = not declared: colour planes only, W * H * 4 apart)
     int32_t film_planes = 0; uint64_t film_plane_stride = 0;
@@ -305,6 +307,15 @@ double stage_ms(const std::vector<std::pair<hipEvent_t, hipEvent_t>> &ev) {
     return ms;
 }
 
+// film elements (4 per pixel) of the rows a call that renders rows [row_lo, row_hi) can write: the rows and the filter's halo on either side, inside the film
+static uint64_t film_rows_reach(const HostSensor &se, int32_t row_lo, int32_t row_hi, int32_t *first = nullptr, int32_t *end = nullptr) {
+    const int32_t halo = se.filter == FILTER_BOX ? 0 : (int32_t) std::ceil(se.filter_radius - .5f);
+    const int32_t r0 = std::max(row_lo, 0), r1 = std::min(row_hi, se.crop_h);
+    const int32_t lo = std::max(r0 - halo, 0), hi = std::min(r1 + halo, se.crop_h);
+    if (first) *first = lo;
+    if (end) *end = hi;
+    return r1 > r0 ? (uint64_t) (hi - lo) * se.crop_w * 4 : 0;   // an empty band writes nothing
+}
 // The device-film entry points write K colour planes and, for an rgba film, the alpha plane behind them into memory whose size only the caller knows: an rgba scene is
 // refused until the caller has declared a film of K + 1 planes (a caller written for rgb films would have its buffer overrun), and a declared count is checked either way.
 // [row_lo, row_hi): the film rows whose lanes the call renders.  Their splats reach `halo` rows further (the reconstruction filter), so with more than one plane a
@@ -318,10 +329,8 @@ static uint64_t caller_film_stride(const dtof_scene *sc, int n_offsets, int32_t 
         throw std::runtime_error("the device film was declared with " + std::to_string(sc->film_planes) + " planes, this call writes " + std::to_string(need));
     const uint64_t full = (uint64_t) se.crop_w * se.crop_h * 4;
     if (need > 1 && sc->film_plane_stride != 0) {
-        const int32_t halo = se.filter == FILTER_BOX ? 0 : (int32_t) std::ceil(se.filter_radius - .5f);
-        const int32_t r0 = std::max(row_lo, 0), r1 = std::min(row_hi, se.crop_h);
-        const int32_t lo = std::max(r0 - halo, 0), hi = std::min(r1 + halo, se.crop_h);
-        const uint64_t reach = r1 > r0 ? (uint64_t) (hi - lo) * se.crop_w * 4 : 0;   // an empty band writes nothing
+        int32_t lo = 0, hi = 0;
+        const uint64_t reach = film_rows_reach(se, row_lo, row_hi, &lo, &hi);
         if (sc->film_plane_stride < reach)
             throw std::runtime_error("the declared plane stride of " + std::to_string(sc->film_plane_stride) + " floats is smaller than the " + std::to_string(reach) +
                                      " floats of film rows [" + std::to_string(lo) + ", " + std::to_string(hi) + ") this call writes: the planes would overlap");
@@ -346,6 +355,7 @@ struct RenderRequest {
     int films() const { return n_variants > 0 ? n_variants : n_offsets > 0 ? n_offsets : 1; }   // colour films the call writes
     float4 *lane_planes = nullptr;                // lane dumps: [films()][dump_n] results of every film (q.res), besides film 0's in lane_dump
     float *film = nullptr; uint64_t film_stride = 0;   // K films (and the alpha film behind them) film_stride floats apart
+    double *film64 = nullptr; uint64_t film64_stride = 0;   // ... or the float64 film, film64_stride doubles apart: the separate splat stage accumulates in double (dtof_film64.hip)
     dtof_render_stats *stats = nullptr;
     LaneDebug *lane_dump = nullptr; uint64_t dump_begin = 0, dump_n = 0;   // lane_dump != nullptr: evaluate only lanes [dump_begin, dump_begin + dump_n) and copy their records out
     bool deferred = false;                        // dtof_render_rows_async: timings by events, no counters read back, no synchronisation at the end
@@ -643,6 +653,7 @@ FramePlan plan_frame(const dtof_scene *sc, const RenderRequest &rq) {
     // splat kernel, which sums 8 samples per lane before it reduces, is faster
     p.fuse_splat_ok = on("DTOF_FUSE_SPLAT") && p.fused && !rq.lane_dump && p.n_passes == 1 && !se.alpha && rp.filter == FILTER_TENT && rp.filter_radius <= 1.f &&
                       rp.filter_radius > .5f && rp.spp_log2 == 6 && rp.n_offsets == 1 && rq.film != nullptr;
+    if (rq.film64) p.fuse_splat_ok = false;   // the float64 film is the separate splat stage's: k_shade splats in float32
     return p;
 }
 
@@ -734,11 +745,13 @@ void render_rows(dtof_scene *sc, const RenderRequest &rq) {
                     HIP_CHECK(hipMemcpyAsync(rq.lane_planes + (size_t) k * rq.dump_n + (b0 - p.first), q.res + (size_t) k * q.capacity, (size_t) rp.n_lanes * sizeof(float4), hipMemcpyDeviceToHost, s));
             HIP_CHECK(hipStreamSynchronize(s));
         } else if (!rq.lane_dump && !fused_splat_done) {
-            t = tm.begin(kStageSplat, s); launch_splat(rp, q, rq.film, rq.film_stride, p.launch, s);
+            t = tm.begin(kStageSplat, s);
+            if (rq.film64) launch_splat_f64(rp, q, rq.film64, rq.film64_stride, s); else launch_splat(rp, q, rq.film, rq.film_stride, p.launch, s);
             if (sc->host.sensor.alpha) {   // the alpha film (plane K behind the K offset films): the same splat over (valid, 0, 0) -- ImageBlock::put of aovs[3] (integrator.cpp:528-533)
                 RenderParams ra = rp; ra.n_offsets = 1;
                 Queues qa = q; qa.res = q.valid_out;
-                launch_splat(ra, qa, rq.film + (size_t) rp.n_offsets * rq.film_stride, rq.film_stride, p.launch, s);
+                if (rq.film64) launch_splat_f64(ra, qa, rq.film64 + (size_t) rp.n_offsets * rq.film64_stride, rq.film64_stride, s);
+                else launch_splat(ra, qa, rq.film + (size_t) rp.n_offsets * rq.film_stride, rq.film_stride, p.launch, s);
             }
             tm.end(kStageSplat, t, s);
         }
@@ -828,6 +841,30 @@ void render_host_films(dtof_scene *sc, RenderRequest rq, float *out_rgb) {
     if (se.alpha) for (int i = 0; i < k; ++i) launch_develop_rgba(sc->d_film.p + px * 4 * i, sc->d_film.p + px * 4 * k, sc->d_rgb.p + px * 4 * i, (int64_t) px, sc->stream);
     else launch_develop(sc->d_film.p, sc->d_rgb.p, (int64_t) px * k, sc->stream);
     HIP_CHECK(hipMemcpyAsync(out_rgb, sc->d_rgb.p, px * ch * k * sizeof(float), hipMemcpyDeviceToHost, sc->stream));
+    HIP_CHECK(hipStreamSynchronize(sc->stream));
+}
+
+// render_host_films with the library's own FLOAT64 film (dtof_render_variants_f64): developed in double into out_rgb; out_films: the raw film planes, or null
+void render_host_films_f64(dtof_scene *sc, RenderRequest rq, float *out_rgb, double *out_films) {
+    if (!sc || !out_rgb) throw std::runtime_error("null argument");
+    if (sc->pp.integrator != INTEGRATOR_DOPPLER && rq.n_variants > 0) throw std::runtime_error("modulation offsets only apply to the dopplertofpath integrator");
+    if (!sc->host.has_sensor) throw std::runtime_error("the scene does not contain a sensor");
+    ensure_device(sc);
+    sc->stop = false;
+    const int k = rq.films();
+    const HostSensor &se = sc->host.sensor;
+    const size_t px = (size_t) se.crop_w * se.crop_h;
+    const int planes = k + (se.alpha ? 1 : 0), ch = se.alpha ? 4 : 3;
+    sc->d_film64.ensure(px * 4 * planes); sc->d_rgb.ensure(px * ch * k);
+    HIP_CHECK(hipMemsetAsync(sc->d_film64.p, 0, px * 4 * planes * sizeof(double), sc->stream));
+    rq.row_begin = 0; rq.row_end = se.crop_h;
+    rq.film = nullptr; rq.film64 = sc->d_film64.p; rq.film64_stride = px * 4;
+    render_rows(sc, rq);
+    if (se.alpha) for (int i = 0; i < k; ++i) launch_develop_rgba_f64(sc->d_film64.p + px * 4 * i, sc->d_film64.p + px * 4 * k, sc->d_rgb.p + px * 4 * i, (int64_t) px, sc->stream);
+    else launch_develop_f64(sc->d_film64.p, k, 0, sc->d_rgb.p, (int64_t) px, sc->stream);
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipMemcpyAsync(out_rgb, sc->d_rgb.p, px * ch * k * sizeof(float), hipMemcpyDeviceToHost, sc->stream));
+    if (out_films) HIP_CHECK(hipMemcpyAsync(out_films, sc->d_film64.p, px * 4 * planes * sizeof(double), hipMemcpyDeviceToHost, sc->stream));
     HIP_CHECK(hipStreamSynchronize(sc->stream));
 }
 
@@ -1218,61 +1255,126 @@ int dtof_velocity_map_variants(const float *offsets, int n_offsets, dtof_modulat
         }
     });
 }
+// dtof_render_velocity_map / _f64: the same loop over the library's own float32 or float64 film (film64: k_splat_f64 and k_develop_accumulate_f64)
+static void velocity_map_render(dtof_scene *sc, uint32_t n_passes, uint32_t spp, const float *offsets, int n_offsets, double exposure_time, double w_g_mhz,
+                                double *out_velocity, double *out_velocity_pairs, float *out_tof, dtof_render_stats *stats, bool film64) {
+    if (!sc || !offsets || !out_velocity) throw std::runtime_error("null argument");
+    if (n_offsets < 1 || n_offsets > kMaxVelocityPairs) throw std::runtime_error("between 1 and 16 offsets make a velocity map");
+    check_velocity_scalars(n_passes, exposure_time, w_g_mhz);
+    if (sc->pp.integrator != INTEGRATOR_DOPPLER) throw std::runtime_error("modulation offsets only apply to the dopplertofpath integrator");
+    if (!sc->host.has_sensor) throw std::runtime_error("the scene does not contain a sensor");
+    dtof_modulation variants[2 * kMaxVelocityPairs];
+    if (dtof_velocity_map_variants(offsets, n_offsets, variants) != DTOF_OK) throw std::runtime_error(g_last_error);
+    int32_t hom[kMaxVelocityPairs], het[kMaxVelocityPairs];   // offset j of group g = j / 2: its films lie behind the 4 * g planes of the full groups before it
+    for (int j = 0; j < n_offsets; ++j) {
+        const int g = j / 2, n = std::min(2, n_offsets - 2 * g);
+        hom[j] = 4 * g + j % 2; het[j] = 4 * g + n + j % 2;
+    }
+    const VelocityMapArgs a = velocity_args(n_offsets, hom, het, n_passes, exposure_time, w_g_mhz);
+    ensure_device(sc);
+    sc->stop = false;
+    const HostSensor &se = sc->host.sensor;
+    const size_t px = (size_t) se.crop_w * se.crop_h;
+    const int alpha = se.alpha ? 1 : 0;
+    if (film64) sc->d_film64.ensure(px * 4 * (kMaxOffsets + alpha)); else sc->d_film.ensure(px * 4 * (kMaxOffsets + alpha));   // the library's own film: the caller's declared layout is not consulted
+    sc->d_vm_sum.ensure(px * 3 * 2 * n_offsets); sc->d_vm_tof.ensure(px * 2 * n_offsets); sc->d_vm_maps.ensure(px * (n_offsets + 1));
+    const hipStream_t s = sc->stream;
+    const size_t first_frame = sc->deferred.size();   // frames the caller has not collected yet stay his
+    try {
+        for (int g = 0; g < n_offsets; g += 2) {
+            const int films = 2 * std::min(2, n_offsets - g);
+            for (uint32_t pass = 0; pass < n_passes; ++pass) {
+                if (film64) HIP_CHECK(hipMemsetAsync(sc->d_film64.p, 0, px * 4 * (films + alpha) * sizeof(double), s));
+                else HIP_CHECK(hipMemsetAsync(sc->d_film.p, 0, px * 4 * (films + alpha) * sizeof(float), s));
+                dtof_render_stats frame;
+                RenderRequest rq; rq.seed = pass; rq.spp = spp; rq.row_begin = 0; rq.row_end = se.crop_h;
+                if (film64) { rq.film64 = sc->d_film64.p; rq.film64_stride = px * 4; } else { rq.film = sc->d_film.p; rq.film_stride = px * 4; }
+                rq.deferred = true; rq.stats = &frame;
+                set_variants(rq, variants + 2 * g, films);
+                render_rows(sc, rq);
+                // the alpha plane behind them is left out
+                if (film64) launch_develop_accumulate_f64(sc->d_film64.p, films, 0, sc->d_vm_sum.p + px * 3 * 2 * g, (int64_t) px, pass == 0, s);
+                else launch_develop_accumulate(sc->d_film.p, films, 0, sc->d_vm_sum.p + px * 3 * 2 * g, (int64_t) px, pass == 0, s);
+            }
+        }
+        double *d_pairs = sc->d_vm_maps.p + px;
+        launch_velocity_map(sc->d_vm_sum.p, a, (int64_t) px, out_tof ? sc->d_vm_tof.p : nullptr, out_velocity_pairs ? d_pairs : nullptr, sc->d_vm_maps.p, s);
+        HIP_CHECK(hipGetLastError());
+        HIP_CHECK(hipMemcpyAsync(out_velocity, sc->d_vm_maps.p, px * sizeof(double), hipMemcpyDeviceToHost, s));
+        if (out_velocity_pairs) HIP_CHECK(hipMemcpyAsync(out_velocity_pairs, d_pairs, px * n_offsets * sizeof(double), hipMemcpyDeviceToHost, s));
+        if (out_tof) HIP_CHECK(hipMemcpyAsync(out_tof, sc->d_vm_tof.p, px * 2 * n_offsets * sizeof(float), hipMemcpyDeviceToHost, s));
+        HIP_CHECK(hipStreamSynchronize(s));
+        dtof_render_stats sum; memset(&sum, 0, sizeof sum);
+        for (size_t i = first_frame; i < sc->deferred.size(); ++i) add_deferred_frame(&sum, sc->deferred[i]);
+        if (stats) *stats = sum;
+    } catch (...) {   // the frames of this call leave the list either way (their events go back to the pool once no frame is in flight)
+        if (sc->deferred.size() > first_frame) { (void) hipStreamSynchronize(s); sc->deferred.resize(first_frame); }
+        if (sc->deferred.empty()) sc->events_used = 0;
+        throw;
+    }
+    sc->deferred.resize(first_frame);
+    if (sc->deferred.empty()) sc->events_used = 0;
+}
 int dtof_render_velocity_map(dtof_scene *sc, uint32_t n_passes, uint32_t spp, const float *offsets, int n_offsets, double exposure_time, double w_g_mhz,
                              double *out_velocity, double *out_velocity_pairs, float *out_tof, dtof_render_stats *stats) {
+    return guarded([&] { velocity_map_render(sc, n_passes, spp, offsets, n_offsets, exposure_time, w_g_mhz, out_velocity, out_velocity_pairs, out_tof, stats, false); });
+}
+
+// ---------------------------------------------------------------- float64 film (dtof_film64.hip)
+int dtof_render_velocity_map_f64(dtof_scene *sc, uint32_t n_passes, uint32_t spp, const float *offsets, int n_offsets, double exposure_time, double w_g_mhz,
+                                 double *out_velocity, double *out_velocity_pairs, float *out_tof, dtof_render_stats *stats) {
+    return guarded([&] { velocity_map_render(sc, n_passes, spp, offsets, n_offsets, exposure_time, w_g_mhz, out_velocity, out_velocity_pairs, out_tof, stats, true); });
+}
+int dtof_render_variants_f64(dtof_scene *sc, uint32_t seed, uint32_t spp, const dtof_modulation *variants, int n_variants, float *out_images, double *out_films,
+                             dtof_render_stats *stats) {
     return guarded([&] {
-        if (!sc || !offsets || !out_velocity) throw std::runtime_error("null argument");
-        if (n_offsets < 1 || n_offsets > kMaxVelocityPairs) throw std::runtime_error("between 1 and 16 offsets make a velocity map");
-        check_velocity_scalars(n_passes, exposure_time, w_g_mhz);
-        if (sc->pp.integrator != INTEGRATOR_DOPPLER) throw std::runtime_error("modulation offsets only apply to the dopplertofpath integrator");
+        RenderRequest rq; rq.seed = seed; rq.spp = spp; rq.stats = stats; set_variants(rq, variants, n_variants);
+        render_host_films_f64(sc, rq, out_images, out_films);
+    });
+}
+int dtof_render_rows_variants_f64(dtof_scene *sc, uint32_t seed, uint32_t spp, int32_t row_begin, int32_t row_end, const dtof_modulation *variants, int n_variants,
+                                  double *d_film, int32_t planes, uint64_t plane_stride_doubles, dtof_render_stats *stats) {
+    return guarded([&] {
+        if (!sc || !d_film) throw std::runtime_error("null argument");
+        RenderRequest rq; rq.seed = seed; rq.spp = spp; rq.row_begin = row_begin; rq.row_end = row_end; rq.stats = stats;
+        set_variants(rq, variants, n_variants);
+        if (sc->pp.integrator != INTEGRATOR_DOPPLER && rq.n_variants > 0) throw std::runtime_error("modulation offsets only apply to the dopplertofpath integrator");
         if (!sc->host.has_sensor) throw std::runtime_error("the scene does not contain a sensor");
-        dtof_modulation variants[2 * kMaxVelocityPairs];
-        if (dtof_velocity_map_variants(offsets, n_offsets, variants) != DTOF_OK) throw std::runtime_error(g_last_error);
-        int32_t hom[kMaxVelocityPairs], het[kMaxVelocityPairs];   // offset j of group g = j / 2: its films lie behind the 4 * g planes of the full groups before it
-        for (int j = 0; j < n_offsets; ++j) {
-            const int g = j / 2, n = std::min(2, n_offsets - 2 * g);
-            hom[j] = 4 * g + j % 2; het[j] = 4 * g + n + j % 2;
-        }
-        const VelocityMapArgs a = velocity_args(n_offsets, hom, het, n_passes, exposure_time, w_g_mhz);
-        ensure_device(sc);
-        sc->stop = false;
+        if ((uintptr_t) d_film % 8 != 0) throw std::runtime_error("the film must be 8-byte aligned");
         const HostSensor &se = sc->host.sensor;
-        const size_t px = (size_t) se.crop_w * se.crop_h;
-        const int alpha = se.alpha ? 1 : 0;
-        sc->d_film.ensure(px * 4 * (kMaxOffsets + alpha));   // the library's own film: the caller's declared layout is not consulted
-        sc->d_vm_sum.ensure(px * 3 * 2 * n_offsets); sc->d_vm_tof.ensure(px * 2 * n_offsets); sc->d_vm_maps.ensure(px * (n_offsets + 1));
-        const hipStream_t s = sc->stream;
-        const size_t first_frame = sc->deferred.size();   // frames the caller has not collected yet stay his
-        try {
-            for (int g = 0; g < n_offsets; g += 2) {
-                const int films = 2 * std::min(2, n_offsets - g);
-                for (uint32_t pass = 0; pass < n_passes; ++pass) {
-                    HIP_CHECK(hipMemsetAsync(sc->d_film.p, 0, px * 4 * (films + alpha) * sizeof(float), s));
-                    dtof_render_stats frame;
-                    RenderRequest rq; rq.seed = pass; rq.spp = spp; rq.row_begin = 0; rq.row_end = se.crop_h; rq.film = sc->d_film.p; rq.film_stride = px * 4;
-                    rq.deferred = true; rq.stats = &frame;
-                    set_variants(rq, variants + 2 * g, films);
-                    render_rows(sc, rq);
-                    launch_develop_accumulate(sc->d_film.p, films, 0, sc->d_vm_sum.p + px * 3 * 2 * g, (int64_t) px, pass == 0, s);   // the alpha plane behind them is left out
-                }
-            }
-            double *d_pairs = sc->d_vm_maps.p + px;
-            launch_velocity_map(sc->d_vm_sum.p, a, (int64_t) px, out_tof ? sc->d_vm_tof.p : nullptr, out_velocity_pairs ? d_pairs : nullptr, sc->d_vm_maps.p, s);
-            HIP_CHECK(hipGetLastError());
-            HIP_CHECK(hipMemcpyAsync(out_velocity, sc->d_vm_maps.p, px * sizeof(double), hipMemcpyDeviceToHost, s));
-            if (out_velocity_pairs) HIP_CHECK(hipMemcpyAsync(out_velocity_pairs, d_pairs, px * n_offsets * sizeof(double), hipMemcpyDeviceToHost, s));
-            if (out_tof) HIP_CHECK(hipMemcpyAsync(out_tof, sc->d_vm_tof.p, px * 2 * n_offsets * sizeof(float), hipMemcpyDeviceToHost, s));
-            HIP_CHECK(hipStreamSynchronize(s));
-            dtof_render_stats sum; memset(&sum, 0, sizeof sum);
-            for (size_t i = first_frame; i < sc->deferred.size(); ++i) add_deferred_frame(&sum, sc->deferred[i]);
-            if (stats) *stats = sum;
-        } catch (...) {   // the frames of this call leave the list either way (their events go back to the pool once no frame is in flight)
-            if (sc->deferred.size() > first_frame) { (void) hipStreamSynchronize(s); sc->deferred.resize(first_frame); }
-            if (sc->deferred.empty()) sc->events_used = 0;
-            throw;
-        }
-        sc->deferred.resize(first_frame);
-        if (sc->deferred.empty()) sc->events_used = 0;
+        const int need = rq.films() + (se.alpha ? 1 : 0);   // the alpha film lies behind the colour films
+        if (planes < need) throw std::runtime_error("the device film has " + std::to_string(planes) + " planes, this call writes " + std::to_string(need));
+        if (plane_stride_doubles != 0 && (plane_stride_doubles % 4 != 0 || plane_stride_doubles < (uint64_t) se.crop_w * 4))
+            throw std::runtime_error("plane stride must be a multiple of 4 doubles and at least one film row");
+        int32_t lo = 0, hi = 0;
+        const uint64_t reach = film_rows_reach(se, row_begin, row_end, &lo, &hi);
+        if (need > 1 && plane_stride_doubles != 0 && plane_stride_doubles < reach)
+            throw std::runtime_error("the plane stride of " + std::to_string(plane_stride_doubles) + " doubles is smaller than the " + std::to_string(reach) +
+                                     " doubles of film rows [" + std::to_string(lo) + ", " + std::to_string(hi) + ") this call writes: the planes would overlap");
+        rq.film64 = d_film; rq.film64_stride = plane_stride_doubles ? plane_stride_doubles : (uint64_t) se.crop_w * se.crop_h * 4;
+        sc->stop = false;
+        render_rows(sc, rq);
+    });
+}
+int dtof_develop_f64_async(dtof_scene *sc, const double *d_film64, float *d_rgb, int64_t n_pixels) {
+    return guarded([&] {
+        if (!sc || !d_film64 || !d_rgb) throw std::runtime_error("null argument");
+        check_grid(n_pixels);
+        if ((uintptr_t) d_film64 % 8 != 0 || (uintptr_t) d_rgb % 4 != 0) throw std::runtime_error("the film must be 8-byte aligned, the image 4-byte aligned");
+        ensure_device(sc);
+        launch_develop_f64(d_film64, 1, 0, d_rgb, n_pixels, sc->stream);
+        HIP_CHECK(hipGetLastError());
+    });
+}
+int dtof_develop_rgba_f64_async(dtof_scene *sc, const double *d_film64, const double *d_alpha_film64, float *d_rgba, int64_t n_pixels) {
+    return guarded([&] {
+        if (!sc || !d_film64 || !d_alpha_film64 || !d_rgba) throw std::runtime_error("null argument");
+        check_grid(n_pixels);
+        if ((uintptr_t) d_film64 % 8 != 0 || (uintptr_t) d_alpha_film64 % 8 != 0 || (uintptr_t) d_rgba % 16 != 0)
+            throw std::runtime_error("the films must be 8-byte aligned, the image 16-byte aligned");
+        ensure_device(sc);
+        launch_develop_rgba_f64(d_film64, d_alpha_film64, d_rgba, n_pixels, sc->stream);
+        HIP_CHECK(hipGetLastError());
     });
 }
 

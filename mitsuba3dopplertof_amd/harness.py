@@ -65,10 +65,10 @@ def run_scene_doppler_tof_offsets(scene, hetero_offsets, total_spp=1024, output_
     return images
 
 
-def run_scene_doppler_tof_variants(scene, variants, total_spp=1024, output_files=None, **integrator_kwargs):
+def run_scene_doppler_tof_variants(scene, variants, total_spp=1024, output_files=None, film="float32", **integrator_kwargs):
     """run_scene_doppler_tof for SEVERAL (hetero_frequency, hetero_offset) pairs of one otherwise identical setting: neither property reaches anything but the
     modulation weight, so every traversal evaluates up to four pairs at once (dtof_render_variants) and the images of one group share their paths.  Same passes and
-    seeds as run_scene_doppler_tof_offsets; returns the images in the order of `variants`."""
+    seeds as run_scene_doppler_tof_offsets; returns the images in the order of `variants`.  film="float64": every traversal into the float64 film (Scene.render)."""
     single, n_pass = _passes(total_spp)
     integrator_kwargs = dict(integrator_kwargs)
     integrator_kwargs.pop("hetero_offset", None)
@@ -79,7 +79,7 @@ def run_scene_doppler_tof_variants(scene, variants, total_spp=1024, output_files
         group = [(float(f), float(o)) for f, o in variants[g:g + 4]]
         acc = None
         for i in range(n_pass):
-            img = scene.render(seed=i, spp=single, variants=group).astype(np.float32)
+            img = scene.render(seed=i, spp=single, variants=group, film=film).astype(np.float32)
             stats.append(scene.last_stats)
             acc = img if acc is None else acc + img
         images += list(acc / np.float32(n_pass))
@@ -91,7 +91,7 @@ def run_scene_doppler_tof_variants(scene, variants, total_spp=1024, output_files
     return images
 
 
-def run_scene_velocity_map(scene, total_spp=1024, offsets=(0.0, 0.25), **integrator_kwargs):
+def run_scene_velocity_map(scene, total_spp=1024, offsets=(0.0, 0.25), film="float32", **integrator_kwargs):
     """The radial velocity map of image_utils.py:170-199 from ONE traversal per pass: the homodyne (hetero_frequency 0) and heterodyne (1) films of every offset are
     variants of the same paths, so their ratio's noise is correlated instead of independent.  Two offsets are the four films of one traversal; more are grouped by
     pairs of offsets.  Returns (velocity map (H, W), {"homodyne": [...], "heterodyne": [...]} ToF images in the order of `offsets`)."""
@@ -99,7 +99,7 @@ def run_scene_velocity_map(scene, total_spp=1024, offsets=(0.0, 0.25), **integra
     variants = []
     for g in range(0, len(offsets), 2):   # a homodyne / heterodyne pair never straddles two traversals
         variants += [(0.0, o) for o in offsets[g:g + 2]] + [(1.0, o) for o in offsets[g:g + 2]]
-    images = run_scene_doppler_tof_variants(scene, variants, total_spp, **integrator_kwargs)
+    images = run_scene_doppler_tof_variants(scene, variants, total_spp, film=film, **integrator_kwargs)
     exposure_time, w_g = integrator_kwargs.get("exposure_time", 0.0015), integrator_kwargs.get("w_g", 30)
     homo, hetero = [], []
     for g in range(0, len(offsets), 2):
@@ -109,7 +109,7 @@ def run_scene_velocity_map(scene, total_spp=1024, offsets=(0.0, 0.25), **integra
     return calc_velocity_from_homo_heteros(homo, hetero, exposure_time, w_g), {"homodyne": homo, "heterodyne": hetero}
 
 
-def run_scene_velocity_map_device(scene, total_spp=1024, offsets=(0.0, 0.25), **integrator_kwargs):
+def run_scene_velocity_map_device(scene, total_spp=1024, offsets=(0.0, 0.25), film="float32", **integrator_kwargs):
     """run_scene_velocity_map with everything behind the film splat on the GPU (Scene.render_velocity_map): the same integrator, passes, seeds and traversals, but the
     films are developed, averaged and turned into the map by two kernels and only the results cross to the host.  Same return value; the map is bit for bit what
     calc_velocity_from_homo_heteros makes of the returned ToF images."""
@@ -119,7 +119,7 @@ def run_scene_velocity_map_device(scene, total_spp=1024, offsets=(0.0, 0.25), **
     integrator_kwargs.pop("hetero_frequency", None)
     scene.set_integrator(doppler_integrator_dict(hetero_frequency=0.0, hetero_offset=0.0, **integrator_kwargs))
     exposure_time, w_g = integrator_kwargs.get("exposure_time", 0.0015), integrator_kwargs.get("w_g", 30)
-    return scene.render_velocity_map(n_pass, single, [float(o) for o in offsets], exposure_time, w_g)
+    return scene.render_velocity_map(n_pass, single, [float(o) for o in offsets], exposure_time, w_g, film=film)
 
 
 def run_scene_velocity(scene, total_spp=1024, output_file=None):
