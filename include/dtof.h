@@ -128,6 +128,8 @@ int dtof_scene_get_info(const dtof_scene *scene, dtof_scene_info *info);
  * kind 25: the shading frames of a small rectangle-only scene's flat table (empty for any other scene) -> per top-level object 13 floats: instance mark (0 plain
  *                             rectangle, 1 instance, 2 instance of one rectangle), the rectangle's n[3] and dp_du[3], and the tangents sh_s[3], sh_t[3] of its shading frame
  *                             (initialize_sh_frame, include/mitsuba/render/interaction.h:258-268) as precomputed for the kernels; zeros for an instance
+ * kind 26: what a frame plan takes from the flat table (automatic pipeline, default switches) -> 4 floats: the one instance is the memo object of one rectangle
+ *                             (0 / 1), the table's shape is compiled into kernels (0 / 1: at most 8 objects), its object count, the index of the instance
  * kind 10: roughplastic tables -> per roughplastic shape the 64 values of m_external_transmittance (roughplastic.cpp:222-257)
  * Returns the number of floats written (<= capacity) through *n_written. */
 int dtof_scene_export(const dtof_scene *scene, int kind, float *out, size_t capacity, size_t *n_written);

@@ -57,6 +57,10 @@ class _Info(C.Structure):
                 ("filter_radius", C.c_float), ("filter_halo", C.c_int32), ("has_alpha", C.c_int32)]
 
 
+# dtof_kernels.h: kFlatShapeFields -- the presence bit, the object count (bits 19 .. 22) and the wall's index (bits 23 .. 25)
+_FLAT_SHAPE_FIELDS = 1 << 18 | 0xf << 19 | 0x7 << 23
+
+
 def lib_path():
     return os.environ.get("DTOF_LIB") or os.path.join(_HERE, "libdtof.so")   # DTOF_LIB: A/B timing of two builds (tools/ab_time.sh)
 
@@ -291,9 +295,21 @@ class Scene:
         return int(_lib().dtof_scene_plan_facts_launches(self._h))
 
     @property
-    def last_plan_facts(self):
-        """the FACTS mask of the first-bounce kernel compiled with the frame plan's constants that the last frame launched, 0 if it launched none"""
+    def last_plan_mask(self):
+        """the FACTS mask of the first-bounce kernel compiled with the frame plan's constants that the last frame launched, 0 if it launched none: what
+        dtof_scene_last_plan_facts reports -- the one-bit facts and, from bit 18 up, the shape fields of the flat table (dtof_kernels.h: kFactFlatShape)"""
         return int(_lib().dtof_scene_last_plan_facts(self._h))
+
+    @property
+    def last_plan_facts(self):
+        """the one-bit facts of last_plan_mask (bits 0 .. 17): what callers compare with the masks of facts; the shape fields are values and come as last_plan_shape"""
+        return self.last_plan_mask & ~_FLAT_SHAPE_FIELDS
+
+    @property
+    def last_plan_shape(self):
+        """(objects of the flat table, index of its one wall) compiled into the kernel the last frame launched, None if that kernel has no shape"""
+        m = self.last_plan_mask
+        return ((m >> 19) & 0xf, (m >> 23) & 0x7) if m & (1 << 18) else None
 
     def set_integrator(self, props):
         _check(_lib().dtof_scene_set_integrator(self._h, *_plugin_args(props)))

@@ -186,7 +186,24 @@ enum : uint32_t {
     kFactSineLowPass    = 1u << 15,  // rp.low_pass != 0 and rp.wave_type == WAVE_SIN: modulation_weight is amp * cos_(fmod_pos(w_d * t + phase + phi))
     kFactEmitterSampled = 1u << 16,  // depth + rp.inline_iters < rp.max_depth: every iteration of the launch samples an emitter (k_shade: active_next)
     kFactIdShift24      = 1u << 17,  // q.id_shift == 24
+    // ... and the SHAPE of the one-wall flat table: a presence bit and two fields that are VALUES, not facts of one bit each -- see flat_shape_fact
+    kFactFlatShape      = 1u << 18,  // (with kFactOneWall) bits 19 .. 22 hold rp.flat_objects (1 .. 8), bits 23 .. 25 rp.memo_obj (< rp.flat_objects)
 };
+// The shape fields: a launch's mask carries them whenever kFactOneWall holds and the table has at most 8 objects (FramePlan::launch_facts, read off the plan's blob);
+// a kernel compiled with a shape is taken only by a launch whose fields EQUAL its own (facts_hold), every other shape falls back to the kernels without one.
+constexpr uint32_t kFlatShapeCountShift = 19, kFlatShapeWallShift = 23, kFlatShapeMax = 8;
+constexpr uint32_t kFlatShapeFields = kFactFlatShape | 0xfu << kFlatShapeCountShift | 0x7u << kFlatShapeWallShift;
+constexpr uint32_t flat_shape_fact(uint32_t n_objects, uint32_t wall) {
+    return n_objects >= 1 && n_objects <= kFlatShapeMax && wall < n_objects ? kFactFlatShape | n_objects << kFlatShapeCountShift | wall << kFlatShapeWallShift : 0u;
+}
+constexpr uint32_t flat_shape_count(uint32_t facts) { return (facts & kFactFlatShape) ? (facts >> kFlatShapeCountShift) & 0xfu : 0u; }
+constexpr uint32_t flat_shape_wall(uint32_t facts) { return (facts >> kFlatShapeWallShift) & 0x7u; }
+// does a launch that satisfies `launch` meet every fact of the mask `kernel` was compiled with?  The one-bit facts as a subset, the shape fields by equality.
+constexpr bool facts_hold(uint32_t launch, uint32_t kernel) {
+    return (launch & kernel & ~kFlatShapeFields) == (kernel & ~kFlatShapeFields) && (!(kernel & kFactFlatShape) || (launch & kFlatShapeFields) == (kernel & kFlatShapeFields));
+}
+constexpr uint32_t kFactsFlatTable = kFactOneWall | kFlatShapeFields;   // what of a kernel's mask trace_flat is instantiated with
+static_assert(flat_shape_fact(5, 2) == 0x12c0000u && flat_shape_count(flat_shape_fact(5, 2)) == 5 && flat_shape_wall(flat_shape_fact(5, 2)) == 2 && flat_shape_fact(9, 2) == 0 && flat_shape_fact(5, 5) == 0, "shape fields");
 // The facts of (h).  A kernel that carries any of them AND kFactWavePixel also takes the lane mappings kFactWavePixel proves -- global lane = virtual lane (no stripes), the
 // pixel a shift of the wave's first lane by rp.spp_log2, the sample index a mask -- which the kernels compiled before (h) keep reading: their machine code does not move.
 constexpr uint32_t kFactsSampling = kFactStratifiedPairs | kFactPow2Strata | kFactSineLowPass | kFactEmitterSampled | kFactIdShift24;
@@ -202,13 +219,30 @@ constexpr uint32_t kHeadlineFacts = DTOF_HEADLINE_FACTS;
 #define DTOF_HEADLINE_FUSED 1
 #endif
 constexpr uint32_t kHeadlineFusedFacts = DTOF_HEADLINE_FUSED ? (kHeadlineFacts | kFactFusedSplat) : 0u;
-// ... and a third with the route facts of (h) on top of that: C2 again (stratified pairs, 32 strata, the sinusoidal low-pass weight), tried first; C3 (antithetic_mirror)
+// ... and a third with the route facts of (h) on top of that: C2 again (stratified pairs, 32 strata, the sinusoidal low-pass weight), tried before them; C3 (antithetic_mirror)
 // and whatever else breaks one of them keep the kernels above.  0: not built; A/B of a subset: DEFS=-DDTOF_HEADLINE_C2=0x6000
 #ifndef DTOF_HEADLINE_C2
 #define DTOF_HEADLINE_C2 0x3e000
 #endif
 constexpr uint32_t kHeadlineC2Facts = (DTOF_HEADLINE_C2) != 0 && kHeadlineFusedFacts != 0 ? (kHeadlineFusedFacts | (DTOF_HEADLINE_C2)) : 0u;
 static_assert(((DTOF_HEADLINE_C2) & ~kFactsSampling) == 0, "DTOF_HEADLINE_C2 names route facts only (bits 13 and up)");
+// ... and a fourth, tried first of all, with the shape of cornell_wall's flat table on top of that (i): DTOF_HEADLINE_SHAPE_COUNT rectangles, the wall at index
+// DTOF_HEADLINE_SHAPE_WALL.  A one-wall room of any other shape takes the kernel above.  A/B without it: DEFS=-DDTOF_HEADLINE_SHAPE_COUNT=0
+#ifndef DTOF_HEADLINE_SHAPE_COUNT
+#define DTOF_HEADLINE_SHAPE_COUNT 5
+#endif
+#ifndef DTOF_HEADLINE_SHAPE_WALL
+#define DTOF_HEADLINE_SHAPE_WALL 2
+#endif
+constexpr uint32_t kHeadlineShapeFacts = (DTOF_HEADLINE_SHAPE_COUNT) != 0 && (kHeadlineC2Facts & kFactOneWall) != 0 ? (kHeadlineC2Facts | flat_shape_fact(DTOF_HEADLINE_SHAPE_COUNT, DTOF_HEADLINE_SHAPE_WALL)) : 0u;
+static_assert((DTOF_HEADLINE_SHAPE_COUNT) == 0 || (kHeadlineC2Facts & kFactOneWall) == 0 || (kHeadlineShapeFacts & kFactFlatShape) != 0, "a shape has 1 .. 8 objects and the wall among them");
+// The two steps of (i) inside trace_flat under a shape, each with a switch for its A/B: the occlusion queries' straight-line sweep, the closest-hit queries' written-out walk
+#ifndef DTOF_FLAT_SHAPE_ANY
+#define DTOF_FLAT_SHAPE_ANY 1
+#endif
+#ifndef DTOF_FLAT_SHAPE_CLOSEST
+#define DTOF_FLAT_SHAPE_CLOSEST 1
+#endif
 // DTOF_WALL_FRAMES (default 1): under kFactOneWall the shading frames come precomputed -- the plain rectangles' from the DFlatFrame table of the blob, the moving wall's
 // normal and tangent from two registers filled once per path (k_shade) -- so that compute_surface runs no normalisation.  0 builds the facts without them (A/B).
 #ifndef DTOF_WALL_FRAMES

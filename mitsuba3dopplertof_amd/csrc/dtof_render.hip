@@ -422,6 +422,21 @@ SceneTraits scene_traits(const dtof_scene &sc) {
 // What one launch of the bounce loop covers when it starts at an iteration
 struct LaunchSpan { uint32_t span, chunk_blocks, res_units; bool next_runs, splat_here, terminal, resident; };
 
+// What a frame's plan takes from the scene's flat table (plan_frame; dtof_scene_export kind 26 shows it for the automatic pipeline and the default switches):
+struct FlatChoice { uint32_t memo_obj, flat_objects, facts; };
+FlatChoice flat_choice(const SceneTraits &t, bool fused, bool memo_on, bool flat_on) {
+    FlatChoice c;
+    // instance memo (dtof_traverse.h): pays when there is exactly one instance object, which then nearly every ray visits
+    c.memo_obj = fused && t.n_instances == 1 && memo_on ? t.last_instance : 0xffffffffu;
+    // a handful of rectangles: test them all instead of walking a tree (trace_flat in dtof_traverse.h)
+    c.flat_objects = fused && !t.has_tris && t.flat_off != 0 && flat_on ? t.n_objects : 0u;
+    // ... whose only instance is the memo object and holds one rectangle (kFactOneWall; the launch of such a scene keeps the instance matrix in LDS, k_shade: memo_m_lds),
+    // and then the table's shape, read off the blob's own counts: how many objects, and which of them the wall is (kFactFlatShape; 0 for more than 8 objects)
+    const bool one_wall = c.flat_objects != 0 && c.memo_obj < 32u && t.flat_general == 0 && t.flat_memo == (1u << c.memo_obj);
+    c.facts = one_wall ? kFactOneWall | flat_shape_fact(c.flat_objects, c.memo_obj) : 0u;
+    return c;
+}
+
 // Every decision of a frame, taken before its first launch.  The batch loop reads it and sets only the per-batch and per-launch fields of its copy of rp.
 struct FramePlan {
     RenderParams rp;                      // the frame's parameters, with the scene's flags and the kernel choices they carry
@@ -429,6 +444,7 @@ struct FramePlan {
     uint32_t n_passes = 1, run_passes = 1, dump_pass = 0;
     uint64_t lanes_per_row = 0, first = 0, last = 0, batch = 1;   // every pass: lanes [first, last) in batches of `batch`
     bool fused = false, first_inline = false, skip_tail = false, fuse_splat_ok = false, terminal_ok = false, plan_facts = false, one_wall = false;
+    uint32_t flat_shape = 0;              // the shape fields of the flat table under one_wall (flat_shape_fact), 0 if it has none
     uint32_t max_inline = 1, chunk_segs = 0, res_units = 1, n_emitters = 0, id_shift = 0;   // id_shift: Queues::id_shift of the frame's launches
     ResidentStage resident;
     LaunchSwitches launch;                // launch.defer: the DEFER mode, 0 when the workspaces have no DEFER lists
@@ -470,7 +486,7 @@ struct FramePlan {
         if (l.chunk_blocks == 1) f |= kFactOneBlock;
         if (n_emitters == 1) f |= kFactOneEmitter;
         if (r.flat_objects != 0) f |= kFactFlat;
-        if (one_wall) f |= kFactOneWall;
+        if (one_wall) f |= kFactOneWall | flat_shape;   // the shape fields are values: a launcher matches them by equality (facts_hold)
         // the routes of the correlated sampler's time draw and of the modulation weight; n_stratum & (n_stratum - 1): a power of two has one bit
         if ((f & kFactDopplerCorr) && r.time_sampling == TIME_STRATIFIED && r.stratify != 0 && r.tcn == 2 && r.pcn == 2 && r.shutter_open_time > 0.f && r.spp > 1) f |= kFactStratifiedPairs;
         if (r.n_stratum >= 2 && (r.n_stratum & (r.n_stratum - 1u)) == 0) f |= kFactPow2Strata;
@@ -608,13 +624,10 @@ FramePlan plan_frame(const dtof_scene *sc, const RenderRequest &rq) {
     rp.n_tlas_nodes = t.n_tlas_nodes; rp.has_nodes16 = t.has_nodes16; rp.has_blas = t.has_blas;   // deep per-mesh traversals diverge: see ray_shape() in dtof_kernels.hip
     // the eight-wave ray kernels of scenes with a BLAS and no analytic shape can run as a pair of launches, with 20 bytes per lane of lists
     if (!(t.has_blas && t.has_nodes16 && !t.has_analytic)) ls.defer = 0;
-    // instance memo (dtof_traverse.h): pays when there is exactly one instance object, which then nearly every ray visits
-    rp.memo_obj = p.fused && t.n_instances == 1 && on("DTOF_INSTANCE_MEMO") ? t.last_instance : 0xffffffffu;
-    // a handful of rectangles: test them all instead of walking a tree (trace_flat in dtof_traverse.h)
-    rp.flat_objects = p.fused && !rp.has_tris && t.flat_off != 0 && on("DTOF_FLAT") ? t.n_objects : 0u;
-    rp.flat_off = t.flat_off;
-    // ... whose only instance is the memo object and holds one rectangle (kFactOneWall; the launch of such a scene keeps the instance matrix in LDS, k_shade: memo_m_lds)
-    p.one_wall = rp.flat_objects != 0 && rp.memo_obj < 32u && t.flat_general == 0 && t.flat_memo == (1u << rp.memo_obj);
+    // the instance memo, the flat table and what the table proves (flat_choice)
+    const FlatChoice fc = flat_choice(t, p.fused, on("DTOF_INSTANCE_MEMO"), on("DTOF_FLAT"));
+    rp.memo_obj = fc.memo_obj; rp.flat_objects = fc.flat_objects; rp.flat_off = t.flat_off;
+    p.one_wall = (fc.facts & kFactOneWall) != 0; p.flat_shape = fc.facts & kFlatShapeFields;
     // Resident stage of the fused first-bounce kernel (k_shade<..., RESW>): scenes whose blob is too large to stage whole but whose TLAS (at most kResidentNodes nodes,
     // twice that as half-float planes, no per-mesh BLAS) and small records fit one CU's LDS beside the stack columns -- Domino: 1 024 nodes, one shared 12-triangle cube.
     // Waves: 16 (128 VGPRs) beat 12 once the nodes come from LDS, K = 4 too (Domino 44.2 vs 47.8 ms, C5 181.0 vs 192.7; profiles/r03_resident_stage_ab.txt,
@@ -1062,6 +1075,11 @@ int dtof_scene_export(const dtof_scene *sc, int kind, float *out, size_t cap, si
                     v.insert(v.end(), fr[i].s, fr[i].s + 3); v.insert(v.end(), fr[i].t, fr[i].t + 3);
                 }
             }
+        }
+        else if (kind == 26) {   // the flat table's facts as a frame plan takes them (automatic pipeline, default switches): kFactOneWall holds, a shape is known, its object count, its wall index
+            const SceneTraits t = scene_traits(*sc);
+            const FlatChoice c = flat_choice(t, t.blas_triangles <= 32768 && sc->host.textures.empty(), true, true);
+            v.push_back((c.facts & kFactOneWall) ? 1.f : 0.f); v.push_back((c.facts & kFactFlatShape) ? 1.f : 0.f); v.push_back((float) flat_shape_count(c.facts)); v.push_back((float) flat_shape_wall(c.facts));
         }
         else if (kind == 23) for (auto &s : sc->host.shapes) {   // blendbsdf: is one, weight, its texture, kind and two-sidedness of bsdf_1
             v.push_back(s.blend_other ? (s.two_bsdfs ? 2.f : 1.f) : 0.f); v.push_back(s.blend_weight); v.push_back((float) s.tex_blend);   // 1 blendbsdf, 2 twosided with two BSDFs

@@ -4,17 +4,19 @@
 namespace dtof {
 
 // The headline kernel (cornell_wall, C2 / C3: the staged first-bounce kernel of one film without area emitters) compiled with the frame plan's constants
-// (dtof_kernels.h: kFact*): taken when the launch satisfies every fact of its mask.  A kernel compiled with kFactFlat has no traversal stack: its launch carries
-// no stack column (ShadeLaunch::lds_flat).
+// (dtof_kernels.h: kFact*): taken when the launch satisfies every fact of its mask and has the mask's shape fields, if it has any (facts_hold).  A kernel compiled
+// with kFactFlat has no traversal stack: its launch carries no stack column (ShadeLaunch::lds_flat).
 template <uint32_t FACTS> static uint32_t launch_headline(const ShadeLaunch &L) {
-    if (FACTS == 0 || (L.facts & FACTS) != FACTS) return 0u;
+    if (FACTS == 0 || !facts_hold(L.facts, FACTS)) return 0u;
     hipLaunchKernelGGL((k_shade<true, 2, false, 1, false, 0, 0, false, FACTS>), dim3(L.grid), dim3(kShadeBlock), (FACTS & kFactFlat) ? L.lds_flat : L.lds, L.stream, L.args);
     return FACTS;
 }
 uint32_t launch_shade_plain(bool area, bool k4, const ShadeLaunch &L) {
-    // The most specific kernel whose mask holds: C2's with its sampling and modulation routes compiled in (kHeadlineC2Facts), then the one that splats whatever the routes
-    // (kFactFusedSplat), then the one that leaves the film to the splat kernels (C3, box filters); the generic instantiation below otherwise
+    // The most specific kernel whose mask holds: C2's with its sampling and modulation routes and the shape of its flat table compiled in (kHeadlineShapeFacts), then the
+    // one with the routes for a table of any other shape (kHeadlineC2Facts), then the one that splats whatever the routes (kFactFusedSplat), then the one that leaves
+    // the film to the splat kernels (C3, box filters); the generic instantiation below otherwise
     if (!area && !k4 && L.staged && L.mode == 2) {
+        if (uint32_t ran = launch_headline<kHeadlineShapeFacts>(L)) return ran;
         if (uint32_t ran = launch_headline<kHeadlineC2Facts>(L)) return ran;
         if (uint32_t ran = launch_headline<kHeadlineFusedFacts>(L)) return ran;
         if (uint32_t ran = launch_headline<kHeadlineFacts>(L)) return ran;

@@ -542,6 +542,74 @@ DTOF_D bool trace_flat(const SceneView &sv, ConstBytes flat_table, uint32_t flat
             a.c0 = F2{ u2f(r0.x), u2f(r0.y) }; a.c1 = F2{ u2f(r1.x), u2f(r1.y) }; a.c2 = F2{ u2f(r2.x), u2f(r2.y) }; a.c3 = F2{ u2f(r3.x), u2f(r3.y) };
             test(a, k, ro, rd, z);
         };
+        // The table's SHAPE as constants (kFactFlatShape: N objects, the wall at index WALL; DESIGN 8.3 (i), profiles/flat_shape_ab.txt): the walk is straight-line code --
+        // no counter, no compare, no pass loop, the z rows and records at immediate offsets.  One visit is still the one above, operation for operation.
+        constexpr uint32_t N = flat_shape_count(FACTS), WALL = flat_shape_wall(FACTS);
+        if constexpr (N != 0 && ANY && DTOF_FLAT_SHAPE_ANY) {
+            // Occlusion query: ONE sweep over the z rows and their certain-miss tests, then ONE branch -- where no lane of the wave needs a full test (every shadow
+            // ray of a closed room) the query ends there, unoccluded.  `occluded` is an OR: the tail may run the full tests in any order, and runs them in ascending one.
+            const DFlatObject *lts = (const DFlatObject *) (sv.base + flat_off);
+            const uint4 *zts = (const uint4 *) (lts + N) + 1;
+            float inv[12]; instance_memo_load(sv, inv);
+            const V3 wo = xf_point(inv, o), wd = xf_vector(inv, d);
+            bool any_need = false;
+#pragma unroll
+            for (uint32_t k = 0; k < N; ++k) {
+                const uint4 zr = zts[k];
+                const F2 z = k == WALL ? flat_zrow(u2f(zr.x), u2f(zr.y), u2f(zr.z), u2f(zr.w), wo, wd) : flat_zrow(u2f(zr.x), u2f(zr.y), u2f(zr.z), u2f(zr.w), o, d);
+                const bool need = !flat_certain_miss(z.x, z.y, far);
+                DTOF_STAT(kStat); DTOF_STAT_WAVE(kStat + 2);
+                if (!need) DTOF_STAT(kStat + 1);
+                any_need |= need;
+                if ((k & 1u) != 0) __builtin_amdgcn_sched_barrier(0);   // at most two z rows in flight (four registers each)
+            }
+            if (!__ballot(any_need)) return false;   // (uniform)
+            // the tail, out of line: the rectangles some lane still needs, each with the ray it belongs to (the z row again: the same operations give the same bits)
+#pragma unroll 1
+            for (uint32_t k = 0; k < N; ++k) {
+                const bool is_wall = k == WALL;
+                const V3 ro = is_wall ? wo : o, rd = is_wall ? wd : d;
+                const uint4 zr = zts[k];
+                const F2 z = flat_zrow(u2f(zr.x), u2f(zr.y), u2f(zr.z), u2f(zr.w), ro, rd);
+                const bool need = !flat_certain_miss(z.x, z.y, far);
+                if (!__ballot(need)) continue;   // (uniform)
+                DTOF_STAT_WAVE(kStat + 3);
+                const uint4 *rp4 = (const uint4 *) (lts + k);
+                const uint4 r0 = rp4[0], r1 = rp4[1], r2 = rp4[2], r3 = rp4[3];
+                FlatRecord a;
+                a.c0 = F2{ u2f(r0.x), u2f(r0.y) }; a.c1 = F2{ u2f(r1.x), u2f(r1.y) }; a.c2 = F2{ u2f(r2.x), u2f(r2.y) }; a.c3 = F2{ u2f(r3.x), u2f(r3.y) };
+                test(a, k, ro, rd, z);
+            }
+            return occluded;
+        } else if constexpr (N != 0 && !ANY && DTOF_FLAT_SHAPE_CLOSEST) {
+            // Closest hit: the N visits written out in ascending order (strict < keeps the tie rule), each with its forward skip over the full test
+            const DFlatObject *lts = (const DFlatObject *) (sv.base + flat_off);
+            const uint4 *zts = (const uint4 *) (lts + N) + 1;
+            auto visit_at = [&](uint32_t k, const V3 &ro, const V3 &rd) {
+                const uint4 zr = zts[k];
+                const F2 z = flat_zrow(u2f(zr.x), u2f(zr.y), u2f(zr.z), u2f(zr.w), ro, rd);
+                const bool need = !flat_certain_miss(z.x, z.y, far);
+                DTOF_STAT(kStat); DTOF_STAT_WAVE(kStat + 2);
+                if (!need) DTOF_STAT(kStat + 1);
+                if (!__ballot(need)) return;   // (uniform)
+                DTOF_STAT_WAVE(kStat + 3);
+                const uint4 *rp4 = (const uint4 *) (lts + k);
+                const uint4 r0 = rp4[0], r1 = rp4[1], r2 = rp4[2], r3 = rp4[3];
+                FlatRecord a;
+                a.c0 = F2{ u2f(r0.x), u2f(r0.y) }; a.c1 = F2{ u2f(r1.x), u2f(r1.y) }; a.c2 = F2{ u2f(r2.x), u2f(r2.y) }; a.c3 = F2{ u2f(r3.x), u2f(r3.y) };
+                test(a, k, ro, rd, z);
+            };
+#pragma unroll
+            for (uint32_t k = 0; k < N; ++k) {
+                if (k == WALL) {
+                    float inv[12]; instance_memo_load(sv, inv);
+                    const V3 wo = xf_point(inv, o), wd = xf_vector(inv, d);
+                    visit_at(k, wo, wd);
+                } else visit_at(k, o, d);
+                __builtin_amdgcn_sched_barrier(0);   // one visit's reads at a time: hoisted together they take the kernel past its register cap
+            }
+            return best.obj != 0xffffffffu;
+        }
         const uint32_t wall = sv.memo_obj;   // < n_objects: a bit of the table's memo mask (kFactOneWall)
         // ONE copy of the plain rectangles' body, run for both segments (two passes of an outer loop the compiler must keep: written out or unrolled, the three bodies
         // of each of the three call sites take C2's kernel to its register cap and two values to scratch); the wall's body, with its ray, sits behind the first pass.
