@@ -443,6 +443,12 @@ int dtof_ray_intersect(dtof_scene *scene, uint32_t n, const float *rays8, float 
  * coordinates on a triangle, the local position on a rectangle or disk), as the reference's tests of meshes assert them (src/render/tests/test_mesh.py:258-292) */
 int dtof_ray_intersect_uv(dtof_scene *scene, uint32_t n, const float *rays8, float *out19, int32_t *ids3, float *uv4);
 int dtof_ray_test(dtof_scene *scene, uint32_t n, const float *rays8, int32_t *occluded);
+/* The ray query of the fused kernels of FLAT scenes (rectangles only, at most 8 top-level objects: every ray tests them all, no tree) over arrays, through the
+ * instantiations of that query the shade kernels carry.  form 0: the generic walk; 1: the one-wall walk (exactly one instance, of one rectangle); 2: the walk compiled
+ * for the headline's table (5 rectangles, the wall at index 2).  rays8 as above.  any = 0: closest hit, out3 = t, u, v (inf, 0, 0 on a miss), ids = the object (-1 on a
+ * miss); any != 0: occlusion, ids = 1 / 0 (out3 is not written).  DTOF_ERR_INVALID, before anything is launched, for a scene without a flat table, a form whose facts
+ * the scene does not meet, and n above 2^24; non-finite ray components are taken as they are. */
+int dtof_flat_query(dtof_scene *scene, int form, int any, uint32_t n, const float *rays8, float *out3, int32_t *ids);
 
 /* ---------------------------------------------------------------- component evaluation
  * The device functions the shade and splat kernels are built from, evaluated over arrays on the GPU: the counterpart of the

@@ -156,6 +156,7 @@ def _lib():
                        ("dtof_render_stripes_variants", stripes + [C.POINTER(_Stats)]), ("dtof_render_stripes_variants_async", stripes),
                        ("dtof_sample_lanes_variants", [vp, C.c_uint32, C.c_uint32, vp, C.c_int, C.c_uint64, C.c_uint64, vp, vp, vp]),
                        ("dtof_emitter_eval", [vp, C.c_int, C.c_int, C.c_int32, C.c_uint32, vp, vp]),
+                       ("dtof_flat_query", [vp, C.c_int, C.c_int, C.c_uint32, vp, vp, vp]),
                        ("dtof_develop_accumulate_async", [vp, vp, C.c_int32, C.c_uint64, vp, C.c_int64, C.c_int]),
                        ("dtof_velocity_map_async", [vp, vp, C.c_int, vp, vp, C.c_uint32, C.c_double, C.c_double, C.c_int64, vp, vp, vp]),
                        ("dtof_velocity_map_variants", [vp, C.c_int, vp]),
@@ -580,6 +581,18 @@ class Scene:
         occ = np.zeros(len(rays), np.int32)
         _check(_lib().dtof_ray_test(self._h, len(rays), rays.ctypes.data, occ.ctypes.data))
         return occ != 0
+
+    FLAT_FORMS = {"generic": 0, "one_wall": 1, "shape": 2}
+
+    def flat_query(self, rays8, form=0, any=False):
+        """The ray query of a flat scene's fused kernels over an (n, 8) array of rays o, d, time, maxt (dtof_flat_query).  form: 0 / "generic", 1 / "one_wall",
+        2 / "shape" -- the instantiation of trace_flat that runs.  Closest hit -> dict(t, u, v, obj) (inf, 0, 0, -1 on a miss); any=True -> int32 array of 1 / 0.
+        A scene without a flat table, a form whose facts the scene does not meet and more than 2^24 rays raise DtofError; non-finite components are taken as they are."""
+        rays = np.ascontiguousarray(rays8, np.float32).reshape(-1, 8)
+        form = self.FLAT_FORMS.get(form, form)
+        out, ids = np.zeros((len(rays), 3), np.float32), np.zeros(len(rays), np.int32)
+        _check(_lib().dtof_flat_query(self._h, int(form), 1 if any else 0, len(rays), rays.ctypes.data, None if any else out.ctypes.data, ids.ctypes.data))
+        return ids if any else {"t": out[:, 0], "u": out[:, 1], "v": out[:, 2], "obj": ids}
 
     def cancel(self):
         _lib().dtof_cancel(self._h)

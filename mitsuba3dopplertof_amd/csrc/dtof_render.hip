@@ -10,6 +10,7 @@
 #include "dtof_kernels.h"
 #include "dtof_reconstruct.h"
 #include "dtof_film64.h"
+#include "dtof_flat_query.h"
 #include "dtof_scene.h"
 #include "dtof_math.h"
 #include <atomic>
@@ -1806,6 +1807,31 @@ static int ray_query(dtof_scene *sc, uint32_t n, const float *rays8, float *out1
 int dtof_ray_intersect(dtof_scene *sc, uint32_t n, const float *rays8, float *out19, int32_t *ids3) { return ray_query(sc, n, rays8, out19, ids3, false); }
 int dtof_ray_intersect_uv(dtof_scene *sc, uint32_t n, const float *rays8, float *out19, int32_t *ids3, float *uv4) { return ray_query(sc, n, rays8, out19, ids3, false, uv4); }
 int dtof_ray_test(dtof_scene *sc, uint32_t n, const float *rays8, int32_t *occluded) { return ray_query(sc, n, rays8, nullptr, occluded, true); }
+
+// trace_flat over arrays (dtof_flat_query.hip): the query a frame of this scene runs at every path vertex, in the form asked for
+int dtof_flat_query(dtof_scene *sc, int form, int any, uint32_t n, const float *rays8, float *out3, int32_t *ids) {
+    return guarded([&] {
+        if (!sc || (n && (!rays8 || !ids || (!any && !out3)))) throw std::runtime_error("null argument");
+        if (form < 0 || form >= (int) kFlatQueryForms) throw std::runtime_error("dtof_flat_query: form must be 0 (generic), 1 (one_wall) or 2 (shape)");
+        if (n > (1u << 24)) throw std::runtime_error("dtof_flat_query: more than 2^24 rays in one call");
+        // the memo object and the object count of a frame plan (automatic pipeline, default switches: dtof_scene_export kind 26)
+        const SceneTraits t = scene_traits(*sc);
+        const FlatChoice c = flat_choice(t, t.blas_triangles <= 32768 && sc->host.textures.empty(), true, true);
+        if (c.flat_objects == 0) throw std::runtime_error("dtof_flat_query: the scene has no flat table (rectangles only, at most 8 objects, fused pipeline)");
+        if (form >= 1 && !(c.facts & kFactOneWall)) throw std::runtime_error("dtof_flat_query: the one_wall and shape forms need exactly one instance that holds one rectangle");
+        if (form == 2 && (flat_query_facts(2) == 0 || (c.facts & kFlatShapeFields) != (flat_query_facts(2) & kFlatShapeFields)))
+            throw std::runtime_error("dtof_flat_query: the shape form is compiled for a table of " + std::to_string(flat_shape_count(flat_query_facts(2))) + " rectangles with the wall at index " +
+                                     std::to_string(flat_shape_wall(flat_query_facts(2))) + ", this table has " + std::to_string(c.flat_objects) + " and " + std::to_string(c.memo_obj));
+        ensure_device(sc);
+        DevBuf<float> dr, dout; DevBuf<int32_t> dids;
+        dr.ensure((size_t) n * 8); dout.ensure(any ? 1 : (size_t) n * 3); dids.ensure(n);
+        if (n) HIP_CHECK(hipMemcpy(dr.p, rays8, (size_t) n * 32, hipMemcpyHostToDevice));
+        launch_flat_query(sc->d_blob.p, (uint32_t) sc->blob.size(), t.flat_off, c.flat_objects, c.memo_obj, form, any != 0, dr.p, dout.p, dids.p, n, nullptr);
+        HIP_CHECK(hipGetLastError());
+        if (n && !any) HIP_CHECK(hipMemcpy(out3, dout.p, (size_t) n * 12, hipMemcpyDeviceToHost));
+        if (n) HIP_CHECK(hipMemcpy(ids, dids.p, (size_t) n * 4, hipMemcpyDeviceToHost));
+    });
+}
 
 #ifdef DTOF_TRAVERSAL_STATS
 // development builds (make STATS=1): read and reset the traversal counters of dtof_traverse.h

@@ -200,6 +200,8 @@ def lib():
         L.orc_kat_bsdf.argtypes = [C.POINTER(OrcShape), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.orc_kat_bsdf_n.argtypes = [C.POINTER(OrcShape), C.c_uint32, C.c_void_p, C.c_void_p]
         L.orc_kat_emitter_n.argtypes = [C.POINTER(OrcScene), C.c_int, C.c_int32, C.c_uint32, C.c_void_p, C.c_void_p]
+        L.orc_kat_flat_n.restype = C.c_uint32
+        L.orc_kat_flat_n.argtypes = [C.POINTER(OrcScene), C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
         L.orc_kat_emitter_sample.argtypes = [C.POINTER(OrcScene), C.c_int, C.c_void_p, C.c_float, C.c_float, C.c_void_p]
         L.orc_kat_sphere_sample_direction.argtypes = [C.POINTER(OrcShape), C.c_void_p, C.c_float, C.c_float, C.c_void_p]
         L.orc_kat_shape_area.restype = C.c_float
@@ -461,6 +463,19 @@ class Scene:
         p = make_params(pd)
         lib().orc_render_lanes(C.byref(self.c), C.byref(p), seed, spp, lane_begin, n, out.ctypes.data, threads)
         return out
+
+    def flat_n(self, rays8, operands=True):
+        """orc_kat_flat_n: (n, 8) rays o, d, time, maxt -> dict(t, u, v, obj, occluded, rect_obj[, ops (n, rects, ORC_FLAT_OPS): zx, zy, t, u, v, best])"""
+        rays8 = np.ascontiguousarray(rays8, np.float32).reshape(-1, 8)
+        n, L = len(rays8), lib()
+        slots = int(L.orc_kat_flat_n(C.byref(self.c), 0, None, None, None, None, 0, None))
+        out3, ids2, rect_obj = np.zeros((n, 3), np.float32), np.zeros((n, 2), np.int32), np.zeros(max(slots, 1), np.int32)
+        ops = np.zeros((n, slots, 6), np.float32) if operands else None
+        L.orc_kat_flat_n(C.byref(self.c), n, rays8.ctypes.data, out3.ctypes.data, ids2.ctypes.data, ops.ctypes.data if operands and ops.size else None, slots, rect_obj.ctypes.data)
+        r = dict(t=out3[:, 0], u=out3[:, 1], v=out3[:, 2], obj=ids2[:, 0], occluded=ids2[:, 1], rect_obj=rect_obj[:slots])
+        if operands:
+            r["ops"] = ops
+        return r
 
     def render(self, pd, seed=0, spp=None, rows=None, threads=1, raw=False):
         spp = spp or pd["sample_count"]
