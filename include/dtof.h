@@ -372,6 +372,35 @@ int dtof_develop_rgba_f64_async(dtof_scene *scene, const double *d_film64_rgbw, 
 int dtof_render_velocity_map_f64(dtof_scene *scene, uint32_t n_passes, uint32_t spp, const float *offsets, int n_offsets, double exposure_time, double w_g_mhz,
                                  double *out_velocity, double *out_velocity_pairs_or_null, float *out_tof_or_null, dtof_render_stats *stats);
 
+/* ---------------------------------------------------------------- moment film (opt-in)
+ * What the reference's `moment` integrator records (src/integrators/moment.cpp:85-104): besides the image, the XYZ of every sample (srgb_to_xyz,
+ * include/mitsuba/core/spectrum.h:396-402) and its square, as AOVs that ImageBlock::put filters like the image (src/render/imageblock.cpp:414-531) -- here for every
+ * variant of one traversal, plus the cross moment Y_j * Y_k of every pair of variants, which the reference has no counterpart of: the variants share their paths, so
+ * the covariance of a homodyne / heterodyne pair (and with it a standard error of their ratio, the velocity map) is a by-product of the render.  Per lane and variant,
+ * in float32 without fused multiply-adds: X = (0.412453 r + 0.357580 g) + 0.180423 b, Y = (0.212671 r + 0.715160 g) + 0.072169 b,
+ * Z = (0.019334 r + 0.119193 g) + 0.950227 b, the squares X X, Y Y, Z Z and the products Y_j Y_k.  Every value is splatted with the footprint and the float32 weights
+ * of the float64 film: the term value * (wx * wy) is a float32 product (the box filter adds the value itself and 1), converted to double and added in double.
+ * The P(K) = 1 + 6 K + K (K - 1) / 2 planes of K variants, H * W doubles each:
+ *   0                       sum w (shared by all planes)
+ *   1 + 6 k + 0 .. 2        sum w X_k, w Y_k, w Z_k           k = 0 .. K - 1
+ *   1 + 6 k + 3 .. 5        sum w X_k^2, w Y_k^2, w Z_k^2
+ *   1 + 6 K + ...           sum w Y_j Y_k for (j, k) = (0,1), (0,2), (0,3), (1,2), (1,3), (2,3) restricted to k < K, in that order
+ * The moments are those of the colour channels: the alpha film of an rgba scene is not part of them (such a scene is accepted, its alpha is not accumulated).  The
+ * first-bounce kernel never splats into this film: dtof_render_stats::n_fused_splat_launches stays 0. */
+
+/* P(K) of the moment film (the AOV count of src/integrators/moment.cpp:57-65 per integrator, filtered by src/render/imageblock.cpp:414-531, plus the weight and the pair
+ * planes): n_variants 0 counts as 1 (the integrator's own pair); n_variants < 0 or > 4: -1.  Needs no device. */
+int dtof_moment_planes(int n_variants);
+/* The moment film of n_passes traversals (src/integrators/moment.cpp:85-104 through ImageBlock::put, src/render/imageblock.cpp:414-531, with a double accumulator):
+ * the library's own film is zeroed ONCE, pass i is rendered with seed + i and `spp` samples per pixel (0 = the sampler's sample count) and all passes accumulate into
+ * it -- the raw sums add across passes.  developed != 0: every plane but plane 0 is divided in double by (W == 0 ? 1 : W) on the device (the weighted means
+ * E[X], E[X^2], E[Y_j Y_k] that HDRFilm::develop would make of the AOVs, src/films/hdrfilm.cpp:305-406); developed == 0: the raw sums.  out_planes: P(n_variants) planes
+ * of crop_height * crop_width doubles.  variants == NULL with n_variants == 0: the integrator's own pair (K = 1).  `stats` (may be NULL) sums the passes.
+ * DTOF_ERR_INVALID before any device call: a null scene or output, n_passes == 0, n_variants outside 0 .. 4, n_variants > 0 without variants, variants under an integrator
+ * other than `dopplertofpath`.  Without a device: DTOF_ERR_HIP. */
+int dtof_render_moments(dtof_scene *scene, uint32_t seed, uint32_t spp, uint32_t n_passes, const dtof_modulation *variants_or_null, int n_variants, int developed,
+                        double *out_planes, dtof_render_stats *stats);
+
 /* Integrator::cancel / should_stop (include/mitsuba/render/integrator.h:96-109). */
 void dtof_cancel(dtof_scene *scene);
 /* First-bounce launches of this scene, since it was loaded, that ran a kernel compiled with the frame plan's constants (dtof_render_stats::n_plan_facts_launches): the

@@ -16,7 +16,7 @@ import os
 import numpy as np
 
 __all__ = ["load_file", "load_string", "load_dict", "Scene", "Integrator", "Sampler", "DtofError", "render",
-           "render_multi_pass", "to_tof_image", "lib_path", "ETimeSampling", "velocity_map_variants"]
+           "render_multi_pass", "to_tof_image", "lib_path", "ETimeSampling", "velocity_map_variants", "MOMENT_PLANES"]
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB = None
@@ -164,7 +164,9 @@ def _lib():
                        ("dtof_render_velocity_map_f64", [vp, C.c_uint32, C.c_uint32, vp, C.c_int, C.c_double, C.c_double, vp, vp, vp, C.POINTER(_Stats)]),
                        ("dtof_render_variants_f64", [vp, C.c_uint32, C.c_uint32, vp, C.c_int, vp, vp, C.POINTER(_Stats)]),
                        ("dtof_render_rows_variants_f64", rows[:-1] + [vp, C.c_int32, C.c_uint64, C.POINTER(_Stats)]),
-                       ("dtof_develop_f64_async", [vp, vp, vp, C.c_int64]), ("dtof_develop_rgba_f64_async", [vp, vp, vp, vp, C.c_int64])):
+                       ("dtof_develop_f64_async", [vp, vp, vp, C.c_int64]), ("dtof_develop_rgba_f64_async", [vp, vp, vp, vp, C.c_int64]),
+                       ("dtof_moment_planes", [C.c_int]),
+                       ("dtof_render_moments", [vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, C.c_int, C.c_int, vp, C.POINTER(_Stats)])):
         if hasattr(L, name):   # a DTOF_LIB build from before the variants (A/B timing against an older commit) loads; calling what it lacks still raises
             getattr(L, name).argtypes = args
     _LIB = L
@@ -190,6 +192,10 @@ def _plugin_args(d):
     """{'type': 'dopplertofpath', 'max_depth': 4, ...} -> (plugin, names, types, values, n) for the C ABI"""
     d = dict(d)
     plugin = d.pop("type", "")
+    if plugin == "moment":   # its one property is a nested plugin, which these flat arrays cannot carry
+        raise DtofError('the "moment" integrator wraps a nested integrator, which a property dictionary cannot carry here: declare it in the scene file '
+                        '(<integrator type="moment"><integrator type="dopplertofpath"> ... </integrator></integrator>) or set the nested integrator itself; '
+                        'the moments come from Scene.render_moments either way')
     names, types, values = [], [], []
     for k, v in d.items():
         names.append(str(k).encode())
@@ -243,6 +249,14 @@ def _film64(film):
     if film not in FILMS:
         raise DtofError('film must be "float32" or "float64", not %r' % (film,))
     return film == "float64"
+
+
+def MOMENT_PLANES(n_variants=1):
+    """planes of the moment film of `n_variants` variants (dtof_moment_planes): 1 + 6 K + K (K - 1) / 2, 0 counting as 1; -1 outside 0 .. 4"""
+    return int(_lib().dtof_moment_planes(int(n_variants)))
+
+
+_MOMENT_PAIRS = ((0, 1), (0, 2), (0, 3), (1, 2), (1, 3), (2, 3))   # the order of the cross planes (dtof.h), restricted to k < K
 
 
 MAX_VELOCITY_OFFSETS = 16   # offsets one velocity map combines (kMaxVelocityPairs)
@@ -384,6 +398,38 @@ class Scene:
         film, behind the K colour planes of an rgba scene).  The images are the films developed in double: (float) (RGB / (W == 0 ? 1 : W)).  `variants`: up to four
         (hetero_frequency, hetero_offset) pairs; None: the integrator's own pair (K = 1)."""
         return self._render_f64(seed, spp, variants, True)
+
+    def render_moments(self, seed=0, spp=0, n_passes=1, variants=None, raw=False):
+        """The moment film of `n_passes` traversals with seeds seed, seed + 1, ... (dtof_render_moments): per pixel the filtered first and second moments of the
+        samples' XYZ -- what the reference's `moment` integrator writes as AOVs -- of every variant of the traversal, and the cross moments of their Y.  Returns a dict
+        of float64 arrays:
+            "weight" (H, W)           sum of the filter weights
+            "mean"   (K, H, W, 3)     weighted mean of X, Y, Z
+            "m2"     (K, H, W, 3)     weighted mean of X^2, Y^2, Z^2
+            "cross"  (K, K, H, W)     weighted mean of Y_j Y_k: symmetric, its diagonal is m2[..., 1]
+        raw=True: the undivided sums under the same keys.  `variants`: up to four (hetero_frequency, hetero_offset) pairs; None: the integrator's own pair (K = 1).
+        The alpha channel of an rgba film is not part of the moments.  last_stats sums the passes.  harness.moment_statistics turns the dict into variances."""
+        var = None if variants is None else _variant_array(variants)
+        if var is not None and not 1 <= len(var) <= MAX_VARIANTS:
+            raise DtofError("between 1 and 4 modulation variants make a moment film")
+        k = 1 if var is None else len(var)
+        w, h = self.size
+        planes = np.zeros((MOMENT_PLANES(k), h, w), np.float64)
+        st = _Stats()
+        _check(_lib().dtof_render_moments(self._h, int(seed), int(spp), int(n_passes), None if var is None else var.ctypes.data, 0 if var is None else k,
+                                          0 if raw else 1, planes.ctypes.data, C.byref(st)))
+        self.last_stats = st.as_dict()
+        per = planes[1:1 + 6 * k].reshape(k, 6, h, w)
+        cross = np.zeros((k, k, h, w), np.float64)
+        for a in range(k):
+            cross[a, a] = per[a, 4]
+        slot = 1 + 6 * k
+        for a, b in _MOMENT_PAIRS:
+            if b < k:
+                cross[a, b] = cross[b, a] = planes[slot]
+                slot += 1
+        return {"weight": planes[0].copy(), "mean": np.ascontiguousarray(np.moveaxis(per[:, 0:3], 1, -1)),
+                "m2": np.ascontiguousarray(np.moveaxis(per[:, 3:6], 1, -1)), "cross": cross}
 
     def set_film_layout(self, planes, plane_stride_floats=0):
         """Declare the caller's device film for render_rows / render_stripes (dtof_scene_set_film_layout): `planes` RGBW planes, `plane_stride_floats` apart (0 = dense

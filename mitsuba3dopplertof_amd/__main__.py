@@ -5,6 +5,8 @@ plugins this library implements:
                                                [--offsets 0,0.25,0.5,0.75] [--film float64] [-v]
     python -m mitsuba3dopplertof_amd scene.xml --velocity-map 0,0.25 [--w-g 30 --exposure-time 0.0015] [--spp N] [-o out.npy]
         the radial-velocity map of the scene's dopplertofpath integrator (float64 .npy), reconstructed on the GPU: passes of min(1024, N) samples, seeds 0, 1, ...
+    python -m mitsuba3dopplertof_amd scene.xml --moments [--variants 0:0,1:0] [--passes N] [--spp N] [-o out.npz]
+        the per-pixel moment film of one traversal per pass (weight, mean, m2, cross: Scene.render_moments), written with np.savez
     python -m torch.distributed.run --nproc-per-node G --master-addr 127.0.0.1 -m mitsuba3dopplertof_amd scene.xml ...
         one process per GPU: the pixel rows are sharded across the G ranks, rank 0 gathers and writes the image
 """
@@ -34,6 +36,11 @@ def parser():
     ap.add_argument("--exposure-time", type=float, default=0.0015, help="--velocity-map: exposure time in seconds")
     ap.add_argument("--film", default="float32", choices=("float32", "float64"),
                     help="the film's accumulator: float64 sums the splat in double on the GPU (order-independent images and velocity maps; single GPU)")
+    ap.add_argument("--moments", action="store_true",
+                    help="write the per-pixel moment film (sample mean, second moments and the variants' cross moments, float64 .npz) instead of an image")
+    ap.add_argument("--variants", default=None, metavar="F:O,F:O",
+                    help="--moments: up to four hetero_frequency:hetero_offset pairs evaluated in ONE traversal (default: the integrator's own pair)")
+    ap.add_argument("--passes", type=int, default=1, help="--moments: passes with seeds --seed, --seed + 1, ... that accumulate into one film")
     ap.add_argument("-v", "--verbose", action="store_true")
     return ap
 
@@ -60,6 +67,51 @@ def check_velocity_map_args(ap, args):
         ap.error("--velocity-map expects comma separated numbers")
 
 
+def parse_variants(text):
+    """'f:o,f:o,...' -> [(hetero_frequency, hetero_offset), ...]"""
+    pairs = []
+    for item in text.split(","):
+        f, o = item.split(":")
+        pairs.append((float(f), float(o)))
+    return pairs
+
+
+def check_moments_args(ap, args):
+    """what --moments cannot be combined with, refused before the scene is loaded"""
+    if args.velocity_map is not None:
+        ap.error("--moments and --velocity-map are two outputs: run them separately")
+    if args.stripes > 0 or int(os.environ.get("WORLD_SIZE", "1")) > 1:
+        ap.error("--moments is a single-GPU feature: it cannot be combined with --stripes or a multi-GPU launch")
+    if args.film == "float64":
+        ap.error("--moments accumulates in double already: do not combine it with --film float64")
+    if args.offsets is not None:
+        ap.error("--moments takes --variants (hetero_frequency:hetero_offset pairs), not --offsets")
+    if args.passes < 1:
+        ap.error("--passes must be at least 1")
+    if args.output is not None and not args.output.lower().endswith(".npz"):
+        ap.error("--moments writes a float64 .npz file")
+    if args.variants is not None:
+        try:
+            n = len(parse_variants(args.variants))
+        except ValueError:
+            ap.error("--variants expects comma separated hetero_frequency:hetero_offset pairs")
+        if not 1 <= n <= 4:
+            ap.error("--variants takes between 1 and 4 pairs")
+
+
+def moments(args, scene):
+    """--moments: Scene.render_moments of --passes passes, the dict written with np.savez"""
+    out = args.output or os.path.splitext(args.scene)[0] + "_moments.npz"
+    t0 = time.time()
+    m = scene.render_moments(seed=args.seed, spp=args.spp, n_passes=args.passes, variants=parse_variants(args.variants) if args.variants else None)
+    dt = time.time() - t0
+    os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+    np.savez(out, **m)
+    if args.verbose:
+        print("Moment film finished. (took %.1f ms, %d passes, %s)" % (dt * 1e3, args.passes, scene.last_stats))
+    return 0
+
+
 def velocity_map(args, scene):
     """--velocity-map: the passes of harness._passes (the sampler's sample count when --spp is 0), one traversal per two offsets and pass, everything behind the film
     splat on the GPU (Scene.render_velocity_map)"""
@@ -82,6 +134,10 @@ def main(argv=None):
     ap = parser()
     args = ap.parse_args(argv)
     check_film_args(ap, args)
+    if args.moments:
+        check_moments_args(ap, args)
+    elif args.variants is not None or args.passes != 1:
+        ap.error("--variants and --passes belong to --moments")
     if args.velocity_map is not None:
         check_velocity_map_args(ap, args)
     import mitsuba3dopplertof_amd as mi
@@ -96,6 +152,8 @@ def main(argv=None):
         scene = mi.load_file(args.scene, **defines)
         if args.velocity_map is not None:
             return velocity_map(args, scene)
+        if args.moments:
+            return moments(args, scene)
         t0 = time.time()
         offsets = [float(x) for x in args.offsets.split(",")] if args.offsets else None
         world = int(os.environ.get("WORLD_SIZE", "1"))

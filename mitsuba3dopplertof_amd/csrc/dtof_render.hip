@@ -10,6 +10,7 @@
 #include "dtof_kernels.h"
 #include "dtof_reconstruct.h"
 #include "dtof_film64.h"
+#include "dtof_moments.h"
 #include "dtof_flat_query.h"
 #include "dtof_scene.h"
 #include "dtof_math.h"
@@ -102,6 +103,7 @@ struct dtof_scene {
     Workspace ws;
     DevBuf<float> d_film, d_rgb;
     DevBuf<double> d_film64;   // the library's own float64 film (dtof_render_variants_f64, dtof_render_velocity_map_f64)
+    DevBuf<double> d_moments, d_moment_planes;   // the moment film (dtof_render_moments): cells of kMomentCell doubles per pixel, and the dense planes copied out
     DevBuf<float> d_vm_sum, d_vm_tof; DevBuf<double> d_vm_maps;   // dtof_render_velocity_map: the passes' sum, the ToF images, the per-pair maps and the combined map
     // the caller's device film as declared with dtof_scene_set_film_layout (0 = not declared: colour planes only, W * H * 4 apart)
     int32_t film_planes = 0; uint64_t film_plane_stride = 0;
@@ -357,6 +359,7 @@ struct RenderRequest {
     float4 *lane_planes = nullptr;                // lane dumps: [films()][dump_n] results of every film (q.res), besides film 0's in lane_dump
     float *film = nullptr; uint64_t film_stride = 0;   // K films (and the alpha film behind them) film_stride floats apart
     double *film64 = nullptr; uint64_t film64_stride = 0;   // ... or the float64 film, film64_stride doubles apart: the separate splat stage accumulates in double (dtof_film64.hip)
+    double *moments = nullptr;                    // ... or the moment film (dtof_moments.h: cells of kMomentCell doubles), likewise the separate splat stage's; no alpha film
     dtof_render_stats *stats = nullptr;
     LaneDebug *lane_dump = nullptr; uint64_t dump_begin = 0, dump_n = 0;   // lane_dump != nullptr: evaluate only lanes [dump_begin, dump_begin + dump_n) and copy their records out
     bool deferred = false;                        // dtof_render_rows_async: timings by events, no counters read back, no synchronisation at the end
@@ -667,7 +670,7 @@ FramePlan plan_frame(const dtof_scene *sc, const RenderRequest &rq) {
     // splat kernel, which sums 8 samples per lane before it reduces, is faster
     p.fuse_splat_ok = on("DTOF_FUSE_SPLAT") && p.fused && !rq.lane_dump && p.n_passes == 1 && !se.alpha && rp.filter == FILTER_TENT && rp.filter_radius <= 1.f &&
                       rp.filter_radius > .5f && rp.spp_log2 == 6 && rp.n_offsets == 1 && rq.film != nullptr;
-    if (rq.film64) p.fuse_splat_ok = false;   // the float64 film is the separate splat stage's: k_shade splats in float32
+    if (rq.film64 || rq.moments) p.fuse_splat_ok = false;   // the float64 film and the moment film are the separate splat stage's: k_shade splats in float32
     return p;
 }
 
@@ -760,8 +763,9 @@ void render_rows(dtof_scene *sc, const RenderRequest &rq) {
             HIP_CHECK(hipStreamSynchronize(s));
         } else if (!rq.lane_dump && !fused_splat_done) {
             t = tm.begin(kStageSplat, s);
-            if (rq.film64) launch_splat_f64(rp, q, rq.film64, rq.film64_stride, s); else launch_splat(rp, q, rq.film, rq.film_stride, p.launch, s);
-            if (sc->host.sensor.alpha) {   // the alpha film (plane K behind the K offset films): the same splat over (valid, 0, 0) -- ImageBlock::put of aovs[3] (integrator.cpp:528-533)
+            if (rq.moments) launch_splat_moments(rp, q, rq.moments, s);
+            else if (rq.film64) launch_splat_f64(rp, q, rq.film64, rq.film64_stride, s); else launch_splat(rp, q, rq.film, rq.film_stride, p.launch, s);
+            if (sc->host.sensor.alpha && !rq.moments) {   // the alpha film (plane K behind the K offset films): the same splat over (valid, 0, 0) -- ImageBlock::put of aovs[3] (integrator.cpp:528-533)
                 RenderParams ra = rp; ra.n_offsets = 1;
                 Queues qa = q; qa.res = q.valid_out;
                 if (rq.film64) launch_splat_f64(ra, qa, rq.film64 + (size_t) rp.n_offsets * rq.film64_stride, rq.film64_stride, s);
@@ -1375,6 +1379,50 @@ int dtof_render_rows_variants_f64(dtof_scene *sc, uint32_t seed, uint32_t spp, i
         render_rows(sc, rq);
     });
 }
+
+// ---------------------------------------------------------------- moment film (dtof_moments.hip)
+int dtof_moment_planes(int n_variants) { return n_variants < 0 || n_variants > kMaxOffsets ? -1 : moment_planes(std::max(n_variants, 1)); }
+static void add_stats(dtof_render_stats &sum, const dtof_render_stats &f) {
+    sum.n_paths += f.n_paths; sum.n_bounces += f.n_bounces; sum.n_shadow_rays += f.n_shadow_rays;
+    sum.ms_total += f.ms_total; sum.ms_generate += f.ms_generate; sum.ms_trace += f.ms_trace; sum.ms_shade += f.ms_shade; sum.ms_shadow += f.ms_shadow; sum.ms_splat += f.ms_splat;
+    sum.n_launches_trace += f.n_launches_trace; sum.n_launches_shade += f.n_launches_shade; sum.n_launches_shadow += f.n_launches_shadow; sum.n_batches += f.n_batches;
+    sum.n_launches_first += f.n_launches_first; sum.ms_first += f.ms_first; sum.n_inline_iterations += f.n_inline_iterations; sum.n_bounces_inline += f.n_bounces_inline;
+    sum.n_fused_splat_launches += f.n_fused_splat_launches; sum.n_plan_facts_launches += f.n_plan_facts_launches;
+}
+int dtof_render_moments(dtof_scene *sc, uint32_t seed, uint32_t spp, uint32_t n_passes, const dtof_modulation *variants, int n_variants, int developed,
+                        double *out_planes, dtof_render_stats *stats) {
+    return guarded([&] {
+        if (!sc || !out_planes) throw std::runtime_error("null argument");
+        if (n_passes == 0) throw std::runtime_error("the moment film needs at least one pass");
+        if (n_variants < 0 || n_variants > kMaxOffsets) throw std::runtime_error("between 0 and 4 modulation variants make a moment film");
+        if (n_variants > 0 && !variants) throw std::runtime_error("null argument: n_variants > 0 without variants");
+        if (sc->pp.integrator != INTEGRATOR_DOPPLER && n_variants > 0) throw std::runtime_error("modulation offsets only apply to the dopplertofpath integrator");
+        if (!sc->host.has_sensor) throw std::runtime_error("the scene does not contain a sensor");
+        ensure_device(sc);
+        sc->stop = false;
+        const HostSensor &se = sc->host.sensor;
+        const size_t px = (size_t) se.crop_w * se.crop_h;
+        const int planes = moment_planes(std::max(n_variants, 1));
+        sc->d_moments.ensure(px * kMomentCell); sc->d_moment_planes.ensure(px * planes);
+        const hipStream_t s = sc->stream;
+        HIP_CHECK(hipMemsetAsync(sc->d_moments.p, 0, px * kMomentCell * sizeof(double), s));   // once: the raw sums of the passes add up
+        dtof_render_stats sum; memset(&sum, 0, sizeof sum);
+        for (uint32_t pass = 0; pass < n_passes; ++pass) {
+            dtof_render_stats frame;
+            RenderRequest rq; rq.seed = seed + pass; rq.spp = spp; rq.row_begin = 0; rq.row_end = se.crop_h; rq.stats = &frame;
+            rq.moments = sc->d_moments.p;
+            set_variants(rq, variants, n_variants);
+            render_rows(sc, rq);
+            add_stats(sum, frame);
+        }
+        launch_develop_moments(sc->d_moments.p, planes, developed != 0, sc->d_moment_planes.p, (int64_t) px, s);
+        HIP_CHECK(hipGetLastError());
+        HIP_CHECK(hipMemcpyAsync(out_planes, sc->d_moment_planes.p, px * planes * sizeof(double), hipMemcpyDeviceToHost, s));
+        HIP_CHECK(hipStreamSynchronize(s));
+        if (stats) *stats = sum;
+    });
+}
+
 int dtof_develop_f64_async(dtof_scene *sc, const double *d_film64, float *d_rgb, int64_t n_pixels) {
     return guarded([&] {
         if (!sc || !d_film64 || !d_rgb) throw std::runtime_error("null argument");

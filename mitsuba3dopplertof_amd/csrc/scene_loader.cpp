@@ -1407,7 +1407,26 @@ HostScene load_scene_xml(const std::string &text, const std::map<std::string, st
         const Obj &o = *c.second;
         if (o.tag == "integrator") {
             if (have_integrator) fail("Only one integrator can be specified per scene.");
-            sc.integrator = o.props; have_integrator = true;
+            const Obj *integ = &o;
+            if (o.plugin == "moment") {
+                // src/integrators/moment.cpp:37-66 wraps its nested integrators and adds the XYZ of their samples and its square as AOVs; render() returns the first
+                // child's image (:106-107).  Here the ONE nested plugin becomes the scene's integrator with all its properties, and the moments are what
+                // dtof_render_moments accumulates; several children would be several AOV sets, and the library renders one integrator per scene
+                std::vector<const Obj *> nested;
+                for (auto &c : o.children) {
+                    if (!c.second) continue;
+                    if (c.second->tag != "integrator") fail("moment: Child objects must be of type 'SamplingIntegrator'! (found a \"" + c.second->tag + "\")");
+                    nested.push_back(c.second.get());
+                }
+                if (nested.empty()) fail("moment: the integrator needs one nested <integrator> (none was given)");
+                if (nested.size() > 1) fail("moment: " + std::to_string(nested.size()) + " nested integrators were given; this library renders one integrator per scene, "
+                                            "so \"moment\" takes exactly one nested <integrator>");
+                std::vector<std::string> own;
+                for (auto &kv : o.props.values) own.push_back(kv.first);
+                if (!own.empty()) fail_unreferenced(own, "integrator", "moment");   // the plugin queries nothing but its child objects
+                integ = nested[0];
+            }
+            sc.integrator = integ->props; have_integrator = true;
         } else if (o.tag == "sensor") {
             if (have_sensor) fail("only one sensor is supported");
             make_sensor(o, sc); have_sensor = true;

@@ -122,6 +122,54 @@ def run_scene_velocity_map_device(scene, total_spp=1024, offsets=(0.0, 0.25), fi
     return scene.render_velocity_map(n_pass, single, [float(o) for o in offsets], exposure_time, w_g, film=film)
 
 
+def run_scene_moments(scene, total_spp=1024, variants=((0, 0), (1, 0)), **integrator_kwargs):
+    """The moment film of run_scene_doppler_tof_variants' render: the same integrator dictionary, the same passes (min(1024, total_spp) samples each) and seeds
+    0, 1, ..., but ONE Scene.render_moments call whose passes all accumulate into one film.  `variants`: up to four (hetero_frequency, hetero_offset) pairs of one
+    traversal -- the default is the homodyne / heterodyne pair of a velocity map.  Returns (the dict of Scene.render_moments, n_samples = passes x spp, the sample
+    count moment_statistics and velocity_standard_error take)."""
+    single, n_pass = _passes(total_spp)
+    integrator_kwargs = dict(integrator_kwargs)
+    integrator_kwargs.pop("hetero_offset", None)
+    integrator_kwargs.pop("hetero_frequency", None)
+    scene.set_integrator(doppler_integrator_dict(hetero_frequency=0.0, hetero_offset=0.0, **integrator_kwargs))
+    m = scene.render_moments(seed=0, spp=single, n_passes=n_pass, variants=[(float(f), float(o)) for f, o in variants])
+    return m, single * n_pass
+
+
+def moment_statistics(m, n_samples):
+    """Per-pixel sample statistics from the developed dict of Scene.render_moments (all numpy, float64):
+        "variance" (K, H, W, 3)   m2 - mean^2 of X, Y, Z: the variance of ONE sample
+        "cov_y"    (K, K, H, W)   cross[j, k] - mean_y[j] mean_y[k]: the covariance of the Y of two variants of the same paths (its diagonal is variance[..., 1])
+        "stderr"   (K, H, W, 3)   sqrt(max(variance, 0) / n_samples): the standard error of the pixel's mean
+    n_samples is passes x spp.  With a filter wider than the box, a pixel's mean is a weighted mean over its neighbours' samples too, so this is the NOMINAL count:
+    the effective one is (sum w)^2 / sum w^2 of the pixel."""
+    mean, m2, cross = np.asarray(m["mean"], np.float64), np.asarray(m["m2"], np.float64), np.asarray(m["cross"], np.float64)
+    variance = m2 - mean ** 2
+    mean_y = mean[..., 1]
+    cov_y = cross - mean_y[:, None] * mean_y[None, :]
+    return {"variance": variance, "cov_y": cov_y, "stderr": np.sqrt(np.maximum(variance, 0.0) / n_samples)}
+
+
+def velocity_standard_error(m, homodyne, heterodyne, n_samples, exposure_time=0.0015, w_g=30):
+    """The standard error of the velocity map of calc_velocity_from_homo_hetero for the variants `homodyne` and `heterodyne` (indices into the dict of
+    Scene.render_moments), by the delta method on _velocity_from_ratio.  With a, b the Y means of the two variants and r = b / a:
+        Var r   ~ (var_b - 2 r cov_ab + r^2 var_a) / (a^2 n)
+        |dv/dr| = 0.5 * 3e8 / (w_g 1e6) / (T (r - 1)^2)
+    and the result is sqrt(Var r) |dv/dr|, (H, W) float64.  NaN where a == 0 or r lies outside the open clip interval (-1, 0.999): the map is constant there.
+    The exposure-time factor of to_tof_image scales a and b alike and cancels in r (and Y is a luminance with the coefficients of srgb_to_xyz rather than
+    to_tof_image's rounded ones).  n_samples is passes x spp -- for filters wider than the box the nominal count, see moment_statistics."""
+    st = moment_statistics(m, n_samples)
+    mean_y = np.asarray(m["mean"], np.float64)[..., 1]
+    a, b = mean_y[homodyne], mean_y[heterodyne]
+    var_a, var_b, cov = st["cov_y"][homodyne, homodyne], st["cov_y"][heterodyne, heterodyne], st["cov_y"][homodyne, heterodyne]
+    with np.errstate(all="ignore"):
+        r = b / a
+        var_r = (var_b - 2.0 * r * cov + r * r * var_a) / (a * a * n_samples)
+        slope = 0.5 * 3e8 / (w_g * 1e6) / (exposure_time * (r - 1.0) ** 2)
+        se = np.sqrt(np.maximum(var_r, 0.0)) * slope
+    return np.where((a != 0) & (r > -1.0) & (r < 0.999), se, np.nan)
+
+
 def run_scene_velocity(scene, total_spp=1024, output_file=None):
     single, _ = _passes(total_spp)
     img = render_multi_pass(scene, load_dict({"type": "velocity"}), total_spp, single)
