@@ -59,6 +59,8 @@ class _Info(C.Structure):
 
 # dtof_kernels.h: kFlatShapeFields -- the presence bit, the object count (bits 19 .. 22) and the wall's index (bits 23 .. 25)
 _FLAT_SHAPE_FIELDS = 1 << 18 | 0xf << 19 | 0x7 << 23
+# dtof_kernels.h: kFactPairSamples -- above the shape fields: not a fact of the plan's own but work the kernel lets the two lanes of a pair share
+_PAIR_SAMPLES = 1 << 26
 
 
 def lib_path():
@@ -310,10 +312,22 @@ class Scene:
         return int(_lib().dtof_scene_plan_facts_launches(self._h))
 
     @property
-    def last_plan_mask(self):
-        """the FACTS mask of the first-bounce kernel compiled with the frame plan's constants that the last frame launched, 0 if it launched none: what
-        dtof_scene_last_plan_facts reports -- the one-bit facts and, from bit 18 up, the shape fields of the flat table (dtof_kernels.h: kFactFlatShape)"""
+    def last_plan_kernel(self):
+        """the FACTS template argument of the first-bounce kernel compiled with the frame plan's constants that the last frame launched, 0 if it launched none:
+        what dtof_scene_last_plan_facts reports, every bit of it"""
         return int(_lib().dtof_scene_last_plan_facts(self._h))
+
+    @property
+    def last_plan_mask(self):
+        """the plan's constants in last_plan_kernel: the one-bit facts and, from bit 18 up, the shape fields of the flat table (dtof_kernels.h: kFactFlatShape).
+        kFactPairSamples (bit 26) is not among them -- it follows from the facts below it and three inline iterations, and says how the kernel splits work between
+        the lanes of a pair, not what the plan fixed: last_plan_pair_samples"""
+        return self.last_plan_kernel & ~_PAIR_SAMPLES
+
+    @property
+    def last_plan_pair_samples(self):
+        """did the kernel the last frame launched share the BSDF samples of a correlated pair between its two lanes (dtof_kernels.h: kFactPairSamples)?"""
+        return bool(self.last_plan_kernel & _PAIR_SAMPLES)
 
     @property
     def last_plan_facts(self):

@@ -188,6 +188,10 @@ enum : uint32_t {
     kFactIdShift24      = 1u << 17,  // q.id_shift == 24
     // ... and the SHAPE of the one-wall flat table: a presence bit and two fields that are VALUES, not facts of one bit each -- see flat_shape_fact
     kFactFlatShape      = 1u << 18,  // (with kFactOneWall) bits 19 .. 22 hold rp.flat_objects (1 .. 8), bits 23 .. 25 rp.memo_obj (< rp.flat_objects)
+    // ... and, above the shape fields, work the two lanes of a correlated pair can share:
+    kFactPairSamples    = 1u << 26,  // rp.inline_iters == 3 under kFactWholePath, kFactWavePixel, kFactStratifiedPairs, kFactCorrelated, kFactDopplerCorr, kFactNoRoulette and
+                                     // kFactOneEmitter: lanes 2k and 2k + 1 hold the same path stream, every draw of the loop comes from it, and iterations 0 and 1 sample
+                                     // a BSDF while iteration 2 is the terminal one -- a diffuse-only point-light kernel reads two draws per sampling iteration and nothing else
 };
 // The shape fields: a launch's mask carries them whenever kFactOneWall holds and the table has at most 8 objects (FramePlan::launch_facts, read off the plan's blob);
 // a kernel compiled with a shape is taken only by a launch whose fields EQUAL its own (facts_hold), every other shape falls back to the kernels without one.
@@ -236,6 +240,21 @@ static_assert(((DTOF_HEADLINE_C2) & ~kFactsSampling) == 0, "DTOF_HEADLINE_C2 nam
 #endif
 constexpr uint32_t kHeadlineShapeFacts = (DTOF_HEADLINE_SHAPE_COUNT) != 0 && (kHeadlineC2Facts & kFactOneWall) != 0 ? (kHeadlineC2Facts | flat_shape_fact(DTOF_HEADLINE_SHAPE_COUNT, DTOF_HEADLINE_SHAPE_WALL)) : 0u;
 static_assert((DTOF_HEADLINE_SHAPE_COUNT) == 0 || (kHeadlineC2Facts & kFactOneWall) == 0 || (kHeadlineShapeFacts & kFactFlatShape) != 0, "a shape has 1 .. 8 objects and the wall among them");
+// ... and a fifth, tried before all of them, with kFactPairSamples on top of that (j): C2's frame at its max_depth of 4.  The fact stands in front of two steps, each with
+// a switch for its A/B.  DTOF_STREAM_JUMPS: the draws of the path stream whose values this kernel never reads (the emitter pick's two, the lobe pick's, the roulette's)
+// advance the stream by pcg_jump<N> instead of one multiply-add each.  DTOF_PAIR_SAMPLES: each lane of a pair evaluates the BSDF direction of ONE sampling iteration
+// (the even lane iteration 0's, the odd lane iteration 1's) right after generate_lane and the two exchange them; the bounce loop then holds no PCG arithmetic and no
+// cosine_hemisphere.  Both 0: the text of kHeadlineShapeFacts under the new mask.  A/B without the instantiation: DEFS=-DDTOF_HEADLINE_PAIR=0
+#ifndef DTOF_HEADLINE_PAIR
+#define DTOF_HEADLINE_PAIR 1
+#endif
+#ifndef DTOF_STREAM_JUMPS
+#define DTOF_STREAM_JUMPS 1
+#endif
+#ifndef DTOF_PAIR_SAMPLES
+#define DTOF_PAIR_SAMPLES 1
+#endif
+constexpr uint32_t kHeadlinePairFacts = DTOF_HEADLINE_PAIR && kHeadlineShapeFacts != 0 ? (kHeadlineShapeFacts | kFactPairSamples) : 0u;
 // The two steps of (i) inside trace_flat under a shape, each with a switch for its A/B: the occlusion queries' straight-line sweep, the closest-hit queries' written-out walk
 #ifndef DTOF_FLAT_SHAPE_ANY
 #define DTOF_FLAT_SHAPE_ANY 1

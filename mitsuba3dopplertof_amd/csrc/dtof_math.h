@@ -482,6 +482,14 @@ DTOF_HD float pcg_output_f32(uint64_t old) {
 constexpr uint64_t pcg_pow(int n) { uint64_t r = 1; for (int i = 0; i < n; ++i) r *= kPcgMult; return r; }
 constexpr uint64_t kPcgMult6 = pcg_pow(6), kPcgGeom6 = 1 + pcg_pow(1) + pcg_pow(2) + pcg_pow(3) + pcg_pow(4) + pcg_pow(5);
 DTOF_HD uint64_t pcg_jump6(uint64_t state, uint64_t inc) { return state * kPcgMult6 + inc * kPcgGeom6; }
+// ... and N steps at once, for the draws of a stream whose values nobody reads (k_shade under kFactPairSamples): state * M^N + inc * (1 + M + ... + M^(N-1)), the same
+// integer modulo 2^64 as N single steps
+constexpr uint64_t pcg_geom(int n) { uint64_t r = 0, p = 1; for (int i = 0; i < n; ++i) { r += p; p *= kPcgMult; } return r; }
+template <int N> DTOF_HD uint64_t pcg_jump(uint64_t state, uint64_t inc) {
+    constexpr uint64_t m = pcg_pow(N), g = pcg_geom(N);
+    return state * m + inc * g;
+}
+static_assert(pcg_pow(6) == kPcgMult6 && pcg_geom(6) == kPcgGeom6, "pcg_jump<6> is pcg_jump6");
 // PCG32::seed(1, initstate, initseq)
 DTOF_HD void pcg_seed(uint32_t initstate, uint32_t initseq, uint64_t &state, uint64_t &inc) {
     state = 0; inc = ((uint64_t) initseq << 1) | 1u;

@@ -502,6 +502,10 @@ struct FramePlan {
         // lanes [lane_base + 512 S + cbase, + 64), samples of one pixel when spp is a power of two >= 64.  (A striped shard -- a rank's share of a frame, virtual lanes --
         // keeps the run-time test and with it the generic kernel.)
         if (identity_queue && r.stripe_rows == 0 && r.spp_log2 != 0xffffffffu && r.spp_log2 >= 6 && (r.lane_base & 63u) == 0 && (r.n_lanes & 63u) == 0) f |= kFactWavePixel;
+        // the two lanes of a pair can split the BSDF samples of the launch between them: they hold one path stream, every draw comes from it, no draw is
+        // looked at for roulette or for an emitter pick, and the launch is the whole path in three iterations -- two that sample a BSDF and the terminal one
+        constexpr uint32_t pair_needs = kFactWholePath | kFactWavePixel | kFactStratifiedPairs | kFactCorrelated | kFactDopplerCorr | kFactNoRoulette | kFactOneEmitter;
+        if (l.span == 3 && (f & pair_needs) == pair_needs) f |= kFactPairSamples;
         return f;
     }
 };

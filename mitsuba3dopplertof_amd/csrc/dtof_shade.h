@@ -25,9 +25,11 @@ DTOF_D uint32_t wave_append(bool pred, uint32_t &running) {
 // One function for k_shade and for the known-answer entry dtof_bsdf_eval (the reference's BSDF unit tests run against it on the GPU).
 // The two halves can be asked for separately: active_em = value and density for `wo`, want_sample = the sampled continuation.  Without want_sample (uniform; the
 // terminal iteration of k_shade, whose paths nobody continues) the three samples are not read and weight / wo / bs_* come back as zero / false.
+// diffuse_wo (HAVE_WO; k_shade under kFactPairSamples only): cosine_hemisphere(s2x, s2y) of this vertex, evaluated ahead of the loop; the diffuse lobe takes it where it would
+// call the warp, and everything that depends on the lane (the side test, the density, the weight, the two-sided flip) stays where it is.
 struct BsdfOut { V3 val, weight, wo; float pdf, bs_pdf, bs_eta; bool bs_delta, bs_null; };   // bs_null: has_flag(bs.sampled_type, BSDFFlags::Null)
-template <int SPEC>
-DTOF_D void bsdf_eval_pdf_sample(const SceneView &sv, const DShape *sh, Surface &si, V3 wo, bool active_em, float sample_1, float s2x, float s2y, BsdfOut &out, bool want_sample = true) {
+template <int SPEC, bool HAVE_WO = false>
+DTOF_D void bsdf_eval_pdf_sample(const SceneView &sv, const DShape *sh, Surface &si, V3 wo, bool active_em, float sample_1, float s2x, float s2y, BsdfOut &out, bool want_sample = true, const V3 *diffuse_wo = nullptr) {
     // ---- the shape's BSDF.  Outermost a `mask`, if any: MaskBSDF (src/bsdfs/mask.cpp:125-163) -- with probability 1 - opacity the path goes straight on (a null
     // interaction: wo = -wi, weight 1, pdf 1 - opacity), otherwise the nested BSDF is sampled with sample1 / opacity; eval and pdf of the nested BSDF are scaled by it.
     const bool masked = SPEC && (sh->flags & SF_MASK);
@@ -247,6 +249,7 @@ DTOF_D void bsdf_eval_pdf_sample(const SceneView &sv, const DShape *sh, Surface 
         } else {
             if (wiz > 0.f && woz > 0.f) { bsdf_val = mk(refl.x * kInvPi * woz, refl.y * kInvPi * woz, refl.z * kInvPi * woz); bsdf_pdf = kInvPi * woz; }
             if (want_sample && wiz > 0.f) {
+                if constexpr (HAVE_WO) bs_wo = *diffuse_wo; else
                 bs_wo = cosine_hemisphere(s2x, s2y);
                 bs_pdf = kInvPi * bs_wo.z;
                 bs_eta = 1.f;
@@ -410,6 +413,12 @@ __global__ __launch_bounds__(RESW ? RESW * 64 : kShadeBlock, RESW ? RESW / 4 : (
     constexpr bool F_FLAT = (FACTS & kFactFlat) != 0, F_ONE_WALL = (FACTS & kFactOneWall) != 0, F_FUSED_SPLAT = (FACTS & kFactFusedSplat) != 0;
     // the routes of the sampler and of the modulation weight are taken inside generate_lane / next_time / modulation_weight, which get FACTS; here:
     constexpr bool F_EMITTER_SAMPLED = (FACTS & kFactEmitterSampled) != 0, F_ID24 = (FACTS & kFactIdShift24) != 0, F_SHIFTS = facts_lane_shifts(FACTS);
+    // the two lanes of a pair hold ONE path stream and every draw of the loop comes from it, so the draws -- and the warp of the two that are read --
+    // are the pair's, not the lane's.  JUMPS: the draws nobody reads advance the stream by pcg_jump; PAIR: a lane evaluates one iteration's direction, its partner the other's
+    constexpr bool F_PAIR = (FACTS & kFactPairSamples) != 0, JUMPS = F_PAIR && DTOF_STREAM_JUMPS, PAIR = F_PAIR && DTOF_PAIR_SAMPLES;
+    static_assert(!F_PAIR || F_WAVE_PIXEL, "a lane reads its partner's registers: the whole wave is active where it does");
+    static_assert(!F_PAIR || (!AREA && SPEC == 0 && KMAX == 1 && F_ONE_EMITTER), "a diffuse BSDF picks no lobe and a lone point light samples nothing: of an iteration's six draws only s2x and s2y are read");
+    static_assert(!F_PAIR || (F_NO_RR && F_CORRELATED && F_DOPPLER_CORR && F_WHOLE_PATH && F_SINGLE_PASS && (FACTS & kFactStratifiedPairs) != 0), "every draw comes from the stream lanes 2k and 2k + 1 share, none is looked at for roulette, no state outlives the launch");
     constexpr bool F_FRAMES = F_ONE_WALL && DTOF_WALL_FRAMES;   // shading frames precomputed: the wall's once per path, the plain rectangles' on the host (compute_surface)
     static_assert(!F_FLAT || (!MESH && SPEC == 0 && RESW == 0), "trace_flat serves the staged rectangle-only diffuse kernels");
     static_assert(!F_ONE_WALL || F_FLAT, "the one wall is an object of the flat table");
@@ -579,6 +588,7 @@ __global__ __launch_bounds__(RESW ? RESW * 64 : kShadeBlock, RESW ? RESW / 4 : (
         wf.n = mk(0.f, 0.f, 1.f); wf.s = mk(1.f, 0.f, 0.f);
         wf.table = (const DFlatFrame *) ((const uint4 *) ((const DFlatObject *) (sv.base + rp.flat_off) + rp.flat_objects) + 1 + rp.flat_objects);
     }
+    V3 pair_wo = mk(0.f, 0.f, 1.f), pair_wo_next = pair_wo;   // PAIR: the BSDF's sampled direction (local frame) of the iteration that runs and of the one after it
     bool lane_on = in_range;
 #ifdef DTOF_TRAVERSAL_STATS   // development builds: lanes without a path carry a poison pattern; DTOF_POISON_CHECK counts it wherever path state is written out (statistic [14])
     constexpr uint64_t kPoisonState = 0xdeadbeefcafef00dull;
@@ -600,6 +610,31 @@ __global__ __launch_bounds__(RESW ? RESW * 64 : kShadeBlock, RESW ? RESW / 4 : (
         if (FIRST) {
             const PrimaryLane pl = generate_lane<SPEC == 0, FACTS>(rp, global_lane<FACTS>(rp, rp.lane_base + l), wave_pixel, rp.lane_base + l);
             ra = pl.ray_a; rb = pl.ray_b; main = pl.main; path = pl.path; st = make_float4(1.f, 1.f, 1.f, 0.f);
+            if constexpr (PAIR) {
+                // Iteration i reads the draws at offsets 6 i + 3 and 6 i + 4 of the stream generate_lane leaves (s2x, s2y) and warps them; the terminal iteration reads none.
+                // The even lane of a pair does that for iteration 0, the odd lane for iteration 1 -- one instruction stream, the state chosen by parity -- and each hands
+                // its three components to both (quad_perm [0, 0, 2, 2] and [1, 1, 3, 3]; kFactWavePixel: every lane of the wave is active here).  The stream is dead afterwards.
+                const bool odd = lane_id & 1u;   // (lane_base, the segment and the chunk are even: the lane's parity is its parity in the wave)
+                uint64_t sx;
+                if constexpr (JUMPS) {   // pcg_jump<9> in the odd lanes, pcg_jump<3> in the even ones: ONE jump whose two constants the parity selects
+                    constexpr uint64_t m3 = pcg_pow(3), g3 = pcg_geom(3), m9 = pcg_pow(9), g9 = pcg_geom(9);
+                    sx = path.state * (odd ? m9 : m3) + path.inc * (odd ? g9 : g3);
+                } else {
+                    uint64_t s3 = path.state;
+                    for (int i = 0; i < 3; ++i) s3 = s3 * kPcgMult + path.inc;
+                    uint64_t s9 = s3;
+                    for (int i = 0; i < 6; ++i) s9 = s9 * kPcgMult + path.inc;
+                    sx = odd ? s9 : s3;
+                }
+                const uint64_t sy = sx * kPcgMult + path.inc;
+                const V3 mine = cosine_hemisphere(pcg_output_f32(sx), pcg_output_f32(sy));
+                pair_wo = mk(__int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(mine.x), 0xa0, 0xf, 0xf, false)),
+                             __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(mine.y), 0xa0, 0xf, 0xf, false)),
+                             __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(mine.z), 0xa0, 0xf, 0xf, false)));
+                pair_wo_next = mk(__int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(mine.x), 0xf5, 0xf, 0xf, false)),
+                                  __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(mine.y), 0xf5, 0xf, 0xf, false)),
+                                  __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(mine.z), 0xf5, 0xf, 0xf, false)));
+            }
             if (PARK) park_store();
             pos_reg = pl.pos;
             if (!fuse_splat) {   // what the later launches (stream selectors) and the splat kernels (sample position) read
@@ -762,7 +797,8 @@ __global__ __launch_bounds__(RESW ? RESW * 64 : kShadeBlock, RESW ? RESW / 4 : (
             // is moved six steps at once at the end (pcg_jump6: the same integers as six single steps).
             const bool use_path = !single && correlate;
             Rng sel = use_path ? path : main;
-            float e1 = next_f32(sel), e2 = next_f32(sel);
+            float e1 = 0.f, e2 = 0.f;   // (F_PAIR: a lone point light reads neither)
+            if constexpr (!JUMPS && !PAIR) { e1 = next_f32(sel); e2 = next_f32(sel); }
             // has_flag(bsdf->flags(), BSDFFlags::Smooth) (:178): diffuse, (rough)plastic and roughconductor have a smooth lobe
             bool active_em = active_next && (F_ONE_EMITTER || sv.n_emitters > 0) && (!SPEC || bsdf_is_smooth(sh->bsdf) || ((sh->flags & (SF_BLEND | SF_TWOSIDED2)) && bsdf_is_smooth(sv.shapes[sh->blend_other].bsdf)));   // a blend (a twosided of two BSDFs) has the flags of both
             V3 em_weight = mk(0, 0, 0), wo = mk(0, 0, 0); float ds_dist = 0.f, ds_pdf = 0.f; bool ds_delta = true;
@@ -780,10 +816,16 @@ __global__ __launch_bounds__(RESW ? RESW * 64 : kShadeBlock, RESW ? RESW / 4 : (
                 wo = want_frame ? mk(dot(dd, si.sh_s), dot(dd, si.sh_t), dot(dd, si.sh_n)) : mk(0.f, 0.f, dot(dd, si.sh_n));
             }
             float sample_1 = 0.f, s2x = 0.f, s2y = 0.f;   // terminal: the BSDF is not sampled, and the stream states are dropped with the path
+            if constexpr (PAIR) { }   // the direction is in pair_wo
+            else if constexpr (JUMPS) {   // e1, e2 and sample_1 are three steps nobody looks at; s2x and s2y are the draws of the same two states as before
+                if (!terminal) { sel.state = pcg_jump<3>(sel.state, sel.inc); s2x = next_f32(sel); s2y = pcg_output_f32(sel.state); }
+            } else
             if (!terminal) { sample_1 = next_f32(sel); s2x = next_f32(sel); s2y = next_f32(sel); }
 
             // ---- the shape's BSDF with its adapters (mask, blendbsdf, twosided, normalmap / bumpmap): bsdf_eval_pdf_sample above
             BsdfOut bo;
+            if constexpr (PAIR) bsdf_eval_pdf_sample<SPEC, true>(sv, sh, si, wo, active_em, sample_1, s2x, s2y, bo, !terminal, &pair_wo);
+            else
             bsdf_eval_pdf_sample<SPEC>(sv, sh, si, wo, active_em, sample_1, s2x, s2y, bo, !terminal);
             const V3 bsdf_val = bo.val, bs_wo = bo.wo; V3 bsdf_weight = bo.weight;
             const float bsdf_pdf = bo.pdf, bs_pdf = bo.bs_pdf, bs_eta = bo.bs_eta; const bool bs_delta = bo.bs_delta, bs_null = bo.bs_null;
@@ -826,9 +868,14 @@ __global__ __launch_bounds__(RESW ? RESW * 64 : kShadeBlock, RESW ? RESW / 4 : (
             float thr_max = fmax_(fmax_(thr.x, thr.y), thr.z);
             float rr_prob = fmin_(thr_max * sqr(eta), .95f);
             bool rr_active = !F_NO_RR && ndepth >= rp.rr_depth;   // (the fact: the draw below still advances the stream, its value is not looked at)
-            bool rr_continue = next_f32(sel) < rr_prob;
+            bool rr_continue = true;
+            if constexpr (PAIR) { }   // no stream is read again
+            else if constexpr (JUMPS) path.state = pcg_jump<2>(sel.state, sel.inc);   // s2y's step and the roulette's: the state the iteration leaves is the one after six steps
+            else {
+            rr_continue = next_f32(sel) < rr_prob;
             if (use_path) { path.state = sel.state; main.state = pcg_jump6(main.state, main.inc); }
             else { main.state = sel.state; if (!single) path.state = pcg_jump6(path.state, path.inc); }
+            }
             if (rr_active) thr = thr * rcp(rr_prob);
             alive = active_next && (!rr_active || rr_continue) && thr_max != 0.f;
             // valid_ray |= active && si.is_valid() && !has_flag(bsdf_sample.sampled_type, BSDFFlags::Null) (:252-253)
@@ -929,6 +976,7 @@ __global__ __launch_bounds__(RESW ? RESW * 64 : kShadeBlock, RESW ? RESW / 4 : (
     // bounce computed them); a lane whose path ended sits out the remaining iterations
     lane_on = alive;
     if (alive) { ra = nra; rb = nrb; DTOF_POISON_CHECK(); }
+    if constexpr (PAIR) pair_wo = pair_wo_next;
     }   // inline iterations
     if constexpr (!RES_LDS) if (FIRST && fuse_splat) {   // ---- ImageBlock::put (imageblock.cpp:414-531) of the wave's samples: tent filter of radius <= 1, a 3 x 3 footprint anchored at the sample's pixel
         const uint32_t W = (uint32_t) rp.crop_w;

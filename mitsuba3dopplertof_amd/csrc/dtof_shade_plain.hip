@@ -12,10 +12,12 @@ template <uint32_t FACTS> static uint32_t launch_headline(const ShadeLaunch &L) 
     return FACTS;
 }
 uint32_t launch_shade_plain(bool area, bool k4, const ShadeLaunch &L) {
-    // The most specific kernel whose mask holds: C2's with its sampling and modulation routes and the shape of its flat table compiled in (kHeadlineShapeFacts), then the
+    // The most specific kernel whose mask holds: C2's at three inline iterations, whose pairs share their BSDF samples (kHeadlinePairFacts), then C2's with its sampling
+    // and modulation routes and the shape of its flat table compiled in (kHeadlineShapeFacts), then the
     // one with the routes for a table of any other shape (kHeadlineC2Facts), then the one that splats whatever the routes (kFactFusedSplat), then the one that leaves
     // the film to the splat kernels (C3, box filters); the generic instantiation below otherwise
     if (!area && !k4 && L.staged && L.mode == 2) {
+        if (uint32_t ran = launch_headline<kHeadlinePairFacts>(L)) return ran;
         if (uint32_t ran = launch_headline<kHeadlineShapeFacts>(L)) return ran;
         if (uint32_t ran = launch_headline<kHeadlineC2Facts>(L)) return ran;
         if (uint32_t ran = launch_headline<kHeadlineFusedFacts>(L)) return ran;

@@ -12,7 +12,7 @@ FIELDS = [("vgpr", ".vgpr_count"), ("agpr", ".agpr_count"), ("sgpr", ".sgpr_coun
 
 
 # (RESW, mask) of the specialised instantiations with the default -D values: the C2 / C3 kernels of dtof_shade_plain.hip and the resident Domino kernel of dtof_shade_res0.hip
-FACT_MASKS = {("0", 0x12fffff): " = kHeadlineShapeFacts", ("0", 0x3ffff): " = kHeadlineC2Facts", ("0", 0x1fff): " = kHeadlineFusedFacts", ("0", 0xfff): " = kHeadlineFacts", ("16", 0x37f): " = kResidentFacts"}
+FACT_MASKS = {("0", 0x52fffff): " = kHeadlinePairFacts", ("0", 0x12fffff): " = kHeadlineShapeFacts", ("0", 0x3ffff): " = kHeadlineC2Facts", ("0", 0x1fff): " = kHeadlineFusedFacts", ("0", 0xfff): " = kHeadlineFacts", ("16", 0x37f): " = kResidentFacts"}
 
 
 def run(*a):

@@ -28,9 +28,9 @@ FAST = {"v_fma_f32", "v_fmac_f32", "v_mul_f32", "v_add_f32", "v_sub_f32", "v_sub
 QUARTER = {"v_rcp_f32", "v_sqrt_f32", "v_rsq_f32", "v_sin_f32", "v_cos_f32", "v_exp_f32", "v_log_f32", "v_rcp_iflag_f32"}
 C_FAST, C_SLOW, C_QUARTER = 2.25, 4.1, 8.2      # nominal 2.4 GHz cycles per wave64 instruction per SIMD, W >= 4 (the measured table)
 # the kernels the bench configurations are dominated by (pmc_summary.short() names)
-# (c2: the instantiation compiled with the frame plan's constants, the fused splat, the route facts and the flat table's shape, FACTS = kHeadlineShapeFacts = 19922943; c3: kHeadlineFacts = 4095; c4: kResidentFacts = 895;
+# (c2: the instantiation compiled with the frame plan's constants, the fused splat, the route facts, the flat table's shape and the pair samples, FACTS = kHeadlinePairFacts = 87031807; c3: kHeadlineFacts = 4095; c4: kResidentFacts = 895;
 #  the four-film resident kernel carries none)
-WANTED = {"c2": "_ZN4dtof7k_shadeILb1ELi2ELb0ELi1ELb0ELi0ELi0ELb0ELj19922943EEEvNS_9ShadeArgsE",
+WANTED = {"c2": "_ZN4dtof7k_shadeILb1ELi2ELb0ELi1ELb0ELi0ELi0ELb0ELj87031807EEEvNS_9ShadeArgsE",
           "c3": "_ZN4dtof7k_shadeILb1ELi2ELb0ELi1ELb0ELi0ELi0ELb0ELj4095EEEvNS_9ShadeArgsE",
           "c4": "_ZN4dtof7k_shadeILb0ELi2ELb0ELi1ELb1ELi0ELi16ELb0ELj895EEEvNS_9ShadeArgsE",
           "c5": "_ZN4dtof7k_shadeILb0ELi2ELb0ELi4ELb1ELi0ELi16ELb0ELj0EEEvNS_9ShadeArgsE"}
