@@ -401,6 +401,69 @@ int dtof_moment_planes(int n_variants);
 int dtof_render_moments(dtof_scene *scene, uint32_t seed, uint32_t spp, uint32_t n_passes, const dtof_modulation *variants_or_null, int n_variants, int developed,
                         double *out_planes, dtof_render_stats *stats);
 
+/* ---------------------------------------------------------------- geometry channels of the `aov` integrator (opt-in)
+ * What the reference's `aov` integrator records (src/integrators/aov.cpp:196-330): the camera ray of every sample is intersected once
+ * (scene->ray_intersect(ray, RayFlags::All, ...), :206-207), the interaction is zeroed on a miss (:208) and its fields become channels that ImageBlock::put filters
+ * like the image (src/render/imageblock.cpp:414-531).  The types of aov.cpp:118-171 this library writes, their channels and the suffixes of their names:
+ *   DTOF_AOV_DEPTH        1  si.t, 0 on a miss (:247-249)                                  name.T
+ *   DTOF_AOV_POSITION     3  si.p (:251-255)                                               name.X name.Y name.Z
+ *   DTOF_AOV_UV           2  si.uv (:257-260)                                              name.U name.V
+ *   DTOF_AOV_GEO_NORMAL   3  si.n (:262-266)                                               name.X name.Y name.Z
+ *   DTOF_AOV_SH_NORMAL    3  si.sh_frame.n (:268-272): the shape's shading normal, before any normalmap / bumpmap adapter of its BSDF        name.X name.Y name.Z
+ *   DTOF_AOV_DP_DU        3  si.dp_du (:278-282)                                           name.X name.Y name.Z
+ *   DTOF_AOV_DP_DV        3  si.dp_dv (:284-288)                                           name.X name.Y name.Z
+ *   DTOF_AOV_PRIM_INDEX   1  (float) si.prim_index (:300-302)                              name.I
+ *   DTOF_AOV_SHAPE_INDEX  1  see below (:304-306)                                          name.I
+ * Every channel is +0 on a miss.  SHAPE INDEX: the reference writes the bits of a registry id or of a pointer (:305), which no other build can reproduce.  Here the
+ * value is 1 + the index of the hit shape's record in the scene's shape table, which holds the shapes in the order in which the scene file declares them: a
+ * scene-level shape where it stands, the shapes of a shapegroup where the group is declared, an animated shape (which loads as a group of one and its instance,
+ * src/core/xml.cpp:1165-1195) where it stands; 0 on a miss.  As in the reference, where si.shape is the shape inside the group and
+ * si.instance the instance (src/shapes/instance.cpp:247), every instance of a group reports the shape of the group.
+ * Refused with DTOF_ERR_INVALID and a message that names the type: `albedo` (:229-246 needs BSDF::eval_diffuse_reflectance of every BSDF), `boundary_test` (:274-276),
+ * `duv_dx` and `duv_dy` (:290-298: this build carries no ray differentials).  Any other type fails with the reference's `Invalid AOV type "x"!` (:173).
+ * THE LANES ARE THE SCENE INTEGRATOR'S OWN: lane i of an aov render has the sample position, the time and the camera ray (with its maxt) that dtof_sample_lanes reports
+ * for the same seed and spp -- the Doppler branch of render_sample for `dopplertofpath`, the plain branch for `path` and `velocity` (src/render/integrator.cpp:409-543)
+ * -- and the ray is intersected at its own time.  (The reference's `aov` is no Doppler integrator and would draw the rays of a nested `dopplertofpath` through the
+ * plain branch; with a nested `path` the lanes are the reference's own.)  The RGBA channels of the nested integrator (aov.cpp:308-323) are not part of this film: the
+ * image comes from dtof_render.
+ * FILM: 1 + C planes of crop_height * crop_width doubles, plane 0 the sum of the filter weights, plane 1 + c channel c in the order of the types; C <= 31.  Terms are
+ * formed like the moment film's: value * (wx * wy) is a float32 product (the box filter adds the value itself and 1), converted to double, then only double additions. */
+#define DTOF_AOV_DEPTH        0
+#define DTOF_AOV_POSITION     1
+#define DTOF_AOV_UV           2
+#define DTOF_AOV_GEO_NORMAL   3
+#define DTOF_AOV_SH_NORMAL    4
+#define DTOF_AOV_DP_DU        5
+#define DTOF_AOV_DP_DV        6
+#define DTOF_AOV_PRIM_INDEX   7
+#define DTOF_AOV_SHAPE_INDEX  8
+#define DTOF_AOV_MAX_CHANNELS 31
+
+/* The constructor's parse of the `aovs` property (src/integrators/aov.cpp:109-175): tokens split at ',' and ' ' (string::tokenize, include/mitsuba/core/string.h:104-106;
+ * empty tokens are dropped), each token split at ':' into <name>:<type>.  types[0 .. *n_types) receives the DTOF_AOV_* constants, names_buf the channel names in film
+ * order, each followed by a NUL (aov.cpp:118-171), *n_channels their number.  types / names_buf may be NULL (only the counts are wanted); otherwise a capacity too small
+ * for the result is an error.  An empty spec is 0 types (the reference warns, :192-193).  A token that is not <name>:<type> is an error here (the reference warns and
+ * then reads item[1] out of range, :115-118).  DTOF_ERR_INVALID with the messages above.  Needs no device. */
+int dtof_aov_parse(const char *spec, int32_t *types, int capacity, int *n_types, char *names_buf, size_t names_capacity, int *n_channels);
+/* The `aovs` string of a scene whose integrator is <integrator type="aov"> (src/integrators/aov.cpp:109-110), NUL-terminated into buf; the empty string for every other
+ * scene.  Returns DTOF_ERR_INVALID if capacity cannot hold it.  Such a scene has exactly one nested <integrator> (aov.cpp:177-190), which is the scene's integrator
+ * with all its properties: dtof_render returns its image. */
+int dtof_scene_get_aovs(const dtof_scene *scene, char *buf, size_t capacity);
+/* The aov film of n_passes traversals of the camera rays (src/integrators/aov.cpp:196-330 through ImageBlock::put, src/render/imageblock.cpp:414-531, with a double
+ * accumulator): the library's own film is zeroed ONCE, pass i generates its lanes with seed + i and `spp` samples per pixel (0 = the sampler's sample count) and all
+ * passes accumulate into it, as in dtof_render_moments.  developed != 0: every plane but plane 0 is divided in double by (W == 0 ? 1 : W) on the device (what
+ * HDRFilm::develop makes of the channels, src/films/hdrfilm.cpp:305-406); developed == 0: the raw sums.  out_planes: 1 + C planes of crop_height * crop_width doubles.
+ * `stats` (may be NULL) sums the passes: n_paths counts the lanes, n_fused_splat_launches stays 0, the kernel's time is ms_trace.
+ * DTOF_ERR_INVALID before any device call: a null argument, n_passes == 0, n_types < 1, a type outside the DTOF_AOV_* constants, more than 31 channels.  Without a
+ * device: DTOF_ERR_HIP. */
+int dtof_render_aovs(dtof_scene *scene, uint32_t seed, uint32_t spp, uint32_t n_passes, const int32_t *types, int n_types, int developed, double *out_planes,
+                     dtof_render_stats *stats);
+/* The per-lane entry beside dtof_sample_lanes, through the same kernel without its splat (src/integrators/aov.cpp:196-330 per sample): out_lanes12 as
+ * dtof_sample_lanes writes it (the sample position, time and camera ray are those the aov kernel read; rgb is the scene integrator's), out_values[n][C] the channels
+ * of every lane in the order of the types.  Refusals as above. */
+int dtof_sample_aov_lanes(dtof_scene *scene, uint32_t seed, uint32_t spp, const int32_t *types, int n_types, uint64_t lane_begin, uint64_t n, float *out_lanes12,
+                          float *out_values);
+
 /* Integrator::cancel / should_stop (include/mitsuba/render/integrator.h:96-109). */
 void dtof_cancel(dtof_scene *scene);
 /* First-bounce launches of this scene, since it was loaded, that ran a kernel compiled with the frame plan's constants (dtof_render_stats::n_plan_facts_launches): the

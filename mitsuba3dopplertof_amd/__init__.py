@@ -16,7 +16,7 @@ import os
 import numpy as np
 
 __all__ = ["load_file", "load_string", "load_dict", "Scene", "Integrator", "Sampler", "DtofError", "render",
-           "render_multi_pass", "to_tof_image", "lib_path", "ETimeSampling", "velocity_map_variants", "MOMENT_PLANES"]
+           "render_multi_pass", "to_tof_image", "lib_path", "ETimeSampling", "velocity_map_variants", "MOMENT_PLANES", "aov_channels", "AOV_TYPES"]
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB = None
@@ -168,7 +168,11 @@ def _lib():
                        ("dtof_render_rows_variants_f64", rows[:-1] + [vp, C.c_int32, C.c_uint64, C.POINTER(_Stats)]),
                        ("dtof_develop_f64_async", [vp, vp, vp, C.c_int64]), ("dtof_develop_rgba_f64_async", [vp, vp, vp, vp, C.c_int64]),
                        ("dtof_moment_planes", [C.c_int]),
-                       ("dtof_render_moments", [vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, C.c_int, C.c_int, vp, C.POINTER(_Stats)])):
+                       ("dtof_render_moments", [vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, C.c_int, C.c_int, vp, C.POINTER(_Stats)]),
+                       ("dtof_aov_parse", [C.c_char_p, vp, C.c_int, C.POINTER(C.c_int), vp, C.c_size_t, C.POINTER(C.c_int)]),
+                       ("dtof_scene_get_aovs", [vp, vp, C.c_size_t]),
+                       ("dtof_render_aovs", [vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, C.c_int, C.c_int, vp, C.POINTER(_Stats)]),
+                       ("dtof_sample_aov_lanes", [vp, C.c_uint32, C.c_uint32, vp, C.c_int, C.c_uint64, C.c_uint64, vp, vp])):
         if hasattr(L, name):   # a DTOF_LIB build from before the variants (A/B timing against an older commit) loads; calling what it lacks still raises
             getattr(L, name).argtypes = args
     _LIB = L
@@ -194,6 +198,10 @@ def _plugin_args(d):
     """{'type': 'dopplertofpath', 'max_depth': 4, ...} -> (plugin, names, types, values, n) for the C ABI"""
     d = dict(d)
     plugin = d.pop("type", "")
+    if plugin == "aov":      # likewise: a nested plugin beside its `aovs` string
+        raise DtofError('the "aov" integrator wraps a nested integrator, which a property dictionary cannot carry here: declare it in the scene file '
+                        '(<integrator type="aov"><string name="aovs" value="..."/><integrator type="dopplertofpath"> ... </integrator></integrator>) or set the '
+                        'nested integrator itself; the channels come from Scene.render_aovs(aovs=...) either way')
     if plugin == "moment":   # its one property is a nested plugin, which these flat arrays cannot carry
         raise DtofError('the "moment" integrator wraps a nested integrator, which a property dictionary cannot carry here: declare it in the scene file '
                         '(<integrator type="moment"><integrator type="dopplertofpath"> ... </integrator></integrator>) or set the nested integrator itself; '
@@ -259,6 +267,30 @@ def MOMENT_PLANES(n_variants=1):
 
 
 _MOMENT_PAIRS = ((0, 1), (0, 2), (0, 3), (1, 2), (1, 3), (2, 3))   # the order of the cross planes (dtof.h), restricted to k < K
+
+
+AOV_TYPES = ("depth", "position", "uv", "geo_normal", "sh_normal", "dp_du", "dp_dv", "prim_index", "shape_index")   # the DTOF_AOV_* constants, in their order
+
+
+_AOV_CHANNELS = (1, 3, 2, 3, 3, 3, 3, 1, 1)   # channels per type
+
+
+def _aov_parse(spec):
+    """dtof_aov_parse -> (types int32 array, channel names)"""
+    text = str(spec).encode()
+    nt, nc = C.c_int(0), C.c_int(0)
+    _check(_lib().dtof_aov_parse(text, None, 0, C.byref(nt), None, 0, C.byref(nc)))
+    types = np.zeros(max(nt.value, 1), np.int32)
+    buf = C.create_string_buffer(len(text) * 3 + 16 * max(nc.value, 1))      # a channel name is its token's name and a two-character suffix
+    _check(_lib().dtof_aov_parse(text, types.ctypes.data, nt.value, C.byref(nt), buf, len(buf), C.byref(nc)))
+    names = buf.raw.split(b"\0")[:nc.value]
+    return types[:nt.value], [n.decode() for n in names]
+
+
+def aov_channels(spec):
+    """The channel names of an `aovs` string as the reference's `aov` integrator names them (dtof_aov_parse): "dd:depth,nn:sh_normal" ->
+    ["dd.T", "nn.X", "nn.Y", "nn.Z"].  Raises DtofError for an unknown or unsupported type and for a token that is not <name>:<type>."""
+    return _aov_parse(spec)[1]
 
 
 MAX_VELOCITY_OFFSETS = 16   # offsets one velocity map combines (kMaxVelocityPairs)
@@ -444,6 +476,46 @@ class Scene:
                 slot += 1
         return {"weight": planes[0].copy(), "mean": np.ascontiguousarray(np.moveaxis(per[:, 0:3], 1, -1)),
                 "m2": np.ascontiguousarray(np.moveaxis(per[:, 3:6], 1, -1)), "cross": cross}
+
+    @property
+    def aovs(self):
+        """the `aovs` string of a scene whose integrator is <integrator type="aov"> (dtof_scene_get_aovs), None for every other scene"""
+        buf = C.create_string_buffer(1 << 16)
+        _check(_lib().dtof_scene_get_aovs(self._h, buf, len(buf)))
+        return buf.value.decode() or None
+
+    def render_aovs(self, aovs=None, seed=0, spp=0, n_passes=1, raw=False):
+        """The geometry channels of the reference's `aov` integrator along the scene integrator's own camera rays (dtof_render_aovs), accumulated in double over
+        `n_passes` passes with seeds seed, seed + 1, ...  `aovs`: the reference's spec, "name:type,name:type" with the types of AOV_TYPES; None: the spec of the scene
+        file's <integrator type="aov">.  Returns a dict of float64 arrays: "weight" (H, W), the sum of the filter weights; per name (H, W) for a one-channel type and
+        (H, W, n) for the others, the weighted means (raw=True: the undivided sums); and "channels", the list of channel names in film order.  Every value is 0 where
+        the camera ray leaves the scene.  last_stats sums the passes."""
+        spec = self.aovs if aovs is None else aovs
+        if spec is None:
+            raise DtofError("render_aovs: the scene's integrator is no \"aov\" integrator, so the `aovs` spec must be given")
+        types, names = _aov_parse(spec)
+        w, h = self.size
+        planes = np.zeros((1 + len(names), h, w), np.float64)
+        st = _Stats()
+        _check(_lib().dtof_render_aovs(self._h, int(seed), int(spp), int(n_passes), types.ctypes.data, len(types), 0 if raw else 1, planes.ctypes.data, C.byref(st)))
+        self.last_stats = st.as_dict()
+        out = {"weight": planes[0].copy(), "channels": names}
+        c = 1
+        for t in types:      # the channels of one token follow each other: name.X, name.Y, name.Z
+            n, name = _AOV_CHANNELS[t], names[c - 1].rsplit(".", 1)[0]
+            if name in out:
+                raise DtofError("render_aovs: the name \"%s\" occurs twice in the spec or is a key of the result; dtof_render_aovs returns such a film as planes" % name)
+            out[name] = planes[c].copy() if n == 1 else np.ascontiguousarray(np.moveaxis(planes[c:c + n], 0, -1))
+            c += n
+        return out
+
+    def sample_aov_lanes(self, aovs, seed, spp, lane_begin, n):
+        """sample_lanes of an aov render (dtof_sample_aov_lanes): the dict of sample_lanes without `valid`, plus "values" (n, C) float32, the channels of every lane in
+        the order of aov_channels(aovs), and "channels"."""
+        types, names = _aov_parse(aovs)
+        out, values = np.zeros((n, 12), np.float32), np.zeros((n, len(names)), np.float32)
+        _check(_lib().dtof_sample_aov_lanes(self._h, seed, spp, types.ctypes.data, len(types), lane_begin, n, out.ctypes.data, values.ctypes.data))
+        return {"sample_pos": out[:, 0:2], "time": out[:, 2], "ray_o": out[:, 3:6], "ray_d": out[:, 6:9], "rgb": out[:, 9:12], "values": values, "channels": names}
 
     def set_film_layout(self, planes, plane_stride_floats=0):
         """Declare the caller's device film for render_rows / render_stripes (dtof_scene_set_film_layout): `planes` RGBW planes, `plane_stride_floats` apart (0 = dense

@@ -7,6 +7,8 @@ plugins this library implements:
         the radial-velocity map of the scene's dopplertofpath integrator (float64 .npy), reconstructed on the GPU: passes of min(1024, N) samples, seeds 0, 1, ...
     python -m mitsuba3dopplertof_amd scene.xml --moments [--variants 0:0,1:0] [--passes N] [--spp N] [-o out.npz]
         the per-pixel moment film of one traversal per pass (weight, mean, m2, cross: Scene.render_moments), written with np.savez
+    python -m mitsuba3dopplertof_amd scene.xml --aovs dd:depth,nn:sh_normal [--passes N] [--spp N] [-o out.npz]
+        the geometry channels of the reference's `aov` integrator along the scene integrator's camera rays (Scene.render_aovs), written with np.savez
     python -m torch.distributed.run --nproc-per-node G --master-addr 127.0.0.1 -m mitsuba3dopplertof_amd scene.xml ...
         one process per GPU: the pixel rows are sharded across the G ranks, rank 0 gathers and writes the image
 """
@@ -40,7 +42,10 @@ def parser():
                     help="write the per-pixel moment film (sample mean, second moments and the variants' cross moments, float64 .npz) instead of an image")
     ap.add_argument("--variants", default=None, metavar="F:O,F:O",
                     help="--moments: up to four hetero_frequency:hetero_offset pairs evaluated in ONE traversal (default: the integrator's own pair)")
-    ap.add_argument("--passes", type=int, default=1, help="--moments: passes with seeds --seed, --seed + 1, ... that accumulate into one film")
+    ap.add_argument("--passes", type=int, default=1, help="--moments, --aovs: passes with seeds --seed, --seed + 1, ... that accumulate into one film")
+    ap.add_argument("--aovs", default=None, metavar="NAME:TYPE,...",
+                    help="write the geometry channels under each pixel (depth, position, uv, geo_normal, sh_normal, dp_du, dp_dv, prim_index, shape_index; float64 "
+                         ".npz) instead of an image: the `aovs` string of the reference's aov integrator")
     ap.add_argument("-v", "--verbose", action="store_true")
     return ap
 
@@ -99,6 +104,43 @@ def check_moments_args(ap, args):
             ap.error("--variants takes between 1 and 4 pairs")
 
 
+def check_aovs_args(ap, args):
+    """what --aovs cannot be combined with, refused before the scene is loaded"""
+    if args.moments:
+        ap.error("--aovs and --moments are two outputs: run them separately")
+    if args.velocity_map is not None:
+        ap.error("--aovs and --velocity-map are two outputs: run them separately")
+    if args.stripes > 0 or int(os.environ.get("WORLD_SIZE", "1")) > 1:
+        ap.error("--aovs is a single-GPU feature: it cannot be combined with --stripes or a multi-GPU launch")
+    if args.film == "float64":
+        ap.error("--aovs accumulates in double already: do not combine it with --film float64")
+    if args.offsets is not None or args.variants is not None:
+        ap.error("--aovs records geometry, which no modulation changes: --offsets and --variants do not apply")
+    if args.passes < 1:
+        ap.error("--passes must be at least 1")
+    if args.output is not None and not args.output.lower().endswith(".npz"):
+        ap.error("--aovs writes a float64 .npz file")
+    import mitsuba3dopplertof_amd as mi
+    try:
+        if not mi.aov_channels(args.aovs):
+            ap.error("--aovs names no channel")
+    except mi.DtofError as e:
+        ap.error("--aovs: %s" % e)
+
+
+def aovs(args, scene):
+    """--aovs: Scene.render_aovs of --passes passes, the dict written with np.savez"""
+    out = args.output or os.path.splitext(args.scene)[0] + "_aovs.npz"
+    t0 = time.time()
+    m = scene.render_aovs(args.aovs, seed=args.seed, spp=args.spp, n_passes=args.passes)
+    dt = time.time() - t0
+    os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+    np.savez(out, **m)
+    if args.verbose:
+        print("AOV film finished. (took %.1f ms, %d passes, %s)" % (dt * 1e3, args.passes, scene.last_stats))
+    return 0
+
+
 def moments(args, scene):
     """--moments: Scene.render_moments of --passes passes, the dict written with np.savez"""
     out = args.output or os.path.splitext(args.scene)[0] + "_moments.npz"
@@ -134,7 +176,9 @@ def main(argv=None):
     ap = parser()
     args = ap.parse_args(argv)
     check_film_args(ap, args)
-    if args.moments:
+    if args.aovs is not None:
+        check_aovs_args(ap, args)
+    elif args.moments:
         check_moments_args(ap, args)
     elif args.variants is not None or args.passes != 1:
         ap.error("--variants and --passes belong to --moments")
@@ -154,6 +198,8 @@ def main(argv=None):
             return velocity_map(args, scene)
         if args.moments:
             return moments(args, scene)
+        if args.aovs is not None:
+            return aovs(args, scene)
         t0 = time.time()
         offsets = [float(x) for x in args.offsets.split(",")] if args.offsets else None
         world = int(os.environ.get("WORLD_SIZE", "1"))

@@ -1,0 +1,153 @@
+// dtof_aov.hip -- the geometry channels of the reference's `aov` integrator (src/integrators/aov.cpp:196-330), from the camera ray to the film in one kernel:
+//   query    the lane's camera ray as k_generate left it (origin, direction, time, maxt), one closest hit at the ray's OWN time (Scene::ray_intersect with
+//            RayFlags::All, aov.cpp:206-207) through trace_rays, the scene staged as k_velocity stages it
+//   surface  compute_surface with the frames on: dp_du / dp_dv come through instances (dtof_shading.h); every value is +0 on a miss (aov.cpp:208)
+//   select   the lane's 20 values stay in registers; channel c is value slot[c], picked by selects on a wave-uniform counter (dtof_aov.h: the slots)
+//   splat    the footprint, float32 weights and run reduction of k_splat_moments_f64 (dtof_moments.hip, dtof_splat_runs.h): the term value * (wx * wy) is a float32
+//            product (the box filter adds the value itself and 1.f), converted to double; runs of lanes with one footprint anchor are summed in the wave and the run's
+//            last lane issues one atomic per cell and channel; footprints wider than 5 x 5 take one atomic per lane, cell and channel
+// With AovArgs::values the lane's channels are written out instead of the splat (dtof_sample_aov_lanes): the same code up to the selection.
+// Compiled with -ffp-contract=off like every kernel here.
+#include "dtof_device.h"
+#include "dtof_splat_runs.h"
+#include "dtof_aov.h"
+
+namespace dtof {
+
+namespace {
+static_assert(kAovMaxChannels <= 3 * (int) kAovSlotsPerWord && kAovSlots <= 32, "the channel table is three words of twelve 5-bit slots");
+
+// Value j of the lane's 20 for a wave-uniform j.  Twenty scalars and a chain of selects, as in dtof_moments.hip: an array or a struct that is indexed goes to scratch.
+#define DTOF_AOV_LIST(X) X(0) X(1) X(2) X(3) X(4) X(5) X(6) X(7) X(8) X(9) X(10) X(11) X(12) X(13) X(14) X(15) X(16) X(17) X(18) X(19)
+#define DTOF_AOV_PICK(k) v = j == k ? v##k : v;
+#define DTOF_AOV_SEL(j_) ([&] { const uint32_t j = (j_); float v = 0.f; DTOF_AOV_LIST(DTOF_AOV_PICK) return v; }())
+// c is wave-uniform: scalar shifts of three argument words (an indexed table in the argument block would be copied to scratch)
+DTOF_D uint32_t slot_of(const AovArgs &a, uint32_t c) {
+    const uint64_t w = c < kAovSlotsPerWord ? a.slots[0] : c < 2 * kAovSlotsPerWord ? a.slots[1] : a.slots[2];
+    const uint32_t k = c < kAovSlotsPerWord ? c : c < 2 * kAovSlotsPerWord ? c - kAovSlotsPerWord : c - 2 * kAovSlotsPerWord;
+    return (uint32_t) (w >> (5u * k)) & 31u;
+}
+DTOF_D double term(float v, float w, bool box) { return (double) (box ? v : v * w); }   // the box filter adds the value itself (value * 1.f is the same float)
+
+// Every thread of the block stays in the kernel up to the splat (the staging barrier, and the shuffles of run_sum are wave-wide); a thread without a lane has no ray,
+// is a run of its own and adds nothing.
+template <bool LDS>
+__global__ __launch_bounds__(kBlock) void k_aov(const uint8_t *scene, uint32_t scene_bytes, uint32_t stage_words, RenderParams rp, Queues q, AovArgs a) {
+    extern __shared__ uint4 lds[];
+    const uint8_t *base = LDS ? stage_scene(scene, scene_bytes, lds) : scene;
+    uint32_t *stack = (uint32_t *) (lds + stage_words) + threadIdx.x;
+    const SceneView sv = make_view(base);
+    const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+    const bool valid = i < rp.n_lanes;
+    float4 ra = make_float4(0.f, 0.f, 0.f, 0.f), rb = make_float4(0.f, 0.f, 1.f, 0.f);
+    if (valid) { ra = q.ray_a[i]; rb = q.ray_b[i]; }
+    const V3 o = mk(ra.x, ra.y, ra.z), d = mk(rb.x, rb.y, rb.z);
+    Hit h;
+    const bool found = trace_rays<false, true>(sv, stack, valid, o, d, ra.w, rb.w, h);
+#define DTOF_AOV_DECL(k) float v##k = 0.f;
+    DTOF_AOV_LIST(DTOF_AOV_DECL)
+#undef DTOF_AOV_DECL
+    if (found) {
+        Surface si;
+        compute_surface<true>(sv, h.obj, h.shape, h.prim, h.t, h.u, h.v, o, d, ra.w, si);
+        v0 = h.t;
+        v1 = si.p.x; v2 = si.p.y; v3 = si.p.z;
+        v4 = si.u; v5 = si.v;
+        v6 = si.n.x; v7 = si.n.y; v8 = si.n.z;
+        v9 = si.sh_n.x; v10 = si.sh_n.y; v11 = si.sh_n.z;
+        v12 = si.dp_du.x; v13 = si.dp_du.y; v14 = si.dp_du.z;
+        v15 = si.dp_dv.x; v16 = si.dp_dv.y; v17 = si.dp_dv.z;
+        v18 = (float) h.prim;
+        v19 = (float) (1u + (uint32_t) (si.shape - sv.shapes));
+    }
+    const uint32_t C = a.n_channels;
+    if (a.values) {   // the per-lane entry: the channels of the lane, no splat
+        if (!valid) return;
+        float *out = a.values + (size_t) i * C;
+#pragma unroll 1
+        for (uint32_t c = 0; c < C; ++c) out[c] = DTOF_AOV_SEL(slot_of(a, c));
+        return;
+    }
+    double *const film = a.film;
+    const int W = rp.crop_w, H = rp.crop_h;
+    const bool box = rp.filter == FILTER_BOX;
+    const int n = box ? 0 : (int) ceilf(rp.filter_radius - .5f), cnt = 2 * n + 1;
+    const float2 p = valid ? q.pos[i] : make_float2(0.f, 0.f);
+    // the footprint's anchor in film coordinates (splat_lane): the box filter splats at the lane's own pixel, every other at floor(position) - n
+    int ax, ay; float relx = 0.f, rely = 0.f;
+    if (box) {
+        const uint32_t pix = fdiv(global_lane(rp, rp.lane_base + (valid ? i : 0u)), rp.d_spp);
+        ay = (int) fdiv(pix, rp.d_w); ax = (int) (pix - (uint32_t) W * (uint32_t) ay);
+    } else {
+        const int pix = (int) floorf(p.x) - n, piy = (int) floorf(p.y) - n;
+        relx = (float) pix + .5f - p.x; rely = (float) piy + .5f - p.y;
+        ax = pix - rp.crop_x; ay = piy - rp.crop_y;
+    }
+    if (cnt > kRunCells) {   // wide footprints (the Lanczos filter's 7 x 7): one atomic per lane, cell and channel
+        if (!valid) return;
+#pragma unroll 1
+        for (int ys = 0; ys < cnt; ++ys) {
+            const float wy = filter_weight(rp, rely + (float) ys);
+#pragma unroll 1
+            for (int xs = 0; xs < cnt; ++xs) {
+                const float w = filter_weight(rp, relx + (float) xs) * wy;
+                const int x = ax + xs, y = ay + ys;
+                if ((unsigned) x >= (unsigned) W || (unsigned) y >= (unsigned) H) continue;
+                double *cell = film + (size_t) kMomentCell * ((size_t) y * W + x);
+                add_f64(cell, (double) w);
+#pragma unroll 1
+                for (uint32_t c = 0; c < C; ++c) add_f64(cell + 1 + c, (double) (DTOF_AOV_SEL(slot_of(a, c)) * w));
+            }
+        }
+        return;
+    }
+    const Runs runs = find_runs(ax, ay, valid);
+    const uint32_t dist = runs.dist, steps = runs.steps;
+    static_assert(kRunCells == 5, "five column and five row weights are kept in registers");
+#define DTOF_W(rel, k) (k < cnt && !box ? filter_weight(rp, rel + (float) k) : 0.f)
+    const float wx0 = DTOF_W(relx, 0), wx1 = DTOF_W(relx, 1), wx2 = DTOF_W(relx, 2), wx3 = DTOF_W(relx, 3), wx4 = DTOF_W(relx, 4);
+    const float wy0 = DTOF_W(rely, 0), wy1 = DTOF_W(rely, 1), wy2 = DTOF_W(rely, 2), wy3 = DTOF_W(rely, 3), wy4 = DTOF_W(rely, 4);
+#undef DTOF_W
+    // The PLANE loop is the outer one (plane 0: the weight, the value 1; plane 1 + c: channel c), so a channel's value is selected once and not once per cell; the
+    // cell loops inside it redo a cell's address and weight per plane, a handful of instructions against the twenty selects.  All three loops stay rolled: their
+    // counters are scalars.  1.f * w is w, so the weight takes the channels' code.
+#pragma unroll 1
+    for (uint32_t pl = 0; pl <= C; ++pl) {
+        const float v = pl == 0 ? (valid ? 1.f : 0.f) : DTOF_AOV_SEL(slot_of(a, pl - 1u));
+#pragma unroll 1
+        for (int ys = 0; ys < cnt; ++ys) {
+            float wys = wy0; wys = ys == 1 ? wy1 : wys; wys = ys == 2 ? wy2 : wys; wys = ys == 3 ? wy3 : wys; wys = ys == 4 ? wy4 : wys;
+#pragma unroll 1
+            for (int xs = 0; xs < cnt; ++xs) {
+                const int x = ax + xs, y = ay + ys;
+                const bool write = valid && runs.last && (unsigned) x < (unsigned) W && (unsigned) y < (unsigned) H;   // the same cell for every lane of the run
+                float wxs = wx0; wxs = xs == 1 ? wx1 : wxs; wxs = xs == 2 ? wx2 : wxs; wxs = xs == 3 ? wx3 : wxs; wxs = xs == 4 ? wx4 : wxs;
+                const double sum = run_sum(term(v, wxs * wys, box), dist, steps);
+                if (write) add_f64(film + (size_t) kMomentCell * ((size_t) y * W + x) + pl, sum);
+            }
+        }
+    }
+}
+#undef DTOF_AOV_SEL
+#undef DTOF_AOV_PICK
+#undef DTOF_AOV_LIST
+
+// launch_velocity's staging rule (dtof_kernels.hip): the blob goes to LDS while it is small and leaves room for the stack columns within the 64 KiB a block may ask for
+constexpr uint32_t kAovSceneLimit = 16 * 1024, kAovBlockLimit = 64 * 1024;
+}  // namespace
+
+void launch_aov(const uint8_t *scene, uint32_t scene_bytes, const RenderParams &rp, const Queues &q, const AovArgs &a, uint32_t stack_depth, const LaunchSwitches &ls,
+                hipStream_t s) {
+    if (rp.n_lanes == 0) return;
+    if (a.n_channels < 1 || a.n_channels > (uint32_t) kAovMaxChannels || (!a.film && !a.values)) throw std::runtime_error("internal error: launch_aov without channels or without a destination");
+    for (uint32_t c = 0; c < a.n_channels; ++c)
+        if (((a.slots[c / kAovSlotsPerWord] >> (5u * (c % kAovSlotsPerWord))) & 31u) >= (uint64_t) kAovSlots) throw std::runtime_error("internal error: launch_aov with a channel table beyond the lane's values");
+    const uint32_t stack = stack_bytes(stack_depth), words = (scene_bytes + 15) / 16;
+    const uint32_t sw = ls.stage && scene_bytes <= kAovSceneLimit && words * 16 + stack + 64 <= kAovBlockLimit ? words : 0;
+    const uint32_t lds = sw * 16 + stack;
+    if (lds + 64 > kAovBlockLimit) throw std::runtime_error("the BVH of this scene is too deep for the LDS traversal stack");
+    if (sw) hipLaunchKernelGGL(k_aov<true>, dim3(nblk(rp.n_lanes)), dim3(kBlock), lds, s, scene, scene_bytes, sw, rp, q, a);
+    else hipLaunchKernelGGL(k_aov<false>, dim3(nblk(rp.n_lanes)), dim3(kBlock), lds, s, scene, scene_bytes, sw, rp, q, a);
+}
+
+}  // namespace dtof

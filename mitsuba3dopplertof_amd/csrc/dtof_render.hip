@@ -11,6 +11,7 @@
 #include "dtof_reconstruct.h"
 #include "dtof_film64.h"
 #include "dtof_moments.h"
+#include "dtof_aov.h"
 #include "dtof_flat_query.h"
 #include "dtof_scene.h"
 #include "dtof_math.h"
@@ -103,7 +104,7 @@ struct dtof_scene {
     Workspace ws;
     DevBuf<float> d_film, d_rgb;
     DevBuf<double> d_film64;   // the library's own float64 film (dtof_render_variants_f64, dtof_render_velocity_map_f64)
-    DevBuf<double> d_moments, d_moment_planes;   // the moment film (dtof_render_moments): cells of kMomentCell doubles per pixel, and the dense planes copied out
+    DevBuf<double> d_moments, d_moment_planes;   // the moment film (dtof_render_moments) or the aov film (dtof_render_aovs) of the call: cells of kMomentCell doubles per pixel, and the dense planes copied out
     DevBuf<float> d_vm_sum, d_vm_tof; DevBuf<double> d_vm_maps;   // dtof_render_velocity_map: the passes' sum, the ToF images, the per-pair maps and the combined map
     // the caller's device film as declared with dtof_scene_set_film_layout (0 = not declared: colour planes only, W * H * 4 apart)
     int32_t film_planes = 0; uint64_t film_plane_stride = 0;
@@ -360,6 +361,8 @@ struct RenderRequest {
     float *film = nullptr; uint64_t film_stride = 0;   // K films (and the alpha film behind them) film_stride floats apart
     double *film64 = nullptr; uint64_t film64_stride = 0;   // ... or the float64 film, film64_stride doubles apart: the separate splat stage accumulates in double (dtof_film64.hip)
     double *moments = nullptr;                    // ... or the moment film (dtof_moments.h: cells of kMomentCell doubles), likewise the separate splat stage's; no alpha film
+    const AovArgs *aov = nullptr;                 // ... or the geometry channels of the `aov` integrator (dtof_aov.h): k_aov takes the shade loop's place behind k_generate and
+                                                  // splats into aov->film itself, or -- with a lane dump -- writes the dumped lanes' channels to aov->values ([dump_n][n_channels])
     dtof_render_stats *stats = nullptr;
     LaneDebug *lane_dump = nullptr; uint64_t dump_begin = 0, dump_n = 0;   // lane_dump != nullptr: evaluate only lanes [dump_begin, dump_begin + dump_n) and copy their records out
     bool deferred = false;                        // dtof_render_rows_async: timings by events, no counters read back, no synchronisation at the end
@@ -670,11 +673,12 @@ FramePlan plan_frame(const dtof_scene *sc, const RenderRequest &rq) {
     rp.emitter_pmf = bh_emitters(*sc) ? 1.f / (float) bh_emitters(*sc) : 0.f;   // m_emitter_pmf (scene.cpp:96)
     // fused pipeline: the first bounce kernel generates the lanes and traces the primary rays itself
     p.first_inline = p.fused && rp.integrator != INTEGRATOR_VELOCITY && p.iteration_runs(0) && on("DTOF_FUSE_FIRST");
+    if (rq.aov) p.first_inline = false;   // k_aov reads the camera rays k_generate writes: the fused first-bounce kernel is never involved
     // exactly one wave per pixel, one film: measured (profiles/r04_fused_splat_ab.txt) -- with more waves per pixel (C3: 256 spp) or four films (C5) the separate
     // splat kernel, which sums 8 samples per lane before it reduces, is faster
     p.fuse_splat_ok = on("DTOF_FUSE_SPLAT") && p.fused && !rq.lane_dump && p.n_passes == 1 && !se.alpha && rp.filter == FILTER_TENT && rp.filter_radius <= 1.f &&
                       rp.filter_radius > .5f && rp.spp_log2 == 6 && rp.n_offsets == 1 && rq.film != nullptr;
-    if (rq.film64 || rq.moments) p.fuse_splat_ok = false;   // the float64 film and the moment film are the separate splat stage's: k_shade splats in float32
+    if (rq.film64 || rq.moments || rq.aov) p.fuse_splat_ok = false;   // the float64 film and the moment film are the separate splat stage's: k_shade splats in float32
     return p;
 }
 
@@ -701,6 +705,9 @@ void render_rows(dtof_scene *sc, const RenderRequest &rq) {
         rp.pass_rng = sc->d_pass_rng.p; rp.pass_first = (uint32_t) p.first;
     }
     const bool velocity = rp.integrator == INTEGRATOR_VELOCITY;
+    // An aov call runs k_aov where the integrator would run.  The integrator itself still runs in every pass that another pass follows: a later pass draws its lanes
+    // from the streams the paths of the earlier one left behind (Sampler::advance, sampler.cpp:52-55), and the lanes of an aov render are the scene integrator's own.
+    const bool aov = rq.aov != nullptr;
     // The host runs at most two batches ahead of the device: dtof_cancel (Integrator::cancel, integrator.h:96-109) is looked at when a
     // batch is enqueued, so an unbounded run-ahead would leave nothing to cancel once the launches of a long render are queued.
     hipEvent_t batch_done[2] = { sc->take_event(), sc->take_event() };
@@ -721,8 +728,14 @@ void render_rows(dtof_scene *sc, const RenderRequest &rq) {
         }
         const uint32_t *qin = nullptr, *count_in = nullptr; uint32_t it = 0;
         bool fused_splat_done = false;   // the first-bounce kernel of this batch splatted its lanes itself
-        if (velocity) { t = tm.begin(kStageTrace, s); launch_velocity(blob, blob_bytes, rp, q, stack_depth, p.launch, s); tm.end(kStageTrace, t, s); }
-        for (; !velocity && p.iteration_runs(it); ++it) {
+        const bool integrate = !aov || (p.n_passes > 1 && pass + 1 < p.run_passes);
+        if (aov && (!rq.lane_dump || dump_now)) {   // before the shade loop of a multi-pass render overwrites the camera rays
+            AovArgs a = *rq.aov;
+            if (a.values) a.values += (size_t) (b0 - p.first) * a.n_channels;
+            t = tm.begin(kStageTrace, s); launch_aov(blob, blob_bytes, rp, q, a, stack_depth, p.launch, s); tm.end(kStageTrace, t, s);
+        }
+        if (velocity && !aov) { t = tm.begin(kStageTrace, s); launch_velocity(blob, blob_bytes, rp, q, stack_depth, p.launch, s); tm.end(kStageTrace, t, s); }
+        for (; !velocity && integrate && p.iteration_runs(it); ++it) {
             if (it >= 8 && (it & 3) == 0) {   // unbounded depth: stop once every segment has drained
                 std::vector<uint32_t> alive(n_seg);
                 HIP_CHECK(hipMemcpyAsync(alive.data(), count_in, (size_t) n_seg * 4, hipMemcpyDeviceToHost, s));
@@ -765,7 +778,7 @@ void render_rows(dtof_scene *sc, const RenderRequest &rq) {
                 for (int k = 0; k < rp.n_offsets; ++k)
                     HIP_CHECK(hipMemcpyAsync(rq.lane_planes + (size_t) k * rq.dump_n + (b0 - p.first), q.res + (size_t) k * q.capacity, (size_t) rp.n_lanes * sizeof(float4), hipMemcpyDeviceToHost, s));
             HIP_CHECK(hipStreamSynchronize(s));
-        } else if (!rq.lane_dump && !fused_splat_done) {
+        } else if (!rq.lane_dump && !fused_splat_done && !aov) {
             t = tm.begin(kStageSplat, s);
             if (rq.moments) launch_splat_moments(rp, q, rq.moments, s);
             else if (rq.film64) launch_splat_f64(rp, q, rq.film64, rq.film64_stride, s); else launch_splat(rp, q, rq.film, rq.film_stride, p.launch, s);
@@ -1424,6 +1437,98 @@ int dtof_render_moments(dtof_scene *sc, uint32_t seed, uint32_t spp, uint32_t n_
         HIP_CHECK(hipMemcpyAsync(out_planes, sc->d_moment_planes.p, px * planes * sizeof(double), hipMemcpyDeviceToHost, s));
         HIP_CHECK(hipStreamSynchronize(s));
         if (stats) *stats = sum;
+    });
+}
+
+// ---------------------------------------------------------------- geometry channels of the `aov` integrator (dtof_aov.hip)
+int dtof_aov_parse(const char *spec, int32_t *types, int capacity, int *n_types, char *names_buf, size_t names_capacity, int *n_channels) {
+    return guarded([&] {
+        if (!spec) throw std::runtime_error("null argument");
+        std::vector<int32_t> t; std::vector<std::string> names;
+        parse_aovs(spec, t, names);
+        if (n_types) *n_types = (int) t.size();
+        if (n_channels) *n_channels = (int) names.size();
+        if (types) {
+            if (capacity < (int) t.size()) throw std::runtime_error("dtof_aov_parse: the spec has " + std::to_string(t.size()) + " types, the buffer holds " + std::to_string(std::max(capacity, 0)));
+            std::copy(t.begin(), t.end(), types);
+        }
+        if (names_buf) {
+            size_t need = 0; for (auto &n : names) need += n.size() + 1;
+            if (names_capacity < need) throw std::runtime_error("dtof_aov_parse: the channel names take " + std::to_string(need) + " bytes, the buffer holds " + std::to_string(names_capacity));
+            char *w = names_buf;
+            for (auto &n : names) { memcpy(w, n.c_str(), n.size() + 1); w += n.size() + 1; }
+        }
+    });
+}
+int dtof_scene_get_aovs(const dtof_scene *sc, char *buf, size_t capacity) {
+    return guarded([&] {
+        if (!sc || !buf) throw std::runtime_error("null argument");
+        if (capacity < sc->host.aovs.size() + 1) throw std::runtime_error("dtof_scene_get_aovs: the spec takes " + std::to_string(sc->host.aovs.size() + 1) + " bytes");
+        memcpy(buf, sc->host.aovs.c_str(), sc->host.aovs.size() + 1);
+    });
+}
+// the channel table of a call: everything a call can be refused for, before any device call
+static AovArgs aov_args(const dtof_scene *sc, const int32_t *types, int n_types) {
+    if (!types) throw std::runtime_error("null argument");
+    if (n_types < 1) throw std::runtime_error("No AOVs were specified!");
+    if (!sc->host.has_sensor) throw std::runtime_error("the scene does not contain a sensor");
+    AovArgs a; a.film = nullptr; a.values = nullptr; a.n_channels = 0; a.slots[0] = a.slots[1] = a.slots[2] = 0;
+    for (int i = 0; i < n_types; ++i) {
+        if (types[i] < 0 || types[i] >= kAovTypes) throw std::runtime_error("AOV type " + std::to_string(types[i]) + " is not one of the DTOF_AOV_* constants");
+        for (int k = 0; k < kAovTypeChannels[types[i]]; ++k, ++a.n_channels) {
+            if (a.n_channels >= (uint32_t) kAovMaxChannels)
+                throw std::runtime_error("the aov film holds at most " + std::to_string(kAovMaxChannels) + " channels beside the weight (a pixel is a cell of 32 doubles)");
+            a.slots[a.n_channels / kAovSlotsPerWord] |= (uint64_t) (kAovTypeSlot[types[i]] + k) << (5u * (a.n_channels % kAovSlotsPerWord));
+        }
+    }
+    return a;
+}
+int dtof_render_aovs(dtof_scene *sc, uint32_t seed, uint32_t spp, uint32_t n_passes, const int32_t *types, int n_types, int developed, double *out_planes,
+                     dtof_render_stats *stats) {
+    return guarded([&] {
+        if (!sc || !out_planes) throw std::runtime_error("null argument");
+        if (n_passes == 0) throw std::runtime_error("the aov film needs at least one pass");
+        AovArgs a = aov_args(sc, types, n_types);
+        ensure_device(sc);
+        sc->stop = false;
+        const HostSensor &se = sc->host.sensor;
+        const size_t px = (size_t) se.crop_w * se.crop_h;
+        const int planes = 1 + (int) a.n_channels;
+        sc->d_moments.ensure(px * kMomentCell); sc->d_moment_planes.ensure(px * planes);
+        const hipStream_t s = sc->stream;
+        HIP_CHECK(hipMemsetAsync(sc->d_moments.p, 0, px * kMomentCell * sizeof(double), s));   // once: the raw sums of the passes add up
+        a.film = sc->d_moments.p;
+        dtof_render_stats sum; memset(&sum, 0, sizeof sum);
+        for (uint32_t pass = 0; pass < n_passes; ++pass) {
+            dtof_render_stats frame;
+            RenderRequest rq; rq.seed = seed + pass; rq.spp = spp; rq.row_begin = 0; rq.row_end = se.crop_h; rq.stats = &frame; rq.aov = &a;
+            render_rows(sc, rq);
+            add_stats(sum, frame);
+        }
+        launch_develop_moments(sc->d_moments.p, planes, developed != 0, sc->d_moment_planes.p, (int64_t) px, s);
+        HIP_CHECK(hipGetLastError());
+        HIP_CHECK(hipMemcpyAsync(out_planes, sc->d_moment_planes.p, px * planes * sizeof(double), hipMemcpyDeviceToHost, s));
+        HIP_CHECK(hipStreamSynchronize(s));
+        if (stats) *stats = sum;
+    });
+}
+int dtof_sample_aov_lanes(dtof_scene *sc, uint32_t seed, uint32_t spp, const int32_t *types, int n_types, uint64_t lane_begin, uint64_t n, float *out_lanes12,
+                          float *out_values) {
+    return guarded([&] {
+        if (!sc || !out_lanes12 || !out_values) throw std::runtime_error("null argument");
+        AovArgs a = aov_args(sc, types, n_types);
+        ensure_device(sc);
+        sc->stop = false;
+        if (n == 0) return;
+        // the scene integrator's lanes, for their rgb ...
+        std::vector<LaneDebug> lanes(n), own(n);
+        { RenderRequest rq; rq.seed = seed; rq.spp = spp; rq.lane_dump = own.data(); rq.dump_begin = lane_begin; rq.dump_n = n; render_rows(sc, rq); }
+        // ... and the aov kernel's: the sample position, time and camera ray are the ones it read
+        DevBuf<float> d_values; d_values.ensure((size_t) n * a.n_channels);
+        a.values = d_values.p;
+        { RenderRequest rq; rq.seed = seed; rq.spp = spp; rq.lane_dump = lanes.data(); rq.dump_begin = lane_begin; rq.dump_n = n; rq.aov = &a; render_rows(sc, rq); }
+        HIP_CHECK(hipMemcpy(out_values, d_values.p, (size_t) n * a.n_channels * sizeof(float), hipMemcpyDeviceToHost));
+        for (uint64_t i = 0; i < n; ++i) { memcpy(out_lanes12 + 12 * i, &lanes[i], 36); memcpy(out_lanes12 + 12 * i + 9, own[i].rgb, 12); }
     });
 }
 

@@ -257,7 +257,12 @@ struct HostScene {
     std::vector<HostTexture> textures;
     HostSensor sensor; bool has_sensor = true;   // a scene without a <sensor> loads, as in the reference; rendering it fails
     PropBag integrator, sampler;
+    std::string aovs;   // <integrator type="aov">: its `aovs` string (src/integrators/aov.cpp:109-110); `integrator` is the nested plugin's bag
 };
+
+// AOVIntegrator's parse of `aovs` (src/integrators/aov.cpp:109-175; scene_loader.cpp): the types as DTOF_AOV_* constants (include/dtof.h) and the channel names in film
+// order.  Throws std::runtime_error with the reference's message for an unknown type, and for the types this library refuses and for malformed tokens with its own.
+void parse_aovs(const std::string &spec, std::vector<int32_t> &types, std::vector<std::string> &names);
 
 // XML front end (scene_loader.cpp): the tag subset of SURVEY §8a row X1.  `base_dir` is what the reference's FileResolver
 // holds for a scene file (its directory): relative `filename` properties of obj / ply shapes resolve against it.

@@ -1424,6 +1424,32 @@ HostScene load_scene_xml(const std::string &text, const std::map<std::string, st
                 std::vector<std::string> own;
                 for (auto &kv : o.props.values) own.push_back(kv.first);
                 if (!own.empty()) fail_unreferenced(own, "integrator", "moment");   // the plugin queries nothing but its child objects
+                if (nested[0]->plugin == "aov" || nested[0]->plugin == "moment")
+                    fail("moment: a nested \"" + nested[0]->plugin + "\" integrator is not supported: the moment film and the aov film are separate renders of one "
+                         "scene integrator (dtof_render_moments, dtof_render_aovs); nest a dopplertofpath, path or velocity integrator");
+                integ = nested[0];
+            } else if (o.plugin == "aov") {
+                // src/integrators/aov.cpp:109-194 parses `aovs` and wraps its nested integrators, whose RGBA follow the geometry channels (:308-323); render() of the
+                // scene is the first child's image.  Here, as with `moment`, the ONE nested plugin becomes the scene's integrator with all its properties; the
+                // geometry channels are what dtof_render_aovs accumulates from that integrator's own camera rays, and the spec is kept on the scene.
+                std::vector<const Obj *> nested;
+                for (auto &c : o.children) {
+                    if (!c.second) continue;
+                    if (c.second->tag != "integrator") fail("aov: Child objects must be of type 'SamplingIntegrator'! (found a \"" + c.second->tag + "\")");
+                    nested.push_back(c.second.get());
+                }
+                if (nested.empty()) fail("aov: the integrator needs one nested <integrator> (none was given)");
+                if (nested.size() > 1) fail("aov: " + std::to_string(nested.size()) + " nested integrators were given; this library renders one integrator per scene, "
+                                            "so \"aov\" takes exactly one nested <integrator>");
+                if (nested[0]->plugin == "aov" || nested[0]->plugin == "moment")
+                    fail("aov: a nested \"" + nested[0]->plugin + "\" integrator is not supported: the aov film and the moment film are separate renders of one "
+                         "scene integrator (dtof_render_aovs, dtof_render_moments); nest a dopplertofpath, path or velocity integrator");
+                if (!o.props.has("aovs")) fail("Property \"aovs\" has not been specified!");   // props.string("aovs") without a default (aov.cpp:110)
+                sc.aovs = o.props.get_string("aovs", "");
+                std::vector<int32_t> types; std::vector<std::string> names;
+                parse_aovs(sc.aovs, types, names);   // the constructor's checks
+                auto u = o.props.unqueried();
+                if (!u.empty()) fail_unreferenced(u, "integrator", "aov");
                 integ = nested[0];
             }
             sc.integrator = integ->props; have_integrator = true;
@@ -1569,6 +1595,38 @@ HostScene load_scene_xml(const std::string &text, const std::map<std::string, st
     sc.has_sensor = have_sensor;   // a scene without a sensor loads (as in the reference); rendering it is the error
     if (!have_integrator) { sc.integrator = PropBag(); sc.integrator.plugin = "path"; }
     return sc;
+}
+
+void parse_aovs(const std::string &spec, std::vector<int32_t> &types, std::vector<std::string> &names) {
+    // string::tokenize (include/mitsuba/core/string.h:104-106, src/core/string.cpp): split at any of the delimiters, empty tokens dropped
+    const auto tokenize = [](const std::string &text, const char *delim) {
+        std::vector<std::string> out;
+        size_t last = 0, pos;
+        while ((pos = text.find_first_of(delim, last)) != std::string::npos) {
+            if (pos != last) out.push_back(text.substr(last, pos - last));
+            last = pos + 1;
+        }
+        if (last != text.size()) out.push_back(text.substr(last));
+        return out;
+    };
+    struct Known { const char *type; int32_t id; const char *suffixes; };
+    static const Known known[] = { { "depth", 0, "T" }, { "position", 1, "XYZ" }, { "uv", 2, "UV" }, { "geo_normal", 3, "XYZ" }, { "sh_normal", 4, "XYZ" },
+                                   { "dp_du", 5, "XYZ" }, { "dp_dv", 6, "XYZ" }, { "prim_index", 7, "I" }, { "shape_index", 8, "I" } };
+    types.clear(); names.clear();
+    for (const std::string &token : tokenize(spec, ", ")) {
+        const std::vector<std::string> item = tokenize(token, ":");
+        if (item.size() != 2) fail("Invalid AOV specification \"" + token + "\": require <name>:<type> pair");   // (aov.cpp:115-116 warns and goes on to read item[1])
+        const std::string &type = item[1];
+        if (type == "albedo") fail("AOV type \"albedo\" is not supported: it needs BSDF::eval_diffuse_reflectance of every BSDF (aov.cpp:229-246), which this library does not implement");
+        if (type == "boundary_test") fail("AOV type \"boundary_test\" is not supported: no shape of this library computes SurfaceInteraction::boundary_test (aov.cpp:274-276)");
+        if (type == "duv_dx" || type == "duv_dy")
+            fail("AOV type \"" + type + "\" is not supported: this build carries no ray differentials, so SurfaceInteraction::duv_dx / duv_dy (aov.cpp:290-298) do not exist");
+        const Known *k = nullptr;
+        for (const Known &c : known) if (type == c.type) k = &c;
+        if (!k) fail("Invalid AOV type \"" + type + "\"!");   // aov.cpp:173
+        types.push_back(k->id);
+        for (const char *sfx = k->suffixes; *sfx; ++sfx) names.push_back(item[0] + "." + *sfx);
+    }
 }
 
 std::string read_file(const std::string &path) {

@@ -136,6 +136,16 @@ def run_scene_moments(scene, total_spp=1024, variants=((0, 0), (1, 0)), **integr
     return m, single * n_pass
 
 
+def run_scene_aovs(scene, total_spp, aovs, **integrator_kwargs):
+    """The geometry channels along the camera rays of run_scene_doppler_tof's render: the same integrator dictionary, the same passes (min(1024, total_spp) samples
+    each) and seeds 0, 1, ... as run_scene_moments, in ONE Scene.render_aovs call whose passes all accumulate into one film.  `aovs`: the `aovs` string of the
+    reference's aov integrator.  Returns (the dict of Scene.render_aovs, n_samples = passes x spp)."""
+    single, n_pass = _passes(total_spp)
+    scene.set_integrator(doppler_integrator_dict(**integrator_kwargs))
+    m = scene.render_aovs(aovs, seed=0, spp=single, n_passes=n_pass)
+    return m, single * n_pass
+
+
 def moment_statistics(m, n_samples):
     """Per-pixel sample statistics from the developed dict of Scene.render_moments (all numpy, float64):
         "variance" (K, H, W, 3)   m2 - mean^2 of X, Y, Z: the variance of ONE sample
