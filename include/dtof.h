@@ -541,6 +541,10 @@ int dtof_ray_test(dtof_scene *scene, uint32_t n, const float *rays8, int32_t *oc
  * miss); any != 0: occlusion, ids = 1 / 0 (out3 is not written).  DTOF_ERR_INVALID, before anything is launched, for a scene without a flat table, a form whose facts
  * the scene does not meet, and n above 2^24; non-finite ray components are taken as they are. */
 int dtof_flat_query(dtof_scene *scene, int form, int any, uint32_t n, const float *rays8, float *out3, int32_t *ids);
+/* The same through the PAIR form of the walk of form 2, which a frame's kernel runs where the two lanes of a correlated pair hold the same ray: n is even, rays 2k
+ * and 2k + 1 are equal in o, d and maxt bit for bit (their times are their own), and each pair shares the plain rectangles between its two lanes.  Results as above.
+ * DTOF_ERR_INVALID, before anything is launched, for an odd n, a pair that differs and a table other than 5 rectangles with the wall at index 2. */
+int dtof_flat_query_pairs(dtof_scene *scene, int any, uint32_t n, const float *rays8, float *out3, int32_t *ids);
 
 /* ---------------------------------------------------------------- component evaluation
  * The device functions the shade and splat kernels are built from, evaluated over arrays on the GPU: the counterpart of the

@@ -159,6 +159,7 @@ def _lib():
                        ("dtof_sample_lanes_variants", [vp, C.c_uint32, C.c_uint32, vp, C.c_int, C.c_uint64, C.c_uint64, vp, vp, vp]),
                        ("dtof_emitter_eval", [vp, C.c_int, C.c_int, C.c_int32, C.c_uint32, vp, vp]),
                        ("dtof_flat_query", [vp, C.c_int, C.c_int, C.c_uint32, vp, vp, vp]),
+                       ("dtof_flat_query_pairs", [vp, C.c_int, C.c_uint32, vp, vp, vp]),
                        ("dtof_develop_accumulate_async", [vp, vp, C.c_int32, C.c_uint64, vp, C.c_int64, C.c_int]),
                        ("dtof_velocity_map_async", [vp, vp, C.c_int, vp, vp, C.c_uint32, C.c_double, C.c_double, C.c_int64, vp, vp, vp]),
                        ("dtof_velocity_map_variants", [vp, C.c_int, vp]),
@@ -724,6 +725,15 @@ class Scene:
         form = self.FLAT_FORMS.get(form, form)
         out, ids = np.zeros((len(rays), 3), np.float32), np.zeros(len(rays), np.int32)
         _check(_lib().dtof_flat_query(self._h, int(form), 1 if any else 0, len(rays), rays.ctypes.data, None if any else out.ctypes.data, ids.ctypes.data))
+        return ids if any else {"t": out[:, 0], "u": out[:, 1], "v": out[:, 2], "obj": ids}
+
+    def flat_query_pairs(self, rays8, any=False):
+        """flat_query in the pair form of the "shape" walk (dtof_flat_query_pairs), the one a frame's kernel runs where the two lanes of a correlated pair hold the same
+        ray: rays 2k and 2k + 1 are equal in o, d and maxt, bit for bit, and have times of their own.  Same results as flat_query.  An odd count, a pair that differs
+        and a table other than five rectangles with the wall at index 2 raise DtofError."""
+        rays = np.ascontiguousarray(rays8, np.float32).reshape(-1, 8)
+        out, ids = np.zeros((len(rays), 3), np.float32), np.zeros(len(rays), np.int32)
+        _check(_lib().dtof_flat_query_pairs(self._h, 1 if any else 0, len(rays), rays.ctypes.data, None if any else out.ctypes.data, ids.ctypes.data))
         return ids if any else {"t": out[:, 0], "u": out[:, 1], "v": out[:, 2], "obj": ids}
 
     def cancel(self):

@@ -8,9 +8,9 @@ namespace dtof {
 
 static_assert(kHeadlineShapeFacts == 0 || (flat_query_facts(2) & kFactFlatShape) != 0, "form 2 is the shaped walk");
 
-template <bool ANY, uint32_t FACTS>
-__global__ __launch_bounds__(kShadeBlock) void k_flat_query(const uint8_t *scene, uint32_t scene_bytes, uint32_t stage_words, uint32_t flat_off, uint32_t flat_objects,
-                                                             uint32_t memo_obj, const float *rays, float *out3, int32_t *ids, uint32_t n) {
+template <bool ANY, uint32_t FACTS, bool PAIR_RAYS>
+DTOF_D void flat_query_lane(const uint8_t *scene, uint32_t scene_bytes, uint32_t stage_words, uint32_t flat_off, uint32_t flat_objects,
+                            uint32_t memo_obj, const float *rays, float *out3, int32_t *ids, uint32_t n) {
     extern __shared__ uint4 lds[];
     constexpr bool F_ONE_WALL = (FACTS & kFactOneWall) != 0;
     const uint8_t *base = stage_scene(scene, scene_bytes, lds);
@@ -26,11 +26,23 @@ __global__ __launch_bounds__(kShadeBlock) void k_flat_query(const uint8_t *scene
     float memo_m[12], memo_inv[12];
     if (have_memo) instance_memo_fill(sv, time, memo_m, memo_inv);
     Hit h;
-    const bool found = trace_flat<ANY, true, FACTS>(sv, (ConstBytes) scene + flat_off, flat_off, flat_objects, nullptr, o, d, time, maxt, h);
+    const bool found = trace_flat<ANY, true, FACTS, PAIR_RAYS>(sv, (ConstBytes) scene + flat_off, flat_off, flat_objects, nullptr, o, d, time, maxt, h);
     if (ANY) { ids[i] = found ? 1 : 0; return; }
     float *w = out3 + (size_t) i * 3;
     ids[i] = found ? (int32_t) h.obj : -1;
     w[0] = found ? h.t : u2f(0x7f800000u); w[1] = found ? h.u : 0.f; w[2] = found ? h.v : 0.f;
+}
+template <bool ANY, uint32_t FACTS>
+__global__ __launch_bounds__(kShadeBlock) void k_flat_query(const uint8_t *scene, uint32_t scene_bytes, uint32_t stage_words, uint32_t flat_off, uint32_t flat_objects,
+                                                             uint32_t memo_obj, const float *rays, float *out3, int32_t *ids, uint32_t n) {
+    flat_query_lane<ANY, FACTS, false>(scene, scene_bytes, stage_words, flat_off, flat_objects, memo_obj, rays, out3, ids, n);
+}
+// trace_flat's pair form (dtof_pair_walk.h): n is even and rays 2k and 2k + 1 hold the same o, d and maxt (dtof_flat_query_pairs checks both), so the two lanes of a pair
+// are in range together -- a block holds whole pairs -- and the form's premise holds in every wave
+template <bool ANY>
+__global__ __launch_bounds__(kShadeBlock) void k_flat_query_pairs(const uint8_t *scene, uint32_t scene_bytes, uint32_t stage_words, uint32_t flat_off, uint32_t flat_objects,
+                                                                   uint32_t memo_obj, const float *rays, float *out3, int32_t *ids, uint32_t n) {
+    if constexpr (kFlatQueryPairsBuilt) flat_query_lane<ANY, flat_query_facts(2), true>(scene, scene_bytes, stage_words, flat_off, flat_objects, memo_obj, rays, out3, ids, n);
 }
 
 template <uint32_t FACTS>
@@ -48,7 +60,10 @@ void launch_flat_query(const uint8_t *scene, uint32_t scene_bytes, uint32_t flat
     const uint32_t lds = ShadeLds::classic(stage_words, true, memo_obj != 0xffffffffu, 1u).without_stack();
     if (scene_bytes > 16u * 1024u) throw std::runtime_error("dtof_flat_query: the scene does not fit the LDS stage");   // (launch_shade stages up to 16 KiB)
     const uint32_t grid = (n + kShadeBlock - 1u) / kShadeBlock;
-    if (form == 2) launch_form<flat_query_facts(2)>(any, grid, lds, s, scene, scene_bytes, stage_words, flat_off, flat_objects, memo_obj, rays, out3, ids, n);
+    if (form == kFlatQueryPairs) {
+        if (any) hipLaunchKernelGGL((k_flat_query_pairs<true>), dim3(grid), dim3(kShadeBlock), lds, s, scene, scene_bytes, stage_words, flat_off, flat_objects, memo_obj, rays, out3, ids, n);
+        else hipLaunchKernelGGL((k_flat_query_pairs<false>), dim3(grid), dim3(kShadeBlock), lds, s, scene, scene_bytes, stage_words, flat_off, flat_objects, memo_obj, rays, out3, ids, n);
+    } else if (form == 2) launch_form<flat_query_facts(2)>(any, grid, lds, s, scene, scene_bytes, stage_words, flat_off, flat_objects, memo_obj, rays, out3, ids, n);
     else if (form == 1) launch_form<flat_query_facts(1)>(any, grid, lds, s, scene, scene_bytes, stage_words, flat_off, flat_objects, memo_obj, rays, out3, ids, n);
     else launch_form<flat_query_facts(0)>(any, grid, lds, s, scene, scene_bytes, stage_words, flat_off, flat_objects, memo_obj, rays, out3, ids, n);
 }

@@ -255,6 +255,20 @@ static_assert((DTOF_HEADLINE_SHAPE_COUNT) == 0 || (kHeadlineC2Facts & kFactOneWa
 #define DTOF_PAIR_SAMPLES 1
 #endif
 constexpr uint32_t kHeadlinePairFacts = DTOF_HEADLINE_PAIR && kHeadlineShapeFacts != 0 ? (kHeadlineShapeFacts | kFactPairSamples) : 0u;
+// ... and one more step behind the same fact (k).  DTOF_PAIR_WALK_PRIMARY: the camera ray, which is the same ray in the two lanes of a pair, splits its plain
+// rectangles between the lanes (trace_flat's PAIR_RAYS form, dtof_pair_walk.h; written for a table of 5 with the wall at 2, every other shape keeps its text).
+// The builds with the traversal counters compile the form out: a lane of it tests three rectangles, and the counters' slots 20 .. 23 count five.
+// (The same form for iteration 0's shadow and continuation rays, in the waves whose primary hits are all off the wall, was built behind a switch of its own and
+//  made the frame slower, alone and on top of this step: DESIGN 8.3 (k), profiles/pair_walk_ab.txt.  Removed.)
+#ifndef DTOF_PAIR_WALK_PRIMARY
+#define DTOF_PAIR_WALK_PRIMARY 1
+#endif
+#ifdef DTOF_TRAVERSAL_STATS
+constexpr bool kPairWalkCompiled = false;
+#else
+constexpr bool kPairWalkCompiled = true;
+#endif
+constexpr bool pair_walk_shape(uint32_t facts) { return (facts & kFactOneWall) != 0 && flat_shape_count(facts) == 5 && flat_shape_wall(facts) == 2; }
 // The two steps of (i) inside trace_flat under a shape, each with a switch for its A/B: the occlusion queries' straight-line sweep, the closest-hit queries' written-out walk
 #ifndef DTOF_FLAT_SHAPE_ANY
 #define DTOF_FLAT_SHAPE_ANY 1

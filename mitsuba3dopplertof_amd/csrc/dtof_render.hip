@@ -1990,6 +1990,34 @@ int dtof_flat_query(dtof_scene *sc, int form, int any, uint32_t n, const float *
     });
 }
 
+// ... and the pair form of the shaped walk (trace_flat: PAIR_RAYS), which k_shade runs where the two lanes of a correlated pair hold the same ray: rays 2k and 2k + 1
+// must be equal in o, d and maxt, bit for bit (their times are their own); anything else is refused here, on the host, before a lane relies on it
+int dtof_flat_query_pairs(dtof_scene *sc, int any, uint32_t n, const float *rays8, float *out3, int32_t *ids) {
+    return guarded([&] {
+        if (!sc || (n && (!rays8 || !ids || (!any && !out3)))) throw std::runtime_error("null argument");
+        if (n & 1u) throw std::runtime_error("dtof_flat_query_pairs: an odd number of rays");
+        if (n > (1u << 24)) throw std::runtime_error("dtof_flat_query_pairs: more than 2^24 rays in one call");
+        for (uint32_t i = 0; i < n; i += 2) {
+            const float *a = rays8 + (size_t) i * 8, *b = a + 8;
+            if (memcmp(a, b, 24) != 0 || memcmp(a + 7, b + 7, 4) != 0)
+                throw std::runtime_error("dtof_flat_query_pairs: rays " + std::to_string(i) + " and " + std::to_string(i + 1) + " differ in o, d or maxt");
+        }
+        const SceneTraits t = scene_traits(*sc);
+        const FlatChoice c = flat_choice(t, t.blas_triangles <= 32768 && sc->host.textures.empty(), true, true);
+        if (!kFlatQueryPairsBuilt || c.flat_objects == 0 || !(c.facts & kFactOneWall) || (c.facts & kFlatShapeFields) != (flat_query_facts(2) & kFlatShapeFields))
+            throw std::runtime_error("dtof_flat_query_pairs: the pair form is compiled for a flat table of 5 rectangles whose one instance, of one rectangle, is at index 2" +
+                                     (c.flat_objects ? ", this table has " + std::to_string(c.flat_objects) + " objects" : std::string(", this scene has no flat table")));
+        ensure_device(sc);
+        DevBuf<float> dr, dout; DevBuf<int32_t> dids;
+        dr.ensure((size_t) n * 8); dout.ensure(any ? 1 : (size_t) n * 3); dids.ensure(n);
+        if (n) HIP_CHECK(hipMemcpy(dr.p, rays8, (size_t) n * 32, hipMemcpyHostToDevice));
+        launch_flat_query(sc->d_blob.p, (uint32_t) sc->blob.size(), t.flat_off, c.flat_objects, c.memo_obj, kFlatQueryPairs, any != 0, dr.p, dout.p, dids.p, n, nullptr);
+        HIP_CHECK(hipGetLastError());
+        if (n && !any) HIP_CHECK(hipMemcpy(out3, dout.p, (size_t) n * 12, hipMemcpyDeviceToHost));
+        if (n) HIP_CHECK(hipMemcpy(ids, dids.p, (size_t) n * 4, hipMemcpyDeviceToHost));
+    });
+}
+
 #ifdef DTOF_TRAVERSAL_STATS
 // development builds (make STATS=1): read and reset the traversal counters of dtof_traverse.h
 // (`n` of the kTravStats slots into out8; dtof_debug_traversal_stats: the first 16)

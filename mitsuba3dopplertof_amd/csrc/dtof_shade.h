@@ -416,6 +416,8 @@ __global__ __launch_bounds__(RESW ? RESW * 64 : kShadeBlock, RESW ? RESW / 4 : (
     // the two lanes of a pair hold ONE path stream and every draw of the loop comes from it, so the draws -- and the warp of the two that are read --
     // are the pair's, not the lane's.  JUMPS: the draws nobody reads advance the stream by pcg_jump; PAIR: a lane evaluates one iteration's direction, its partner the other's
     constexpr bool F_PAIR = (FACTS & kFactPairSamples) != 0, JUMPS = F_PAIR && DTOF_STREAM_JUMPS, PAIR = F_PAIR && DTOF_PAIR_SAMPLES;
+    // ... and (k): the camera ray, which the two lanes of a pair share, splits its plain rectangles between them (trace_flat: PAIR_RAYS)
+    constexpr bool WALK_PRIMARY = F_PAIR && DTOF_PAIR_WALK_PRIMARY && pair_walk_shape(FACTS);
     static_assert(!F_PAIR || F_WAVE_PIXEL, "a lane reads its partner's registers: the whole wave is active where it does");
     static_assert(!F_PAIR || (!AREA && SPEC == 0 && KMAX == 1 && F_ONE_EMITTER), "a diffuse BSDF picks no lobe and a lone point light samples nothing: of an iteration's six draws only s2x and s2y are read");
     static_assert(!F_PAIR || (F_NO_RR && F_CORRELATED && F_DOPPLER_CORR && F_WHOLE_PATH && F_SINGLE_PASS && (FACTS & kFactStratifiedPairs) != 0), "every draw comes from the stream lanes 2k and 2k + 1 share, none is looked at for roulette, no state outlives the launch");
@@ -654,7 +656,9 @@ __global__ __launch_bounds__(RESW ? RESW * 64 : kShadeBlock, RESW ? RESW / 4 : (
                 if (du.x == 0.f && du.y == 0.f && du.z == 0.f) { V3 tt; coordinate_system(wf.n, wf.s, tt); }
             }
             Hit h;
-            bool found = (F_FLAT || flat) ? trace_flat<false, true, FACTS & kFactsFlatTable>(sv, (ConstBytes) A.scene + rp.flat_off, rp.flat_off, flat, stack, mk(ra.x, ra.y, ra.z), mk(rb.x, rb.y, rb.z), ra.w, rb.w, h)
+            // (WALK_PRIMARY: kFactStratifiedPairs gives lanes 2k and 2k + 1 one pixel jitter from the stream they share and times of their own -- the same o, d and maxt --
+            //  and kFactWavePixel has every lane of the wave here)
+            bool found = (F_FLAT || flat) ? trace_flat<false, true, FACTS & kFactsFlatTable, WALK_PRIMARY>(sv, (ConstBytes) A.scene + rp.flat_off, rp.flat_off, flat, stack, mk(ra.x, ra.y, ra.z), mk(rb.x, rb.y, rb.z), ra.w, rb.w, h)
                               : trace_scene<false, MESH, FUSED, RESW != 0, kStackStride, S16, 0u, false, RH16>(sv, stack, mk(ra.x, ra.y, ra.z), mk(rb.x, rb.y, rb.z), ra.w, rb.w, h);
             hh = make_uint4(f2u(h.t), f2u(h.u), f2u(h.v), h.prim);
             hid = found ? (h.obj | (h.shape << (F_ID24 ? 24u : q.id_shift))) : 0xffffffffu;

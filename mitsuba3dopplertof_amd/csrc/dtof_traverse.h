@@ -5,6 +5,7 @@
 #include "dtof_scene.h"
 #include "dtof_math.h"
 #include "dtof_flat_cull.h"
+#include "dtof_pair_walk.h"
 
 #ifndef DTOF_D
 #define DTOF_D __device__ __forceinline__
@@ -498,7 +499,12 @@ DTOF_D F2 flat_zrow(float z0, float z1, float z2, float z3, V3 ro, V3 rd) {
 //                 selects between the two by copying six registers (profiles/flat_peel_ab.txt).  No DFlatKinds loads, no instance loop.
 //   otherwise     one loop that picks each object's ray; the instance marks are two scalar loads (DFlatKinds), the instances are intersected after the rectangles.
 // One visit is the same in both, operation for operation.  (Sharing its text as one lambda changes the generic kernels' code; the twelve lines are written twice.)
-template <bool ANY, bool MEMO, uint32_t FACTS = 0>
+//   PAIR_RAYS     (closest hit, with a shape of 5 and the wall at 2) the caller vouches that lanes 2k and 2k + 1 are both active or both not and hold the same o, d and
+//                 maxt (their times may differ: only the wall reads the time).  The plain rectangles are then split between the two lanes -- the even lane tests 0 and
+//                 1, the odd lane 3 and 4, through z-row and record addresses that differ by a per-lane constant -- and the wall is tested by both.  dtof_pair_walk.h
+//                 has the argument.  One visit is still the one above, operation for operation.  An occlusion query has no such form and takes the sweep as it is: the
+//                 form was built for it and for the queries of iteration 0 and cost more than it saved there, DESIGN 8.3 (k), profiles/pair_walk_ab.txt.
+template <bool ANY, bool MEMO, uint32_t FACTS = 0, bool PAIR_RAYS = false>
 DTOF_D bool trace_flat(const SceneView &sv, ConstBytes flat_table, uint32_t flat_off, uint32_t n_objects, uint32_t *stack, V3 o, V3 d, float time, float maxt, Hit &best) {
     best.t = maxt; best.u = best.v = 0.f; best.obj = 0xffffffffu; best.shape = 0; best.prim = 0;
     bool occluded = false;
@@ -545,6 +551,8 @@ DTOF_D bool trace_flat(const SceneView &sv, ConstBytes flat_table, uint32_t flat
         // The table's SHAPE as constants (kFactFlatShape: N objects, the wall at index WALL; DESIGN 8.3 (i), profiles/flat_shape_ab.txt): the walk is straight-line code --
         // no counter, no compare, no pass loop, the z rows and records at immediate offsets.  One visit is still the one above, operation for operation.
         constexpr uint32_t N = flat_shape_count(FACTS), WALL = flat_shape_wall(FACTS);
+        constexpr bool PAIR = PAIR_RAYS && kPairWalkCompiled;
+        static_assert(!PAIR_RAYS || pair_walk_shape(FACTS), "the pair form is written for five rectangles with the wall at index 2: {0, 1} below it, {3, 4} above");
         if constexpr (N != 0 && ANY && DTOF_FLAT_SHAPE_ANY) {
             // Occlusion query: ONE sweep over the z rows and their certain-miss tests, then ONE branch -- where no lane of the wave needs a full test (every shadow
             // ray of a closed room) the query ends there, unoccluded.  `occluded` is an OR: the tail may run the full tests in any order, and runs them in ascending one.
@@ -599,6 +607,48 @@ DTOF_D bool trace_flat(const SceneView &sv, ConstBytes flat_table, uint32_t flat
                 a.c0 = F2{ u2f(r0.x), u2f(r0.y) }; a.c1 = F2{ u2f(r1.x), u2f(r1.y) }; a.c2 = F2{ u2f(r2.x), u2f(r2.y) }; a.c3 = F2{ u2f(r3.x), u2f(r3.y) };
                 test(a, k, ro, rd, z);
             };
+            if constexpr (PAIR) {
+                // lower | wall | upper (dtof_pair_walk.h).  The two half walks run as ONE instruction stream: slot s of a lane is rectangle s + 3 * (lane & 1), its z row
+                // 48 bytes and its record 192 bytes behind the even lane's, at the same immediate offsets.  The skip over a full test stays a wave-wide ballot.
+                const uint32_t first = (__lane_id() & 1u) * (WALL + 1u);
+                const DFlatObject *ltp = lts + first;
+                const uint4 *ztp = zts + first;
+#pragma unroll
+                for (uint32_t s = 0; s < 2u; ++s) {
+                    const uint4 zr = ztp[s];
+                    const F2 z = flat_zrow(u2f(zr.x), u2f(zr.y), u2f(zr.z), u2f(zr.w), o, d);
+                    const bool need = !flat_certain_miss(z.x, z.y, far);
+                    if (__ballot(need)) {   // (uniform)
+                        const uint4 *rp4 = (const uint4 *) (ltp + s);
+                        const uint4 r0 = rp4[0], r1 = rp4[1], r2 = rp4[2], r3 = rp4[3];
+                        FlatRecord a;
+                        a.c0 = F2{ u2f(r0.x), u2f(r0.y) }; a.c1 = F2{ u2f(r1.x), u2f(r1.y) }; a.c2 = F2{ u2f(r2.x), u2f(r2.y) }; a.c3 = F2{ u2f(r3.x), u2f(r3.y) };
+                        test(a, first + s, o, d, z);
+                    }
+                    __builtin_amdgcn_sched_barrier(0);
+                }
+                // every lane takes the even lane's state (quad_perm [0, 0, 2, 2]) and keeps the odd lane's (quad_perm [1, 1, 3, 3]) for the merge: two broadcasts, no
+                // select on the parity -- an exchange (quad_perm [1, 0, 3, 2]) would need eight of those to order the two halves
+                FlatBest upper;
+                upper.t = __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(best.t), 0xf5, 0xf, 0xf, false));
+                upper.u = __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(best.u), 0xf5, 0xf, 0xf, false));
+                upper.v = __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(best.v), 0xf5, 0xf, 0xf, false));
+                upper.obj = (uint32_t) __builtin_amdgcn_update_dpp(0, (int) best.obj, 0xf5, 0xf, 0xf, false);
+                best.t = __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(best.t), 0xa0, 0xf, 0xf, false));
+                best.u = __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(best.u), 0xa0, 0xf, 0xf, false));
+                best.v = __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(best.v), 0xa0, 0xf, 0xf, false));
+                best.obj = (uint32_t) __builtin_amdgcn_update_dpp(0, (int) best.obj, 0xa0, 0xf, 0xf, false);
+                {
+                    float inv[12]; instance_memo_load(sv, inv);
+                    const V3 wo = xf_point(inv, o), wd = xf_vector(inv, d);
+                    visit_at(WALL, wo, wd);
+                }
+                __builtin_amdgcn_sched_barrier(0);
+                FlatBest b{ best.t, best.u, best.v, best.obj };
+                pair_merge_upper(b, upper);
+                best.t = b.t; best.u = b.u; best.v = b.v; best.obj = b.obj;
+                return best.obj != 0xffffffffu;
+            }
 #pragma unroll
             for (uint32_t k = 0; k < N; ++k) {
                 if (k == WALL) {
