@@ -529,7 +529,7 @@ int dtof_eval_modulation(dtof_scene *scene, int mode, const float *t, const floa
  * Scene::ray_intersect / Scene::ray_test (include/mitsuba/render/scene.h; src/render/scene.cpp -> scene_embree.inl:202-333,349-426) over
  * arrays, through the same TLAS / BLAS traversal and surface-interaction code the render kernels use.  rays8: per ray o[3], d[3], time,
  * maxt.  out19: t (inf on a miss), p[3], n[3], sh_frame.n[3], sh_frame.s[3], sh_frame.t[3], wi[3]; ids3: object, shape-in-group,
- * primitive (-1 on a miss).  dtof_ray_test writes 1 / 0 per ray. */
+ * primitive (-1 on a miss; a triangle is named by its face index in the mesh's own order, PreliminaryIntersection::prim_index).  dtof_ray_test writes 1 / 0 per ray. */
 int dtof_ray_intersect(dtof_scene *scene, uint32_t n, const float *rays8, float *out19, int32_t *ids3);
 /* the same, plus uv4 per ray: si.uv[2] (the surface parameterisation, interaction.h) and pi.prim_uv[2] (PreliminaryIntersection::prim_uv: the barycentric
  * coordinates on a triangle, the local position on a rectangle or disk), as the reference's tests of meshes assert them (src/render/tests/test_mesh.py:258-292) */
@@ -545,6 +545,15 @@ int dtof_flat_query(dtof_scene *scene, int form, int any, uint32_t n, const floa
  * and 2k + 1 are equal in o, d and maxt bit for bit (their times are their own), and each pair shares the plain rectangles between its two lanes.  Results as above.
  * DTOF_ERR_INVALID, before anything is launched, for an odd n, a pair that differs and a table other than 5 rectangles with the wall at index 2. */
 int dtof_flat_query_pairs(dtof_scene *scene, int any, uint32_t n, const float *rays8, float *out3, int32_t *ids);
+/* The TLAS / BLAS ray query (every scene with a mesh, a sphere, more than eight objects or a BLAS) over arrays, through the instantiations of it that the ray kernels
+ * of a frame carry.  form 0: float nodes and a 32-bit LDS stack (what dtof_ray_intersect runs); 1: half-float nodes, a 16-entry LDS stack with a private overflow
+ * array, triangle and rectangle code only; 2: form 1 with the TLAS nodes read from a copy in LDS; 3: the two-launch pair of form 1 -- the TLAS walk puts the meshes
+ * behind a BLAS aside, a second walk enters them -- run by one lane on its own candidate list (the same device functions as the two launches, without the queue
+ * compaction between them); 4: half-float nodes with every shape's code.  rays8 as above.  any = 0: closest hit, out3 = t, u, v (inf, 0, 0 on a miss), ids3 = object,
+ * shape in its group, primitive (-1 on a miss); any != 0: occlusion, ids3[i] = 1 / 0 (one word per ray, out3 is not written).  DTOF_ERR_INVALID, before anything is
+ * launched or written, for a form the scene does not meet -- no half-float nodes (forms 1 to 4), an analytic shape, a stack deeper than 64 entries or a TLAS of more
+ * than 16 nodes for form 2 (forms 1 to 3) -- and for n above 2^24; non-finite ray components are taken as they are. */
+int dtof_tree_query(dtof_scene *scene, int form, int any, uint32_t n, const float *rays8, float *out3, int32_t *ids3);
 
 /* ---------------------------------------------------------------- component evaluation
  * The device functions the shade and splat kernels are built from, evaluated over arrays on the GPU: the counterpart of the

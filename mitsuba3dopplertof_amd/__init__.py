@@ -160,6 +160,7 @@ def _lib():
                        ("dtof_emitter_eval", [vp, C.c_int, C.c_int, C.c_int32, C.c_uint32, vp, vp]),
                        ("dtof_flat_query", [vp, C.c_int, C.c_int, C.c_uint32, vp, vp, vp]),
                        ("dtof_flat_query_pairs", [vp, C.c_int, C.c_uint32, vp, vp, vp]),
+                       ("dtof_tree_query", [vp, C.c_int, C.c_int, C.c_uint32, vp, vp, vp]),
                        ("dtof_develop_accumulate_async", [vp, vp, C.c_int32, C.c_uint64, vp, C.c_int64, C.c_int]),
                        ("dtof_velocity_map_async", [vp, vp, C.c_int, vp, vp, C.c_uint32, C.c_double, C.c_double, C.c_int64, vp, vp, vp]),
                        ("dtof_velocity_map_variants", [vp, C.c_int, vp]),
@@ -735,6 +736,19 @@ class Scene:
         out, ids = np.zeros((len(rays), 3), np.float32), np.zeros(len(rays), np.int32)
         _check(_lib().dtof_flat_query_pairs(self._h, 1 if any else 0, len(rays), rays.ctypes.data, None if any else out.ctypes.data, ids.ctypes.data))
         return ids if any else {"t": out[:, 0], "u": out[:, 1], "v": out[:, 2], "obj": ids}
+
+    TREE_FORMS = {"float": 0, "half_overflow": 1, "half_overflow_tlas_lds": 2, "defer_pair": 3, "half_every_shape": 4}
+
+    def tree_query(self, rays8, form=0, any=False):
+        """The TLAS / BLAS ray query over an (n, 8) array of rays o, d, time, maxt in the form a frame's ray kernels run it (dtof_tree_query).  form: 0 / "float",
+        1 / "half_overflow", 2 / "half_overflow_tlas_lds", 3 / "defer_pair", 4 / "half_every_shape".  Closest hit -> dict(t, u, v, ids (n, 3): object, shape in its
+        group, primitive) (inf, 0, 0, -1 on a miss); any=True -> int32 array of 1 / 0.  A form the scene does not meet and more than 2^24 rays raise DtofError;
+        non-finite components are taken as they are."""
+        rays = np.ascontiguousarray(rays8, np.float32).reshape(-1, 8)
+        form = self.TREE_FORMS.get(form, form)
+        out, ids = np.zeros((len(rays), 3), np.float32), np.zeros(len(rays) if any else (len(rays), 3), np.int32)
+        _check(_lib().dtof_tree_query(self._h, int(form), 1 if any else 0, len(rays), rays.ctypes.data, None if any else out.ctypes.data, ids.ctypes.data))
+        return ids if any else {"t": out[:, 0], "u": out[:, 1], "v": out[:, 2], "ids": ids}
 
     def cancel(self):
         _lib().dtof_cancel(self._h)

@@ -57,7 +57,7 @@ __global__ __launch_bounds__(kBlock) void k_aov(const uint8_t *scene, uint32_t s
         v9 = si.sh_n.x; v10 = si.sh_n.y; v11 = si.sh_n.z;
         v12 = si.dp_du.x; v13 = si.dp_du.y; v14 = si.dp_du.z;
         v15 = si.dp_dv.x; v16 = si.dp_dv.y; v17 = si.dp_dv.z;
-        v18 = (float) h.prim;
+        v18 = (float) hit_prim_index(sv, h);
         v19 = (float) (1u + (uint32_t) (si.shape - sv.shapes));
     }
     const uint32_t C = a.n_channels;

@@ -371,6 +371,9 @@ void launch_emitter_eval_mesh(const uint8_t *scene, int level, int mode, uint32_
 void launch_emitter_eval_spec1(const uint8_t *scene, int level, int mode, uint32_t index, float pmf, const float *in, float *out, uint32_t n, hipStream_t s);
 void launch_emitter_eval_spec2(const uint8_t *scene, int level, int mode, uint32_t index, float pmf, const float *in, float *out, uint32_t n, hipStream_t s);
 void launch_camera_rays(const RenderParams &rp, const float *in, float *out, uint32_t n, hipStream_t s);   // Sensor::sample_ray over arrays (known-answer entry)
+// The eight-wave ray kernels (k_trace / k_shadow<..., W8>, dtof_kernels.hip): LDS entries of a lane's traversal stack and entries of its private overflow array; the
+// largest TLAS they copy into LDS (nodes)
+constexpr uint32_t kLdsStack8 = 16, kOvfStack8 = 48, kTlasLds8 = 16;
 // Scene::ray_intersect / ray_test over arrays
 void launch_ray_query(const uint8_t *scene, const float *rays, float *out, int32_t *ids, float *uv4, uint32_t n, bool any, uint32_t stack_depth, hipStream_t s);
 

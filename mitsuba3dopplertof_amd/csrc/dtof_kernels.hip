@@ -45,11 +45,11 @@ __global__ __launch_bounds__(kBlock) void k_generate(RenderParams rp, Queues q) 
 // W8: the ray kernels of scenes with LARGE triangle meshes and no analytic shapes (the mesh room: 522 k triangles behind two BLAS, bound by the latency of its L2 misses).
 // Eight waves per SIMD instead of six -- more misses in flight per CU -- need (a) at most 64 VGPRs: the instantiation carries triangle and rectangle code only (MESH = 2: no
 // float64 sphere / cylinder arithmetic), and (b) 32 one-wave blocks in a CU's LDS: the stack column holds kLdsStack8 entries, deeper ones overflow into a private array.
-constexpr uint32_t kLdsStack8 = 16, kOvfStack8 = 48;
+// (kLdsStack8, kOvfStack8: dtof_kernels.h -- the tree query of dtof_tree_query.hip runs the same instantiations)
 // TL (round 5): the eight-wave kernels were measured with their texture-address / data units 87 - 90 % busy (profiles/r05_mesh_room.txt): every node step is four 16-byte
 // loads per lane, and a third of the loads a ray issues walk the TLAS -- a handful of nodes in such scenes (the mesh room: walls, a light, two blobs).  A TLAS of at most
 // kTlasLds8 nodes is copied behind the block's stack column (32 blocks x (4 KiB + 1 KiB) = the CU's 160 KiB) and walked with ds_read_b128; the BLAS stay in global memory.
-constexpr uint32_t kTlasLds8 = 16;
+// (kTlasLds8: dtof_kernels.h)
 // XCD-aware block order of the unstaged ray kernels (guide: cdna_hip_programming.md T1).  Blocks are dealt round-robin over the 8 XCDs, each with an L2 of its own (4 MiB):
 // with block b tracing queue segment b, every XCD sees rays from all over the image and all eight L2s fight over the same 35 MB of nodes and triangle records.  The remap gives
 // the blocks that share an XCD a CONTIGUOUS run of segments (= a band of the image for the primary and shadow rays), so each L2 mostly holds the geometry of its band.
@@ -898,7 +898,7 @@ __global__ __launch_bounds__(64) void k_ray_query(const uint8_t *scene, const fl
     if (ANY) { ids[i] = found ? 1 : 0; return; }
     float *w = out + (size_t) i * 19;
     for (int k = 0; k < 19; ++k) w[k] = 0.f;
-    ids[3 * i] = found ? (int32_t) h.obj : -1; ids[3 * i + 1] = found ? (int32_t) h.shape : -1; ids[3 * i + 2] = found ? (int32_t) h.prim : -1;
+    ids[3 * i] = found ? (int32_t) h.obj : -1; ids[3 * i + 1] = found ? (int32_t) h.shape : -1; ids[3 * i + 2] = found ? (int32_t) hit_prim_index(sv, h) : -1;
     if (uv4) for (int k = 0; k < 4; ++k) uv4[(size_t) i * 4 + k] = 0.f;
     if (!found) { w[0] = u2f(0x7f800000u); return; }
     Surface si;

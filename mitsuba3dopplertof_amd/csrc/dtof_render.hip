@@ -13,6 +13,7 @@
 #include "dtof_moments.h"
 #include "dtof_aov.h"
 #include "dtof_flat_query.h"
+#include "dtof_tree_query.h"
 #include "dtof_scene.h"
 #include "dtof_math.h"
 #include <atomic>
@@ -2015,6 +2016,27 @@ int dtof_flat_query_pairs(dtof_scene *sc, int any, uint32_t n, const float *rays
         HIP_CHECK(hipGetLastError());
         if (n && !any) HIP_CHECK(hipMemcpy(out3, dout.p, (size_t) n * 12, hipMemcpyDeviceToHost));
         if (n) HIP_CHECK(hipMemcpy(ids, dids.p, (size_t) n * 4, hipMemcpyDeviceToHost));
+    });
+}
+
+// trace_scene / trace_deferred over arrays (dtof_tree_query.hip): the TLAS / BLAS query in the form a frame's ray kernels run it.  A form the scene does not meet is
+// refused before anything is launched or written.
+int dtof_tree_query(dtof_scene *sc, int form, int any, uint32_t n, const float *rays8, float *out3, int32_t *ids3) {
+    return guarded([&] {
+        if (!sc || (n && (!rays8 || !ids3 || (!any && !out3)))) throw std::runtime_error("null argument");
+        if (n > (1u << 24)) throw std::runtime_error("dtof_tree_query: more than 2^24 rays in one call");
+        const SceneTraits t = scene_traits(*sc);
+        const TreeQueryScene q { t.stack_depth, t.n_tlas_nodes, t.has_nodes16, t.has_analytic };
+        if (const char *why = tree_query_refusal(form, q)) throw std::runtime_error(std::string("dtof_tree_query: ") + why);
+        ensure_device(sc);
+        const size_t per = any ? 1 : 3;
+        DevBuf<float> dr, dout; DevBuf<int32_t> dids;
+        dr.ensure((size_t) n * 8); dout.ensure(any ? 1 : (size_t) n * 3); dids.ensure((size_t) n * per);
+        if (n) HIP_CHECK(hipMemcpy(dr.p, rays8, (size_t) n * 32, hipMemcpyHostToDevice));
+        launch_tree_query(sc->d_blob.p, q, form, any != 0, dr.p, dout.p, dids.p, n, nullptr);
+        HIP_CHECK(hipGetLastError());
+        if (n && !any) HIP_CHECK(hipMemcpy(out3, dout.p, (size_t) n * 12, hipMemcpyDeviceToHost));
+        if (n) HIP_CHECK(hipMemcpy(ids3, dids.p, (size_t) n * per * 4, hipMemcpyDeviceToHost));
     });
 }
 

@@ -5,6 +5,7 @@
 #include "dtof_scene.h"
 #include "dtof_math.h"
 #include "dtof_flat_cull.h"
+#include "dtof_box_cull.h"
 #include "dtof_pair_walk.h"
 
 #ifndef DTOF_D
@@ -89,6 +90,14 @@ static const int g_trav_stats_registered = (register_traversal_stats_reader(read
 #define DTOF_STAT(i) ((void) 0)
 #define DTOF_STAT_WAVE(i) ((void) 0)
 #endif
+
+// What a query REPORTS as a hit's primitive: Hit::prim addresses the scene's triangle arrays, which a mesh's BLAS build permutes (compute_surface reads them through
+// it); PreliminaryIntersection::prim_index is the face in the mesh's own order.  The primitive of any other shape is reported as it is.
+DTOF_D uint32_t hit_prim_index(const SceneView &sv, const Hit &h) {
+    const DObject &ob = sv.objects[h.obj];
+    const DShape &sh = sv.shapes[(ob.kind == OBJ_INSTANCE ? sv.groups[ob.index].first_shape : ob.index) + h.shape];
+    return sh.kind == SHAPE_MESH ? sv.tris[sh.first_tri + h.prim].face : h.prim;
+}
 
 // ---------------------------------------------------------------------------- primitives
 // Rectangle::ray_intersect_preliminary_impl, src/shapes/rectangle.cpp:201-224
@@ -212,27 +221,9 @@ DTOF_D void instance_memo_load(const SceneView &sv, float *inv) {
     for (uint32_t k = 0; k < kMemoWords; ++k) inv[k] = sv.memo[k * kMemoStride];
 }
 
-// Slab test of a padded box.  A plane at coordinate b is crossed at t = b * id - o * id: ONE multiply-add per plane with `noid` = -(o * id) computed once per ray (the
-// difference-then-product form costs two instructions per plane, 12 more per node step of an issue-bound traversal).  The test only culls -- which primitive is hit, and
-// where, is decided by the primitive tests -- so it has to be conservative, not equal to anything: its rounding error is 2^-24 (|o| + |t / id|) |id| per plane against
-// the padding of (1e-5 max(|b|, extent) + 1e-6) |id| the host puts around every box (scene_build.cpp: Box::pad), the same order as the other form's 2^-23 |b - o| |id|
-// since |o| <= |b - o| + |b|.  NaNs fall out of the min / max chain (fminf / fmaxf return the other operand); a box whose test has no number left is missed.
-struct SlabRay { V3 id, noid; };
-DTOF_D SlabRay slab_ray(V3 o, V3 d) {
-    // direction reciprocal for the slab test only (exact zero components are nudged); v_rcp_f32 (1 ulp) is enough here, see the padding above
-    SlabRay r;
-    r.id = mk(__builtin_amdgcn_rcpf(d.x == 0.f ? 1e-30f : d.x), __builtin_amdgcn_rcpf(d.y == 0.f ? 1e-30f : d.y), __builtin_amdgcn_rcpf(d.z == 0.f ? 1e-30f : d.z));
-    r.noid = mk(-(o.x * r.id.x), -(o.y * r.id.y), -(o.z * r.id.z));
-    return r;
-}
-DTOF_D bool box_hit(const float *bmin, const float *bmax, const SlabRay &r, float tbest, float &tn) {
-    const float tx0 = fmaf(bmin[0], r.id.x, r.noid.x), tx1 = fmaf(bmax[0], r.id.x, r.noid.x);
-    const float ty0 = fmaf(bmin[1], r.id.y, r.noid.y), ty1 = fmaf(bmax[1], r.id.y, r.noid.y);
-    const float tz0 = fmaf(bmin[2], r.id.z, r.noid.z), tz1 = fmaf(bmax[2], r.id.z, r.noid.z);
-    tn = fmaxf(fmaxf(fminf(tx0, tx1), fminf(ty0, ty1)), fmaxf(fminf(tz0, tz1), 0.f));
-    const float tf = fminf(fminf(fmaxf(tx0, tx1), fmaxf(ty0, ty1)), fminf(fmaxf(tz0, tz1), tbest));
-    return tn <= tf;
-}
+// Slab test of a padded box: dtof_box_cull.h (slab_ray, box_hit; a header a host program can compile) has the functions, their contract -- the test only culls, and
+// never a box the exact ray meets within [0, tbest] -- and the error bound behind it.
+DTOF_D SlabRay slab_ray(V3 o, V3 d) { return slab_ray(o.x, o.y, o.z, d.x, d.y, d.z); }
 // Traversal stack entry `sp` of this thread: a per-thread LDS column (32-bit, or 16-bit in the resident kernels of several films) -- and, in the eight-waves-per-SIMD
 // ray kernels of large meshes (k_trace / k_shadow<..., W8>), only its first LDSN entries: deeper ones overflow into a private array `ovf` (scratch memory; a BLAS of half a
 // million triangles is 20-odd levels deep, a traversal rarely holds more than a dozen entries), so that 32 one-wave blocks fit a CU's LDS instead of 23.

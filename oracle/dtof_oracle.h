@@ -357,6 +357,9 @@ void     orc_kat_emitter_n(const orc_scene *sc, int mode, int32_t index, uint32_
 /* Closest hit and occlusion over arrays of rays, with the operands of each rectangle's compares (see dtof_oracle.c) */
 enum { ORC_FLAT_ZX = 0, ORC_FLAT_ZY = 1, ORC_FLAT_T = 2, ORC_FLAT_U = 3, ORC_FLAT_V = 4, ORC_FLAT_BEST = 5, ORC_FLAT_OPS = 6 };
 uint32_t orc_kat_flat_n(const orc_scene *sc, uint32_t n, const float *rays8, float *out3, int32_t *ids2, float *ops, uint32_t max_rects, int32_t *rect_obj);
+/* scene_closest and scene_occluded over arrays, with all three ids (dtof_tree_query): out3 = t, u, v; ids4 = object, shape, primitive, occluded; prim_t / prim_ids
+ * (optional): every primitive's own hit distance per ray and the ids of those slots.  Returns the number of primitive slots. */
+uint32_t orc_kat_tree_n(const orc_scene *sc, uint32_t n, const float *rays8, float *out3, int32_t *ids4, float *prim_t, uint32_t max_prims, int32_t *prim_ids);
 void     orc_texture_eval(const orc_texture *tex, float u, float v, float *out3);
 float    orc_texture_eval_1(const orc_texture *tex, float u, float v);   /* Texture::eval_1: a 1-channel texel, the luminance of an RGB texel, the mean of a checkerboard colour */
 void     orc_kat_sphere_sample_direction(const orc_shape *sh, const float *ref, float s_x, float s_y, float *out11);

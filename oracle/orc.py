@@ -202,6 +202,8 @@ def lib():
         L.orc_kat_emitter_n.argtypes = [C.POINTER(OrcScene), C.c_int, C.c_int32, C.c_uint32, C.c_void_p, C.c_void_p]
         L.orc_kat_flat_n.restype = C.c_uint32
         L.orc_kat_flat_n.argtypes = [C.POINTER(OrcScene), C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
+        L.orc_kat_tree_n.restype = C.c_uint32
+        L.orc_kat_tree_n.argtypes = [C.POINTER(OrcScene), C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
         L.orc_kat_emitter_sample.argtypes = [C.POINTER(OrcScene), C.c_int, C.c_void_p, C.c_float, C.c_float, C.c_void_p]
         L.orc_kat_sphere_sample_direction.argtypes = [C.POINTER(OrcShape), C.c_void_p, C.c_float, C.c_float, C.c_void_p]
         L.orc_kat_shape_area.restype = C.c_float
@@ -475,6 +477,20 @@ class Scene:
         r = dict(t=out3[:, 0], u=out3[:, 1], v=out3[:, 2], obj=ids2[:, 0], occluded=ids2[:, 1], rect_obj=rect_obj[:slots])
         if operands:
             r["ops"] = ops
+        return r
+
+    def tree_n(self, rays8, per_prim=False):
+        """orc_kat_tree_n: (n, 8) rays o, d, time, maxt -> dict(tuv (n, 3), ids (n, 3), occluded (n,)[, prim_t (n, prims), prim_ids (prims, 3)])"""
+        rays8 = np.ascontiguousarray(rays8, np.float32).reshape(-1, 8)
+        n, L = len(rays8), lib()
+        out3, ids4 = np.zeros((n, 3), np.float32), np.zeros((n, 4), np.int32)
+        r = dict(tuv=out3, ids=ids4[:, :3], occluded=ids4[:, 3])
+        if per_prim:
+            slots = int(L.orc_kat_tree_n(C.byref(self.c), 0, None, None, None, None, 0, None))
+            r["prim_t"], r["prim_ids"] = np.zeros((n, slots), np.float32), np.zeros((slots, 3), np.int32)
+            L.orc_kat_tree_n(C.byref(self.c), n, rays8.ctypes.data, out3.ctypes.data, ids4.ctypes.data, r["prim_t"].ctypes.data, slots, r["prim_ids"].ctypes.data)
+        else:
+            L.orc_kat_tree_n(C.byref(self.c), n, rays8.ctypes.data, out3.ctypes.data, ids4.ctypes.data, None, 0, None)
         return r
 
     def render(self, pd, seed=0, spp=None, rows=None, threads=1, raw=False):
