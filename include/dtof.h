@@ -545,6 +545,14 @@ int dtof_flat_query(dtof_scene *scene, int form, int any, uint32_t n, const floa
  * and 2k + 1 are equal in o, d and maxt bit for bit (their times are their own), and each pair shares the plain rectangles between its two lanes.  Results as above.
  * DTOF_ERR_INVALID, before anything is launched, for an odd n, a pair that differs and a table other than 5 rectangles with the wall at index 2. */
 int dtof_flat_query_pairs(dtof_scene *scene, int any, uint32_t n, const float *rays8, float *out3, int32_t *ids);
+/* Lane generation of the headline frame's kernel over arrays: lanes [lane_begin, lane_begin + n) of a render with `seed` and `spp`, walked in 512-lane segments of
+ * 64-lane chunks as the first-bounce launch walks them.  form 0: every lane generates itself; form 1: what lanes 2k and 2k + 1 share -- path stream, pixel jitter,
+ * sample position, camera ray -- is evaluated once per pair, for the pairs of two consecutive chunks at a time, and fetched by both lanes.  out16: 16 words per lane --
+ * sample position[2], time, o[3], d[3], maxt (floats), the path stream's state after the two jitter draws (low, high word), its selector, and three zeros.  The first
+ * nine equal dtof_sample_lanes.  DTOF_ERR_INVALID, before anything is launched, for a scene or sample count that does not meet the facts the kernels are compiled with
+ * (one pass, dopplertofpath with the correlated sampler, stratified pairs, a power-of-two stratum count, spp a power of two >= 64, the perspective camera), for a
+ * lane_begin or n that is not a multiple of 64, for n above 2^24 and for a range beyond the wavefront. */
+int dtof_pair_setup_lanes(dtof_scene *scene, int form, uint32_t seed, uint32_t spp, uint64_t lane_begin, uint64_t n, uint32_t *out16);
 /* The TLAS / BLAS ray query (every scene with a mesh, a sphere, more than eight objects or a BLAS) over arrays, through the instantiations of it that the ray kernels
  * of a frame carry.  form 0: float nodes and a 32-bit LDS stack (what dtof_ray_intersect runs); 1: half-float nodes, a 16-entry LDS stack with a private overflow
  * array, triangle and rectangle code only; 2: form 1 with the TLAS nodes read from a copy in LDS; 3: the two-launch pair of form 1 -- the TLAS walk puts the meshes

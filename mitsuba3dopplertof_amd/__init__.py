@@ -161,6 +161,7 @@ def _lib():
                        ("dtof_flat_query", [vp, C.c_int, C.c_int, C.c_uint32, vp, vp, vp]),
                        ("dtof_flat_query_pairs", [vp, C.c_int, C.c_uint32, vp, vp, vp]),
                        ("dtof_tree_query", [vp, C.c_int, C.c_int, C.c_uint32, vp, vp, vp]),
+                       ("dtof_pair_setup_lanes", [vp, C.c_int, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64, vp]),
                        ("dtof_develop_accumulate_async", [vp, vp, C.c_int32, C.c_uint64, vp, C.c_int64, C.c_int]),
                        ("dtof_velocity_map_async", [vp, vp, C.c_int, vp, vp, C.c_uint32, C.c_double, C.c_double, C.c_int64, vp, vp, vp]),
                        ("dtof_velocity_map_variants", [vp, C.c_int, vp]),
@@ -736,6 +737,16 @@ class Scene:
         out, ids = np.zeros((len(rays), 3), np.float32), np.zeros(len(rays), np.int32)
         _check(_lib().dtof_flat_query_pairs(self._h, 1 if any else 0, len(rays), rays.ctypes.data, None if any else out.ctypes.data, ids.ctypes.data))
         return ids if any else {"t": out[:, 0], "u": out[:, 1], "v": out[:, 2], "obj": ids}
+
+    def pair_setup_lanes(self, seed, spp, lane_begin, n, form=1):
+        """Lane generation of the headline frame's kernel over lanes [lane_begin, lane_begin + n) (dtof_pair_setup_lanes), walked in 512-lane segments of 64-lane chunks
+        as the first-bounce launch walks them.  form 0: every lane generates itself; form 1: what the two lanes of a correlated pair share is evaluated once per pair,
+        for the pairs of two chunks at a time.  -> (n, 16) uint32: sample_pos[2], time, ray_o[3], ray_d[3], maxt as float bits, the path stream's state (low, high
+        word), its selector, three zeros.  A scene or sample count the kernels are not compiled for, a lane_begin or n that is no multiple of 64 and n above 2^24
+        raise DtofError before anything is launched."""
+        out = np.zeros((int(n), 16), np.uint32)
+        _check(_lib().dtof_pair_setup_lanes(self._h, int(form), seed, spp, lane_begin, n, out.ctypes.data))
+        return out
 
     TREE_FORMS = {"float": 0, "half_overflow": 1, "half_overflow_tlas_lds": 2, "defer_pair": 3, "half_every_shape": 4}
 

@@ -263,6 +263,21 @@ constexpr uint32_t kHeadlinePairFacts = DTOF_HEADLINE_PAIR && kHeadlineShapeFact
 #ifndef DTOF_PAIR_WALK_PRIMARY
 #define DTOF_PAIR_WALK_PRIMARY 1
 #endif
+// ... and another (l).  DTOF_PAIR_SETUP: what generate_lane computes for the PAIR -- the path stream's seeding, its two jitter draws, the sample position, the camera
+// ray -- is evaluated once per pair instead of once per lane.  A block walks the chunks of its segment in sequence; at every even chunk lane L sets up pair L >> 1 of
+// this chunk (L even) or of the next (L odd), the results stay in registers across the two chunks, and every lane of a chunk fetches its pair's from the lane that
+// holds them (dtof_pair_setup.h).  0: generate_lane per lane, the parent's text.  DTOF_PAIR_SETUP_BPERMUTE: the fetch by ds_bpermute_b32, one text for both
+// chunks; 0 (A/B): by DPP moves, quad_perm [0, 0, 2, 2] / [1, 1, 3, 3] behind a wave-uniform branch -- measured slower (profiles/pair_setup_ab.txt).
+#ifndef DTOF_PAIR_SETUP
+#define DTOF_PAIR_SETUP 1
+#endif
+#ifndef DTOF_PAIR_SETUP_BPERMUTE
+#define DTOF_PAIR_SETUP_BPERMUTE 1
+#endif
+// the facts under which a lane's generation splits into a pair's piece and a lane's (dtof_sampling.h: generate_pair_part, generate_lane_part): one pass, the Doppler
+// integrator's correlated sampler with every jitter draw from the path stream, stratified pairs, whole waves of one pixel
+constexpr uint32_t kFactsLaneSplit = kFactSinglePass | kFactDopplerCorr | kFactCorrelated | kFactStratifiedPairs | kFactWavePixel;
+constexpr bool lane_split_facts(uint32_t facts) { return (facts & kFactsLaneSplit) == kFactsLaneSplit; }
 #ifdef DTOF_TRAVERSAL_STATS
 constexpr bool kPairWalkCompiled = false;
 #else

@@ -13,6 +13,7 @@
 #include "dtof_moments.h"
 #include "dtof_aov.h"
 #include "dtof_flat_query.h"
+#include "dtof_pair_setup.h"
 #include "dtof_tree_query.h"
 #include "dtof_scene.h"
 #include "dtof_math.h"
@@ -2016,6 +2017,40 @@ int dtof_flat_query_pairs(dtof_scene *sc, int any, uint32_t n, const float *rays
         HIP_CHECK(hipGetLastError());
         if (n && !any) HIP_CHECK(hipMemcpy(out3, dout.p, (size_t) n * 12, hipMemcpyDeviceToHost));
         if (n) HIP_CHECK(hipMemcpy(ids, dids.p, (size_t) n * 4, hipMemcpyDeviceToHost));
+    });
+}
+
+// Lane generation over arrays (dtof_pair_setup.hip): what C2's kernel computes at the head of every chunk, per lane (form 0) or with the pair's piece evaluated once
+// for the pairs of two chunks (form 1).  The kernels are compiled with the facts of kHeadlinePairFacts that lane generation reads (kPairSetupLaneFacts); a scene, a
+// sample count or a range that does not meet them is refused here, before anything is launched or written.
+int dtof_pair_setup_lanes(dtof_scene *sc, int form, uint32_t seed, uint32_t spp, uint64_t lane_begin, uint64_t n, uint32_t *out16) {
+    return guarded([&] {
+        if (!sc || (n && !out16)) throw std::runtime_error("null argument");
+        if (form != 0 && form != 1) throw std::runtime_error("dtof_pair_setup_lanes: form must be 0 (per lane) or 1 (chunk pairs)");
+        if (!sc->host.has_sensor) throw std::runtime_error("the scene does not contain a sensor");
+        if ((lane_begin & 63u) != 0 || (n & 63u) != 0) throw std::runtime_error("dtof_pair_setup_lanes: lane_begin and n must be multiples of 64 (whole chunks)");
+        if (n > (1u << 24)) throw std::runtime_error("dtof_pair_setup_lanes: more than 2^24 lanes in one call");
+        FramePlan p; RenderRequest rq; rq.seed = seed; rq.spp = spp;
+        plan_lanes(p, sc, rq);
+        RenderParams &rp = p.rp;
+        const auto need = [](bool ok, const char *what) { if (!ok) throw std::runtime_error(std::string("dtof_pair_setup_lanes: lane generation is compiled for ") + what); };
+        need(p.n_passes == 1, "a single pass");
+        need(rp.integrator == 0 && rp.sampler_kind == SAMPLER_CORRELATED, "the dopplertofpath integrator with the correlated sampler");
+        need(rp.path_correlation_depth > 0, "a path-correlated camera sample (path_correlation_depth > 0)");
+        need(rp.time_sampling == TIME_STRATIFIED && rp.stratify != 0 && rp.tcn == 2 && rp.pcn == 2 && rp.shutter_open_time > 0.f && rp.spp > 1,
+             "stratified time sampling per interval with pairs (time_correlate_number = path_correlate_number = 2) and an open shutter");
+        need(rp.n_stratum >= 2 && (rp.n_stratum & (rp.n_stratum - 1u)) == 0, "a power-of-two stratum count");
+        need(rp.spp_log2 != 0xffffffffu && rp.spp_log2 >= 6, "a power-of-two sample count of at least 64 (whole waves of one pixel)");
+        need(!rp.orthographic && rp.aperture_radius == 0.f, "the perspective camera");
+        const uint64_t total = (uint64_t) sc->host.sensor.crop_w * sc->host.sensor.crop_h * rp.spp;
+        if (lane_begin + n > total) throw std::runtime_error("lane range exceeds the wavefront");
+        if (n == 0) return;
+        ensure_device(sc);
+        rp.lane_base = (uint32_t) lane_begin; rp.n_lanes = (uint32_t) n;
+        DevBuf<uint32_t> dout; dout.ensure((size_t) n * kPairSetupWords);
+        launch_pair_setup_lanes(rp, form, dout.p, nullptr);
+        HIP_CHECK(hipGetLastError());
+        HIP_CHECK(hipMemcpy(out16, dout.p, (size_t) n * kPairSetupWords * 4, hipMemcpyDeviceToHost));
     });
 }
 

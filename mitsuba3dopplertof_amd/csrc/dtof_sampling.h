@@ -166,6 +166,45 @@ DTOF_D void camera_ray(const RenderParams &rp, float ax, float ay, float apx, fl
     maxt = far_t - near_t;
 }
 
+// The two pieces generate_lane comes to under the facts of kFactsLaneSplit (dtof_kernels.h) and the plain perspective camera, each with its operations in the order
+// generate_lane has them.  generate_lane keeps its own text: written as the call of the two, the three kernels that carry these facts came out with
+// the same instructions in another order, and a kernel that does not take the pair form keeps its machine code.  The array entry (dtof_pair_setup.hip) holds the
+// pieces to generate_lane bit for bit.  kFactStratifiedPairs gives lanes 2k and 2k + 1 ONE path stream, and kFactCorrelated makes both jitter draws its draws: the
+// sample position and the whole camera ray are the pair's.  What is a lane's own is its main stream, its stratified time, and everything downstream of the time.
+// The pair's piece: the path stream seeded with the pair's index (`lane` is either lane of the pair), the two next_correlate draws as they read and advance that stream,
+// the sample position in the pixel at (posx, posy) (pixel_info), the camera ray.  path_sel: the stream's 32-bit selector, inc = path_sel << 1 | 1.
+struct PairPart { V3 o, d; float maxt; float2 pos; uint64_t path_state; uint32_t path_sel; };
+template <uint32_t FACTS>
+DTOF_D PairPart generate_pair_part(const RenderParams &rp, uint32_t lane, float posx, float posy) {
+    static_assert(lane_split_facts(FACTS), "the pair's piece is the text of generate_lane under these facts");
+    Rng path = seed_stream(rp.seed_value + 2, lane >> 1);
+    const uint64_t sx = path.state, sy = sx * kPcgMult + path.inc;   // next_correlate(main, path, true) twice: the draws belong to the states before each step
+    path.state = sy * kPcgMult + path.inc;
+    const float jx = pcg_output_f32(sx), jy = pcg_output_f32(sy);
+    const float spx = posx + jx, spy = posy + jy;
+    const float ax = fmaf(spx, rp.scale_x, rp.offset_x), ay = fmaf(spy, rp.scale_y, rp.offset_y);
+    PairPart pp;
+    camera_ray<true>(rp, ax, ay, .5f, .5f, pp.o, pp.d, pp.maxt);
+    pp.pos = make_float2(spx, spy); pp.path_state = path.state; pp.path_sel = (uint32_t) (path.inc >> 1);
+    return pp;
+}
+// The lane's piece: the main stream seeded with the lane's index, the two steps next_correlate makes on it beside the path stream's draws (nobody reads their values),
+// the stratified time of sample `lane & (spp - 1)` with the pixel's permutation seed, the wrap at T (dopplertofpath.cpp:93)
+struct LanePart { Rng main; float time; };
+template <uint32_t FACTS>
+DTOF_D LanePart generate_lane_part(const RenderParams &rp, uint32_t lane, uint32_t perm_seed) {
+    static_assert(lane_split_facts(FACTS), "the lane's piece is the text of generate_lane under these facts");
+    LanePart lp; Rng tm; tm.state = 0; tm.inc = 1;
+    lp.main = seed_stream(rp.seed_value, lane);
+    lp.main.state = lp.main.state * kPcgMult + lp.main.inc;
+    lp.main.state = lp.main.state * kPcgMult + lp.main.inc;
+    uint32_t dim = 0;
+    const float u = next_time<FACTS>(rp, lp.main, tm, lane & (rp.spp - 1u), perm_seed, dim);
+    const float time = rp.shutter_open + u * rp.shutter_open_time;
+    lp.time = time < rp.T ? time : time - rp.T;
+    return lp;
+}
+
 // PERSPECTIVE_ONLY: the sensor is known to be the plain perspective camera (the diffuse-only kernels: scenes with a thinlens / orthographic sensor run the every-BSDF
 // instantiations) -- the aperture draw and the two other ray constructions are not compiled in
 // FACTS: plan facts taken as constants (dtof_kernels.h: kFact*; k_shade): a single pass, the Doppler integrator with the correlated sampler, `correlate` at every depth

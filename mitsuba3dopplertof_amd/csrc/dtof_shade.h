@@ -3,6 +3,7 @@
 // the dtof_shade_*.hip files instantiate.
 #pragma once
 #include "dtof_device.h"
+#include "dtof_pair_setup.h"
 #include <atomic>
 #include <initializer_list>
 #include <type_traits>
@@ -418,6 +419,10 @@ __global__ __launch_bounds__(RESW ? RESW * 64 : kShadeBlock, RESW ? RESW / 4 : (
     constexpr bool F_PAIR = (FACTS & kFactPairSamples) != 0, JUMPS = F_PAIR && DTOF_STREAM_JUMPS, PAIR = F_PAIR && DTOF_PAIR_SAMPLES;
     // ... and (k): the camera ray, which the two lanes of a pair share, splits its plain rectangles between them (trace_flat: PAIR_RAYS)
     constexpr bool WALK_PRIMARY = F_PAIR && DTOF_PAIR_WALK_PRIMARY && pair_walk_shape(FACTS);
+    // ... and (l): the pair's piece of lane generation is evaluated once per pair, for the pairs of two chunks at a time (dtof_pair_setup.h).  The block walks its
+    // segment from chunk 0 (kFactOneBlock), its lanes are the segment's own (kFactIdentityQueue), and only the diffuse-only kernels generate perspective rays alone
+    constexpr bool PAIR_SETUP = F_PAIR && DTOF_PAIR_SETUP && F_ONE_BLOCK && F_IDENTITY && SPEC == 0 && lane_split_facts(FACTS);
+    static_assert(kPairChunk == (uint32_t) kShadeBlock, "a chunk of the pair setup is one block of k_shade");
     static_assert(!F_PAIR || F_WAVE_PIXEL, "a lane reads its partner's registers: the whole wave is active where it does");
     static_assert(!F_PAIR || (!AREA && SPEC == 0 && KMAX == 1 && F_ONE_EMITTER), "a diffuse BSDF picks no lobe and a lone point light samples nothing: of an iteration's six draws only s2x and s2y are read");
     static_assert(!F_PAIR || (F_NO_RR && F_CORRELATED && F_DOPPLER_CORR && F_WHOLE_PATH && F_SINGLE_PASS && (FACTS & kFactStratifiedPairs) != 0), "every draw comes from the stream lanes 2k and 2k + 1 share, none is looked at for roulette, no state outlives the launch");
@@ -512,6 +517,7 @@ __global__ __launch_bounds__(RESW ? RESW * 64 : kShadeBlock, RESW ? RESW / 4 : (
     SceneView sv = RESW ? sv_res : make_view(base);
     if (FUSED) { sv.memo_obj = A0.rp.memo_obj; sv.memo = (float *) (lds + stage_words) + (RESW ? wave_id * kMemoWords * kMemoStride + lane_id : threadIdx.x); sv.memo_m = memo_m_lds; }
     const bool have_memo = F_ONE_WALL || (FUSED && sv.memo_obj != 0xffffffffu);
+    PairPart pair_carried = pair_part_zero();   // PAIR_SETUP: the pair values an even chunk leaves for itself and for the chunk after it
     for (uint32_t cbase = sub > 1 ? sub_index * unit_lanes : 0u; cbase < (sub > 1 ? (sub_index + 1) * unit_lanes < count ? (sub_index + 1) * unit_lanes : count : count); cbase += kShadeBlock) {
     uint32_t rebase = 0;
     asm volatile("" : "+s"(rebase));
@@ -610,7 +616,10 @@ __global__ __launch_bounds__(RESW ? RESW * 64 : kShadeBlock, RESW ? RESW / 4 : (
     if (in_range) {
         l = qin ? qin[seg * kSeg + j] : seg * kSeg + j;
         if (FIRST) {
-            const PrimaryLane pl = generate_lane<SPEC == 0, FACTS>(rp, global_lane<FACTS>(rp, rp.lane_base + l), wave_pixel, rp.lane_base + l);
+            // (PAIR_SETUP: l = seg * kSeg + cbase + lane_id, and the global lane is the virtual one under the lane shifts)
+            PrimaryLane pl;
+            if constexpr (PAIR_SETUP) pl = pair_setup_chunk<FACTS, DTOF_PAIR_SETUP_BPERMUTE != 0>(rp, rp.lane_base + seg * kSeg + cbase, lane_id, ((cbase >> 6) & 1u) != 0, pair_carried);
+            else pl = generate_lane<SPEC == 0, FACTS>(rp, global_lane<FACTS>(rp, rp.lane_base + l), wave_pixel, rp.lane_base + l);
             ra = pl.ray_a; rb = pl.ray_b; main = pl.main; path = pl.path; st = make_float4(1.f, 1.f, 1.f, 0.f);
             if constexpr (PAIR) {
                 // Iteration i reads the draws at offsets 6 i + 3 and 6 i + 4 of the stream generate_lane leaves (s2x, s2y) and warps them; the terminal iteration reads none.
