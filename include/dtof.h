@@ -464,6 +464,35 @@ int dtof_render_aovs(dtof_scene *scene, uint32_t seed, uint32_t spp, uint32_t n_
 int dtof_sample_aov_lanes(dtof_scene *scene, uint32_t seed, uint32_t spp, const int32_t *types, int n_types, uint64_t lane_begin, uint64_t n, float *out_lanes12,
                           float *out_values);
 
+/* ---------------------------------------------------------------- denoiser
+ * The counterpart of the reference's OptixDenoiser (src/render/python/optixdenoiser_v.cpp; its tests: src/render/tests/test_optixdenoiser.py), written from scratch:
+ * an edge-avoiding a-trous wavelet filter (Dammertz et al. 2010) whose luminance term is normalised by the per-pixel variance (the spatial pass of SVGF), over
+ * n_planes colour planes that share ONE set of weights -- the four films of a velocity map's traversal, so that the heterodyne / homodyne ratio of a pixel stays a
+ * ratio of identically weighted neighbourhoods.  All in double, no fused multiply-add; tests/denoise_ref.py is the definition:
+ *   level l = 0 .. levels - 1, step s = 2^l, reads the result of level l - 1 (level 0: the inputs converted to double); the guides never change
+ *   taps    q = p + s (i, j), i, j in -2 .. 2, j outer, i inner; taps outside the image and invalid taps are skipped
+ *   valid   every colour word of every plane, every variance and every present guide word of the pixel is finite; an invalid centre is copied through
+ *   weight  w = (b[i] b[j]) exp(-((dn + dx) + dl)), b = (1/16, 1/4, 3/8, 1/4, 1/16); dn = |n_p - n_q|^2 / sigma_normal^2, dx = |x_p - x_q|^2 / sigma_position^2
+ *           (squared norms (a a + b b) + c c; 0 without the guide); dl = max_k d_k (0 without a variance) with Y_k = (0.2126 r + 0.7152 g) + 0.0722 b,
+ *           den_k = sigma_luminance sqrt(max(var_k(p), 0)) at the CENTRE, d_k = |Y_k(p) - Y_k(q)| / den_k if den_k > 0, else 0 for equal luminances and +inf
+ *   result  c'_k(p) = (sum_q w c_k(q)) / (sum_q w), var'_k(p) = (sum_q w^2 var_k(q)) / (sum_q w)^2
+ * colour[n_planes][height][width][3] float32; variance_or_null[n_planes][height][width] double, the variance of plane k's luminance estimate;
+ * normal_or_null, position_or_null [height][width][3] float32.  out_colour[n_planes][height][width][3] double; out_variance_or_null[n_planes][height][width] double.
+ * DTOF_ERR_INVALID before any HIP call, with no output touched: n_planes outside 1 .. 4, levels outside 1 .. 6, width or height < 1 (or > 65535), a sigma of a
+ * present guide that is not finite or not > 0 (or whose square is not), a null colour, output or params pointer, out_variance without variance, a misaligned
+ * buffer, an output that overlaps an input.  With valid arguments and no device: DTOF_ERR_HIP.  There is no CPU fallback. */
+typedef struct {
+    int32_t levels;                                          /* 1 .. 6 */
+    double sigma_normal, sigma_position, sigma_luminance;    /* read only when the guide is present */
+} dtof_denoise_params;
+/* DEVICE pointers; 1 + levels launches on the scene's stream, no host wait.  Scratch comes from a per-scene cache. */
+int dtof_denoise_async(dtof_scene *scene, const float *d_colour, int n_planes, int32_t width, int32_t height, const double *d_variance_or_null,
+                       const float *d_normal_or_null, const float *d_position_or_null, const dtof_denoise_params *params, double *d_out_colour,
+                       double *d_out_variance_or_null);
+/* The same with HOST pointers and no scene: uploads, runs, downloads and synchronises once. */
+int dtof_denoise(const float *colour, int n_planes, int32_t width, int32_t height, const double *variance_or_null, const float *normal_or_null,
+                 const float *position_or_null, const dtof_denoise_params *params, double *out_colour, double *out_variance_or_null);
+
 /* Integrator::cancel / should_stop (include/mitsuba/render/integrator.h:96-109). */
 void dtof_cancel(dtof_scene *scene);
 /* First-bounce launches of this scene, since it was loaded, that ran a kernel compiled with the frame plan's constants (dtof_render_stats::n_plan_facts_launches): the

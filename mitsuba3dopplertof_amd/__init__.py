@@ -16,7 +16,7 @@ import os
 import numpy as np
 
 __all__ = ["load_file", "load_string", "load_dict", "Scene", "Integrator", "Sampler", "DtofError", "render",
-           "render_multi_pass", "to_tof_image", "lib_path", "ETimeSampling", "velocity_map_variants", "MOMENT_PLANES", "aov_channels", "AOV_TYPES"]
+           "render_multi_pass", "to_tof_image", "lib_path", "ETimeSampling", "velocity_map_variants", "MOMENT_PLANES", "aov_channels", "AOV_TYPES", "Denoiser"]
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB = None
@@ -175,7 +175,9 @@ def _lib():
                        ("dtof_aov_parse", [C.c_char_p, vp, C.c_int, C.POINTER(C.c_int), vp, C.c_size_t, C.POINTER(C.c_int)]),
                        ("dtof_scene_get_aovs", [vp, vp, C.c_size_t]),
                        ("dtof_render_aovs", [vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, C.c_int, C.c_int, vp, C.POINTER(_Stats)]),
-                       ("dtof_sample_aov_lanes", [vp, C.c_uint32, C.c_uint32, vp, C.c_int, C.c_uint64, C.c_uint64, vp, vp])):
+                       ("dtof_sample_aov_lanes", [vp, C.c_uint32, C.c_uint32, vp, C.c_int, C.c_uint64, C.c_uint64, vp, vp]),
+                       ("dtof_denoise_async", [vp, vp, C.c_int, C.c_int32, C.c_int32, vp, vp, vp, vp, vp, vp]),
+                       ("dtof_denoise", [vp, C.c_int, C.c_int32, C.c_int32, vp, vp, vp, vp, vp, vp])):
         if hasattr(L, name):   # a DTOF_LIB build from before the variants (A/B timing against an older commit) loads; calling what it lacks still raises
             getattr(L, name).argtypes = args
     _LIB = L
@@ -306,6 +308,77 @@ def velocity_map_variants(offsets):
     out = np.zeros((2 * len(o), 2), np.float32)
     _check(_lib().dtof_velocity_map_variants(o.ctypes.data, len(o), out.ctypes.data))
     return out
+
+
+class _DenoiseParams(C.Structure):   # dtof_denoise_params
+    _fields_ = [("levels", C.c_int32), ("sigma_normal", C.c_double), ("sigma_position", C.c_double), ("sigma_luminance", C.c_double)]
+
+
+class Denoiser:
+    """The counterpart of the reference's mi.OptixDenoiser(input_size, albedo, normals, temporal) (src/render/python/optixdenoiser_v.cpp), written in HIP
+    (dtof_denoise): an edge-avoiding a-trous wavelet filter whose luminance term is normalised by the per-pixel variance, over up to four images that share ONE set
+    of weights (include/dtof.h has the definition).  `input_size`: (width, height).  `normals`, `position`, `variance`: which guides every call will bring.
+    `sigma_position=None`: 1 % of the largest extent of the finite positions of a call, computed with numpy and kept in `last_sigma_position`.  There is no albedo
+    guide (the aov film refuses that channel), no alpha plane and no temporal accumulation.
+
+        denoised = mi.Denoiser((w, h))(noisy)
+        denoised, variance = mi.Denoiser((w, h), normals=True, position=True, variance=True)(noisy, normals=n, position=p, variance=v)"""
+
+    def __init__(self, input_size, normals=False, position=False, variance=False, levels=5, sigma_normal=0.1, sigma_position=None, sigma_luminance=4.0):
+        try:
+            w, h = (int(v) for v in input_size)
+        except (TypeError, ValueError):
+            raise DtofError("Denoiser: input_size must be (width, height)")
+        if w < 1 or h < 1:
+            raise DtofError("Denoiser: input_size must be at least 1 x 1")
+        if not 1 <= int(levels) <= 6:
+            raise DtofError("Denoiser: levels must be between 1 and 6")
+        self.input_size = (w, h)
+        self.normals, self.position, self.variance = bool(normals), bool(position), bool(variance)
+        self.levels = int(levels)
+        self.sigma_normal, self.sigma_position, self.sigma_luminance = float(sigma_normal), None if sigma_position is None else float(sigma_position), float(sigma_luminance)
+        self.last_sigma_position = None
+
+    def _guide(self, name, declared, value, shape, dtype):
+        if declared != (value is not None):
+            raise DtofError("Denoiser: the denoiser was created with %s=%s, so the call must %s it" % (name, declared, "bring" if declared else "not bring"))
+        if value is None:
+            return None
+        a = np.ascontiguousarray(value, dtype=dtype)
+        if a.shape != shape:
+            raise DtofError("Denoiser: %s must have the shape %s, not %s" % (name, shape, a.shape))
+        return a
+
+    def __call__(self, noisy, normals=None, position=None, variance=None):
+        """noisy (H, W, 3) or (K, H, W, 3), K <= 4; normals, position (H, W, 3); variance (H, W) or (K, H, W): the variance of every image's luminance estimate.
+        Returns the filtered images as float64 in the shape of `noisy`, and with a variance the tuple (images, filtered variance)."""
+        w, h = self.input_size
+        col = np.ascontiguousarray(noisy, dtype=np.float32)
+        single = col.ndim == 3
+        if single:
+            col = col[None]
+        if col.ndim != 4 or col.shape[1:] != (h, w, 3) or not 1 <= col.shape[0] <= MAX_VARIANTS:
+            raise DtofError("Denoiser: noisy must be (%d, %d, 3) or (K, %d, %d, 3) with 1 <= K <= 4, not %s" % (h, w, h, w, np.shape(noisy)))
+        k = col.shape[0]
+        nrm = self._guide("normals", self.normals, normals, (h, w, 3), np.float32)
+        pos = self._guide("position", self.position, position, (h, w, 3), np.float32)
+        if variance is not None and single and np.ndim(variance) == 2:
+            variance = np.asarray(variance)[None]
+        var = self._guide("variance", self.variance, variance, (k, h, w), np.float64)
+        sigma_x = self.sigma_position
+        if pos is not None and sigma_x is None:
+            finite = pos[np.isfinite(pos).all(axis=2)].astype(np.float64)
+            extent = float((finite.max(axis=0) - finite.min(axis=0)).max()) if len(finite) else 0.0
+            sigma_x = 0.01 * extent if extent > 0 else 1.0      # one point: every position difference is 0 whatever the sigma
+            self.last_sigma_position = sigma_x
+        prm = _DenoiseParams(self.levels, self.sigma_normal, 1.0 if sigma_x is None else sigma_x, self.sigma_luminance)
+        out = np.zeros((k, h, w, 3), np.float64)
+        out_var = None if var is None else np.zeros((k, h, w), np.float64)
+        _check(_lib().dtof_denoise(col.ctypes.data, k, w, h, None if var is None else var.ctypes.data, None if nrm is None else nrm.ctypes.data,
+                                   None if pos is None else pos.ctypes.data, C.byref(prm), out.ctypes.data, None if out_var is None else out_var.ctypes.data))
+        if single:
+            out, out_var = out[0], None if out_var is None else out_var[0]
+        return out if out_var is None else (out, out_var)
 
 
 class Scene:
@@ -479,6 +552,38 @@ class Scene:
                 slot += 1
         return {"weight": planes[0].copy(), "mean": np.ascontiguousarray(np.moveaxis(per[:, 0:3], 1, -1)),
                 "m2": np.ascontiguousarray(np.moveaxis(per[:, 3:6], 1, -1)), "cross": cross}
+
+    def render_denoised(self, seed=0, spp=0, n_passes=1, variants=None, **denoiser_kw):
+        """The images of render(variants=...) and their jointly denoised versions (Denoiser), guided by what the moment film and the aov film provide.  THREE
+        renders with the same seeds seed, seed + 1, ...: render() for the images (the float32 mean of the passes), render_moments for the variance of every
+        variant's luminance estimate -- (m2_Y - mean_Y^2) / (samples per pixel x passes), harness.moment_statistics -- and render_aovs("p:position,n:sh_normal") for
+        the guides; then ONE Denoiser call over all variants, which therefore share their weights.  That these are three traversals of the scene is accepted for
+        now: fusing them on the device is a later step.  `variants`: up to four (hetero_frequency, hetero_offset) pairs; None: the integrator's own pair.
+        `denoiser_kw`: levels and the sigmas of Denoiser.  Returns a dict: "image" (K, H, W, 3 | 4) float32 -- (H, W, 3 | 4) without variants --, "denoised"
+        float64 (the first three channels: an alpha plane is not denoised), "variance" and "denoised_variance" (K, H, W) -- (H, W) -- float64, and "denoiser"."""
+        from .harness import moment_statistics
+        if variants is not None and not 1 <= len(variants) <= MAX_VARIANTS:
+            raise DtofError("between 1 and 4 modulation variants can be denoised jointly")
+        n_passes = int(n_passes)
+        if n_passes < 1:
+            raise DtofError("n_passes must be at least 1")
+        image = self.render(seed=seed, spp=spp, variants=variants)
+        for i in range(1, n_passes):
+            image = image + self.render(seed=seed + i, spp=spp, variants=variants)
+        if n_passes > 1:
+            image = image / np.float32(n_passes)
+        stats = self.last_stats
+        m = self.render_moments(seed=seed, spp=spp, n_passes=n_passes, variants=variants)
+        per_pixel = self.last_stats["n_paths"] / float(self.size[0] * self.size[1])        # samples per pixel x passes, as rendered
+        variance = moment_statistics(m, per_pixel)["variance"][..., 1] / per_pixel
+        guides = self.render_aovs("p:position,n:sh_normal", seed=seed, spp=spp, n_passes=n_passes)
+        self.last_stats = stats
+        den = Denoiser(self.size, normals=True, position=True, variance=True, **denoiser_kw)
+        noisy = image[..., :3]
+        if variants is None:
+            variance = variance[0]
+        denoised, denoised_variance = den(noisy, normals=guides["n"], position=guides["p"], variance=variance)
+        return {"image": image, "denoised": denoised, "variance": variance, "denoised_variance": denoised_variance, "denoiser": den}
 
     @property
     def aovs(self):

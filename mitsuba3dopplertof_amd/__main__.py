@@ -9,6 +9,9 @@ plugins this library implements:
         the per-pixel moment film of one traversal per pass (weight, mean, m2, cross: Scene.render_moments), written with np.savez
     python -m mitsuba3dopplertof_amd scene.xml --aovs dd:depth,nn:sh_normal [--passes N] [--spp N] [-o out.npz]
         the geometry channels of the reference's `aov` integrator along the scene integrator's camera rays (Scene.render_aovs), written with np.savez
+    python -m mitsuba3dopplertof_amd scene.xml --denoise [--denoise-levels 5] [--denoise-sigma n,x,l] [--velocity-map 0,0.25] [--spp N] [-o out.exr|.npy]
+        the image (or, with --velocity-map and two offsets, the velocity map) with the joint variance-guided a-trous denoiser behind the films (Denoiser): the
+        denoised result goes to the output file, the noisy one to its _noisy sibling
     python -m torch.distributed.run --nproc-per-node G --master-addr 127.0.0.1 -m mitsuba3dopplertof_amd scene.xml ...
         one process per GPU: the pixel rows are sharded across the G ranks, rank 0 gathers and writes the image
 """
@@ -46,8 +49,47 @@ def parser():
     ap.add_argument("--aovs", default=None, metavar="NAME:TYPE,...",
                     help="write the geometry channels under each pixel (depth, position, uv, geo_normal, sh_normal, dp_du, dp_dv, prim_index, shape_index; float64 "
                          ".npz) instead of an image: the `aovs` string of the reference's aov integrator")
+    ap.add_argument("--denoise", action="store_true",
+                    help="denoise the image, or the four films of a --velocity-map of two offsets, guided by the moment film's variance and the aov film's position and "
+                         "shading normal (three traversals); the noisy result is written to the output's _noisy sibling")
+    ap.add_argument("--denoise-levels", type=int, default=None, metavar="L", help="--denoise: a-trous levels, 1 .. 6 (default 5)")
+    ap.add_argument("--denoise-sigma", default=None, metavar="N,X,L",
+                    help="--denoise: sigma_normal,sigma_position,sigma_luminance (default 0.1, 1 %% of the scene's extent, 4)")
     ap.add_argument("-v", "--verbose", action="store_true")
     return ap
+
+
+def check_denoise_args(ap, args):
+    """what --denoise cannot be combined with, refused before the scene is loaded -> the keyword arguments of Denoiser"""
+    if args.moments or args.aovs is not None:
+        ap.error("--denoise filters an image or a velocity map: --moments and --aovs write the films it is guided by, run them separately")
+    if args.stripes > 0 or int(os.environ.get("WORLD_SIZE", "1")) > 1:
+        ap.error("--denoise is a single-GPU feature: it cannot be combined with --stripes or a multi-GPU launch")
+    if args.film == "float64":
+        ap.error("--denoise reads the float32 images: do not combine it with --film float64")
+    if args.offsets is not None:
+        ap.error("--denoise takes the integrator's own image or a --velocity-map, not --offsets")
+    kw = {}
+    if args.denoise_levels is not None:
+        if not 1 <= args.denoise_levels <= 6:
+            ap.error("--denoise-levels must be between 1 and 6")
+        kw["levels"] = args.denoise_levels
+    if args.denoise_sigma is not None:
+        try:
+            sn, sx, sl = (float(x) for x in args.denoise_sigma.split(","))
+        except ValueError:
+            ap.error("--denoise-sigma expects three comma separated numbers: normal,position,luminance")
+        if not all(np.isfinite(v) and v > 0 for v in (sn, sx, sl)):
+            ap.error("--denoise-sigma: every sigma must be finite and > 0")
+        kw.update(sigma_normal=sn, sigma_position=sx, sigma_luminance=sl)
+    if args.velocity_map is not None and len(args.velocity_map.split(",")) != 2:
+        ap.error("--denoise with --velocity-map takes two offsets: the four films of one traversal share their weights")
+    return kw
+
+
+def _noisy_sibling(path):
+    base, ext = os.path.splitext(path)
+    return base + "_noisy" + ext
 
 
 def check_film_args(ap, args):
@@ -162,9 +204,14 @@ def velocity_map(args, scene):
     out = args.output or os.path.splitext(args.scene)[0] + "_velocity.npy"
     single, n_pass = _passes(args.spp or scene.info()["sample_count"])
     t0 = time.time()
-    v, _films = scene.render_velocity_map(n_pass, single, offsets, exposure_time=args.exposure_time, w_g=args.w_g, film=args.film)
-    dt = time.time() - t0
     os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+    if args.denoise:   # the host route: the films have to reach the denoiser before the ratio is formed
+        from mitsuba3dopplertof_amd.harness import velocity_map_denoised
+        noisy, v = velocity_map_denoised(scene, n_pass, single, offsets, exposure_time=args.exposure_time, w_g=args.w_g, **args.denoise_kw)
+        np.save(_noisy_sibling(out), noisy)
+    else:
+        v, _films = scene.render_velocity_map(n_pass, single, offsets, exposure_time=args.exposure_time, w_g=args.w_g, film=args.film)
+    dt = time.time() - t0
     np.save(out, v)
     if args.verbose:
         st = scene.last_stats
@@ -184,6 +231,10 @@ def main(argv=None):
         ap.error("--variants and --passes belong to --moments")
     if args.velocity_map is not None:
         check_velocity_map_args(ap, args)
+    if args.denoise:
+        args.denoise_kw = check_denoise_args(ap, args)
+    elif args.denoise_levels is not None or args.denoise_sigma is not None:
+        ap.error("--denoise-levels and --denoise-sigma belong to --denoise")
     import mitsuba3dopplertof_amd as mi
     from mitsuba3dopplertof_amd.io import write_image
     defines = {}
@@ -218,6 +269,9 @@ def main(argv=None):
             dist.destroy_process_group()
             if img is None:
                 return 0
+        elif args.denoise:
+            d = scene.render_denoised(seed=args.seed, spp=args.spp, **args.denoise_kw)
+            img, noisy = d["denoised"], d["image"]
         else:
             img = scene.render(seed=args.seed, spp=args.spp, offsets=offsets, film=args.film)
         dt = time.time() - t0
@@ -225,7 +279,14 @@ def main(argv=None):
         print("Error: %s" % e, file=sys.stderr)
         return 1
     out = args.output or os.path.splitext(args.scene)[0] + ".exr"
-    if offsets is None:
+    if args.denoise:
+        if out.lower().endswith(".npy"):      # the denoiser's float64 survives in a .npy file only
+            os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+            np.save(out, img)
+        else:
+            write_image(out, img.astype(np.float32))
+        write_image(_noisy_sibling(out), noisy)
+    elif offsets is None:
         write_image(out, img)
     else:
         base, ext = os.path.splitext(out)

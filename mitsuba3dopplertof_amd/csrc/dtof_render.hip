@@ -9,6 +9,7 @@
 #include "../../include/dtof.h"
 #include "dtof_kernels.h"
 #include "dtof_reconstruct.h"
+#include "dtof_denoise.h"
 #include "dtof_film64.h"
 #include "dtof_moments.h"
 #include "dtof_aov.h"
@@ -107,6 +108,7 @@ struct dtof_scene {
     DevBuf<float> d_film, d_rgb;
     DevBuf<double> d_film64;   // the library's own float64 film (dtof_render_variants_f64, dtof_render_velocity_map_f64)
     DevBuf<double> d_moments, d_moment_planes;   // the moment film (dtof_render_moments) or the aov film (dtof_render_aovs) of the call: cells of kMomentCell doubles per pixel, and the dense planes copied out
+    DevBuf<double> d_denoise;   // dtof_denoise_async: the guide records and the two sets of working planes
     DevBuf<float> d_vm_sum, d_vm_tof; DevBuf<double> d_vm_maps;   // dtof_render_velocity_map: the passes' sum, the ToF images, the per-pair maps and the combined map
     // the caller's device film as declared with dtof_scene_set_film_layout (0 = not declared: colour planes only, W * H * 4 apart)
     int32_t film_planes = 0; uint64_t film_plane_stride = 0;
@@ -1553,6 +1555,48 @@ int dtof_develop_rgba_f64_async(dtof_scene *sc, const double *d_film64, const do
         ensure_device(sc);
         launch_develop_rgba_f64(d_film64, d_alpha_film64, d_rgba, n_pixels, sc->stream);
         HIP_CHECK(hipGetLastError());
+    });
+}
+
+// ---------------------------------------------------------------- denoiser (dtof_denoise.hip)
+// every refusal of the two entries (denoise_check, dtof_denoise_args.h), before a device is touched
+static DenoiseArgs denoise_args(const float *colour, int n_planes, int32_t width, int32_t height, const double *variance, const float *normal, const float *position,
+                                const dtof_denoise_params *p, const double *out_colour, const double *out_variance) {
+    DenoiseBuffers b { colour, variance, normal, position, out_colour, out_variance };
+    DenoiseArgs a;
+    const std::string err = denoise_check(b, n_planes, width, height, p == nullptr, p ? p->levels : 0, p ? p->sigma_normal : 0.0, p ? p->sigma_position : 0.0,
+                                          p ? p->sigma_luminance : 0.0, &a);
+    if (!err.empty()) throw std::runtime_error("dtof_denoise: " + err);
+    return a;
+}
+int dtof_denoise_async(dtof_scene *sc, const float *d_colour, int n_planes, int32_t width, int32_t height, const double *d_variance, const float *d_normal,
+                       const float *d_position, const dtof_denoise_params *params, double *d_out_colour, double *d_out_variance) {
+    return guarded([&] {
+        if (!sc) throw std::runtime_error("null argument");
+        const DenoiseArgs a = denoise_args(d_colour, n_planes, width, height, d_variance, d_normal, d_position, params, d_out_colour, d_out_variance);
+        ensure_device(sc);
+        sc->d_denoise.ensure(denoise_scratch_doubles(a));
+        launch_denoise(a, d_colour, d_variance, d_normal, d_position, d_out_colour, d_out_variance, sc->d_denoise.p, sc->stream);
+        HIP_CHECK(hipGetLastError());
+    });
+}
+int dtof_denoise(const float *colour, int n_planes, int32_t width, int32_t height, const double *variance, const float *normal, const float *position,
+                 const dtof_denoise_params *params, double *out_colour, double *out_variance) {
+    return guarded([&] {
+        const DenoiseArgs a = denoise_args(colour, n_planes, width, height, variance, normal, position, params, out_colour, out_variance);
+        const size_t n = (size_t) width * height, k = (size_t) n_planes;
+        DevBuf<float> d_colour, d_normal, d_position; DevBuf<double> d_variance, d_out_colour, d_out_variance, d_scratch;
+        d_colour.ensure(k * n * 3); d_out_colour.ensure(k * n * 3); d_scratch.ensure(denoise_scratch_doubles(a));
+        HIP_CHECK(hipMemcpyAsync(d_colour.p, colour, k * n * 3 * sizeof(float), hipMemcpyHostToDevice, nullptr));
+        if (variance) { d_variance.ensure(k * n); HIP_CHECK(hipMemcpyAsync(d_variance.p, variance, k * n * sizeof(double), hipMemcpyHostToDevice, nullptr)); }
+        if (normal) { d_normal.ensure(n * 3); HIP_CHECK(hipMemcpyAsync(d_normal.p, normal, n * 3 * sizeof(float), hipMemcpyHostToDevice, nullptr)); }
+        if (position) { d_position.ensure(n * 3); HIP_CHECK(hipMemcpyAsync(d_position.p, position, n * 3 * sizeof(float), hipMemcpyHostToDevice, nullptr)); }
+        if (out_variance) d_out_variance.ensure(k * n);
+        launch_denoise(a, d_colour.p, d_variance.p, d_normal.p, d_position.p, d_out_colour.p, d_out_variance.p, d_scratch.p, nullptr);
+        HIP_CHECK(hipGetLastError());
+        HIP_CHECK(hipMemcpyAsync(out_colour, d_out_colour.p, k * n * 3 * sizeof(double), hipMemcpyDeviceToHost, nullptr));
+        if (out_variance) HIP_CHECK(hipMemcpyAsync(out_variance, d_out_variance.p, k * n * sizeof(double), hipMemcpyDeviceToHost, nullptr));
+        HIP_CHECK(hipStreamSynchronize(nullptr));
     });
 }
 

@@ -122,6 +122,57 @@ def run_scene_velocity_map_device(scene, total_spp=1024, offsets=(0.0, 0.25), fi
     return scene.render_velocity_map(n_pass, single, [float(o) for o in offsets], exposure_time, w_g, film=film)
 
 
+def velocity_map_denoised(scene, n_passes, spp, offsets=(0.0, 0.25), exposure_time=0.0015, w_g=30, **denoiser_kw):
+    """The velocity map of the scene's OWN dopplertofpath integrator with the four ToF films of its traversal denoised JOINTLY before the ratio is formed
+    (Denoiser): one set of weights for (0, o0), (0, o1), (1, o0), (1, o1), so a pixel's heterodyne / homodyne ratio stays a ratio of identically weighted
+    neighbourhoods.  Exactly two offsets: one traversal group.  The films are accumulated over passes of `spp` samples with seeds 0, 1, ... and turned into
+    to_tof_image values as run_scene_velocity_map does; the variance of every ToF film is that of the pass mean from the moment film of the same passes and seeds,
+    (m2_Y - mean_Y^2) / (passes x spp) times exposure_time^2 (Y of the moment film is a luminance with the coefficients of srgb_to_xyz rather than to_tof_image's
+    rounded ones); the guides are the position and shading normal of the aov film.  The luminance of a ToF plane is the plane itself: it is handed to the denoiser
+    REPLICATED into three channels (the weights (0.2126 + 0.7152) + 0.0722 sum to 1 up to rounding, and the three outputs are equal) and channel 0 of the result is
+    taken -- the C entry has no one-channel path.  These are three traversals per pass (images, moments, aovs); fusing them on the device is a later step.
+    `denoiser_kw`: levels and the sigmas of Denoiser.  Returns (noisy map (H, W), denoised map (H, W)); the films, their variances, the guides and the Denoiser are
+    left in scene.denoise_details."""
+    from . import Denoiser
+    offsets = [float(o) for o in offsets]
+    if len(offsets) != 2:
+        raise ValueError("a denoised velocity map takes two offsets: the four films of one traversal")
+    variants = [(0.0, o) for o in offsets] + [(1.0, o) for o in offsets]
+    acc = None
+    for i in range(n_passes):
+        img = scene.render(seed=i, spp=spp, variants=variants).astype(np.float32)
+        acc = img if acc is None else acc + img
+    stats = scene.last_stats
+    tof = [to_tof_image(im, exposure_time) for im in acc / np.float32(n_passes)]
+    noisy_map = calc_velocity_from_homo_heteros(tof[:2], tof[2:], exposure_time, w_g)
+    m = scene.render_moments(seed=0, spp=spp, n_passes=n_passes, variants=variants)
+    n_samples = scene.last_stats["n_paths"] / float(tof[0].shape[0] * tof[0].shape[1])           # passes x spp as rendered (spp = 0: the sampler's count)
+    variance = moment_statistics(m, n_samples)["variance"][..., 1] / n_samples * (exposure_time * exposure_time)
+    guides = scene.render_aovs("p:position,n:sh_normal", seed=0, spp=spp, n_passes=n_passes)
+    scene.last_stats = stats
+    films = np.stack(tof).astype(np.float32)                                                     # (4, H, W)
+    h, w = films.shape[1:]
+    den = Denoiser((w, h), normals=True, position=True, variance=True, **denoiser_kw)
+    out, out_var = den(np.repeat(films[..., None], 3, axis=3), normals=guides["n"], position=guides["p"], variance=variance)
+    out = out[..., 0]
+    denoised_map = calc_velocity_from_homo_heteros(list(out[:2]), list(out[2:]), exposure_time, w_g)
+    scene.denoise_details = {"homodyne": tof[:2], "heterodyne": tof[2:], "denoised_homodyne": list(out[:2]), "denoised_heterodyne": list(out[2:]),
+                             "variance": variance, "denoised_variance": out_var, "guides": guides, "denoiser": den}
+    return noisy_map, denoised_map
+
+
+def run_scene_velocity_map_denoised(scene, total_spp, offsets=(0.0, 0.25), denoiser=None, **integrator_kwargs):
+    """velocity_map_denoised under run_scene_velocity_map's integrator dictionary, passes (min(1024, total_spp) samples each) and seeds: the noisy map it returns is
+    computed as run_scene_velocity_map computes it.  `denoiser`: a dict of Denoiser keyword arguments (levels, sigmas).  Returns (noisy map, denoised map)."""
+    single, n_pass = _passes(total_spp)
+    integrator_kwargs = dict(integrator_kwargs)
+    integrator_kwargs.pop("hetero_offset", None)
+    integrator_kwargs.pop("hetero_frequency", None)
+    scene.set_integrator(doppler_integrator_dict(hetero_frequency=0.0, hetero_offset=0.0, **integrator_kwargs))
+    exposure_time, w_g = integrator_kwargs.get("exposure_time", 0.0015), integrator_kwargs.get("w_g", 30)
+    return velocity_map_denoised(scene, n_pass, single, offsets, exposure_time, w_g, **(denoiser or {}))
+
+
 def run_scene_moments(scene, total_spp=1024, variants=((0, 0), (1, 0)), **integrator_kwargs):
     """The moment film of run_scene_doppler_tof_variants' render: the same integrator dictionary, the same passes (min(1024, total_spp) samples each) and seeds
     0, 1, ..., but ONE Scene.render_moments call whose passes all accumulate into one film.  `variants`: up to four (hetero_frequency, hetero_offset) pairs of one
