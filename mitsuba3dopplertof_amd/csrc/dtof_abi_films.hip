@@ -1,0 +1,603 @@
+// dtof_abi_films.hip -- the C ABI (include/dtof.h) of rendering: every entry that renders into a film (the caller's device film, the library's own float32 / float64
+// film, the moment and aov cells, lane dumps), develops one, reconstructs the radial-velocity map or denoises, and dtof_async_collect.  All of them end in render_rows
+// (dtof_render.hip) or in one of the launchers of the small kernel files.
+#include "dtof_host.h"
+#include "dtof_reconstruct.h"
+#include "dtof_denoise.h"
+#include "dtof_film64.h"
+#include "dtof_moments.h"
+#include <cmath>
+
+using namespace dtof;
+
+// film elements (4 per pixel) of the rows a call that renders rows [row_lo, row_hi) can write: the rows and the filter's halo on either side, inside the film
+static uint64_t film_rows_reach(const HostSensor &se, int32_t row_lo, int32_t row_hi, int32_t *first = nullptr, int32_t *end = nullptr) {
+    const int32_t halo = se.filter == FILTER_BOX ? 0 : (int32_t) std::ceil(se.filter_radius - .5f);
+    const int32_t r0 = std::max(row_lo, 0), r1 = std::min(row_hi, se.crop_h);
+    const int32_t lo = std::max(r0 - halo, 0), hi = std::min(r1 + halo, se.crop_h);
+    if (first) *first = lo;
+    if (end) *end = hi;
+    return r1 > r0 ? (uint64_t) (hi - lo) * se.crop_w * 4 : 0;   // an empty band writes nothing
+}
+// ... which a plane stride (0: dense planes) of a film of several planes must hold, or plane k + 1 would be added into plane k; `what` and `unit` name it in the refusal
+static void check_stride_reach(const HostSensor &se, uint64_t stride, int32_t row_lo, int32_t row_hi, const char *what, const char *unit) {
+    int32_t lo = 0, hi = 0;
+    const uint64_t reach = film_rows_reach(se, row_lo, row_hi, &lo, &hi);
+    if (stride != 0 && stride < reach)
+        throw std::runtime_error(std::string("the ") + what + " of " + std::to_string(stride) + " " + unit + " is smaller than the " + std::to_string(reach) + " " + unit +
+                                 " of film rows [" + std::to_string(lo) + ", " + std::to_string(hi) + ") this call writes: the planes would overlap");
+}
+// The device-film entry points write K colour planes and, for an rgba film, the alpha plane behind them into memory whose size only the caller knows: an rgba scene is
+// refused until the caller has declared a film of K + 1 planes (a caller written for rgb films would have its buffer overrun), and a declared count is checked either way.
+// [row_lo, row_hi): the film rows whose lanes the call renders.  Their splats reach `halo` rows further (the reconstruction filter), so with more than one plane a
+// declared stride must hold rows [max(row_lo - halo, 0), min(row_hi + halo, H)) or plane k + 1 would be added into plane k: such a call is refused before any launch.
+static uint64_t caller_film_stride(const dtof_scene *sc, int n_offsets, int32_t row_lo, int32_t row_hi) {
+    const HostSensor &se = sc->host.sensor;
+    const int need = (n_offsets <= 0 ? 1 : n_offsets) + (se.alpha ? 1 : 0);
+    if (se.alpha && sc->film_planes < need)
+        throw std::runtime_error("rgba film: the device film needs " + std::to_string(need) + " RGBW planes (the alpha film lies behind the colour films); declare them with dtof_scene_set_film_layout");
+    if (sc->film_planes != 0 && sc->film_planes < need)
+        throw std::runtime_error("the device film was declared with " + std::to_string(sc->film_planes) + " planes, this call writes " + std::to_string(need));
+    if (need > 1) check_stride_reach(se, sc->film_plane_stride, row_lo, row_hi, "declared plane stride", "floats");
+    return sc->film_plane_stride ? sc->film_plane_stride : (uint64_t) se.crop_w * se.crop_h * 4;
+}
+// the rows [first, last + 1) that hold the stripes [first_row + k * stripe_period, ... + stripe_rows) below the film's height (the mapping of plan_lanes)
+static std::pair<int32_t, int32_t> stripe_span(const dtof_scene *sc, int32_t first_row, int32_t stripe_rows, int32_t stripe_period) {
+    const int32_t h = sc->host.sensor.crop_h, first = std::max(first_row, 0);
+    const int64_t span = std::max<int64_t>(h - first, 0), v_rows = (span / stripe_period) * stripe_rows + std::min<int64_t>(span % stripe_period, stripe_rows);
+    if (v_rows == 0) return {first, first};
+    return {first, (int32_t) (first + ((v_rows - 1) / stripe_rows) * stripe_period + (v_rows - 1) % stripe_rows + 1)};
+}
+
+// The variants arguments of the C ABI as a request carries them: NULL / 0 = the integrator's own pair; the count is checked here, before anything is enqueued
+static void set_variants(RenderRequest &rq, const dtof_modulation *variants, int n_variants) {
+    if (!variants || n_variants <= 0) return;
+    if (n_variants > kMaxOffsets) throw std::runtime_error("at most 4 modulation variants can be batched per traversal");
+    rq.variants = variants; rq.n_variants = n_variants;
+}
+// The device-film entry points: a rows or stripes request with the call's offsets or variants (their count is refused before a null scene or film is), the null and
+// stripe checks, the caller's film layout, and for the async forms the events a refused frame took go back to the pool
+static int device_film(dtof_scene *sc, RenderRequest rq, const float *offsets, int n_offsets, const dtof_modulation *variants, int n_variants, float *d_film) {
+    return guarded([&] {
+        rq.offsets = offsets; rq.n_offsets = n_offsets; rq.film = d_film;
+        set_variants(rq, variants, n_variants);
+        if (!sc || !rq.film) throw std::runtime_error("null argument");
+        if (rq.stripes) {
+            if (rq.row_begin < 0 || rq.stripe_rows <= 0 || rq.stripe_period < rq.stripe_rows) throw std::runtime_error("invalid stripe layout");
+            rq.row_end = sc->host.sensor.crop_h;
+        }
+        sc->stop = false;
+        const std::pair<int32_t, int32_t> rows = rq.stripes ? stripe_span(sc, rq.row_begin, rq.stripe_rows, rq.stripe_period) : std::make_pair(rq.row_begin, rq.row_end);
+        rq.film_stride = caller_film_stride(sc, rq.films(), rows.first, rows.second);
+        dtof_render_stats local;
+        if (rq.deferred) rq.stats = &local;
+        try { render_rows(sc, rq); }
+        catch (...) { if (rq.deferred && sc->deferred.empty()) sc->events_used = 0; throw; }
+    });
+}
+
+// The library's own film, float32 or float64: the buffer it lives in, the fields of a request that name it, its develop launchers, and whether its host-buffer render
+// asks for the sensor before the first HIP call (the float64 one does; the float32 one leaves that to render_rows, behind ensure_device)
+template <typename T> struct OwnFilm;
+template <> struct OwnFilm<float> {
+    static constexpr bool sensor_first = false;
+    static DevBuf<float> &buf(dtof_scene *sc) { return sc->d_film; }
+    static void attach(RenderRequest &rq, float *film, uint64_t stride) { rq.film = film; rq.film_stride = stride; }
+    static void develop(const float *film, int k, float *rgb, int64_t px, hipStream_t s) { launch_develop(film, rgb, px * k, s); }
+    static void develop_rgba(const float *film, const float *alpha, float *rgba, int64_t px, hipStream_t s) { launch_develop_rgba(film, alpha, rgba, px, s); }
+    static void develop_accumulate(const float *film, int k, float *sum, int64_t px, bool first, hipStream_t s) { launch_develop_accumulate(film, k, 0, sum, px, first, s); }
+};
+template <> struct OwnFilm<double> {
+    static constexpr bool sensor_first = true;
+    static DevBuf<double> &buf(dtof_scene *sc) { return sc->d_film64; }
+    static void attach(RenderRequest &rq, double *film, uint64_t stride) { rq.film64 = film; rq.film64_stride = stride; }
+    static void develop(const double *film, int k, float *rgb, int64_t px, hipStream_t s) { launch_develop_f64(film, k, 0, rgb, px, s); }
+    static void develop_rgba(const double *film, const double *alpha, float *rgba, int64_t px, hipStream_t s) { launch_develop_rgba_f64(film, alpha, rgba, px, s); }
+    static void develop_accumulate(const double *film, int k, float *sum, int64_t px, bool first, hipStream_t s) { launch_develop_accumulate_f64(film, k, 0, sum, px, first, s); }
+};
+
+// The host-buffer renders (dtof_render_offsets / _variants / _variants_f64): the library's own film of rq.films() colour planes (and the alpha plane), developed into
+// out_rgb; out_films: the raw film planes as well, or null
+template <typename T> static void render_host_films(dtof_scene *sc, RenderRequest rq, float *out_rgb, T *out_films = nullptr) {
+    using F = OwnFilm<T>;
+    if (!sc || !out_rgb) throw std::runtime_error("null argument");
+    need_doppler_for(sc, rq.n_variants > 0);   // before the film is cleared
+    if (F::sensor_first) need_sensor(sc);
+    ensure_device(sc);
+    sc->stop = false;
+    const int k = rq.films();
+    const HostSensor &se = sc->host.sensor;
+    const size_t px = (size_t) se.crop_w * se.crop_h;
+    const int planes = k + (se.alpha ? 1 : 0), ch = se.alpha ? 4 : 3;   // rgba: one more film plane for the alpha channel, four channels out
+    F::buf(sc).ensure(px * 4 * planes); sc->d_rgb.ensure(px * ch * k);
+    T *const film = F::buf(sc).p;
+    HIP_CHECK(hipMemsetAsync(film, 0, px * 4 * planes * sizeof(T), sc->stream));
+    rq.row_begin = 0; rq.row_end = se.crop_h;
+    F::attach(rq, film, px * 4);
+    render_rows(sc, rq);
+    if (se.alpha) for (int i = 0; i < k; ++i) F::develop_rgba(film + px * 4 * i, film + px * 4 * k, sc->d_rgb.p + px * 4 * i, (int64_t) px, sc->stream);
+    else F::develop(film, k, sc->d_rgb.p, (int64_t) px, sc->stream);
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipMemcpyAsync(out_rgb, sc->d_rgb.p, px * ch * k * sizeof(float), hipMemcpyDeviceToHost, sc->stream));
+    if (out_films) HIP_CHECK(hipMemcpyAsync(out_films, film, px * 4 * planes * sizeof(T), hipMemcpyDeviceToHost, sc->stream));
+    HIP_CHECK(hipStreamSynchronize(sc->stream));
+}
+
+extern "C" {
+
+int dtof_render_rows(dtof_scene *sc, uint32_t seed, uint32_t spp, int32_t row_begin, int32_t row_end,
+                     const float *offsets, int n_offsets, float *d_film, dtof_render_stats *stats) {
+    return device_film(sc, rows_request(seed, spp, row_begin, row_end, stats), offsets, n_offsets, nullptr, 0, d_film);
+}
+int dtof_render_rows_async(dtof_scene *sc, uint32_t seed, uint32_t spp, int32_t row_begin, int32_t row_end, const float *offsets, int n_offsets, float *d_film) {
+    return device_film(sc, rows_request(seed, spp, row_begin, row_end, nullptr, true), offsets, n_offsets, nullptr, 0, d_film);
+}
+int dtof_render_stripes(dtof_scene *sc, uint32_t seed, uint32_t spp, int32_t first_row, int32_t stripe_rows, int32_t stripe_period,
+                        const float *offsets, int n_offsets, float *d_film, dtof_render_stats *stats) {
+    return device_film(sc, stripes_request(seed, spp, first_row, stripe_rows, stripe_period, stats), offsets, n_offsets, nullptr, 0, d_film);
+}
+int dtof_render_stripes_async(dtof_scene *sc, uint32_t seed, uint32_t spp, int32_t first_row, int32_t stripe_rows, int32_t stripe_period,
+                              const float *offsets, int n_offsets, float *d_film) {
+    return device_film(sc, stripes_request(seed, spp, first_row, stripe_rows, stripe_period, nullptr, true), offsets, n_offsets, nullptr, 0, d_film);
+}
+int dtof_render_rows_variants(dtof_scene *sc, uint32_t seed, uint32_t spp, int32_t row_begin, int32_t row_end,
+                              const dtof_modulation *variants, int n_variants, float *d_film, dtof_render_stats *stats) {
+    return device_film(sc, rows_request(seed, spp, row_begin, row_end, stats), nullptr, 0, variants, n_variants, d_film);
+}
+int dtof_render_rows_variants_async(dtof_scene *sc, uint32_t seed, uint32_t spp, int32_t row_begin, int32_t row_end,
+                                    const dtof_modulation *variants, int n_variants, float *d_film) {
+    return device_film(sc, rows_request(seed, spp, row_begin, row_end, nullptr, true), nullptr, 0, variants, n_variants, d_film);
+}
+int dtof_render_stripes_variants(dtof_scene *sc, uint32_t seed, uint32_t spp, int32_t first_row, int32_t stripe_rows, int32_t stripe_period,
+                                 const dtof_modulation *variants, int n_variants, float *d_film, dtof_render_stats *stats) {
+    return device_film(sc, stripes_request(seed, spp, first_row, stripe_rows, stripe_period, stats), nullptr, 0, variants, n_variants, d_film);
+}
+int dtof_render_stripes_variants_async(dtof_scene *sc, uint32_t seed, uint32_t spp, int32_t first_row, int32_t stripe_rows, int32_t stripe_period,
+                                       const dtof_modulation *variants, int n_variants, float *d_film) {
+    return device_film(sc, stripes_request(seed, spp, first_row, stripe_rows, stripe_period, nullptr, true), nullptr, 0, variants, n_variants, d_film);
+}
+
+int dtof_render_offsets(dtof_scene *sc, uint32_t seed, uint32_t spp, const float *offsets, int n_offsets, float *out_rgb, dtof_render_stats *stats) {
+    return guarded([&] { RenderRequest rq = rows_request(seed, spp, 0, 0, stats); rq.offsets = offsets; rq.n_offsets = n_offsets; render_host_films<float>(sc, rq, out_rgb); });
+}
+int dtof_render_variants(dtof_scene *sc, uint32_t seed, uint32_t spp, const dtof_modulation *variants, int n_variants, float *out_rgb, dtof_render_stats *stats) {
+    return guarded([&] { RenderRequest rq = rows_request(seed, spp, 0, 0, stats); set_variants(rq, variants, n_variants); render_host_films<float>(sc, rq, out_rgb); });
+}
+int dtof_render_variants_f64(dtof_scene *sc, uint32_t seed, uint32_t spp, const dtof_modulation *variants, int n_variants, float *out_images, double *out_films,
+                             dtof_render_stats *stats) {
+    return guarded([&] { RenderRequest rq = rows_request(seed, spp, 0, 0, stats); set_variants(rq, variants, n_variants); render_host_films<double>(sc, rq, out_images, out_films); });
+}
+int dtof_render(dtof_scene *sc, uint32_t sensor_index, uint32_t seed, uint32_t spp, float *out_rgb, dtof_render_stats *stats) {
+    if (sensor_index != 0) { g_last_error = "Scene::render(): sensor index " + std::to_string(sensor_index) + " is out of bounds!"; return DTOF_ERR_INVALID; }
+    return dtof_render_offsets(sc, seed, spp, nullptr, 0, out_rgb, stats);
+}
+
+int dtof_clear_async(dtof_scene *sc, void *d_ptr, size_t bytes) {
+    return guarded([&] {
+        if (!sc || !d_ptr) throw std::runtime_error("null argument");
+        ensure_device(sc);
+        HIP_CHECK(hipMemsetAsync(d_ptr, 0, bytes, sc->stream));
+    });
+}
+int dtof_develop_async(dtof_scene *sc, const float *d_film, float *d_rgb, int64_t n_pixels) {
+    return guarded([&] {
+        if (!sc || !d_film || !d_rgb) throw std::runtime_error("null argument");
+        ensure_device(sc);
+        launch_develop(d_film, d_rgb, n_pixels, sc->stream);
+        HIP_CHECK(hipGetLastError());
+    });
+}
+// one finished deferred frame added to a statistics block (its stream has been waited for); returns the frame's duration
+static float add_deferred_frame(dtof_render_stats *sum, const dtof_scene::DeferredFrame &f) {
+    float t = 0; HIP_CHECK(hipEventElapsedTime(&t, f.ev0, f.ev1));
+    sum->ms_total += t;
+    sum->ms_generate += stage_ms(f.ev[kStageGenerate]); sum->ms_trace += stage_ms(f.ev[kStageTrace]); sum->ms_first += stage_ms(f.ev[kStageFirst]);
+    sum->ms_shade += stage_ms(f.ev[kStageShade]) + stage_ms(f.ev[kStageFirst]); sum->ms_shadow += stage_ms(f.ev[kStageShadow]); sum->ms_splat += stage_ms(f.ev[kStageSplat]);
+    sum->n_paths += f.counters.n_paths; sum->n_batches += f.counters.n_batches;
+    sum->n_launches_trace += f.counters.n_launches_trace; sum->n_launches_shade += f.counters.n_launches_shade; sum->n_launches_shadow += f.counters.n_launches_shadow;
+    sum->n_launches_first += f.counters.n_launches_first; sum->n_inline_iterations += f.counters.n_inline_iterations; sum->n_fused_splat_launches += f.counters.n_fused_splat_launches; sum->n_plan_facts_launches += f.counters.n_plan_facts_launches;
+    return t;
+}
+int dtof_async_collect(dtof_scene *sc, dtof_render_stats *sum, double *frame_ms, uint32_t capacity, uint32_t *n_frames) {
+    return guarded([&] {
+        if (!sc || !sum || !n_frames) throw std::runtime_error("null argument");
+        ensure_device(sc);
+        HIP_CHECK(hipStreamSynchronize(sc->stream));
+        memset(sum, 0, sizeof *sum);
+        *n_frames = (uint32_t) sc->deferred.size();
+        uint32_t i = 0;
+        for (auto &f : sc->deferred) {
+            const float t = add_deferred_frame(sum, f);
+            if (frame_ms && i < capacity) frame_ms[i] = t;
+            ++i;
+        }
+        sc->deferred.clear(); sc->events_used = 0;
+    });
+}
+
+// ---------------------------------------------------------------- radial-velocity map (dtof_reconstruct.hip)
+// The checks the three entries share, made before a device is touched: a refused call enqueues and writes nothing.
+static void check_velocity_scalars(uint32_t n_passes, double exposure_time, double w_g_mhz) {
+    if (n_passes == 0) throw std::runtime_error("n_passes must be at least 1");
+    if (!std::isfinite(exposure_time) || !(exposure_time > 0)) throw std::runtime_error("exposure_time must be finite and > 0");
+    if (!std::isfinite(w_g_mhz) || !(w_g_mhz > 0)) throw std::runtime_error("w_g_mhz must be finite and > 0");
+}
+static void check_grid(int64_t n_pixels) {   // one lane per pixel in blocks of 256: the block count is a 32-bit grid dimension
+    if (n_pixels < 0) throw std::runtime_error("negative pixel count");
+    if (n_pixels > (int64_t) 0x7fffffff * 256) throw std::runtime_error("too many pixels for one launch");
+}
+static VelocityMapArgs velocity_args(int n_pairs, const int32_t *hom, const int32_t *het, uint32_t n_passes, double exposure_time, double w_g_mhz) {
+    VelocityMapArgs a; memset(&a, 0, sizeof a);
+    a.n_pairs = n_pairs;
+    for (int k = 0; k < n_pairs; ++k) {
+        if (hom[k] < 0 || hom[k] >= 2 * n_pairs || het[k] < 0 || het[k] >= 2 * n_pairs)
+            throw std::runtime_error("pair " + std::to_string(k) + ": plane index outside the " + std::to_string(2 * n_pairs) + " planes of the sum");
+        a.hom[k] = hom[k]; a.het[k] = het[k];
+    }
+    a.n_passes = (float) n_passes; a.exposure_time = (float) exposure_time;
+    a.inv_time = 1.0 / exposure_time; a.w_g_hz = w_g_mhz * 1e6; a.conf_floor = 1e-5 * 0.0015;   // in double, once, as Python forms them
+    return a;
+}
+
+int dtof_develop_accumulate_async(dtof_scene *sc, const float *d_film, int32_t planes, uint64_t plane_stride_floats, float *d_rgb_sum, int64_t n_pixels, int first) {
+    return guarded([&] {
+        if (!sc || !d_film || !d_rgb_sum) throw std::runtime_error("null argument");
+        if (planes < 1 || planes > 65535) throw std::runtime_error("the film must have between 1 and 65535 planes");
+        check_grid(n_pixels);
+        check_plane_stride(plane_stride_floats, (uint64_t) n_pixels * 4, "floats", "n_pixels * 4");
+        if ((uintptr_t) d_film % 16 != 0 || (uintptr_t) d_rgb_sum % 4 != 0) throw std::runtime_error("the film must be 16-byte aligned, the sum 4-byte aligned");
+        ensure_device(sc);
+        launch_develop_accumulate(d_film, planes, plane_stride_floats, d_rgb_sum, n_pixels, first != 0, sc->stream);
+        HIP_CHECK(hipGetLastError());
+    });
+}
+int dtof_velocity_map_async(dtof_scene *sc, const float *d_rgb_sum, int n_pairs, const int32_t *homodyne_planes, const int32_t *heterodyne_planes, uint32_t n_passes,
+                            double exposure_time, double w_g_mhz, int64_t n_pixels, float *d_tof, double *d_velocity_pairs, double *d_velocity) {
+    return guarded([&] {
+        if (!sc || !d_rgb_sum || !homodyne_planes || !heterodyne_planes || !d_velocity) throw std::runtime_error("null argument");
+        if (n_pairs < 1 || n_pairs > kMaxVelocityPairs) throw std::runtime_error("between 1 and 16 (homodyne, heterodyne) pairs can be combined");
+        check_velocity_scalars(n_passes, exposure_time, w_g_mhz);
+        check_grid(n_pixels);
+        if ((uintptr_t) d_rgb_sum % 4 != 0 || (uintptr_t) d_tof % 4 != 0 || (uintptr_t) d_velocity_pairs % 8 != 0 || (uintptr_t) d_velocity % 8 != 0)
+            throw std::runtime_error("misaligned buffer");
+        const VelocityMapArgs a = velocity_args(n_pairs, homodyne_planes, heterodyne_planes, n_passes, exposure_time, w_g_mhz);
+        ensure_device(sc);
+        launch_velocity_map(d_rgb_sum, a, n_pixels, d_tof, d_velocity_pairs, d_velocity, sc->stream);
+        HIP_CHECK(hipGetLastError());
+    });
+}
+int dtof_velocity_map_variants(const float *offsets, int n_offsets, dtof_modulation *out_variants) {
+    return guarded([&] {
+        if (!offsets || !out_variants) throw std::runtime_error("null argument");
+        if (n_offsets < 1 || n_offsets > kMaxVelocityPairs) throw std::runtime_error("between 1 and 16 offsets make a velocity map");
+        for (int g = 0; g < n_offsets; g += 2) {   // a homodyne / heterodyne pair never straddles two traversals
+            const int n = std::min(2, n_offsets - g);
+            for (int j = 0; j < n; ++j) {
+                out_variants[2 * g + j] = dtof_modulation { 0.f, offsets[g + j] };
+                out_variants[2 * g + n + j] = dtof_modulation { 1.f, offsets[g + j] };
+            }
+        }
+    });
+}
+}  // extern "C"
+// dtof_render_velocity_map / _f64: the same loop over the library's own float32 or float64 film (double: k_splat_f64 and k_develop_accumulate_f64)
+template <typename T> static void velocity_map_render(dtof_scene *sc, uint32_t n_passes, uint32_t spp, const float *offsets, int n_offsets, double exposure_time, double w_g_mhz,
+                                                      double *out_velocity, double *out_velocity_pairs, float *out_tof, dtof_render_stats *stats) {
+    using F = OwnFilm<T>;
+    if (!sc || !offsets || !out_velocity) throw std::runtime_error("null argument");
+    if (n_offsets < 1 || n_offsets > kMaxVelocityPairs) throw std::runtime_error("between 1 and 16 offsets make a velocity map");
+    check_velocity_scalars(n_passes, exposure_time, w_g_mhz);
+    need_doppler_for(sc, true);
+    need_sensor(sc);
+    dtof_modulation variants[2 * kMaxVelocityPairs];
+    if (dtof_velocity_map_variants(offsets, n_offsets, variants) != DTOF_OK) throw std::runtime_error(g_last_error);
+    int32_t hom[kMaxVelocityPairs], het[kMaxVelocityPairs];   // offset j of group g = j / 2: its films lie behind the 4 * g planes of the full groups before it
+    for (int j = 0; j < n_offsets; ++j) {
+        const int g = j / 2, n = std::min(2, n_offsets - 2 * g);
+        hom[j] = 4 * g + j % 2; het[j] = 4 * g + n + j % 2;
+    }
+    const VelocityMapArgs a = velocity_args(n_offsets, hom, het, n_passes, exposure_time, w_g_mhz);
+    ensure_device(sc);
+    sc->stop = false;
+    const HostSensor &se = sc->host.sensor;
+    const size_t px = (size_t) se.crop_w * se.crop_h;
+    const int alpha = se.alpha ? 1 : 0;
+    F::buf(sc).ensure(px * 4 * (kMaxOffsets + alpha));   // the library's own film: the caller's declared layout is not consulted
+    T *const film = F::buf(sc).p;
+    sc->d_vm_sum.ensure(px * 3 * 2 * n_offsets); sc->d_vm_tof.ensure(px * 2 * n_offsets); sc->d_vm_maps.ensure(px * (n_offsets + 1));
+    const hipStream_t s = sc->stream;
+    const size_t first_frame = sc->deferred.size();   // frames the caller has not collected yet stay his
+    try {
+        for (int g = 0; g < n_offsets; g += 2) {
+            const int films = 2 * std::min(2, n_offsets - g);
+            for (uint32_t pass = 0; pass < n_passes; ++pass) {
+                HIP_CHECK(hipMemsetAsync(film, 0, px * 4 * (films + alpha) * sizeof(T), s));
+                dtof_render_stats frame;
+                RenderRequest rq = rows_request(pass, spp, 0, se.crop_h, &frame, true);
+                F::attach(rq, film, px * 4);
+                set_variants(rq, variants + 2 * g, films);
+                render_rows(sc, rq);
+                F::develop_accumulate(film, films, sc->d_vm_sum.p + px * 3 * 2 * g, (int64_t) px, pass == 0, s);   // the alpha plane behind them is left out
+            }
+        }
+        double *d_pairs = sc->d_vm_maps.p + px;
+        launch_velocity_map(sc->d_vm_sum.p, a, (int64_t) px, out_tof ? sc->d_vm_tof.p : nullptr, out_velocity_pairs ? d_pairs : nullptr, sc->d_vm_maps.p, s);
+        HIP_CHECK(hipGetLastError());
+        HIP_CHECK(hipMemcpyAsync(out_velocity, sc->d_vm_maps.p, px * sizeof(double), hipMemcpyDeviceToHost, s));
+        if (out_velocity_pairs) HIP_CHECK(hipMemcpyAsync(out_velocity_pairs, d_pairs, px * n_offsets * sizeof(double), hipMemcpyDeviceToHost, s));
+        if (out_tof) HIP_CHECK(hipMemcpyAsync(out_tof, sc->d_vm_tof.p, px * 2 * n_offsets * sizeof(float), hipMemcpyDeviceToHost, s));
+        HIP_CHECK(hipStreamSynchronize(s));
+        dtof_render_stats sum; memset(&sum, 0, sizeof sum);
+        for (size_t i = first_frame; i < sc->deferred.size(); ++i) add_deferred_frame(&sum, sc->deferred[i]);
+        if (stats) *stats = sum;
+    } catch (...) {   // the frames of this call leave the list either way (their events go back to the pool once no frame is in flight)
+        if (sc->deferred.size() > first_frame) { (void) hipStreamSynchronize(s); sc->deferred.resize(first_frame); }
+        if (sc->deferred.empty()) sc->events_used = 0;
+        throw;
+    }
+    sc->deferred.resize(first_frame);
+    if (sc->deferred.empty()) sc->events_used = 0;
+}
+extern "C" {
+int dtof_render_velocity_map(dtof_scene *sc, uint32_t n_passes, uint32_t spp, const float *offsets, int n_offsets, double exposure_time, double w_g_mhz,
+                             double *out_velocity, double *out_velocity_pairs, float *out_tof, dtof_render_stats *stats) {
+    return guarded([&] { velocity_map_render<float>(sc, n_passes, spp, offsets, n_offsets, exposure_time, w_g_mhz, out_velocity, out_velocity_pairs, out_tof, stats); });
+}
+
+// ---------------------------------------------------------------- float64 film (dtof_film64.hip)
+int dtof_render_velocity_map_f64(dtof_scene *sc, uint32_t n_passes, uint32_t spp, const float *offsets, int n_offsets, double exposure_time, double w_g_mhz,
+                                 double *out_velocity, double *out_velocity_pairs, float *out_tof, dtof_render_stats *stats) {
+    return guarded([&] { velocity_map_render<double>(sc, n_passes, spp, offsets, n_offsets, exposure_time, w_g_mhz, out_velocity, out_velocity_pairs, out_tof, stats); });
+}
+int dtof_render_rows_variants_f64(dtof_scene *sc, uint32_t seed, uint32_t spp, int32_t row_begin, int32_t row_end, const dtof_modulation *variants, int n_variants,
+                                  double *d_film, int32_t planes, uint64_t plane_stride_doubles, dtof_render_stats *stats) {
+    return guarded([&] {
+        if (!sc || !d_film) throw std::runtime_error("null argument");
+        RenderRequest rq = rows_request(seed, spp, row_begin, row_end, stats);
+        set_variants(rq, variants, n_variants);
+        need_doppler_for(sc, rq.n_variants > 0);
+        need_sensor(sc);
+        if ((uintptr_t) d_film % 8 != 0) throw std::runtime_error("the film must be 8-byte aligned");
+        const HostSensor &se = sc->host.sensor;
+        const int need = rq.films() + (se.alpha ? 1 : 0);   // the alpha film lies behind the colour films
+        if (planes < need) throw std::runtime_error("the device film has " + std::to_string(planes) + " planes, this call writes " + std::to_string(need));
+        check_plane_stride(plane_stride_doubles, (uint64_t) se.crop_w * 4, "doubles", "one film row");
+        if (need > 1) check_stride_reach(se, plane_stride_doubles, row_begin, row_end, "plane stride", "doubles");
+        rq.film64 = d_film; rq.film64_stride = plane_stride_doubles ? plane_stride_doubles : (uint64_t) se.crop_w * se.crop_h * 4;
+        sc->stop = false;
+        render_rows(sc, rq);
+    });
+}
+
+// ---------------------------------------------------------------- moment film (dtof_moments.hip)
+int dtof_moment_planes(int n_variants) { return n_variants < 0 || n_variants > kMaxOffsets ? -1 : moment_planes(std::max(n_variants, 1)); }
+static void add_stats(dtof_render_stats &sum, const dtof_render_stats &f) {
+    sum.n_paths += f.n_paths; sum.n_bounces += f.n_bounces; sum.n_shadow_rays += f.n_shadow_rays;
+    sum.ms_total += f.ms_total; sum.ms_generate += f.ms_generate; sum.ms_trace += f.ms_trace; sum.ms_shade += f.ms_shade; sum.ms_shadow += f.ms_shadow; sum.ms_splat += f.ms_splat;
+    sum.n_launches_trace += f.n_launches_trace; sum.n_launches_shade += f.n_launches_shade; sum.n_launches_shadow += f.n_launches_shadow; sum.n_batches += f.n_batches;
+    sum.n_launches_first += f.n_launches_first; sum.ms_first += f.ms_first; sum.n_inline_iterations += f.n_inline_iterations; sum.n_bounces_inline += f.n_bounces_inline;
+    sum.n_fused_splat_launches += f.n_fused_splat_launches; sum.n_plan_facts_launches += f.n_plan_facts_launches;
+}
+// dtof_render_moments / _aovs: n_passes frames (seeds rq.seed, + 1, ...) accumulated into the cell film, `planes` planes developed from it and copied out.  rq carries
+// what the call's passes render beside that (the variants); aov: the channel table of an aov call, whose film the cells become, or null for the moment film
+static void render_cells(dtof_scene *sc, RenderRequest rq, AovArgs *aov, uint32_t n_passes, int planes, int developed, double *out_planes, dtof_render_stats *stats) {
+    ensure_device(sc);
+    sc->stop = false;
+    const HostSensor &se = sc->host.sensor;
+    const size_t px = (size_t) se.crop_w * se.crop_h;
+    sc->d_moments.ensure(px * kMomentCell); sc->d_moment_planes.ensure(px * planes);
+    const hipStream_t s = sc->stream;
+    HIP_CHECK(hipMemsetAsync(sc->d_moments.p, 0, px * kMomentCell * sizeof(double), s));   // once: the raw sums of the passes add up
+    if (aov) { aov->film = sc->d_moments.p; rq.aov = aov; } else rq.moments = sc->d_moments.p;
+    rq.row_begin = 0; rq.row_end = se.crop_h;
+    dtof_render_stats sum, frame; memset(&sum, 0, sizeof sum);
+    rq.stats = &frame;
+    for (uint32_t pass = 0; pass < n_passes; ++pass, ++rq.seed) {
+        render_rows(sc, rq);
+        add_stats(sum, frame);
+    }
+    launch_develop_moments(sc->d_moments.p, planes, developed != 0, sc->d_moment_planes.p, (int64_t) px, s);
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipMemcpyAsync(out_planes, sc->d_moment_planes.p, px * planes * sizeof(double), hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipStreamSynchronize(s));
+    if (stats) *stats = sum;
+}
+int dtof_render_moments(dtof_scene *sc, uint32_t seed, uint32_t spp, uint32_t n_passes, const dtof_modulation *variants, int n_variants, int developed,
+                        double *out_planes, dtof_render_stats *stats) {
+    return guarded([&] {
+        if (!sc || !out_planes) throw std::runtime_error("null argument");
+        if (n_passes == 0) throw std::runtime_error("the moment film needs at least one pass");
+        if (n_variants < 0 || n_variants > kMaxOffsets) throw std::runtime_error("between 0 and 4 modulation variants make a moment film");
+        if (n_variants > 0 && !variants) throw std::runtime_error("null argument: n_variants > 0 without variants");
+        need_doppler_for(sc, n_variants > 0);
+        need_sensor(sc);
+        RenderRequest rq = rows_request(seed, spp, 0, 0);
+        set_variants(rq, variants, n_variants);
+        render_cells(sc, rq, nullptr, n_passes, moment_planes(std::max(n_variants, 1)), developed, out_planes, stats);
+    });
+}
+
+// ---------------------------------------------------------------- geometry channels of the `aov` integrator (dtof_aov.hip)
+int dtof_aov_parse(const char *spec, int32_t *types, int capacity, int *n_types, char *names_buf, size_t names_capacity, int *n_channels) {
+    return guarded([&] {
+        if (!spec) throw std::runtime_error("null argument");
+        std::vector<int32_t> t; std::vector<std::string> names;
+        parse_aovs(spec, t, names);
+        if (n_types) *n_types = (int) t.size();
+        if (n_channels) *n_channels = (int) names.size();
+        if (types) {
+            if (capacity < (int) t.size()) throw std::runtime_error("dtof_aov_parse: the spec has " + std::to_string(t.size()) + " types, the buffer holds " + std::to_string(std::max(capacity, 0)));
+            std::copy(t.begin(), t.end(), types);
+        }
+        if (names_buf) {
+            size_t need = 0; for (auto &n : names) need += n.size() + 1;
+            if (names_capacity < need) throw std::runtime_error("dtof_aov_parse: the channel names take " + std::to_string(need) + " bytes, the buffer holds " + std::to_string(names_capacity));
+            char *w = names_buf;
+            for (auto &n : names) { memcpy(w, n.c_str(), n.size() + 1); w += n.size() + 1; }
+        }
+    });
+}
+int dtof_scene_get_aovs(const dtof_scene *sc, char *buf, size_t capacity) {
+    return guarded([&] {
+        if (!sc || !buf) throw std::runtime_error("null argument");
+        if (capacity < sc->host.aovs.size() + 1) throw std::runtime_error("dtof_scene_get_aovs: the spec takes " + std::to_string(sc->host.aovs.size() + 1) + " bytes");
+        memcpy(buf, sc->host.aovs.c_str(), sc->host.aovs.size() + 1);
+    });
+}
+// the channel table of a call: everything a call can be refused for, before any device call
+static AovArgs aov_args(const dtof_scene *sc, const int32_t *types, int n_types) {
+    if (!types) throw std::runtime_error("null argument");
+    if (n_types < 1) throw std::runtime_error("No AOVs were specified!");
+    need_sensor(sc);
+    AovArgs a; a.film = nullptr; a.values = nullptr; a.n_channels = 0; a.slots[0] = a.slots[1] = a.slots[2] = 0;
+    for (int i = 0; i < n_types; ++i) {
+        if (types[i] < 0 || types[i] >= kAovTypes) throw std::runtime_error("AOV type " + std::to_string(types[i]) + " is not one of the DTOF_AOV_* constants");
+        for (int k = 0; k < kAovTypeChannels[types[i]]; ++k, ++a.n_channels) {
+            if (a.n_channels >= (uint32_t) kAovMaxChannels)
+                throw std::runtime_error("the aov film holds at most " + std::to_string(kAovMaxChannels) + " channels beside the weight (a pixel is a cell of 32 doubles)");
+            a.slots[a.n_channels / kAovSlotsPerWord] |= (uint64_t) (kAovTypeSlot[types[i]] + k) << (5u * (a.n_channels % kAovSlotsPerWord));
+        }
+    }
+    return a;
+}
+int dtof_render_aovs(dtof_scene *sc, uint32_t seed, uint32_t spp, uint32_t n_passes, const int32_t *types, int n_types, int developed, double *out_planes,
+                     dtof_render_stats *stats) {
+    return guarded([&] {
+        if (!sc || !out_planes) throw std::runtime_error("null argument");
+        if (n_passes == 0) throw std::runtime_error("the aov film needs at least one pass");
+        AovArgs a = aov_args(sc, types, n_types);
+        render_cells(sc, rows_request(seed, spp, 0, 0), &a, n_passes, 1 + (int) a.n_channels, developed, out_planes, stats);
+    });
+}
+int dtof_sample_aov_lanes(dtof_scene *sc, uint32_t seed, uint32_t spp, const int32_t *types, int n_types, uint64_t lane_begin, uint64_t n, float *out_lanes12,
+                          float *out_values) {
+    return guarded([&] {
+        if (!sc || !out_lanes12 || !out_values) throw std::runtime_error("null argument");
+        AovArgs a = aov_args(sc, types, n_types);
+        ensure_device(sc);
+        sc->stop = false;
+        if (n == 0) return;
+        // the scene integrator's lanes, for their rgb ...
+        std::vector<LaneDebug> lanes(n), own(n);
+        { RenderRequest rq; rq.seed = seed; rq.spp = spp; rq.lane_dump = own.data(); rq.dump_begin = lane_begin; rq.dump_n = n; render_rows(sc, rq); }
+        // ... and the aov kernel's: the sample position, time and camera ray are the ones it read
+        DevBuf<float> d_values; d_values.ensure((size_t) n * a.n_channels);
+        a.values = d_values.p;
+        { RenderRequest rq; rq.seed = seed; rq.spp = spp; rq.lane_dump = lanes.data(); rq.dump_begin = lane_begin; rq.dump_n = n; rq.aov = &a; render_rows(sc, rq); }
+        HIP_CHECK(hipMemcpy(out_values, d_values.p, (size_t) n * a.n_channels * sizeof(float), hipMemcpyDeviceToHost));
+        for (uint64_t i = 0; i < n; ++i) { memcpy(out_lanes12 + 12 * i, &lanes[i], 36); memcpy(out_lanes12 + 12 * i + 9, own[i].rgb, 12); }
+    });
+}
+
+int dtof_develop_f64_async(dtof_scene *sc, const double *d_film64, float *d_rgb, int64_t n_pixels) {
+    return guarded([&] {
+        if (!sc || !d_film64 || !d_rgb) throw std::runtime_error("null argument");
+        check_grid(n_pixels);
+        if ((uintptr_t) d_film64 % 8 != 0 || (uintptr_t) d_rgb % 4 != 0) throw std::runtime_error("the film must be 8-byte aligned, the image 4-byte aligned");
+        ensure_device(sc);
+        launch_develop_f64(d_film64, 1, 0, d_rgb, n_pixels, sc->stream);
+        HIP_CHECK(hipGetLastError());
+    });
+}
+int dtof_develop_rgba_f64_async(dtof_scene *sc, const double *d_film64, const double *d_alpha_film64, float *d_rgba, int64_t n_pixels) {
+    return guarded([&] {
+        if (!sc || !d_film64 || !d_alpha_film64 || !d_rgba) throw std::runtime_error("null argument");
+        check_grid(n_pixels);
+        if ((uintptr_t) d_film64 % 8 != 0 || (uintptr_t) d_alpha_film64 % 8 != 0 || (uintptr_t) d_rgba % 16 != 0)
+            throw std::runtime_error("the films must be 8-byte aligned, the image 16-byte aligned");
+        ensure_device(sc);
+        launch_develop_rgba_f64(d_film64, d_alpha_film64, d_rgba, n_pixels, sc->stream);
+        HIP_CHECK(hipGetLastError());
+    });
+}
+
+// ---------------------------------------------------------------- denoiser (dtof_denoise.hip)
+// every refusal of the two entries (denoise_check, dtof_denoise_args.h), before a device is touched
+static DenoiseArgs denoise_args(const float *colour, int n_planes, int32_t width, int32_t height, const double *variance, const float *normal, const float *position,
+                                const dtof_denoise_params *p, const double *out_colour, const double *out_variance) {
+    DenoiseBuffers b { colour, variance, normal, position, out_colour, out_variance };
+    DenoiseArgs a;
+    const std::string err = denoise_check(b, n_planes, width, height, p == nullptr, p ? p->levels : 0, p ? p->sigma_normal : 0.0, p ? p->sigma_position : 0.0,
+                                          p ? p->sigma_luminance : 0.0, &a);
+    if (!err.empty()) throw std::runtime_error("dtof_denoise: " + err);
+    return a;
+}
+int dtof_denoise_async(dtof_scene *sc, const float *d_colour, int n_planes, int32_t width, int32_t height, const double *d_variance, const float *d_normal,
+                       const float *d_position, const dtof_denoise_params *params, double *d_out_colour, double *d_out_variance) {
+    return guarded([&] {
+        if (!sc) throw std::runtime_error("null argument");
+        const DenoiseArgs a = denoise_args(d_colour, n_planes, width, height, d_variance, d_normal, d_position, params, d_out_colour, d_out_variance);
+        ensure_device(sc);
+        sc->d_denoise.ensure(denoise_scratch_doubles(a));
+        launch_denoise(a, d_colour, d_variance, d_normal, d_position, d_out_colour, d_out_variance, sc->d_denoise.p, sc->stream);
+        HIP_CHECK(hipGetLastError());
+    });
+}
+int dtof_denoise(const float *colour, int n_planes, int32_t width, int32_t height, const double *variance, const float *normal, const float *position,
+                 const dtof_denoise_params *params, double *out_colour, double *out_variance) {
+    return guarded([&] {
+        const DenoiseArgs a = denoise_args(colour, n_planes, width, height, variance, normal, position, params, out_colour, out_variance);
+        const size_t n = (size_t) width * height, k = (size_t) n_planes;
+        DevBuf<double> d_scratch; d_scratch.ensure(denoise_scratch_doubles(a));
+        round_trip({ { colour, k * n * 3 * sizeof(float) }, { variance, variance ? k * n * sizeof(double) : 0 }, { normal, normal ? n * 3 * sizeof(float) : 0 }, { position, position ? n * 3 * sizeof(float) : 0 } },
+                   { { out_colour, k * n * 3 * sizeof(double) }, { out_variance, out_variance ? k * n * sizeof(double) : 0 } }, [&](void *const *in, void *const *out) {
+            launch_denoise(a, (const float *) in[0], (const double *) in[1], (const float *) in[2], (const float *) in[3], (double *) out[0], (double *) out[1], d_scratch.p, nullptr);
+        });
+    });
+}
+
+int dtof_develop(const float *d_film, float *d_rgb, int64_t n_pixels) {
+    return guarded([&] {
+        if (!d_film || !d_rgb) throw std::runtime_error("null argument");
+        launch_develop(d_film, d_rgb, n_pixels, nullptr);
+        HIP_CHECK(hipGetLastError()); HIP_CHECK(hipStreamSynchronize(nullptr));
+    });
+}
+
+// the lane dumps: lanes [lane_begin, lane_begin + n) of rq's render into out (12 floats each) and valid, and with out_rgb the rgb of every film of theirs
+static void dump_lanes(dtof_scene *sc, RenderRequest rq, uint64_t lane_begin, uint64_t n, float *out, uint32_t *valid, float *out_rgb) {
+    static_assert(sizeof(LaneDebug) == 52, "LaneDebug is 13 floats");
+    sc->stop = false;
+    if (n == 0) return;
+    std::vector<LaneDebug> lanes(n);
+    std::vector<float4> planes(out_rgb ? (size_t) rq.films() * n : 0);
+    rq.lane_dump = lanes.data(); rq.dump_begin = lane_begin; rq.dump_n = n; rq.lane_planes = out_rgb ? planes.data() : nullptr;
+    render_rows(sc, rq);
+    for (uint64_t i = 0; i < n; ++i) { memcpy(out + 12 * i, &lanes[i], 48); if (valid) valid[i] = lanes[i].valid != 0.f ? 1u : 0u; }
+    for (size_t i = 0; i < planes.size(); ++i) { out_rgb[3 * i] = planes[i].x; out_rgb[3 * i + 1] = planes[i].y; out_rgb[3 * i + 2] = planes[i].z; }
+}
+int dtof_sample_lanes_valid(dtof_scene *sc, uint32_t seed, uint32_t spp, uint64_t lane_begin, uint64_t n, float *out, uint32_t *valid) {
+    return guarded([&] {
+        if (!sc || !out) throw std::runtime_error("null argument");
+        dump_lanes(sc, rows_request(seed, spp, 0, 0), lane_begin, n, out, valid, nullptr);
+    });
+}
+int dtof_sample_lanes_variants(dtof_scene *sc, uint32_t seed, uint32_t spp, const dtof_modulation *variants, int n_variants,
+                               uint64_t lane_begin, uint64_t n, float *out, uint32_t *valid, float *out_rgb) {
+    return guarded([&] {
+        if (!sc || !out || !out_rgb) throw std::runtime_error("null argument");
+        RenderRequest rq = rows_request(seed, spp, 0, 0);
+        set_variants(rq, variants, n_variants);
+        need_doppler_for(sc, rq.n_variants > 0);
+        dump_lanes(sc, rq, lane_begin, n, out, valid, out_rgb);
+    });
+}
+int dtof_sample_lanes(dtof_scene *sc, uint32_t seed, uint32_t spp, uint64_t lane_begin, uint64_t n, float *out) {
+    return dtof_sample_lanes_valid(sc, seed, spp, lane_begin, n, out, nullptr);
+}
+int dtof_develop_on_stream(const float *d_film, float *d_rgb, int64_t n_pixels, void *hip_stream) {
+    return guarded([&] {
+        if (!d_film || !d_rgb) throw std::runtime_error("null argument");
+        launch_develop(d_film, d_rgb, n_pixels, (hipStream_t) hip_stream);
+        HIP_CHECK(hipGetLastError());
+    });
+}
+int dtof_develop_rgba(const float *d_film, const float *d_alpha_film, float *d_rgba, int64_t n_pixels) {
+    return guarded([&] {
+        if (!d_film || !d_alpha_film || !d_rgba) throw std::runtime_error("null argument");
+        launch_develop_rgba(d_film, d_alpha_film, d_rgba, n_pixels, nullptr);
+        HIP_CHECK(hipGetLastError()); HIP_CHECK(hipStreamSynchronize(nullptr));
+    });
+}
+
+}  // extern "C"

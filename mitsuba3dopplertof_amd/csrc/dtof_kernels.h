@@ -1,5 +1,5 @@
 // dtof_kernels.h -- kernel parameter blocks and queue layout shared by the host
-// orchestration (dtof_render.hip) and the kernels (dtof_kernels.hip).
+// orchestration (dtof_render.hip, dtof_abi_*.hip through dtof_host.h) and the kernels (dtof_kernels.hip).
 #pragma once
 #include <stdint.h>
 #include <hip/hip_runtime.h>
@@ -322,7 +322,7 @@ inline ShadeLds resident_lds(const RenderParams &rp, const ResidentStage &st, ui
 uint32_t device_lds_limit();   // asked once per frame (plan_frame): hipDeviceAttributeMaxSharedMemoryPerBlock of the current device (160 KiB on gfx950), minus the kernels' static LDS
 uint32_t device_cu_count();    // ... and hipDeviceAttributeMultiprocessorCount
 
-// The launchers' development switches, read once per frame with the others (dtof_render.hip: read_switches, which lists them)
+// The launchers' development switches, read once per frame with the others (dtof_render.hip: plan_frame, which lists them)
 struct LaunchSwitches {
     int defer = 2;                              // DTOF_DEFER: ray kernels as a pair of launches (0 when the frame's workspace has no DEFER lists)
     bool trace8 = true, nodes16 = true, tlas_lds = true, stage = true;   // DTOF_TRACE8 / NODES16 / TLAS_LDS / STAGE

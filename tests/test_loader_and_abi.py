@@ -175,6 +175,23 @@ def test_capi_exports_every_declared_symbol(mi):
     assert b"dopplertofpath" in lib.dtof_version()
 
 
+def test_the_exported_dtof_symbols_are_exactly_the_declared_functions(mi):
+    """Both ways, from the symbol table: a function of include/dtof.h that a move between the library's translation units left `static` is missing here, and
+    nothing named dtof_* leaves the library undeclared.  The header does not declare the two traversal-counter entries of the DTOF_TRAVERSAL_STATS build
+    (tools and tests declare them where they use them): libdtof_stats.so exports the header's set and those two, libdtof.so the header's set alone."""
+    import subprocess
+    hdr = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "dtof.h")).read(), flags=re.S)
+    declared = set(re.findall(r"\b(dtof_[a-z0-9_]+)\s*\(", hdr))
+    assert len(declared) >= 28 and not any(n.startswith("dtof_debug_") for n in declared)
+    stats_only = {"dtof_debug_traversal_stats", "dtof_debug_traversal_stats_n"}
+    stats_lib = os.path.join(ROOT, "mitsuba3dopplertof_amd", "libdtof_stats.so")
+    assert os.path.exists(stats_lib), "libdtof_stats.so is not built (make -C mitsuba3dopplertof_amd/csrc stats; build() makes it)"
+    for path, expected in ((os.path.join(ROOT, "mitsuba3dopplertof_amd", "libdtof.so"), declared), (stats_lib, declared | stats_only)):
+        table = subprocess.run(["nm", "-D", "--defined-only", path], capture_output=True, text=True, check=True).stdout
+        exported = {m.group(1) for m in re.finditer(r"^[0-9a-f]+ T (dtof_\w+)$", table, re.M)}
+        assert exported == expected, (path, sorted(expected - exported), sorted(exported - expected))
+
+
 def test_plugin_shims_export_the_discovery_symbols(mi):
     """MI_EXPORT_PLUGIN's two extern "C" symbols with the reference's strings (dopplertofpath.cpp:330, correlated.cpp:195)."""
     for so, name, descr in [("dopplertofpath", b"DopplerToFPathIntegrator", b"Doppler ToF Path Tracer integrator"),
