@@ -493,6 +493,73 @@ int dtof_denoise_async(dtof_scene *scene, const float *d_colour, int n_planes, i
 int dtof_denoise(const float *colour, int n_planes, int32_t width, int32_t height, const double *variance_or_null, const float *normal_or_null,
                  const float *position_or_null, const dtof_denoise_params *params, double *out_colour, double *out_variance_or_null);
 
+/* ---------------------------------------------------------------- adaptive sampling (opt-in)
+ * A dense base pass, then further passes only over the pixels whose ESTIMATED error is still above a tolerance; the estimate comes from the moment film of the passes so
+ * far.  The reference renders every pixel in every pass (render_multi_pass, doppler_tutorials/src/program_runner.py:11-31); this has no counterpart there.
+ * PIXEL LISTS.  A list is n strictly ascending flat indices y * crop_width + x of the crop window.  A render over a list evaluates, for every listed pixel, exactly the
+ * lanes pixel * spp + sample of the dense render with the same seed (a lane's streams are functions of the seed and that index alone, src/render/sampler.cpp:115-134,
+ * src/samplers/correlated.cpp:38-64), and splats them like the dense render: the films of the FULL list are the dense films.  A list takes the float64 film and the moment
+ * film only, and one pass per render: an integrator whose samples_per_pass is below the sample count is refused.
+ * SELECTION, all in double without fused multiply-add, in exactly this order.  S = the P(K) raw moment sums of the pixel (see the moment film), count = the samples
+ * rendered IN the pixel so far, max(x, y) = (x >= y || x is NaN) ? x : y:
+ *   per variant k   Wd = (S[0] == 0 ? 1 : S[0]); mean_k = S[1 + 6 k + 1] / Wd; m2_k = S[1 + 6 k + 4] / Wd; var_k = m2_k - mean_k * mean_k; n = (double) count
+ *   image mode      se_k = sqrt(max(var_k, 0) / n); metric = max over k of se_k / max(|mean_k|, floor); selected iff metric > tol; count == 0: metric 0, not selected
+ *   velocity mode   per pair (h, t) of a homodyne and a heterodyne variant, the delta method on the ratio the velocity map is made of
+ *                   (doppler_tutorials/src/utils/image_utils.py:140-199): a = mean_h, b = mean_t, cov = S[cross(h, t)] / Wd - a * b, r = b / a,
+ *                   var_r = ((var_t - (2 r) cov) + (r r) var_h) / ((a a) n), slope = ((0.5 * 3e8) / (w_g_mhz * 1e6)) / (exposure_time * ((r - 1) * (r - 1))),
+ *                   se = sqrt(max(var_r, 0)) * slope.  The pair is valid iff a != 0 && r > -1 && r < 0.999 (the open clip interval of the map).  A valid pair with a
+ *                   finite se selects the pixel iff se > tol; any other pair selects it iff var_h > 0 || var_t > 0 (no usable estimate, but something varies).  The pixel
+ *                   is selected if any pair selects it; metric = the largest finite se over the valid pairs, NaN if there is none.
+ * The list of the selected pixels is ascending (wave ballots, block counts, a scan in launches of its own, a scatter: no kernel waits on another block), so a run is
+ * reproducible.  count is raised by spp for the selected pixels.
+ * BIAS.  Selecting by an estimated variance makes the estimator slightly biased: a pixel whose samples happen to look converged stops early and keeps its chance value.
+ * base_passes and spp bound the effect (the estimate that stops a pixel rests on at least base_passes * spp samples).  With a filter wider than the box a pixel's sums hold
+ * its neighbours' samples too, so count is the NOMINAL sample count, as with the moment film's statistics. */
+#define DTOF_ADAPTIVE_IMAGE    0
+#define DTOF_ADAPTIVE_VELOCITY 1
+typedef struct {
+    int32_t mode;                        /* DTOF_ADAPTIVE_IMAGE | DTOF_ADAPTIVE_VELOCITY */
+    int32_t n_pairs;                     /* velocity mode: 1 or 2 pairs */
+    int32_t homodyne[2], heterodyne[2];  /* ... variant indices of every pair, homodyne[i] != heterodyne[i] */
+    double  tol;                         /* not NaN; +inf selects nothing in image mode */
+    double  floor;                       /* image mode: not NaN, >= 0 */
+    double  exposure_time, w_g_mhz;      /* velocity mode: finite and > 0 (the doubles of dtof_velocity_map_async) */
+} dtof_adaptive_params;
+/* The selection over HOST arrays (no scene): planes[P(n_variants)][n_pixels] RAW moment sums (dtof_render_moments with developed == 0), count[n_pixels] read and updated,
+ * out_pixels[n_pixels] the ascending list (its first *out_n entries are written), out_metric_or_null[n_pixels].  One upload, the launches, one download.
+ * DTOF_ERR_INVALID before any device call: a null argument, n_variants outside 1 .. 4, n_pixels < 0 or > 2^24, spp == 0, an unknown mode, a NaN tol, a floor that is NaN or
+ * negative (image), n_pairs outside 1 .. 2, a variant index outside the variants, homodyne == heterodyne, an exposure_time or w_g_mhz that is not finite and > 0
+ * (velocity).  Without a device: DTOF_ERR_HIP. */
+int dtof_adaptive_select(const double *planes, int64_t n_pixels, int n_variants, const dtof_adaptive_params *params, uint32_t spp, uint32_t *count,
+                         uint32_t *out_pixels, uint32_t *out_n, double *out_metric_or_null);
+/* ONE traversal of the listed pixels (a HOST list), region-of-interest rendering in its own right: out_moments_or_null receives the P(n_variants) moment planes of
+ * crop_height * crop_width doubles (developed != 0: divided by the weight as in dtof_render_moments), out_films_or_null the raw float64 film planes (n_variants, + 1 for an
+ * rgba scene: the alpha film, which the moment planes never hold) of crop_height * crop_width * 4 doubles; at least one of the two.  Pixels outside every listed footprint
+ * stay 0.  n_pixels == 0 launches nothing.  DTOF_ERR_INVALID before any device call: null arguments, both outputs null, a list that is not strictly ascending or leaves
+ * the crop window, the variants refusals of dtof_render_moments, samples_per_pass below the sample count. */
+int dtof_render_pixels(dtof_scene *scene, uint32_t seed, uint32_t spp, const uint32_t *pixels, uint32_t n_pixels, const dtof_modulation *variants_or_null, int n_variants,
+                       int developed, double *out_moments_or_null, double *out_films_or_null, dtof_render_stats *stats);
+/* dtof_sample_lanes_variants over a list: the records of all n_pixels * spp lanes of the listed pixels, pixel by pixel -- record i * spp + j is lane pixels[i] * spp + j
+ * of the dense render.  out_lanes12[n_pixels * spp][12], out_valid_or_null[n_pixels * spp], out_rgb_or_null[max(n_variants, 1)][n_pixels * spp][3]. */
+int dtof_sample_lanes_pixels(dtof_scene *scene, uint32_t seed, uint32_t spp, const uint32_t *pixels, uint32_t n_pixels, const dtof_modulation *variants_or_null,
+                             int n_variants, float *out_lanes12, uint32_t *out_valid_or_null, float *out_rgb_or_null);
+/* The adaptive loop.  Passes 0 .. base_passes - 1 are dense, with seeds seed + pass.  Every later pass p < max_passes selects from the cells so far (count = spp * the
+ * passes that rendered the pixel); an empty list ends the loop, otherwise the list is rendered with seed + p.  All passes accumulate into ONE moment film and ONE float64
+ * film (both splatted from the same traversal).  The host reads 4 bytes per sparse pass: the list's length.
+ *   out_moments_or_null  P(n_variants) planes, raw or developed as in dtof_render_moments
+ *   out_images_or_null   max(n_variants, 1) float32 images developed from the float64 film (rgb, or rgba for an rgba scene) as dtof_render_variants_f64 develops them
+ *   out_films_or_null    the raw float64 film, max(n_variants, 1) (+ 1 for rgba) planes of crop_height * crop_width * 4 doubles
+ *   out_count            [crop_height * crop_width] samples rendered in every pixel
+ *   out_metric_or_null   [crop_height * crop_width] the metric of the final cells and counts
+ *   out_pass_pixels      [max_passes] pixels every pass rendered (a dense pass: all of them; passes that did not run: 0); *out_n_passes: the passes that ran
+ *   out_lists_or_null    the lists of the sparse passes one behind the other, at most lists_capacity entries (what does not fit is not written; the lengths tell)
+ * `stats` (may be NULL) sums the passes.  DTOF_ERR_INVALID before any device call: null arguments, base_passes == 0, max_passes < base_passes, the refusals of
+ * dtof_adaptive_select for `params` and of dtof_render_pixels for the scene and the variants.  Without a device: DTOF_ERR_HIP. */
+int dtof_render_adaptive(dtof_scene *scene, uint32_t seed, uint32_t spp, uint32_t base_passes, uint32_t max_passes, const dtof_modulation *variants_or_null,
+                         int n_variants, const dtof_adaptive_params *params, int developed, double *out_moments_or_null, float *out_images_or_null,
+                         double *out_films_or_null, uint32_t *out_count, double *out_metric_or_null, uint32_t *out_pass_pixels, uint32_t *out_n_passes,
+                         uint32_t *out_lists_or_null, uint64_t lists_capacity, dtof_render_stats *stats);
+
 /* Integrator::cancel / should_stop (include/mitsuba/render/integrator.h:96-109). */
 void dtof_cancel(dtof_scene *scene);
 /* First-bounce launches of this scene, since it was loaded, that ran a kernel compiled with the frame plan's constants (dtof_render_stats::n_plan_facts_launches): the

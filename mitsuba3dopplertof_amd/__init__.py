@@ -16,7 +16,8 @@ import os
 import numpy as np
 
 __all__ = ["load_file", "load_string", "load_dict", "Scene", "Integrator", "Sampler", "DtofError", "render",
-           "render_multi_pass", "to_tof_image", "lib_path", "ETimeSampling", "velocity_map_variants", "MOMENT_PLANES", "aov_channels", "AOV_TYPES", "Denoiser"]
+           "render_multi_pass", "to_tof_image", "lib_path", "ETimeSampling", "velocity_map_variants", "MOMENT_PLANES", "aov_channels", "AOV_TYPES", "Denoiser", "adaptive_select",
+           "ADAPTIVE_MODES"]
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB = None
@@ -177,7 +178,12 @@ def _lib():
                        ("dtof_render_aovs", [vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, C.c_int, C.c_int, vp, C.POINTER(_Stats)]),
                        ("dtof_sample_aov_lanes", [vp, C.c_uint32, C.c_uint32, vp, C.c_int, C.c_uint64, C.c_uint64, vp, vp]),
                        ("dtof_denoise_async", [vp, vp, C.c_int, C.c_int32, C.c_int32, vp, vp, vp, vp, vp, vp]),
-                       ("dtof_denoise", [vp, C.c_int, C.c_int32, C.c_int32, vp, vp, vp, vp, vp, vp])):
+                       ("dtof_denoise", [vp, C.c_int, C.c_int32, C.c_int32, vp, vp, vp, vp, vp, vp]),
+                       ("dtof_adaptive_select", [vp, C.c_int64, C.c_int, vp, C.c_uint32, vp, vp, vp, vp]),
+                       ("dtof_render_pixels", [vp, C.c_uint32, C.c_uint32, vp, C.c_uint32, vp, C.c_int, C.c_int, vp, vp, C.POINTER(_Stats)]),
+                       ("dtof_sample_lanes_pixels", [vp, C.c_uint32, C.c_uint32, vp, C.c_uint32, vp, C.c_int, vp, vp, vp]),
+                       ("dtof_render_adaptive", [vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, vp, C.c_int, vp, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, C.c_uint64,
+                                                 C.POINTER(_Stats)])):
         if hasattr(L, name):   # a DTOF_LIB build from before the variants (A/B timing against an older commit) loads; calling what it lacks still raises
             getattr(L, name).argtypes = args
     _LIB = L
@@ -272,6 +278,73 @@ def MOMENT_PLANES(n_variants=1):
 
 
 _MOMENT_PAIRS = ((0, 1), (0, 2), (0, 3), (1, 2), (1, 3), (2, 3))   # the order of the cross planes (dtof.h), restricted to k < K
+
+
+def _moment_dict(planes, k):
+    """the dict of Scene.render_moments from the (P(k), H, W) planes of the C ABI"""
+    h, w = planes.shape[1:]
+    per = planes[1:1 + 6 * k].reshape(k, 6, h, w)
+    cross = np.zeros((k, k, h, w), np.float64)
+    for a in range(k):
+        cross[a, a] = per[a, 4]
+    slot = 1 + 6 * k
+    for a, b in _MOMENT_PAIRS:
+        if b < k:
+            cross[a, b] = cross[b, a] = planes[slot]
+            slot += 1
+    return {"weight": planes[0].copy(), "mean": np.ascontiguousarray(np.moveaxis(per[:, 0:3], 1, -1)),
+            "m2": np.ascontiguousarray(np.moveaxis(per[:, 3:6], 1, -1)), "cross": cross}
+
+
+class _AdaptiveParams(C.Structure):   # dtof_adaptive_params
+    _fields_ = [("mode", C.c_int32), ("n_pairs", C.c_int32), ("homodyne", C.c_int32 * 2), ("heterodyne", C.c_int32 * 2),
+                ("tol", C.c_double), ("floor", C.c_double), ("exposure_time", C.c_double), ("w_g_mhz", C.c_double)]
+
+
+ADAPTIVE_MODES = ("image", "velocity")   # DTOF_ADAPTIVE_IMAGE, DTOF_ADAPTIVE_VELOCITY
+
+
+def _adaptive_params(mode, tol, floor, pairs, exposure_time, w_g):
+    if mode not in ADAPTIVE_MODES:
+        raise DtofError('adaptive mode must be "image" or "velocity", not %r' % (mode,))
+    p = _AdaptiveParams()
+    p.mode, p.tol, p.floor, p.exposure_time, p.w_g_mhz = ADAPTIVE_MODES.index(mode), float(tol), float(floor), float(exposure_time), float(w_g)
+    if mode == "velocity":
+        pairs = [(int(h), int(t)) for h, t in (pairs if pairs is not None else ())]
+        if not 1 <= len(pairs) <= 2:
+            raise DtofError("velocity mode takes 1 or 2 (homodyne, heterodyne) pairs of variant indices")
+        p.n_pairs = len(pairs)
+        for i, (h, t) in enumerate(pairs):
+            p.homodyne[i], p.heterodyne[i] = h, t
+    return p
+
+
+def adaptive_select(planes, count, spp, mode="image", tol=0.0, floor=1e-3, pairs=None, exposure_time=0.0015, w_g=30):
+    """The selection step of adaptive sampling over arrays (dtof_adaptive_select; include/dtof.h has the definition): `planes` (P(K), n) or (P(K), H, W) RAW moment
+    sums (Scene.render_moments(raw=True) stacked in plane order, or the planes of the C ABI), `count` the samples every pixel has had.  mode "image": relative standard
+    error of Y, max over the variants, against `tol` with the denominator floored at `floor`; mode "velocity": standard error of the velocity map of the (homodyne,
+    heterodyne) variant index `pairs`.  Returns (ascending flat indices of the selected pixels (uint32), metric map (n,) float64, updated count (n,) uint32: + spp where
+    selected)."""
+    pl = np.ascontiguousarray(planes, dtype=np.float64)
+    pl = pl.reshape(pl.shape[0], -1)
+    k = {MOMENT_PLANES(v): v for v in (1, 2, 3, 4)}.get(pl.shape[0])
+    if k is None:
+        raise DtofError("adaptive_select: %d planes are not the moment planes of 1 .. 4 variants (7, 14, 22, 31)" % pl.shape[0])
+    n = pl.shape[1]
+    cnt = np.array(count, dtype=np.uint32).reshape(-1)
+    if cnt.size != n:
+        raise DtofError("adaptive_select: count must hold one entry per pixel")
+    prm = _adaptive_params(mode, tol, floor, pairs, exposure_time, w_g)
+    out, out_n, metric = np.zeros(max(n, 1), np.uint32), C.c_uint32(0), np.zeros(max(n, 1), np.float64)
+    _check(_lib().dtof_adaptive_select(pl.ctypes.data, n, k, C.byref(prm), int(spp), cnt.ctypes.data, out.ctypes.data, C.byref(out_n), metric.ctypes.data))
+    return out[:out_n.value].copy(), metric[:n], cnt
+
+
+def _pixel_list(pixels):
+    p = np.ascontiguousarray(pixels, dtype=np.int64).reshape(-1)
+    if len(p) and (p.min() < 0 or p.max() > 0xffffffff):
+        raise DtofError("pixel list: indices must be flat indices y * width + x of the crop window")
+    return p.astype(np.uint32)
 
 
 AOV_TYPES = ("depth", "position", "uv", "geo_normal", "sh_normal", "dp_du", "dp_dv", "prim_index", "shape_index")   # the DTOF_AOV_* constants, in their order
@@ -758,6 +831,86 @@ class Scene:
         _check(_lib().dtof_sample_lanes_variants(self._h, seed, spp, None if var is None else var.ctypes.data, 0 if var is None else len(var),
                                                  lane_begin, n, out.ctypes.data, valid.ctypes.data, rgb.ctypes.data))
         return {"sample_pos": out[:, 0:2], "time": out[:, 2], "ray_o": out[:, 3:6], "ray_d": out[:, 6:9], "rgb": rgb, "valid": valid}
+
+    def _cell_variants(self, variants):
+        var = None if variants is None else _variant_array(variants)
+        if var is not None and not 1 <= len(var) <= MAX_VARIANTS:
+            raise DtofError("between 1 and 4 modulation variants make a moment film")
+        return var, 1 if var is None else len(var)
+
+    def sample_lanes_pixels(self, seed, spp, pixels, variants=None):
+        """sample_lanes_variants of every lane of the listed pixels (dtof_sample_lanes_pixels): `pixels` strictly ascending flat indices y * width + x; record
+        i * spp + j is global lane pixels[i] * spp + j of the dense render with this seed.  Same dict; `rgb` is (K, n, 3)."""
+        var, k = self._cell_variants(variants)
+        pix = _pixel_list(pixels)
+        n = len(pix) * (int(spp) if spp else self.info()["sample_count"])
+        out, valid, rgb = np.zeros((max(n, 1), 12), np.float32), np.zeros(max(n, 1), np.uint32), np.zeros((k, max(n, 1), 3), np.float32)
+        if n == 0:
+            rgb = np.zeros((k, 0, 3), np.float32)
+        _check(_lib().dtof_sample_lanes_pixels(self._h, int(seed), int(spp), pix.ctypes.data if len(pix) else None, len(pix), None if var is None else var.ctypes.data,
+                                               0 if var is None else k, out.ctypes.data, valid.ctypes.data, rgb.ctypes.data))
+        out, valid = out[:n], valid[:n]
+        return {"sample_pos": out[:, 0:2], "time": out[:, 2], "ray_o": out[:, 3:6], "ray_d": out[:, 6:9], "rgb": rgb, "valid": valid}
+
+    def render_pixels(self, pixels, seed=0, spp=0, variants=None, raw=False, films=False, moments=True):
+        """ONE traversal of the listed pixels only (dtof_render_pixels) -- region-of-interest rendering: the lanes of a listed pixel are those of the dense render with
+        this seed, so the full list gives the dense films.  Returns the dict of render_moments (raw=True: the undivided sums); with films=True also "film64"
+        (K, H, W, 4) float64 raw R, G, B, W sums (one more plane, the alpha film, for an rgba scene); moments=False: the float64 film alone.  Pixels outside every
+        listed footprint are 0."""
+        var, k = self._cell_variants(variants)
+        pix = _pixel_list(pixels)
+        w, h = self.size
+        alpha = 1 if self.info()["has_alpha"] else 0
+        planes = np.zeros((MOMENT_PLANES(k), h, w), np.float64) if moments else None
+        film = np.zeros((k + alpha, h, w, 4), np.float64) if films else None
+        st = _Stats()
+        _check(_lib().dtof_render_pixels(self._h, int(seed), int(spp), pix.ctypes.data if len(pix) else None, len(pix), None if var is None else var.ctypes.data,
+                                         0 if var is None else k, 0 if raw else 1, None if planes is None else planes.ctypes.data,
+                                         None if film is None else film.ctypes.data, C.byref(st)))
+        self.last_stats = st.as_dict()
+        out = _moment_dict(planes, k) if moments else {}
+        if films:
+            out["film64"] = film
+        return out
+
+    def render_adaptive(self, seed=0, spp=0, base_passes=1, max_passes=4, variants=None, mode="image", tol=0.05, floor=1e-3, pairs=None, exposure_time=0.0015, w_g=30,
+                        raw=False, films=False, lists=False):
+        """Adaptive sampling (dtof_render_adaptive; include/dtof.h has the definition): `base_passes` dense passes with seeds seed, seed + 1, ..., then up to
+        max_passes - base_passes passes that render only the pixels whose estimated error is still above `tol` -- mode "image": the relative standard error of Y,
+        the largest over the variants; mode "velocity": the standard error (m/s) of the velocity map of the (homodyne, heterodyne) variant index `pairs`.  All passes
+        accumulate into one moment film and one float64 film.  Returns a dict: the keys of render_moments (raw=True: undivided sums), "images" (K, H, W, 3 | 4)
+        float32 developed from the float64 film, "count" (H, W) uint32 samples rendered in every pixel, "metric" (H, W) float64 of the final state,
+        "pass_pixels" (pixels every pass that ran rendered); films=True: "film64"; lists=True: "lists", the pixel list of every sparse pass.
+        Selecting by an estimated variance biases the estimator slightly: pixels that look converged by chance stop early; base_passes and spp bound that.  With a
+        filter wider than the box, count is the nominal sample count (harness.moment_statistics)."""
+        var, k = self._cell_variants(variants)
+        prm = _adaptive_params(mode, tol, floor, pairs, exposure_time, w_g)
+        base_passes, max_passes = int(base_passes), int(max_passes)
+        if base_passes < 1 or max_passes < base_passes:
+            raise DtofError("render_adaptive: base_passes must be at least 1 and max_passes at least base_passes")
+        w, h = self.size
+        alpha = 1 if self.info()["has_alpha"] else 0
+        planes = np.zeros((MOMENT_PLANES(k), h, w), np.float64)
+        images = np.zeros((k, h, w, 3 + alpha), np.float32)
+        film = np.zeros((k + alpha, h, w, 4), np.float64) if films else None
+        count, metric = np.zeros((h, w), np.uint32), np.zeros((h, w), np.float64)
+        pass_pixels, n_passes = np.zeros(max_passes, np.uint32), C.c_uint32(0)
+        cap = (max_passes - base_passes) * w * h if lists else 0
+        flat = np.zeros(max(cap, 1), np.uint32)
+        st = _Stats()
+        _check(_lib().dtof_render_adaptive(self._h, int(seed), int(spp), base_passes, max_passes, None if var is None else var.ctypes.data, 0 if var is None else k,
+                                           C.byref(prm), 0 if raw else 1, planes.ctypes.data, images.ctypes.data, None if film is None else film.ctypes.data,
+                                           count.ctypes.data, metric.ctypes.data, pass_pixels.ctypes.data, C.byref(n_passes), flat.ctypes.data if lists else None, cap,
+                                           C.byref(st)))
+        self.last_stats = st.as_dict()
+        out = _moment_dict(planes, k)
+        out.update(images=images, count=count, metric=metric, pass_pixels=pass_pixels[:n_passes.value].copy())
+        if films:
+            out["film64"] = film
+        if lists:
+            ends = np.cumsum(pass_pixels[base_passes:n_passes.value].astype(np.int64))
+            out["lists"] = [flat[e - m:e].copy() for e, m in zip(ends, pass_pixels[base_passes:n_passes.value])]
+        return out
 
     def bsdf_eval(self, shape_index, queries, spec=-1, geometry=None):
         """BSDF::eval_pdf_sample of shape `shape_index` over an (n, 11) array of (wi, wo, sample1, sample2, uv) -> (n, 14): value[3], pdf, wo[3], pdf, eta, delta,

@@ -12,6 +12,9 @@ plugins this library implements:
     python -m mitsuba3dopplertof_amd scene.xml --denoise [--denoise-levels 5] [--denoise-sigma n,x,l] [--velocity-map 0,0.25] [--spp N] [-o out.exr|.npy]
         the image (or, with --velocity-map and two offsets, the velocity map) with the joint variance-guided a-trous denoiser behind the films (Denoiser): the
         denoised result goes to the output file, the noisy one to its _noisy sibling
+    python -m mitsuba3dopplertof_amd scene.xml --adaptive TOL [--adaptive-mode image|velocity] [--base-passes 1] [--max-passes 4] [--variants ...] [--velocity-map 0,0.25]
+        adaptive sampling (Scene.render_adaptive): dense base passes, then passes over the pixels whose estimated error is still above TOL -- the relative standard
+        error of the image, or with --adaptive-mode velocity and --velocity-map the standard error of the map in m/s; the count map goes to the output's _count sibling
     python -m torch.distributed.run --nproc-per-node G --master-addr 127.0.0.1 -m mitsuba3dopplertof_amd scene.xml ...
         one process per GPU: the pixel rows are sharded across the G ranks, rank 0 gathers and writes the image
 """
@@ -55,8 +58,78 @@ def parser():
     ap.add_argument("--denoise-levels", type=int, default=None, metavar="L", help="--denoise: a-trous levels, 1 .. 6 (default 5)")
     ap.add_argument("--denoise-sigma", default=None, metavar="N,X,L",
                     help="--denoise: sigma_normal,sigma_position,sigma_luminance (default 0.1, 1 %% of the scene's extent, 4)")
+    ap.add_argument("--adaptive", type=float, default=None, metavar="TOL",
+                    help="adaptive sampling: after the dense base passes, render only the pixels whose estimated error is still above TOL (slightly biased: pixels "
+                         "that look converged by chance stop early); the per-pixel sample counts are written next to the output (_count.npy)")
+    ap.add_argument("--adaptive-mode", default="image", choices=("image", "velocity"),
+                    help="--adaptive: TOL is a relative standard error of the image, or (with --velocity-map) the standard error of the velocity map in m/s")
+    ap.add_argument("--base-passes", type=int, default=1, help="--adaptive: dense passes before the first selection")
+    ap.add_argument("--max-passes", type=int, default=4, help="--adaptive: passes at most, the base passes included")
     ap.add_argument("-v", "--verbose", action="store_true")
     return ap
+
+
+def check_adaptive_args(ap, args):
+    """what --adaptive cannot be combined with, refused before the scene is loaded"""
+    if args.moments or args.aovs is not None or args.denoise:
+        ap.error("--adaptive renders an image or a velocity map: do not combine it with --moments, --aovs or --denoise")
+    if args.stripes > 0 or int(os.environ.get("WORLD_SIZE", "1")) > 1:
+        ap.error("--adaptive is a single-GPU feature: it cannot be combined with --stripes or a multi-GPU launch")
+    if args.offsets is not None:
+        ap.error("--adaptive takes --variants (hetero_frequency:hetero_offset pairs) or --velocity-map, not --offsets")
+    if not args.adaptive == args.adaptive or args.adaptive < 0:
+        ap.error("--adaptive expects a tolerance >= 0")
+    if args.base_passes < 1 or args.max_passes < args.base_passes:
+        ap.error("--base-passes must be at least 1 and --max-passes at least --base-passes")
+    if (args.adaptive_mode == "velocity") != (args.velocity_map is not None):
+        ap.error("--adaptive-mode velocity and --velocity-map go together: the tolerance of a velocity map is its standard error in m/s")
+    if args.velocity_map is not None:
+        if args.variants is not None:
+            ap.error("--adaptive with --velocity-map renders the map's own variants: --variants does not apply")
+        if not 1 <= len(args.velocity_map.split(",")) <= 2:
+            ap.error("--adaptive with --velocity-map takes one or two offsets: the films of one traversal")
+    elif args.variants is not None:
+        try:
+            n = len(parse_variants(args.variants))
+        except ValueError:
+            ap.error("--variants expects comma separated hetero_frequency:hetero_offset pairs")
+        if not 1 <= n <= 4:
+            ap.error("--variants takes between 1 and 4 pairs")
+
+
+def _count_sibling(path):
+    return os.path.splitext(path)[0] + "_count.npy"
+
+
+def adaptive(args, scene):
+    """--adaptive: Scene.render_adaptive (image mode: the images of the variants) or harness.velocity_map_adaptive (--velocity-map); the count map beside the output"""
+    from mitsuba3dopplertof_amd.io import write_image
+    t0 = time.time()
+    if args.velocity_map is not None:
+        from mitsuba3dopplertof_amd.harness import velocity_map_adaptive
+        out = args.output or os.path.splitext(args.scene)[0] + "_velocity.npy"
+        v, se, count = velocity_map_adaptive(scene, args.spp, args.max_passes, args.adaptive, [float(x) for x in args.velocity_map.split(",")],
+                                             base_passes=args.base_passes, exposure_time=args.exposure_time, w_g=args.w_g)
+        os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+        np.save(out, v)
+        np.save(os.path.splitext(out)[0] + "_stderr.npy", se)
+    else:
+        out = args.output or os.path.splitext(args.scene)[0] + ".exr"
+        variants = parse_variants(args.variants) if args.variants else None
+        r = scene.render_adaptive(seed=args.seed, spp=args.spp, base_passes=args.base_passes, max_passes=args.max_passes, variants=variants, mode="image", tol=args.adaptive)
+        count = r["count"]
+        os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+        if variants is None:
+            write_image(out, r["images"][0])
+        else:
+            base, ext = os.path.splitext(out)
+            for k in range(len(variants)):
+                write_image("%s_variant_%d%s" % (base, k, ext), r["images"][k])
+    np.save(_count_sibling(out), count)
+    if args.verbose:
+        print("Adaptive render finished. (took %.1f ms, samples per pixel %d .. %d, mean %.1f, %s)"
+              % ((time.time() - t0) * 1e3, count.min(), count.max(), count.mean(), scene.last_stats))
+    return 0
 
 
 def check_denoise_args(ap, args):
@@ -227,7 +300,7 @@ def main(argv=None):
         check_aovs_args(ap, args)
     elif args.moments:
         check_moments_args(ap, args)
-    elif args.variants is not None or args.passes != 1:
+    elif (args.variants is not None and args.adaptive is None) or args.passes != 1:
         ap.error("--variants and --passes belong to --moments")
     if args.velocity_map is not None:
         check_velocity_map_args(ap, args)
@@ -235,6 +308,10 @@ def main(argv=None):
         args.denoise_kw = check_denoise_args(ap, args)
     elif args.denoise_levels is not None or args.denoise_sigma is not None:
         ap.error("--denoise-levels and --denoise-sigma belong to --denoise")
+    if args.adaptive is not None:
+        check_adaptive_args(ap, args)
+    elif args.adaptive_mode != "image" or args.base_passes != 1 or args.max_passes != 4:
+        ap.error("--adaptive-mode, --base-passes and --max-passes belong to --adaptive")
     import mitsuba3dopplertof_amd as mi
     from mitsuba3dopplertof_amd.io import write_image
     defines = {}
@@ -245,6 +322,8 @@ def main(argv=None):
         defines[k] = v
     try:
         scene = mi.load_file(args.scene, **defines)
+        if args.adaptive is not None:
+            return adaptive(args, scene)
         if args.velocity_map is not None:
             return velocity_map(args, scene)
         if args.moments:

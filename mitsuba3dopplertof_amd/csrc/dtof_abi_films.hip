@@ -6,6 +6,7 @@
 #include "dtof_denoise.h"
 #include "dtof_film64.h"
 #include "dtof_moments.h"
+#include "dtof_adaptive.h"
 #include <cmath>
 
 using namespace dtof;
@@ -417,6 +418,206 @@ int dtof_render_moments(dtof_scene *sc, uint32_t seed, uint32_t spp, uint32_t n_
     });
 }
 
+// ---------------------------------------------------------------- adaptive sampling (dtof_adaptive.hip)
+// every refusal of `params` (dtof.h) before a device is touched, and the kernels' argument block for K variants; the caller sets the strides of its cells
+static AdaptiveArgs adaptive_args(const dtof_adaptive_params *p, int K, uint32_t spp) {
+    if (!p) throw std::runtime_error("null argument");
+    if (K < 1 || K > kMaxOffsets) throw std::runtime_error("dtof_adaptive: between 1 and 4 variants make a moment film");
+    if (spp == 0) throw std::runtime_error("dtof_adaptive: sample count must be positive");
+    if (p->tol != p->tol) throw std::runtime_error("dtof_adaptive: tol must not be NaN");
+    AdaptiveArgs a; memset(&a, 0, sizeof a);
+    a.mode = p->mode; a.n_variants = K; a.tol = p->tol; a.floor = p->floor; a.exposure_time = p->exposure_time; a.w_g_mhz = p->w_g_mhz; a.spp = spp;
+    if (p->mode == DTOF_ADAPTIVE_IMAGE) {
+        if (!(p->floor >= 0.0)) throw std::runtime_error("dtof_adaptive: floor must be >= 0 and not NaN");
+    } else if (p->mode == DTOF_ADAPTIVE_VELOCITY) {
+        if (p->n_pairs < 1 || p->n_pairs > kAdaptiveMaxPairs) throw std::runtime_error("dtof_adaptive: velocity mode takes 1 or 2 (homodyne, heterodyne) pairs");
+        a.n_pairs = p->n_pairs;
+        for (int i = 0; i < p->n_pairs; ++i) {
+            const int32_t h = p->homodyne[i], t = p->heterodyne[i];
+            if (h < 0 || h >= K || t < 0 || t >= K) throw std::runtime_error("dtof_adaptive: pair " + std::to_string(i) + " names a variant outside 0 .. " + std::to_string(K - 1));
+            if (h == t) throw std::runtime_error("dtof_adaptive: pair " + std::to_string(i) + " needs two different variants (homodyne == heterodyne)");
+            a.hom[i] = h; a.het[i] = t; a.cross[i] = adaptive_cross_plane(K, h, t);
+        }
+        if (!(std::isfinite(p->exposure_time) && p->exposure_time > 0.0) || !(std::isfinite(p->w_g_mhz) && p->w_g_mhz > 0.0))
+            throw std::runtime_error("dtof_adaptive: exposure_time and w_g_mhz must be finite and > 0");
+    } else throw std::runtime_error("dtof_adaptive: mode must be DTOF_ADAPTIVE_IMAGE or DTOF_ADAPTIVE_VELOCITY");
+    return a;
+}
+// a host pixel list: strictly ascending flat indices inside the crop window
+static void check_host_list(const dtof_scene *sc, const uint32_t *pixels, uint32_t n) {
+    if (n && !pixels) throw std::runtime_error("null argument: n_pixels > 0 without pixels");
+    const uint64_t px = (uint64_t) sc->host.sensor.crop_w * sc->host.sensor.crop_h;
+    for (uint32_t i = 0; i < n; ++i) {
+        if (pixels[i] >= px) throw std::runtime_error("pixel list: entry " + std::to_string(i) + " (" + std::to_string(pixels[i]) + ") lies outside the crop window of " + std::to_string(px) + " pixels");
+        if (i && pixels[i] <= pixels[i - 1]) throw std::runtime_error("pixel list: entry " + std::to_string(i) + " is not above the one before it (the list must be strictly ascending)");
+    }
+}
+static void check_variants_of_cells(const dtof_scene *sc, const dtof_modulation *variants, int n_variants) {
+    if (n_variants < 0 || n_variants > kMaxOffsets) throw std::runtime_error("between 0 and 4 modulation variants make a moment film");
+    if (n_variants > 0 && !variants) throw std::runtime_error("null argument: n_variants > 0 without variants");
+    need_doppler_for(sc, n_variants > 0);
+    need_sensor(sc);
+}
+// The list form's refusals for an entry that has no device buffers yet: the facts of the request it will send (pixel_list_refusal, dtof_pixel_list.h)
+static void check_list_entry(const dtof_scene *sc, uint32_t spp, uint32_t n_pixels, bool moments, bool film64, bool dump = false, uint64_t dump_n = 0) {
+    PixelListFacts f = pixel_list_facts(sc, spp, n_pixels);
+    f.moments = moments; f.film64 = film64; f.lane_dump = dump; f.dump_n = dump_n;
+    refuse_pixel_list(f);
+}
+// the words of sc->d_adaptive for a film of px pixels: count[px] | list[px] | the list's length (2 words) | the selection's scratch
+struct AdaptiveWords { uint32_t *count, *list, *n, *scratch; };
+static AdaptiveWords adaptive_words(dtof_scene *sc, size_t px) {
+    sc->d_adaptive.ensure(2 * px + 2 + adaptive_scratch_words((uint32_t) px));
+    uint32_t *w = sc->d_adaptive.p;
+    return { w, w + px, w + 2 * px, w + 2 * px + 2 };
+}
+// the cells and the float64 film of a call, zeroed; planes / fplanes: moment planes, film planes (the alpha film included)
+static void clear_cells_and_film(dtof_scene *sc, size_t px, bool cells, int planes, bool film, int fplanes) {
+    if (cells) { sc->d_moments.ensure(px * kMomentCell); sc->d_moment_planes.ensure(px * planes); HIP_CHECK(hipMemsetAsync(sc->d_moments.p, 0, px * kMomentCell * sizeof(double), sc->stream)); }
+    if (film) { sc->d_film64.ensure(px * 4 * fplanes); HIP_CHECK(hipMemsetAsync(sc->d_film64.p, 0, px * 4 * fplanes * sizeof(double), sc->stream)); }
+}
+
+int dtof_adaptive_select(const double *planes, int64_t n_pixels, int n_variants, const dtof_adaptive_params *params, uint32_t spp, uint32_t *count,
+                         uint32_t *out_pixels, uint32_t *out_n, double *out_metric) {
+    return guarded([&] {
+        if (!planes || !count || !out_pixels || !out_n) throw std::runtime_error("null argument");
+        if (n_pixels < 0 || n_pixels > (int64_t) kAdaptiveMaxPixels) throw std::runtime_error("dtof_adaptive_select: between 0 and 2^24 pixels");
+        AdaptiveArgs a = adaptive_args(params, n_variants, spp);
+        const size_t n = (size_t) n_pixels, P = (size_t) moment_planes(n_variants);
+        a.pixel_stride = 1; a.plane_stride = (int64_t) n;
+        DevBuf<double> d_planes, d_metric; DevBuf<uint32_t> d_words;   // count[n] | list[n] | length (2 words) | scratch
+        d_planes.ensure(std::max<size_t>(P * n, 1)); d_metric.ensure(std::max<size_t>(out_metric ? n : 0, 1));
+        d_words.ensure(2 * n + 2 + adaptive_scratch_words((uint32_t) n));
+        uint32_t *d_count = d_words.p, *d_list = d_words.p + n, *d_n = d_words.p + 2 * n;
+        if (n) { HIP_CHECK(hipMemcpy(d_planes.p, planes, P * n * sizeof(double), hipMemcpyHostToDevice)); HIP_CHECK(hipMemcpy(d_count, count, n * 4, hipMemcpyHostToDevice)); }
+        launch_adaptive_select(a, d_planes.p, (uint32_t) n, d_count, d_list, d_n, out_metric ? d_metric.p : nullptr, d_n + 2, nullptr);
+        HIP_CHECK(hipGetLastError());
+        uint32_t m = 0;
+        HIP_CHECK(hipMemcpy(&m, d_n, 4, hipMemcpyDeviceToHost));
+        if (m > n) throw HipError("dtof_adaptive_select: the device reported more selected pixels than there are");
+        if (m) HIP_CHECK(hipMemcpy(out_pixels, d_list, (size_t) m * 4, hipMemcpyDeviceToHost));
+        if (n) HIP_CHECK(hipMemcpy(count, d_count, n * 4, hipMemcpyDeviceToHost));
+        if (n && out_metric) HIP_CHECK(hipMemcpy(out_metric, d_metric.p, n * sizeof(double), hipMemcpyDeviceToHost));
+        *out_n = m;
+    });
+}
+int dtof_render_pixels(dtof_scene *sc, uint32_t seed, uint32_t spp, const uint32_t *pixels, uint32_t n_pixels, const dtof_modulation *variants, int n_variants,
+                       int developed, double *out_moments, double *out_films, dtof_render_stats *stats) {
+    return guarded([&] {
+        if (!sc || (!out_moments && !out_films)) throw std::runtime_error("null argument");
+        check_variants_of_cells(sc, variants, n_variants);
+        check_host_list(sc, pixels, n_pixels);
+        dtof_render_stats frame; memset(&frame, 0, sizeof frame);
+        RenderRequest rq = rows_request(seed, spp, 0, 0, &frame);
+        set_variants(rq, variants, n_variants);
+        check_list_entry(sc, spp, n_pixels, out_moments != nullptr, out_films != nullptr);
+        ensure_device(sc);
+        sc->stop = false;
+        const HostSensor &se = sc->host.sensor;
+        const size_t px = (size_t) se.crop_w * se.crop_h;
+        const int K = rq.films(), planes = moment_planes(K), fplanes = K + (se.alpha ? 1 : 0);
+        const hipStream_t s = sc->stream;
+        const AdaptiveWords w = adaptive_words(sc, px);
+        if (n_pixels) HIP_CHECK(hipMemcpyAsync(w.list, pixels, (size_t) n_pixels * 4, hipMemcpyHostToDevice, s));
+        clear_cells_and_film(sc, px, out_moments != nullptr, planes, out_films != nullptr, fplanes);
+        rq.pixels = w.list; rq.n_pixels = n_pixels;
+        rq.moments = out_moments ? sc->d_moments.p : nullptr;
+        if (out_films) { rq.film64 = sc->d_film64.p; rq.film64_stride = px * 4; }
+        render_rows(sc, rq);
+        if (out_moments) {
+            launch_develop_moments(sc->d_moments.p, planes, developed != 0, sc->d_moment_planes.p, (int64_t) px, s);
+            HIP_CHECK(hipGetLastError());
+            HIP_CHECK(hipMemcpyAsync(out_moments, sc->d_moment_planes.p, px * planes * sizeof(double), hipMemcpyDeviceToHost, s));
+        }
+        if (out_films) HIP_CHECK(hipMemcpyAsync(out_films, sc->d_film64.p, px * 4 * fplanes * sizeof(double), hipMemcpyDeviceToHost, s));
+        HIP_CHECK(hipStreamSynchronize(s));
+        if (stats) *stats = frame;
+    });
+}
+int dtof_render_adaptive(dtof_scene *sc, uint32_t seed, uint32_t spp, uint32_t base_passes, uint32_t max_passes, const dtof_modulation *variants, int n_variants,
+                         const dtof_adaptive_params *params, int developed, double *out_moments, float *out_images, double *out_films, uint32_t *out_count,
+                         double *out_metric, uint32_t *out_pass_pixels, uint32_t *out_n_passes, uint32_t *out_lists, uint64_t lists_capacity, dtof_render_stats *stats) {
+    return guarded([&] {
+        if (!sc || !params || !out_count || !out_pass_pixels || !out_n_passes) throw std::runtime_error("null argument");
+        if (base_passes == 0) throw std::runtime_error("dtof_render_adaptive: base_passes must be at least 1 (the selection needs the moments of a dense pass)");
+        if (max_passes < base_passes) throw std::runtime_error("dtof_render_adaptive: max_passes must be at least base_passes");
+        check_variants_of_cells(sc, variants, n_variants);
+        const uint32_t spp_each = spp ? spp : sc->pp.sample_count;
+        AdaptiveArgs a = adaptive_args(params, std::max(n_variants, 1), spp_each);
+        a.pixel_stride = kMomentCell; a.plane_stride = 1;
+        dtof_render_stats sum, frame; memset(&sum, 0, sizeof sum);
+        RenderRequest dense = rows_request(seed, spp, 0, 0, &frame);
+        set_variants(dense, variants, n_variants);
+        check_list_entry(sc, spp, 0, true, true);
+        const HostSensor &se = sc->host.sensor;
+        const size_t px = (size_t) se.crop_w * se.crop_h;
+        if (px > kAdaptiveMaxPixels) throw std::runtime_error("dtof_render_adaptive: the selection handles films of up to 2^24 pixels");
+        if ((uint64_t) spp_each * max_passes > 0xffffffffull) throw std::runtime_error("dtof_render_adaptive: spp * max_passes must fit 32 bits (the count map)");
+        ensure_device(sc);
+        sc->stop = false;
+        const int K = dense.films(), planes = moment_planes(K), fplanes = K + (se.alpha ? 1 : 0), ch = se.alpha ? 4 : 3;
+        const hipStream_t s = sc->stream;
+        const AdaptiveWords w = adaptive_words(sc, px);
+        sc->d_adaptive_metric.ensure(px);
+        clear_cells_and_film(sc, px, true, planes, true, fplanes);
+        dense.moments = sc->d_moments.p; dense.film64 = sc->d_film64.p; dense.film64_stride = px * 4;
+        for (uint32_t p = 0; p < max_passes; ++p) out_pass_pixels[p] = 0;
+        uint32_t pass = 0;
+        for (; pass < base_passes; ++pass) {   // the dense passes: every pixel, seeds seed + pass
+            RenderRequest rq = dense; rq.seed = seed + pass; rq.row_end = se.crop_h;
+            render_rows(sc, rq);
+            add_stats(sum, frame);
+            out_pass_pixels[pass] = (uint32_t) px;
+        }
+        {
+            const std::vector<uint32_t> filled(px, spp_each * base_passes);
+            HIP_CHECK(hipMemcpyAsync(w.count, filled.data(), px * 4, hipMemcpyHostToDevice, s));
+            HIP_CHECK(hipStreamSynchronize(s));   // (the vector goes out of scope)
+        }
+        uint64_t listed = 0;
+        for (; pass < max_passes; ++pass) {   // the sparse passes: select from the cells so far, read the list's length, render the list
+            launch_adaptive_select(a, sc->d_moments.p, (uint32_t) px, w.count, w.list, w.n, nullptr, w.scratch, s);
+            HIP_CHECK(hipGetLastError());
+            uint32_t m = 0;
+            HIP_CHECK(hipMemcpyAsync(&m, w.n, 4, hipMemcpyDeviceToHost, s));
+            HIP_CHECK(hipStreamSynchronize(s));
+            if (m > px) throw HipError("dtof_render_adaptive: the device reported more selected pixels than the film has");
+            if (m == 0) break;
+            if (out_lists && listed < lists_capacity)
+                HIP_CHECK(hipMemcpyAsync(out_lists + listed, w.list, (size_t) std::min<uint64_t>(m, lists_capacity - listed) * 4, hipMemcpyDeviceToHost, s));
+            listed += m;
+            RenderRequest rq = dense; rq.seed = seed + pass; rq.pixels = w.list; rq.n_pixels = m;
+            render_rows(sc, rq);   // (ends with a wait for the stream: the list may be overwritten by the next selection)
+            add_stats(sum, frame);
+            out_pass_pixels[pass] = m;
+        }
+        *out_n_passes = pass;
+        if (out_metric) {
+            launch_adaptive_metric(a, sc->d_moments.p, (uint32_t) px, w.count, sc->d_adaptive_metric.p, w.scratch, s);
+            HIP_CHECK(hipGetLastError());
+            HIP_CHECK(hipMemcpyAsync(out_metric, sc->d_adaptive_metric.p, px * sizeof(double), hipMemcpyDeviceToHost, s));
+        }
+        HIP_CHECK(hipMemcpyAsync(out_count, w.count, px * 4, hipMemcpyDeviceToHost, s));
+        if (out_moments) {
+            launch_develop_moments(sc->d_moments.p, planes, developed != 0, sc->d_moment_planes.p, (int64_t) px, s);
+            HIP_CHECK(hipGetLastError());
+            HIP_CHECK(hipMemcpyAsync(out_moments, sc->d_moment_planes.p, px * planes * sizeof(double), hipMemcpyDeviceToHost, s));
+        }
+        if (out_images) {   // the images of dtof_render_variants_f64, from the film all passes accumulated into
+            using F = OwnFilm<double>;
+            const double *film = sc->d_film64.p;
+            sc->d_rgb.ensure(px * ch * K);
+            if (se.alpha) for (int i = 0; i < K; ++i) F::develop_rgba(film + px * 4 * i, film + px * 4 * K, sc->d_rgb.p + px * 4 * i, (int64_t) px, s);
+            else F::develop(film, K, sc->d_rgb.p, (int64_t) px, s);
+            HIP_CHECK(hipGetLastError());
+            HIP_CHECK(hipMemcpyAsync(out_images, sc->d_rgb.p, px * ch * K * sizeof(float), hipMemcpyDeviceToHost, s));
+        }
+        if (out_films) HIP_CHECK(hipMemcpyAsync(out_films, sc->d_film64.p, px * 4 * fplanes * sizeof(double), hipMemcpyDeviceToHost, s));
+        HIP_CHECK(hipStreamSynchronize(s));
+        if (stats) *stats = sum;
+    });
+}
+
 // ---------------------------------------------------------------- geometry channels of the `aov` integrator (dtof_aov.hip)
 int dtof_aov_parse(const char *spec, int32_t *types, int capacity, int *n_types, char *names_buf, size_t names_capacity, int *n_channels) {
     return guarded([&] {
@@ -580,6 +781,23 @@ int dtof_sample_lanes_variants(dtof_scene *sc, uint32_t seed, uint32_t spp, cons
         set_variants(rq, variants, n_variants);
         need_doppler_for(sc, rq.n_variants > 0);
         dump_lanes(sc, rq, lane_begin, n, out, valid, out_rgb);
+    });
+}
+int dtof_sample_lanes_pixels(dtof_scene *sc, uint32_t seed, uint32_t spp, const uint32_t *pixels, uint32_t n_pixels, const dtof_modulation *variants, int n_variants,
+                             float *out, uint32_t *valid, float *out_rgb) {
+    return guarded([&] {
+        if (!sc || !out) throw std::runtime_error("null argument");
+        check_variants_of_cells(sc, variants, n_variants);
+        check_host_list(sc, pixels, n_pixels);
+        RenderRequest rq = rows_request(seed, spp, 0, 0);
+        set_variants(rq, variants, n_variants);
+        const uint64_t n = (uint64_t) n_pixels * (spp ? spp : sc->pp.sample_count);
+        check_list_entry(sc, spp, n_pixels, false, false, true, n);   // the dump as dump_lanes will ask for it
+        ensure_device(sc);
+        const AdaptiveWords w = adaptive_words(sc, (size_t) sc->host.sensor.crop_w * sc->host.sensor.crop_h);
+        if (n_pixels) HIP_CHECK(hipMemcpy(w.list, pixels, (size_t) n_pixels * 4, hipMemcpyHostToDevice));
+        rq.pixels = w.list; rq.n_pixels = n_pixels;
+        dump_lanes(sc, rq, 0, n, out, valid, out_rgb);
     });
 }
 int dtof_sample_lanes(dtof_scene *sc, uint32_t seed, uint32_t spp, uint64_t lane_begin, uint64_t n, float *out) {

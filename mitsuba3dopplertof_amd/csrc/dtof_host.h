@@ -6,6 +6,7 @@
 #include "dtof_kernels.h"
 #include "dtof_aov.h"
 #include "dtof_scene.h"
+#include "dtof_pixel_list.h"
 #include <atomic>
 #include <cstring>
 #include <initializer_list>
@@ -108,6 +109,7 @@ struct dtof_scene {
     dtof::DevBuf<float> d_film, d_rgb;
     dtof::DevBuf<double> d_film64;   // the library's own float64 film (dtof_render_variants_f64, dtof_render_velocity_map_f64)
     dtof::DevBuf<double> d_moments, d_moment_planes;   // the moment film (dtof_render_moments) or the aov film (dtof_render_aovs) of the call: cells of kMomentCell doubles per pixel, and the dense planes copied out
+    dtof::DevBuf<uint32_t> d_adaptive; dtof::DevBuf<double> d_adaptive_metric;   // dtof_render_adaptive / _pixels: count, the pass's list, its length and the selection's scratch; the metric map
     dtof::DevBuf<double> d_denoise;   // dtof_denoise_async: the guide records and the two sets of working planes
     dtof::DevBuf<float> d_vm_sum, d_vm_tof; dtof::DevBuf<double> d_vm_maps;   // dtof_render_velocity_map: the passes' sum, the ToF images, the per-pair maps and the combined map
     // the caller's device film as declared with dtof_scene_set_film_layout (0 = not declared: colour planes only, W * H * 4 apart)
@@ -171,6 +173,10 @@ struct RenderRequest {
     dtof_render_stats *stats = nullptr;
     LaneDebug *lane_dump = nullptr; uint64_t dump_begin = 0, dump_n = 0;   // lane_dump != nullptr: evaluate only lanes [dump_begin, dump_begin + dump_n) and copy their records out
     bool deferred = false;                        // dtof_render_rows_async: timings by events, no counters read back, no synchronisation at the end
+    // pixels != nullptr: the LIST form -- only the n_pixels listed pixels are rendered (a DEVICE array of strictly ascending flat indices y * crop_w + x of the crop
+    // window; RenderParams::pixels), virtual lanes [0, n_pixels * spp).  An empty list launches nothing.  It takes film64 and / or moments, one pass per render, no
+    // stripes, no row range (row_begin = row_end = 0), no aov; a lane dump covers whole pixels of the list (check_pixel_list, dtof_render.hip).
+    const uint32_t *pixels = nullptr; uint32_t n_pixels = 0;
 };
 // The two shapes of a request: the film rows [row_begin, row_end), or the stripes [first_row + k * stripe_period, ... + stripe_rows) below the film's height
 inline RenderRequest rows_request(uint32_t seed, uint32_t spp, int32_t row_begin, int32_t row_end, dtof_render_stats *stats = nullptr, bool deferred = false) {
@@ -225,6 +231,9 @@ double stage_ms(const std::vector<std::pair<hipEvent_t, hipEvent_t>> &ev);
 SceneTraits scene_traits(const dtof_scene &sc);
 FlatChoice flat_choice(const SceneTraits &t, bool fused, bool memo_on, bool flat_on);
 FlatChoice default_flat_choice(const dtof_scene &sc, const SceneTraits &t);   // ... of the automatic pipeline with the default switches
+void check_pixel_list(const dtof_scene *sc, const RenderRequest &rq);   // the refusals of the list form, before any device call (render_rows makes them first of all)
+PixelListFacts pixel_list_facts(const dtof_scene *sc, uint32_t spp, uint32_t n_pixels);   // the scene's and the call's part of the facts; the entry adds what it renders into
+void refuse_pixel_list(const PixelListFacts &f);   // throws the refusal's message
 void plan_lanes(FramePlan &p, const dtof_scene *sc, const RenderRequest &rq);
 FramePlan plan_frame(const dtof_scene *sc, const RenderRequest &rq);
 void render_rows(dtof_scene *sc, const RenderRequest &rq);

@@ -72,6 +72,10 @@ struct RenderParams {
     // change valid_ray), so k_shade drops the half of the bounce nobody reads -- BSDF sampling, the draws behind the emitter sample, continuation ray, throughput /
     // russian roulette, the advance of both streams -- and, where the iteration has no emitter sampling either (active_next false), everything behind the emitter-hit term
     int32_t terminal;
+    // A pixel list (RenderRequest::pixels; adaptive passes, regions of interest): n strictly ascending flat indices y * crop_w + x of the crop window, device memory.  The
+    // launch's virtual lanes are [0, n * spp); virtual lane v is GLOBAL lane pixels[v / spp] * spp + v % spp (global_lane, dtof_sampling.h), so a listed pixel's lanes
+    // are, stream for stream, those of the dense render with the same seed.  nullptr: no list.  Batches are whole pixels (lane_base is a multiple of spp).
+    const uint32_t *pixels;
 };
 
 // SoA wavefront state for one batch (device pointers; all arrays have `capacity` entries and are
@@ -116,7 +120,7 @@ struct ShadeArgs {
     uint32_t n_seg, res_small_off, res_small_words, res_memo;   // resident stage (RESW != 0): segments of the batch; byte offset / uint4 count of the record block copied to LDS; 1 = the instance memo has LDS
     uint32_t res_park_off;   // resident stage with several films: word offset (behind the memo) of the film-state columns, kParkWords words per thread behind the stack columns
 };
-static_assert(sizeof(ShadeArgs) == 888, "ShadeArgs is k_shade's kernarg block: its layout, order and types do not change");
+static_assert(sizeof(ShadeArgs) == 896, "ShadeArgs is k_shade's kernarg block: its layout, order and types do not change (888 + RenderParams::pixels, the last field of rp)");
 // Resident kernels of several films keep the films' running results in LDS instead of registers (k_shade: RES_LDS): kParkWords of the 3 * kMaxOffsets floats per
 // thread -- what Domino's stage leaves free of the CU's 160 KiB at 16 waves (64 KiB node planes + 3 KiB records + 48 KiB stack columns) -- the last one stays a register
 constexpr uint32_t kParkWords = 11;

@@ -225,7 +225,7 @@ __global__ __launch_bounds__(kBlock) void k_splat_generic(RenderParams rp, Queue
     uint32_t i = blockIdx.x * kBlock + threadIdx.x;
     if (i >= rp.n_lanes) return;
     float2 p = q.pos[i];
-    uint32_t lane = global_lane(rp, rp.lane_base + i);
+    uint32_t lane = global_lane<0, false>(rp, rp.lane_base + i);
     uint32_t pix = fdiv(lane, rp.d_spp), W = (uint32_t) rp.crop_w;
     int py = (int) fdiv(pix, rp.d_w), px = (int) (pix - W * (uint32_t) py);
     for (int k = 0; k < rp.n_offsets; ++k) {
@@ -243,7 +243,7 @@ __global__ __launch_bounds__(kBlock) void k_splat_tent3(RenderParams rp, Queues 
     __shared__ float4 s_acc4[(kBlock / 2) * 9];
     uint32_t i = blockIdx.x * kBlock + threadIdx.x;
     bool in_range = i < rp.n_lanes;
-    uint32_t lane = global_lane(rp, rp.lane_base + (in_range ? i : 0));
+    uint32_t lane = global_lane<0, false>(rp, rp.lane_base + (in_range ? i : 0));
     uint32_t pix = lane >> rp.spp_log2;
     uint32_t W = (uint32_t) rp.crop_w;
     int py = (int) fdiv(pix, rp.d_w), px = (int) (pix - W * (uint32_t) py);
@@ -299,7 +299,7 @@ __global__ __launch_bounds__(kBlock) void k_splat_tent3(RenderParams rp, Queues 
             uint32_t sidx = idx / 36, c = idx - sidx * 36;
             uint32_t first_lane = blockIdx.x * kBlock + sidx * seg;
             if (first_lane >= rp.n_lanes) continue;
-            uint32_t spix = global_lane(rp, rp.lane_base + first_lane) >> rp.spp_log2;
+            uint32_t spix = global_lane<0, false>(rp, rp.lane_base + first_lane) >> rp.spp_log2;
             int sy = (int) fdiv(spix, rp.d_w), sx = (int) (spix - W * (uint32_t) sy);
             int x = sx - 1 + (int) ((c % 12) >> 2), y = sy - 1 + (int) (c / 12);
             float v = s_acc[idx];
@@ -325,7 +325,7 @@ __global__ __launch_bounds__(kBlock) void k_splat_x8(RenderParams rp, Queues q, 
     const uint32_t i = blockIdx.x * kBlock + threadIdx.x, sub = i & (seg8 - 1);
     const uint32_t first = (i - sub) * kSplatPer;           // first sample of this lane's segment (8 seg8 consecutive samples of one pixel)
     const bool in_range = first < rp.n_lanes;               // n_lanes is a multiple of spp, spp of 8 seg8
-    const uint32_t lane = global_lane(rp, rp.lane_base + (in_range ? first : 0));
+    const uint32_t lane = global_lane<0, false>(rp, rp.lane_base + (in_range ? first : 0));
     const uint32_t pix = lane >> rp.spp_log2, W = (uint32_t) rp.crop_w;
     const int py = (int) fdiv(pix, rp.d_w), px = (int) (pix - W * (uint32_t) py);
     const float bx = (float) (px + rp.crop_x - HALF) + .5f, by = (float) (py + rp.crop_y - HALF) + .5f;
@@ -398,7 +398,7 @@ __global__ __launch_bounds__(kBlock) void k_splat_x8(RenderParams rp, Queues q, 
             const uint32_t sidx = idx / (4 * NN), c = idx - sidx * (4 * NN), tap = c >> 2;
             const uint32_t seg_first = (blockIdx.x * kBlock + sidx * seg8) * kSplatPer;
             if (seg_first >= rp.n_lanes) continue;
-            const uint32_t spix = global_lane(rp, rp.lane_base + seg_first) >> rp.spp_log2;
+            const uint32_t spix = global_lane<0, false>(rp, rp.lane_base + seg_first) >> rp.spp_log2;
             const int sy = (int) fdiv(spix, rp.d_w), sx = (int) (spix - W * (uint32_t) sy);
             const int x = sx - HALF + (int) (tap % N), y = sy - HALF + (int) (tap / N);
             const float v = s_acc[idx];
@@ -433,7 +433,7 @@ __global__ __launch_bounds__(64) void k_splat_pixel(RenderParams rp, Queues q, f
         return c0 >= rp.spp ? 0u : (c0 + chunk < rp.spp ? chunk : rp.spp - c0);
     };
     const uint32_t t = t0 + l, mine = count_of(t);
-    const uint32_t pix = fdiv(global_lane(rp, rp.lane_base + (mine ? first_of(t) : 0u)), rp.d_spp), W = (uint32_t) rp.crop_w;
+    const uint32_t pix = fdiv(global_lane<0, false>(rp, rp.lane_base + (mine ? first_of(t) : 0u)), rp.d_spp), W = (uint32_t) rp.crop_w;
     const int py = (int) fdiv(pix, rp.d_w), px = (int) (pix - W * (uint32_t) py);
     const float bx = (float) (px + rp.crop_x - HALF) + .5f, by = (float) (py + rp.crop_y - HALF) + .5f;
     const uint32_t lm = l % kSplatStep, lj = l / kSplatStep;   // loader role: sample lm of the threads lj, lj + 8, ...

@@ -288,12 +288,34 @@ uint32_t FramePlan::launch_facts(const RenderParams &r, const LaunchSpan &l, uin
     // every segment's count is min(512, n_lanes - 512 S), a multiple of 64 if n_lanes is one: each 64-lane chunk is then whole, and its lanes are the 64-aligned
     // lanes [lane_base + 512 S + cbase, + 64), samples of one pixel when spp is a power of two >= 64.  (A striped shard -- a rank's share of a frame, virtual lanes --
     // keeps the run-time test and with it the generic kernel.)
-    if (identity_queue && r.stripe_rows == 0 && r.spp_log2 != 0xffffffffu && r.spp_log2 >= 6 && (r.lane_base & 63u) == 0 && (r.n_lanes & 63u) == 0) f |= kFactWavePixel;
+    // A pixel list likewise: its global lanes come from the table, which only the run-time branch of global_lane reads.
+    if (identity_queue && r.stripe_rows == 0 && r.pixels == nullptr && r.spp_log2 != 0xffffffffu && r.spp_log2 >= 6 && (r.lane_base & 63u) == 0 && (r.n_lanes & 63u) == 0) f |= kFactWavePixel;
     // the two lanes of a pair can split the BSDF samples of the launch between them: they hold one path stream, every draw comes from it, no draw is
     // looked at for roulette or for an emitter pick, and the launch is the whole path in three iterations -- two that sample a BSDF and the terminal one
     constexpr uint32_t pair_needs = kFactWholePath | kFactWavePixel | kFactStratifiedPairs | kFactCorrelated | kFactDopplerCorr | kFactNoRoulette | kFactOneEmitter;
     if (l.span == 3 && (f & pair_needs) == pair_needs) f |= kFactPairSamples;
     return f;
+}
+
+// The list form of a request (RenderRequest::pixels): what it cannot be combined with (pixel_list_refusal, dtof_pixel_list.h).  No device call is made here;
+// render_rows asks before anything else.
+PixelListFacts pixel_list_facts(const dtof_scene *sc, uint32_t spp, uint32_t n_pixels) {
+    PixelListFacts f;
+    f.spp = spp ? spp : sc->pp.sample_count; f.samples_per_pass = sc->pp.samples_per_pass;
+    f.n_pixels = n_pixels; f.crop_pixels = (uint64_t) sc->host.sensor.crop_w * sc->host.sensor.crop_h;
+    return f;
+}
+void refuse_pixel_list(const PixelListFacts &f) {
+    const std::string why = pixel_list_refusal(f);
+    if (!why.empty()) throw std::runtime_error(why);
+}
+void check_pixel_list(const dtof_scene *sc, const RenderRequest &rq) {
+    if (!rq.pixels) return;
+    PixelListFacts f = pixel_list_facts(sc, rq.spp, rq.n_pixels);
+    f.stripes = rq.stripes; f.row_range = rq.row_begin != 0 || rq.row_end != 0; f.aov = rq.aov != nullptr;
+    f.film32 = rq.film != nullptr; f.film64 = rq.film64 != nullptr; f.moments = rq.moments != nullptr;
+    f.lane_dump = rq.lane_dump != nullptr; f.dump_begin = rq.dump_begin; f.dump_n = rq.dump_n;
+    refuse_pixel_list(f);
 }
 
 // Call validation and the split into passes and lane ranges.  SamplingIntegrator::render (integrator.cpp:121-135,227-245): spp_per_pass = min(samples_per_pass, spp)
@@ -338,6 +360,13 @@ void plan_lanes(FramePlan &p, const dtof_scene *sc, const RenderRequest &rq) {
         rp.stripe_rows = stripe_rows; rp.stripe_period = stripe_period; rp.stripe_first = (uint32_t) row_begin; rp.lanes_per_row = (uint32_t) p.lanes_per_row;
         rp.d_lanes_per_row = make_fastdiv(rp.lanes_per_row); rp.d_stripe_rows = make_fastdiv(stripe_rows);
         p.first = 0; p.last = v_rows * p.lanes_per_row;
+    }
+    if (rq.pixels) {   // virtual lanes [0, n_pixels * spp): sample v % spp of listed pixel v / spp; the batches' unit (lanes_per_row) is one pixel
+        if (p.n_passes != 1) throw std::runtime_error("a pixel list needs one pass per render");   // (the carried stream states are indexed by virtual lane)
+        p.rp.pixels = rq.pixels;
+        p.lanes_per_row = spp;
+        p.first = rq.lane_dump ? dump_begin : 0;
+        p.last = rq.lane_dump ? dump_begin + rq.dump_n : (uint64_t) rq.n_pixels * spp;
     }
     p.run_passes = rq.lane_dump ? p.dump_pass + 1 : p.n_passes;   // a lane dump of pass k needs the stream states passes 0 .. k-1 leave
 }
@@ -393,7 +422,8 @@ FramePlan plan_frame(const dtof_scene *sc, const RenderRequest &rq) {
     // batches of 2^27 lanes (26 GB of workspace at 200 B per lane, 40 GB with four offset films -- of 288): every launch ends with a tail in which the CUs run dry one after
     // the other, and a Domino frame in 32 launches of 2^24 lanes lost 7 % to it (C5 206 -> 193 ms, C4 44.8 -> 41.1; profiles/r03_batch_lanes.txt); one launch per C4
     // frame instead of two is another 2 % (34.86 -> 34.14 ms, profiles/r04_domino_waves_batch.txt)
-    p.batch = rq.lane_dump ? std::min<uint64_t>(batch_lanes, std::max<uint64_t>(rq.dump_n, 1)) : std::max<uint64_t>(1, batch_lanes / p.lanes_per_row) * p.lanes_per_row;
+    // (a pixel list's batches are whole pixels, lane dumps included: lanes_per_row is its spp)
+    p.batch = rq.lane_dump && !rq.pixels ? std::min<uint64_t>(batch_lanes, std::max<uint64_t>(rq.dump_n, 1)) : std::max<uint64_t>(1, batch_lanes / p.lanes_per_row) * p.lanes_per_row;
     p.batch = std::min<uint64_t>(p.batch, std::max<uint64_t>(p.last - p.first, 1));
     if (p.batch > sc->ws.capacity) {   // a workspace that has to grow: keep it within the free device memory (168 B + 32 B per offset film per lane, and as much again left free)
         size_t free_b = 0, total_b = 0;
@@ -468,6 +498,7 @@ FramePlan plan_frame(const dtof_scene *sc, const RenderRequest &rq) {
 // The wavefront loop of one call: the plan's batches, each through the bounce loop, accumulated into rq.film.
 void render_rows(dtof_scene *sc, const RenderRequest &rq) {
     need_sensor(sc);
+    check_pixel_list(sc, rq);
     ensure_device(sc);
     const FramePlan p = plan_frame(sc, rq);
     sc->last_plan_facts = 0;
@@ -563,9 +594,11 @@ void render_rows(dtof_scene *sc, const RenderRequest &rq) {
             HIP_CHECK(hipStreamSynchronize(s));
         } else if (!rq.lane_dump && !fused_splat_done && !aov) {
             t = tm.begin(kStageSplat, s);
+            // a request may name BOTH the moment film and the float64 film: one traversal, two films (the alpha plane of an rgba scene then goes to the float64 film only)
             if (rq.moments) launch_splat_moments(rp, q, rq.moments, s);
-            else if (rq.film64) launch_splat_f64(rp, q, rq.film64, rq.film64_stride, s); else launch_splat(rp, q, rq.film, rq.film_stride, p.launch, s);
-            if (sc->host.sensor.alpha && !rq.moments) {   // the alpha film (plane K behind the K offset films): the same splat over (valid, 0, 0) -- ImageBlock::put of aovs[3] (integrator.cpp:528-533)
+            if (rq.film64) launch_splat_f64(rp, q, rq.film64, rq.film64_stride, s);
+            if (!rq.moments && !rq.film64) launch_splat(rp, q, rq.film, rq.film_stride, p.launch, s);
+            if (sc->host.sensor.alpha && (rq.film64 || !rq.moments)) {   // the alpha film (plane K behind the K offset films): the same splat over (valid, 0, 0) -- ImageBlock::put of aovs[3] (integrator.cpp:528-533)
                 RenderParams ra = rp; ra.n_offsets = 1;
                 Queues qa = q; qa.res = q.valid_out;
                 if (rq.film64) launch_splat_f64(ra, qa, rq.film64 + (size_t) rp.n_offsets * rq.film64_stride, rq.film64_stride, s);

@@ -107,10 +107,17 @@ DTOF_D float modulation_weight(const RenderParams &rp, float w_d, float phase, f
 // One lane of render_sample's head (integrator.cpp:476-495 / :416-431): sampler seeding, pixel jitter, time sample, camera ray.
 struct PrimaryLane { float4 ray_a, ray_b; Rng main, path; float2 pos; };
 // global lane index (pixel-major, the index every stream of the sampler is seeded with) of a lane of this launch
-// FACTS: kFactWavePixel holds for launches without stripes only (facts_lane_shifts, dtof_kernels.h)
-template <uint32_t FACTS = 0>
+// FACTS: kFactWavePixel holds for launches without stripes and without a pixel list only (facts_lane_shifts, dtof_kernels.h)
+template <uint32_t FACTS = 0, bool LIST = true>
 DTOF_D uint32_t global_lane(const RenderParams &rp, uint32_t virtual_lane) {
-    if (facts_lane_shifts(FACTS) || rp.stripe_rows == 0) return virtual_lane;
+    if (facts_lane_shifts(FACTS)) return virtual_lane;
+    // a pixel list: sample v % spp of the listed pixel v / spp (a list never comes with stripes).  LIST = false: a kernel no list can reach -- the float32 splat
+    // kernels and the fused splat (check_pixel_list refuses the float32 film), a kernel compiled with kFactWavePixel (FramePlan::launch_facts) -- keeps the parent's text
+    if (LIST && (FACTS & kFactWavePixel) == 0 && rp.pixels != nullptr) {
+        const uint32_t slot = fdiv(virtual_lane, rp.d_spp);
+        return rp.pixels[slot] * rp.spp + (virtual_lane - slot * rp.spp);
+    }
+    if (rp.stripe_rows == 0) return virtual_lane;
     const uint32_t v = fdiv(virtual_lane, rp.d_lanes_per_row), in_row = virtual_lane - v * rp.lanes_per_row;
     const uint32_t s = fdiv(v, rp.d_stripe_rows), y = rp.stripe_first + s * rp.stripe_period + (v - s * rp.stripe_rows);
     return y * rp.lanes_per_row + in_row;

@@ -607,7 +607,9 @@ __global__ __launch_bounds__(RESW ? RESW * 64 : kShadeBlock, RESW ? RESW / 4 : (
 #endif
     // the wave's 64 lanes are the 64-aligned lanes [lane_base + seg * 512 + cbase, + 64): samples of one pixel if spp is a multiple of 64
     // ... AND the whole wave is in range: the pair swap of the correlated seeding (generate_lane) reads the partner lane, which a ragged tail
-    // (dtof_sample_lanes with an odd count) would leave inactive
+    // (dtof_sample_lanes with an odd count) would leave inactive.  Under a pixel list (rp.pixels) the same test holds: spp is a power of two >= 64 and lane_base a
+    // multiple of spp (batches are whole pixels), so the wave's 64 virtual lanes lie in ONE listed pixel and global_lane maps them to 64 consecutive, 64-aligned
+    // global lanes of it -- what generate_lane's pair swap and pixel_info<true> need.  (A launch with a list never carries kFactWavePixel: FramePlan::launch_facts.)
     const bool wave_pixel = F_WAVE_PIXEL || (FIRST && rp.spp_log2 != 0xffffffffu && rp.spp_log2 >= 6 && (rp.lane_base & 63u) == 0 && count - cbase >= (uint32_t) kShadeBlock);
     // Fused splat (uniform): this launch runs the whole path of its lanes (nobody continues) and the host handed in the film -- the wave reduces the footprint
     // values of its 64 samples itself and issues the film atomics, the result never goes through q.res / q.pos and the splat kernel's round trip through HBM
@@ -993,7 +995,7 @@ __global__ __launch_bounds__(RESW ? RESW * 64 : kShadeBlock, RESW ? RESW / 4 : (
     }   // inline iterations
     if constexpr (!RES_LDS) if (FIRST && fuse_splat) {   // ---- ImageBlock::put (imageblock.cpp:414-531) of the wave's samples: tent filter of radius <= 1, a 3 x 3 footprint anchored at the sample's pixel
         const uint32_t W = (uint32_t) rp.crop_w;
-        const uint32_t pix = F_SHIFTS ? (uint32_t) __builtin_amdgcn_readfirstlane((int) (rp.lane_base + l)) >> rp.spp_log2 : fdiv(global_lane(rp, rp.lane_base + l), rp.d_spp);   // (as in generate_lane)
+        const uint32_t pix = F_SHIFTS ? (uint32_t) __builtin_amdgcn_readfirstlane((int) (rp.lane_base + l)) >> rp.spp_log2 : fdiv(global_lane<0, false>(rp, rp.lane_base + l), rp.d_spp);   // (as in generate_lane; the fused splat is the float32 film's: no list)
         const int py = (int) fdiv(pix, rp.d_w), px = (int) (pix - W * (uint32_t) py);
         const float sx = pos_reg.x, sy = pos_reg.y;
         const bool regular = in_range && (int) floorf(sx) - rp.crop_x == px && (int) floorf(sy) - rp.crop_y == py;   // (rarely a float position rounds up into the next pixel)

@@ -231,6 +231,36 @@ def velocity_standard_error(m, homodyne, heterodyne, n_samples, exposure_time=0.
     return np.where((a != 0) & (r > -1.0) & (r < 0.999), se, np.nan)
 
 
+def velocity_map_adaptive(scene, spp, max_passes, tol_mps, offsets=(0.0, 0.25), base_passes=1, seed=0, exposure_time=0.0015, w_g=30):
+    """The velocity map of the scene's OWN dopplertofpath integrator by adaptive sampling (Scene.render_adaptive, mode "velocity"): `base_passes` dense passes of `spp`
+    samples, then up to max_passes - base_passes passes over the pixels whose map's standard error -- the delta method of velocity_standard_error, per offset pair, from
+    the moment film of the passes so far -- is still above `tol_mps` (m/s).  One or two offsets: the films (0, o), (1, o) of ONE traversal.  The ToF images are
+    to_tof_image of the float64 film all passes accumulated into, the map calc_velocity_from_homo_heteros of them.  Returns (map (H, W), its standard-error map (H, W):
+    the largest finite error over the pairs, NaN where no pair has a usable ratio, count (H, W): samples rendered in every pixel).  The adaptive estimator is slightly
+    biased (pixels that look converged by chance stop early); base_passes and spp bound that.  The result dict is left in scene.adaptive_details."""
+    offsets = [float(o) for o in offsets]
+    if not 1 <= len(offsets) <= 2:
+        raise ValueError("an adaptive velocity map takes one or two offsets: the films of one traversal")
+    n = len(offsets)
+    variants = [(0.0, o) for o in offsets] + [(1.0, o) for o in offsets]
+    r = scene.render_adaptive(seed=seed, spp=spp, base_passes=base_passes, max_passes=max_passes, variants=variants, mode="velocity", tol=tol_mps,
+                              pairs=[(k, n + k) for k in range(n)], exposure_time=exposure_time, w_g=w_g)
+    tof = [to_tof_image(im, exposure_time) for im in r["images"]]
+    scene.adaptive_details = r
+    return calc_velocity_from_homo_heteros(tof[:n], tof[n:], exposure_time, w_g), r["metric"], r["count"]
+
+
+def run_scene_velocity_map_adaptive(scene, spp, max_passes, tol_mps, offsets=(0.0, 0.25), base_passes=1, **integrator_kwargs):
+    """velocity_map_adaptive under run_scene_velocity_map's integrator dictionary: passes of `spp` samples with seeds 0, 1, ..., the first `base_passes` of them dense.
+    Returns (velocity map from calc_velocity_from_homo_heteros, its standard-error map, count)."""
+    integrator_kwargs = dict(integrator_kwargs)
+    integrator_kwargs.pop("hetero_offset", None)
+    integrator_kwargs.pop("hetero_frequency", None)
+    scene.set_integrator(doppler_integrator_dict(hetero_frequency=0.0, hetero_offset=0.0, **integrator_kwargs))
+    exposure_time, w_g = integrator_kwargs.get("exposure_time", 0.0015), integrator_kwargs.get("w_g", 30)
+    return velocity_map_adaptive(scene, spp, max_passes, tol_mps, offsets, base_passes=base_passes, exposure_time=exposure_time, w_g=w_g)
+
+
 def run_scene_velocity(scene, total_spp=1024, output_file=None):
     single, _ = _passes(total_spp)
     img = render_multi_pass(scene, load_dict({"type": "velocity"}), total_spp, single)

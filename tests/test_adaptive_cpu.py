@@ -1,0 +1,303 @@
+"""Adaptive sampling (dtof_adaptive_select, dtof_render_pixels, dtof_sample_lanes_pixels, dtof_render_adaptive; mi.adaptive_select, Scene.render_pixels /
+sample_lanes_pixels / render_adaptive, --adaptive) as far as it can be held without a GPU:
+  - the header declares and the library exports the entries; every refusal that needs no device is DTOF_ERR_INVALID with a message and writes nothing;
+    the refusals of the list form that no entry can build (stripes, a row range, an aov request, the float32 film, a ragged lane dump) through the function the
+    frame path asks, compiled into a host program (tests/pixel_list_check.cpp)
+    arguments that pass every check fail with DTOF_ERR_HIP in a process that sees no device
+  - tests/adaptive_ref.py, the numpy definition the GPU tests compare with, is pinned BIT FOR BIT to code merged before it: with a uniform count its velocity metric
+    is harness.velocity_standard_error and its image se_k is harness.moment_statistics(...)["stderr"][..., 1], on random planes and on the edge values
+  - nothing of the feature imports oracle/; the command line parses the new flags."""
+import ctypes as C
+import os
+import re
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+from conftest import SCENES
+import adaptive_ref as aref
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+OK, INVALID, HIP = 0, 1, 2
+WALL = os.path.join(SCENES, "cornell_wall.xml")
+ENTRIES = ("dtof_adaptive_select", "dtof_render_pixels", "dtof_sample_lanes_pixels", "dtof_render_adaptive")
+
+
+def test_header_declares_and_library_exports_the_entries(mi):
+    hdr = open(os.path.join(ROOT, "include", "dtof.h")).read()
+    lib = C.CDLL(mi.lib_path())
+    for name in ENTRIES:
+        assert re.search(r"\bint\s+%s\s*\(([^;]*)\)\s*;" % name, hdr), name
+        assert hasattr(lib, name), name
+    assert "DTOF_ADAPTIVE_IMAGE" in hdr and "DTOF_ADAPTIVE_VELOCITY" in hdr and "dtof_adaptive_params" in hdr
+    section = hdr[hdr.index("adaptive sampling (opt-in)"):hdr.index("int dtof_adaptive_select")]
+    assert "biased" in section and "NOMINAL" in section      # the well-known property is stated where the entries are declared
+    assert C.sizeof(mi._AdaptiveParams) == 56
+
+
+def _params(mi, **kw):
+    d = dict(mode="image", tol=0.1, floor=1e-3, pairs=None, exposure_time=0.0015, w_g=30)
+    d.update(kw)
+    return mi._adaptive_params(d["mode"], d["tol"], d["floor"], d["pairs"], d["exposure_time"], d["w_g"])
+
+
+def test_select_refusals_that_need_no_device(mi):
+    L = mi._lib()
+    n, K = 8, 2
+    planes = np.ones((14, n))
+    count = np.full(n, 7, np.uint32)
+    out, out_n, metric = np.full(n, 99, np.uint32), C.c_uint32(99), np.full(n, 123.25)
+
+    def call(prm=None, planes_=planes.ctypes.data, n_=n, K_=K, spp=4, count_=count.ctypes.data, out_=out.ctypes.data, out_n_=C.byref(out_n)):
+        prm = _params(mi) if prm is None else prm
+        return L.dtof_adaptive_select(planes_, n_, K_, C.byref(prm) if prm != "null" else None, spp, count_, out_, out_n_, metric.ctypes.data)
+
+    vel = dict(mode="velocity", pairs=[(0, 1)])
+    bad_mode = _params(mi); bad_mode.mode = 2
+    three = _params(mi, **vel); three.n_pairs = 3
+    none = _params(mi, **vel); none.n_pairs = 0
+    cases = {"null planes": lambda: call(planes_=None), "null count": lambda: call(count_=None), "null list": lambda: call(out_=None),
+             "null length": lambda: call(out_n_=None), "null params": lambda: call(prm="null"), "0 variants": lambda: call(K_=0), "5 variants": lambda: call(K_=5),
+             "negative size": lambda: call(n_=-1), "too many pixels": lambda: call(n_=(1 << 24) + 1), "spp 0": lambda: call(spp=0), "mode": lambda: call(bad_mode),
+             "NaN tol": lambda: call(_params(mi, tol=float("nan"))), "negative floor": lambda: call(_params(mi, floor=-1.0)),
+             "NaN floor": lambda: call(_params(mi, floor=float("nan"))), "h == t": lambda: call(_params(mi, mode="velocity", pairs=[(1, 1)])),
+             "second pair h == t": lambda: call(_params(mi, mode="velocity", pairs=[(0, 1), (0, 0)])),
+             "index beyond the variants": lambda: call(_params(mi, mode="velocity", pairs=[(0, 2)])), "negative index": lambda: call(_params(mi, mode="velocity", pairs=[(-1, 1)])),
+             "3 pairs": lambda: call(three), "0 pairs": lambda: call(none), "exposure 0": lambda: call(_params(mi, exposure_time=0.0, **vel)),
+             "w_g inf": lambda: call(_params(mi, w_g=float("inf"), **vel))}
+    for name, f in cases.items():
+        assert f() == INVALID, (name, L.dtof_last_error())
+        assert len(L.dtof_last_error()) > 0, name
+    call(_params(mi, mode="velocity", pairs=[(1, 1)]))
+    assert b"homodyne == heterodyne" in L.dtof_last_error()
+    assert (out == 99).all() and out_n.value == 99 and (metric == 123.25).all() and (count == 7).all()      # no refused call wrote
+    with pytest.raises(mi.DtofError, match="image.*velocity"):
+        mi.adaptive_select(planes, count, 4, mode="both")
+    with pytest.raises(mi.DtofError, match="1 or 2"):
+        mi.adaptive_select(planes, count, 4, mode="velocity", pairs=[])
+    with pytest.raises(mi.DtofError, match="moment planes"):
+        mi.adaptive_select(np.ones((9, n)), count, 4)
+    with pytest.raises(mi.DtofError, match="one entry per pixel"):
+        mi.adaptive_select(planes, count[:3], 4)
+
+
+def test_render_refusals_that_need_no_device(mi):
+    L = mi._lib()
+    sc = mi.load_file(WALL, resx=8, resy=8)
+    SENT = 123.25
+    planes, film = np.full((14, 64), SENT), np.full((2, 64, 4), SENT)
+    var = np.asarray([(0, 0), (1, 0), (0, .25), (1, .25), (1, .5)], np.float32)
+    good = np.asarray([0, 5, 63], np.uint32)
+    st = mi._Stats()
+
+    def pixels(scene=sc._h, lst=good, n=None, variants=var.ctypes.data, K=2, moments=planes.ctypes.data, films=film.ctypes.data):
+        lst = np.asarray(lst, np.uint32)
+        return L.dtof_render_pixels(scene, 0, 4, lst.ctypes.data if lst is not None and len(lst) else None, len(lst) if n is None else n, variants, K, 0, moments, films, C.byref(st))
+
+    lanes_out, valid = np.full((3 * 4, 12), SENT, np.float32), np.zeros(12, np.uint32)
+
+    def lanes(lst=good, out=lanes_out.ctypes.data, scene=sc._h):
+        lst = np.asarray(lst, np.uint32)
+        return L.dtof_sample_lanes_pixels(scene, 0, 4, lst.ctypes.data, len(lst), None, 0, out, valid.ctypes.data, None)
+
+    count, metric, pp, npass = np.full(64, 7, np.uint32), np.full(64, SENT), np.full(4, 7, np.uint32), C.c_uint32(7)
+
+    def adaptive(scene=sc._h, base=1, most=4, prm=None, K=2, variants=var.ctypes.data, count_=count.ctypes.data, pp_=pp.ctypes.data, np_=C.byref(npass)):
+        prm = _params(mi) if prm is None else prm
+        return L.dtof_render_adaptive(scene, 0, 4, base, most, variants, K, C.byref(prm) if prm != "null" else None, 0, planes.ctypes.data, None, None, count_,
+                                      metric.ctypes.data, pp_, np_, None, 0, C.byref(st))
+
+    cases = {"pixels: null scene": lambda: pixels(scene=None), "pixels: no output": lambda: pixels(moments=None, films=None),
+             "pixels: unsorted": lambda: pixels(lst=[5, 3]), "pixels: repeated": lambda: pixels(lst=[3, 3]), "pixels: outside the crop": lambda: pixels(lst=[3, 64]),
+             "pixels: a count without a list": lambda: pixels(lst=[], n=2), "pixels: 5 variants": lambda: pixels(K=5), "pixels: -1 variants": lambda: pixels(K=-1),
+             "pixels: a count without variants": lambda: pixels(variants=None),
+             "lanes: null output": lambda: lanes(out=None), "lanes: null scene": lambda: lanes(scene=None), "lanes: unsorted": lambda: lanes(lst=[9, 2]),
+             "lanes: outside the crop": lambda: lanes(lst=[1000]),
+             "adaptive: null scene": lambda: adaptive(scene=None), "adaptive: null params": lambda: adaptive(prm="null"), "adaptive: null count": lambda: adaptive(count_=None),
+             "adaptive: null pass lengths": lambda: adaptive(pp_=None), "adaptive: null pass count": lambda: adaptive(np_=None),
+             "adaptive: base_passes 0": lambda: adaptive(base=0), "adaptive: max_passes below base_passes": lambda: adaptive(base=3, most=2),
+             "adaptive: h == t": lambda: adaptive(prm=_params(mi, mode="velocity", pairs=[(0, 0)])),
+             "adaptive: pair beyond the variants": lambda: adaptive(prm=_params(mi, mode="velocity", pairs=[(0, 3)])), "adaptive: 5 variants": lambda: adaptive(K=5)}
+    for name, f in cases.items():
+        assert f() == INVALID, (name, L.dtof_last_error())
+        assert len(L.dtof_last_error()) > 0, name
+    assert pixels(lst=[5, 3]) == INVALID and b"strictly ascending" in L.dtof_last_error()
+    assert pixels(lst=[3, 64]) == INVALID and b"outside the crop window" in L.dtof_last_error()
+    assert adaptive(base=0) == INVALID and b"base_passes" in L.dtof_last_error()
+    # a list needs one pass per render: samples_per_pass below the sample count is refused by all three, before any device call
+    multi = mi.load_file(WALL, resx=8, resy=8)
+    multi.set_integrator(dict(type="dopplertofpath", samples_per_pass=2))
+    for f in (lambda: pixels(scene=multi._h), lambda: lanes(scene=multi._h), lambda: adaptive(scene=multi._h)):
+        assert f() == INVALID and b"one pass per render" in L.dtof_last_error(), L.dtof_last_error()
+    for plugin in ("path", "velocity"):      # variants under a non-Doppler integrator: the rule of the other variants entries
+        sc.set_integrator(dict(type=plugin))
+        assert pixels() == INVALID and adaptive() == INVALID
+        assert L.dtof_last_error() == b"modulation offsets only apply to the dopplertofpath integrator", (plugin, L.dtof_last_error())
+    assert (planes == SENT).all() and (film == SENT).all() and (lanes_out == SENT).all() and (count == 7).all() and (metric == SENT).all() and (pp == 7).all() and npass.value == 7
+    with pytest.raises(mi.DtofError, match="between 1 and 4"):
+        sc.render_pixels([0], variants=[(0, 0)] * 5)
+    with pytest.raises(mi.DtofError, match="base_passes"):
+        sc.render_adaptive(base_passes=0)
+    with pytest.raises(mi.DtofError, match="flat indices"):
+        sc.render_pixels([-1])
+
+
+NO_DEVICE_CHILD = r"""
+import ctypes as C, sys
+L = C.CDLL(sys.argv[1])
+vp = C.c_void_p
+class P(C.Structure):
+    _fields_ = [("mode", C.c_int32), ("n_pairs", C.c_int32), ("homodyne", C.c_int32 * 2), ("heterodyne", C.c_int32 * 2), ("tol", C.c_double), ("floor", C.c_double),
+                ("exposure_time", C.c_double), ("w_g_mhz", C.c_double)]
+L.dtof_scene_load_file.argtypes = [C.c_char_p, vp, vp, C.c_int, C.POINTER(vp)]
+L.dtof_adaptive_select.argtypes = [vp, C.c_int64, C.c_int, vp, C.c_uint32, vp, vp, vp, vp]
+L.dtof_render_pixels.argtypes = [vp, C.c_uint32, C.c_uint32, vp, C.c_uint32, vp, C.c_int, C.c_int, vp, vp, vp]
+L.dtof_sample_lanes_pixels.argtypes = [vp, C.c_uint32, C.c_uint32, vp, C.c_uint32, vp, C.c_int, vp, vp, vp]
+L.dtof_render_adaptive.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, vp, C.c_int, vp, C.c_int] + [vp] * 8 + [C.c_uint64, vp]
+h = vp()
+names, values = (C.c_char_p * 2)(b"resx", b"resy"), (C.c_char_p * 2)(b"8", b"8")
+assert L.dtof_scene_load_file(sys.argv[2].encode(), names, values, 2, C.byref(h)) == 0
+p = P(0, 0, (C.c_int32 * 2)(0, 0), (C.c_int32 * 2)(0, 0), 0.1, 1e-3, 0.0015, 30.0)
+planes = (C.c_double * (7 * 64))(*([7.0] * (7 * 64)))
+count, lst, n = (C.c_uint32 * 64)(*([4] * 64)), (C.c_uint32 * 64)(*range(64)), C.c_uint32(9)
+lanes, pp = (C.c_float * (64 * 4 * 12))(), (C.c_uint32 * 2)()
+print(L.dtof_adaptive_select(planes, 64, 1, C.byref(p), 4, count, lst, C.byref(n), None), L.dtof_adaptive_select(planes, 0, 1, C.byref(p), 4, count, lst, C.byref(n), None),
+      L.dtof_render_pixels(h, 0, 4, lst, 64, None, 0, 1, planes, None, None), L.dtof_render_pixels(h, 0, 4, None, 0, None, 0, 1, planes, None, None),
+      L.dtof_sample_lanes_pixels(h, 0, 4, lst, 64, None, 0, lanes, None, None),
+      L.dtof_render_adaptive(h, 0, 4, 1, 2, None, 0, C.byref(p), 1, planes, None, None, count, None, pp, C.byref(n), None, 0, None),
+      int(all(x == 7.0 for x in planes) and n.value == 9))
+"""
+
+
+def test_compute_entries_fail_with_err_hip_without_a_device(mi):
+    """no CPU fallback: arguments that pass every check reach the device set-up and fail there -- in a child process that sees no device, whatever this host has"""
+    env = dict(os.environ, HIP_VISIBLE_DEVICES="-1", ROCR_VISIBLE_DEVICES="-1")
+    r = subprocess.run([sys.executable, "-c", NO_DEVICE_CHILD, mi.lib_path(), WALL], capture_output=True, text=True, timeout=120, env=env)
+    assert r.returncode == 0, r.stderr[-2000:]
+    assert r.stdout.split() == [str(HIP)] * 6 + ["1"], r.stdout
+
+
+def test_nothing_of_the_feature_imports_the_oracle():
+    files = [os.path.join(ROOT, "mitsuba3dopplertof_amd", f) for f in ("__init__.py", "__main__.py", "harness.py")] + [os.path.join(ROOT, "tools", "time_adaptive.py")]
+    for path in files:
+        text = open(path).read()
+        assert not re.search(r"^\s*(from|import)\s+oracle\b", text, re.M) and "oracle/" not in text.replace("oracle/_ref", ""), path
+    src = os.path.join(ROOT, "mitsuba3dopplertof_amd", "csrc")
+    for f in ("dtof_adaptive.hip", "dtof_adaptive.h"):
+        assert "oracle" not in open(os.path.join(src, f)).read(), f
+
+
+def _random_planes(seed, K, n=257):
+    rng = np.random.default_rng(seed)
+    noisy = rng.random(n) < 0.5
+    return aref.synthetic(rng, n, K, noisy, edges=True)
+
+
+@pytest.mark.parametrize("K", [1, 2, 4])
+def test_image_se_is_moment_statistics_bit_for_bit(mi, K):
+    from mitsuba3dopplertof_amd import harness
+    S, _ = _random_planes(11 + K, K)
+    n = S.shape[1]
+    for n_samples in (1, 16, 48):
+        with np.errstate(all="ignore"):
+            _, se = aref.image_metric(S, K, np.full(n, n_samples, np.uint32), 1e-3)
+            want = harness.moment_statistics(aref.developed_dict(S, K, (1, n)), n_samples)["stderr"][..., 1].reshape(K, n)
+        assert (np.isnan(se) == np.isnan(want)).all() and np.isinf(want).any()      # (the infinities of the edge pixels)
+        ok = ~np.isnan(want)
+        assert (se[ok].view(np.uint64) == want[ok].view(np.uint64)).all()
+        assert (se[ok] == 0).any() and (se[ok] > 0).any()      # a negative variance clamps to 0
+
+
+@pytest.mark.parametrize("K,pair", [(2, (0, 1)), (4, (2, 3)), (4, (2, 1))])
+def test_velocity_metric_is_velocity_standard_error_bit_for_bit(mi, K, pair):
+    from mitsuba3dopplertof_amd import harness
+    S, _ = _random_planes(23 + K, K)
+    n = S.shape[1]
+    h, t = pair
+    # the edge values by construction: a == 0, r at both ends of the clip interval (closed ends: invalid) and just inside them, a negative var_r
+    S[:, :8] = aref.synthetic(np.random.default_rng(99), n, K, np.ones(n, bool))[0][:, :8]      # (no edge value of the generator's own in these eight)
+    S[0, :8] = 32.0
+    S[aref.cross_plane(K, h, t), 5] = 2.0 * 1.0 * 32.0            # pixel 5: cov = 0
+    S[1 + 6 * h + 1, 0] = 0.0
+    S[1 + 6 * h + 1, 1:8] = 64.0                                  # a = 2
+    S[1 + 6 * t + 1, 1:8] = np.asarray([-1.0, 0.999, np.nextafter(-1.0, 0), np.nextafter(0.999, 0), 0.5, 0.25, -0.5]) * 64.0
+    S[1 + 6 * h + 4, 5:8] = 4.0 * 32.0                            # var_h = 0 ...
+    S[1 + 6 * t + 4, 5] = (0.5 * 2.0) ** 2 * 32.0 * (1 - 2.0 ** -20)      # ... and var_t < 0: a negative var_r
+    for n_samples in (16, 48):
+        with np.errstate(all="ignore"):
+            got, _ = aref.velocity_metric(S, K, np.full(n, n_samples, np.uint32), [pair], 1.0, 0.0015, 30)
+            want = harness.velocity_standard_error(aref.developed_dict(S, K, (1, n)), h, t, n_samples, 0.0015, 30).reshape(n)
+            se, valid, _, _ = aref.pair_se(S, K, np.full(n, n_samples, np.uint32), h, t, 0.0015, 30)
+        assert np.isnan(got[[0, 1, 2]]).all() and np.isnan(want[[0, 1, 2]]).all() and not valid[[0, 1, 2]].any()
+        assert np.isfinite(got[[3, 4, 5, 6, 7]]).all() and got[5] == 0.0 and valid[[3, 4, 5, 6, 7]].all()
+        fin = np.isfinite(want)
+        assert fin.sum() > n // 2
+        assert (got[fin].view(np.uint64) == want[fin].view(np.uint64)).all()      # where the merged code has a number, this is that number
+        assert np.isnan(got[~fin]).all()                                            # NaN or infinite there: no finite se of a valid pair here
+        assert (np.isnan(want) == (~valid | np.isnan(se))).all()
+
+
+def test_reference_selection_is_consistent(mi):
+    """the list, the metric and the count of adaptive_ref.select on inputs with every edge value: ascending, count raised by spp exactly there, count 0 never selected
+    in image mode, an invalid pair with a positive variance always selected in velocity mode"""
+    S, count = _random_planes(5, 4)
+    lst, metric, new = aref.select(S, 4, count, 8, "image", 1e-3)
+    assert (np.diff(lst.astype(np.int64)) > 0).all() and 0 < len(lst) < len(count)
+    assert ((new - count) == np.where(np.isin(np.arange(len(count)), lst), 8, 0)).all()
+    assert not np.isin(np.flatnonzero(count == 0), lst).any() and (metric[count == 0] == 0).all()
+    lst2, metric2, _ = aref.select(S, 4, count, 8, "velocity", 1e9, pairs=[(0, 1), (2, 3)])
+    assert np.isnan(metric2).any() and np.isfinite(metric2).any()
+    assert len(lst2) > 0 and (metric2[lst2][np.isfinite(metric2[lst2])] <= 1e9).all()      # tol above every finite se: only pairs without a usable estimate select
+
+
+def test_command_line_parses_adaptive(mi, capsys):
+    from mitsuba3dopplertof_amd import __main__ as cli
+    args = cli.parser().parse_args(["scene.xml", "--adaptive", "0.05", "--adaptive-mode", "image", "--base-passes", "2", "--max-passes", "6", "--variants", "0:0,1:0"])
+    assert (args.adaptive, args.adaptive_mode, args.base_passes, args.max_passes) == (0.05, "image", 2, 6)
+    d = cli.parser().parse_args(["scene.xml"])
+    assert d.adaptive is None and d.adaptive_mode == "image" and d.base_passes == 1 and d.max_passes == 4
+    v = cli.parser().parse_args(["scene.xml", "--adaptive", "0.5", "--adaptive-mode", "velocity", "--velocity-map", "0,0.25"])
+    assert v.adaptive_mode == "velocity" and v.velocity_map == "0,0.25"
+    refused = {"--adaptive-mode velocity": [WALL, "--adaptive", "0.1", "--adaptive-mode", "velocity"], "stripes": [WALL, "--adaptive", "0.1", "--stripes", "4"],
+               "belong to --adaptive": [WALL, "--base-passes", "2"], "--max-passes": [WALL, "--adaptive", "0.1", "--base-passes", "3", "--max-passes", "2"],
+               "--moments": [WALL, "--adaptive", "0.1", "--moments"]}
+    for what, argv in refused.items():
+        with pytest.raises(SystemExit) as e:
+            cli.main(argv)
+        assert e.value.code == 2 and what in capsys.readouterr().err, what
+
+
+def test_every_refusal_of_the_list_form_on_the_host(tmp_path):
+    """A list with stripes, a row range, an aov request or the float32 film, without a film, with a ragged lane dump, with several passes per render: no entry of the
+    C ABI builds the first five requests, so the function the frame path (check_pixel_list) and the entries call before any device call is driven directly
+    (tests/pixel_list_check.cpp over csrc/dtof_pixel_list.h), every request shape once, and every message is held."""
+    import shutil
+    cxx = shutil.which("c++") or shutil.which("g++")
+    if cxx is None:
+        pytest.fail("no host C++ compiler")
+    exe = str(tmp_path / "pixel_list_check")
+    subprocess.check_call([cxx, "-O1", "-std=c++17", "-Wall", "-Wextra", "-I", os.path.join(ROOT, "mitsuba3dopplertof_amd", "csrc"),
+                           os.path.join(ROOT, "tests", "pixel_list_check.cpp"), "-o", exe])
+    out = subprocess.run([exe], capture_output=True, text=True, timeout=60)
+    assert out.returncode == 0, out.stderr[-2000:]
+    got = dict(ln.split("|", 1) for ln in out.stdout.splitlines())
+    stripes, rows, aov = "a pixel list cannot be combined with stripes", "a pixel list cannot be combined with a row range", "a pixel list cannot be combined with an aov request"
+    film32 = "a pixel list renders into the float64 film or the moment film, not into the float32 film"
+    whole = "the lane dump of a pixel list covers whole pixels of the list"
+    want = {"moments": "", "film64": "", "both films": "", "empty list": "", "full list": "", "samples_per_pass == spp": "", "samples_per_pass 0": "",
+            "dump of whole pixels": "", "stripes": stripes, "row range": rows, "aov": aov, "float32 film": film32, "float32 film alone": film32,
+            "no film": "a pixel list needs a float64 film or a moment film to render into", "spp 0": "sample count must be positive",
+            "samples_per_pass below spp": "a pixel list needs one pass per render: samples_per_pass below the sample count is not supported with a list",
+            "more pixels than the crop": "a pixel list cannot hold more pixels than the crop window", "dump begins inside a pixel": whole,
+            "dump ends inside a pixel": whole, "dump beyond the list": whole, "ragged dump with a film": whole}
+    assert got == want
+    # the frame path and the entries ask this function and nothing else
+    src = os.path.join(ROOT, "mitsuba3dopplertof_amd", "csrc")
+    render, films = open(os.path.join(src, "dtof_render.hip")).read(), open(os.path.join(src, "dtof_abi_films.hip")).read()
+    body = render[render.index("void check_pixel_list("):render.index("// Call validation and the split")]
+    assert "refuse_pixel_list(f)" in body and "pixel_list_refusal(f)" in render and re.search(r"need_sensor\(sc\);\s*check_pixel_list\(sc, rq\);", render)
+    for field in ("stripes", "row_range", "aov", "film32", "film64", "moments", "lane_dump", "dump_begin", "dump_n"):
+        assert "f.%s = " % field in body, field
+    assert films.count("check_list_entry(sc, spp,") == 3 and "refuse_pixel_list(f)" in films
