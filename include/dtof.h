@@ -133,6 +133,14 @@ int dtof_scene_get_info(const dtof_scene *scene, dtof_scene_info *info);
  * kind 10: roughplastic tables -> per roughplastic shape the 64 values of m_external_transmittance (roughplastic.cpp:222-257)
  * Returns the number of floats written (<= capacity) through *n_written. */
 int dtof_scene_export(const dtof_scene *scene, int kind, float *out, size_t capacity, size_t *n_written);
+/* S, world to FILM pixel: the 3 x 4 matrix (rows x, y, w, row-major) with pix(P) = ((S_x . (P, 1)) / (S_w . (P, 1)), (S_y . (P, 1)) / (S_w . (P, 1))) in the
+ * coordinates of the sample_pos of dtof_sample_lanes (film pixels, not crop-relative ones).  Rows x, y, w of camera_to_sample o to_world^-1
+ * (perspective_projection / orthographic_projection, include/mitsuba/render/sensor.h:226-299) scaled by the film size, computed in double on the host from the
+ * loader's float32 sensor.  The depth row is deliberately absent, so near and far clip do not enter.  An orthographic sensor has S_w = (0, 0, 0, 1); a thinlens
+ * sensor gives its pinhole (the lens centre).  S_w . (P, 1) <= 0: the point is not in front of the camera.  What it is for: the screen-space motion of a world
+ * point between two sensors (harness.camera_flow: the flow of static geometry under a moving camera, the `to_sensor` of the reference's denoiser call).
+ * Needs no device.  DTOF_ERR_INVALID: a null argument, a scene without a sensor, a singular to_world. */
+int dtof_scene_world_to_pixel(const dtof_scene *scene, double out12[12]);
 /* Sensor::sample_ray of the scene's sensor over arrays (src/sensors/perspective.cpp:238-279, thinlens.cpp:257-305, orthographic.cpp:169-196), through the device
  * function the first-bounce kernel generates its primary rays with: per sample the position sample x, y in [0, 1]^2 of the crop window and the aperture sample
  * x, y (4 floats) -> ray origin[3], direction[3], maxt (7 floats).  The ray's time is the sampler's business (render_sample, integrator.cpp:494-496). */
@@ -464,6 +472,32 @@ int dtof_render_aovs(dtof_scene *scene, uint32_t seed, uint32_t spp, uint32_t n_
 int dtof_sample_aov_lanes(dtof_scene *scene, uint32_t seed, uint32_t spp, const int32_t *types, int n_types, uint64_t lane_begin, uint64_t n, float *out_lanes12,
                           float *out_values);
 
+/* ---------------------------------------------------------------- the flow film: motion vectors of the camera rays (opt-in)
+ * The producer of the `flow` the denoiser's temporal stage takes, for scenes whose OBJECTS move: the scene carries every object's motion over the shutter as the
+ * two keyframes of its <animation>, and this film exposes it as screen-space motion vectors.  It is not one of the reference's aov types (DTOF_AOV_* and
+ * dtof_aov_parse are not extended); it runs through the aov film's kernel, compiled with two more values per lane, and through its splat, cells and develop.
+ * Per lane the camera ray is the scene integrator's own, with its own time t, exactly as for the aov film.  A miss, or a hit on an object with fewer than two
+ * keyframes, gives flow (+0, +0).  Otherwise everything is in double, formed from float32 inputs -- the hit position p, the keyframes key0, key1 (3 x 4 affine,
+ * row-major) and times t0, t1 of the hit object -- without fused multiply-add, in exactly this order (tests/flow_ref.py is the numpy restatement the tests hold):
+ *   u      x = (t - t0) / (t1 - t0); u = x > 0 ? x : 0; u = u < 1 ? u : 1
+ *   M      M[i] = key0[i] * (1 - u) + key1[i] * u for the 12 words; a_rc = M[4 r + c]
+ *   M^-1   c00 = a11 a22 - a12 a21, c01 = a12 a20 - a10 a22, c02 = a10 a21 - a11 a20; det = (a00 c00 + a01 c01) + a02 c02; id = 1 / det;
+ *          i00 = c00 id, i01 = (a02 a21 - a01 a22) id, i02 = (a01 a12 - a02 a11) id; i10 = c01 id, i11 = (a00 a22 - a02 a20) id, i12 = (a02 a10 - a00 a12) id;
+ *          i20 = c02 id, i21 = (a01 a20 - a00 a21) id, i22 = (a00 a11 - a01 a10) id; with t = (M[3], M[7], M[11]): i_r3 = -((i_r0 t_x + i_r1 t_y) + i_r2 t_z)
+ *   point  a point (x, y, z) through a row (m0, m1, m2, m3) is ((m0 x + m1 y) + m2 z) + m3
+ *   q      = M^-1 p: the hit point in the object's own frame; P0 = key0 q, P1 = key1 q: its positions at shutter open and at shutter close
+ *   pix    with S of dtof_scene_world_to_pixel: w = S_w . P, pix(P) = ((S_x . P) / w, (S_y . P) / w)
+ *   flow   = pix(P1) - pix(P0), each component rounded to float32 once.  If not (w0 > 0 and w1 > 0): both words are the NaN 0x7fc00000, which the temporal stage
+ *          reads as "no history"
+ * flow is the pixel motion over ONE shutter interval, pointing from the earlier position to the later one; a caller whose frame interval differs from the exposure
+ * scales it.  For static geometry under a moving camera see dtof_scene_world_to_pixel.
+ * dtof_render_flow: three planes of crop_height * crop_width doubles -- weight, flow x, flow y -- accumulated, developed and refused exactly as dtof_render_aovs
+ * does with a two-channel film (a NaN lane makes its pixels NaN).  dtof_sample_flow_lanes: the per-lane entry, through the same kernel without its splat, as
+ * dtof_sample_aov_lanes: out_lanes12 as dtof_sample_lanes writes it, out_flow2[n][2].
+ * Out of scope: flow in the sharded renders and on the command line, and fusing this traversal with the images'. */
+int dtof_render_flow(dtof_scene *scene, uint32_t seed, uint32_t spp, uint32_t n_passes, int developed, double *out_planes, dtof_render_stats *stats);
+int dtof_sample_flow_lanes(dtof_scene *scene, uint32_t seed, uint32_t spp, uint64_t lane_begin, uint64_t n, float *out_lanes12, float *out_flow2);
+
 /* ---------------------------------------------------------------- denoiser
  * The counterpart of the reference's OptixDenoiser (src/render/python/optixdenoiser_v.cpp; its tests: src/render/tests/test_optixdenoiser.py), written from scratch:
  * an edge-avoiding a-trous wavelet filter (Dammertz et al. 2010) whose luminance term is normalised by the per-pixel variance (the spatial pass of SVGF), over
@@ -492,6 +526,61 @@ int dtof_denoise_async(dtof_scene *scene, const float *d_colour, int n_planes, i
 /* The same with HOST pointers and no scene: uploads, runs, downloads and synchronises once. */
 int dtof_denoise(const float *colour, int n_planes, int32_t width, int32_t height, const double *variance_or_null, const float *normal_or_null,
                  const float *position_or_null, const dtof_denoise_params *params, double *out_colour, double *out_variance_or_null);
+
+/* ---------------------------------------------------------------- denoiser, temporal stage (opt-in)
+ * The other half of the reference's OptixDenoiser(input_size, albedo, normals, temporal) called with `flow` and `previous_denoised`
+ * (src/render/python/optixdenoiser_v.cpp), written from scratch after SVGF's temporal accumulation: the previous frame's ACCUMULATED films are reprojected through a
+ * screen-space flow field, history that belongs to another surface is rejected per bilinear tap, and mean and variance are blended.  It runs in FRONT of the spatial
+ * levels above: the variance it hands them is the variance of the accumulated estimate.  All in double, no fused multiply-add, no epsilon;
+ * tests/temporal_ref.py is the definition.  For pixel p = (x, y), n_planes = K colour planes sharing one set of tap weights:
+ *   cur_ok   every colour word of every plane, every variance and every present guide word (normal, ids) of p is finite.  If not: the outputs are the converted
+ *            inputs and o_length = 0 (later frames take no history from this pixel)
+ *   taps     rx = x - (double) flow_x, ry = y - (double) flow_y; x0 = floor(rx), a = rx - x0; y0 = floor(ry), b = ry - y0; q = (x0 + i, y0 + j), i, j in {0, 1},
+ *            j outer; wt = (i ? a : 1 - a) * (j ? b : 1 - b).  flow points from the pixel's earlier position to its current one, in pixels
+ *   accepted iff ALL hold: a history is present; both flow words are finite; wt > 0; q lies in the image (decided on the doubles); h_length(q) > 0; every history
+ *            colour, variance and guide word at q is finite; h_ids(q) == ids(p); |n_p - n_q|^2 <= tau_normal^2 (squared norm (a a + b b) + c c of the double
+ *            differences)
+ *   sums     over the accepted taps in tap order: sw += wt; sc_k += wt * h_colour_k(q) per channel; sv_k += wt * h_variance_k(q); sn += wt * (double) h_length(q)
+ *   sw == 0  the outputs are the converted inputs and o_length = 1
+ *   else     hc = sc / sw, hv = sv / sw, hn = sn / sw; n = min(hn + 1, max_length); alpha = max(1 / n, alpha_min);
+ *            o_colour = (1 - alpha) * hc + alpha * colour; o_variance = ((1 - alpha) * (1 - alpha)) * hv + (alpha * alpha) * variance (the frames are independent
+ *            estimates); o_length = (float) n
+ * Scaling colour and h_colour by a power of two c and the variances by c^2 scales the outputs by exactly c and c^2.
+ * The caller keeps the current normal / ids as the next frame's h_normal / h_ids; the stage copies none.  Out of scope: a world-space position test of the history
+ * (it would need the point's previous position as a plane) and SVGF's 3 x 3 variance prefilter.
+ * DTOF_ERR_INVALID before any HIP call, with no output touched: n_planes outside 1 .. 4; width or height < 1 or > 65535; a null buffers, params, colour, flow,
+ * o_colour or o_length pointer; a history that is only partly present (with a history: h_colour, h_length and the history of every present variance / normal / ids);
+ * a history buffer whose current buffer is absent; o_variance present without variance or absent with it; a misaligned buffer; an output that overlaps an input or
+ * another output; alpha_min outside (0, 1], max_length < 1, tau_normal <= 0 with normals (or its square not a finite double > 0), or any of them not finite.
+ * With valid arguments and no device: DTOF_ERR_HIP.  There is no CPU fallback. */
+typedef struct {
+    double alpha_min;      /* (0, 1]: the least weight of the current frame */
+    double max_length;     /* >= 1: the history length is clamped to it */
+    double tau_normal;     /* > 0; read only when normals are present */
+} dtof_temporal_params;
+typedef struct {
+    /* the current frame */
+    const float *colour;            /* [K][H][W][3] */
+    const double *variance;         /* [K][H][W] or NULL */
+    const float *normal;            /* [H][W][3] or NULL */
+    const float *ids;               /* [H][W] or NULL, e.g. the aov film's shape_index plane */
+    const float *flow;              /* [H][W][2] */
+    /* the history: all NULL for a first frame, otherwise h_colour, h_length and the counterpart of every present buffer above */
+    const double *h_colour;         /* [K][H][W][3]: o_colour of the previous call */
+    const double *h_variance;       /* [K][H][W]: o_variance of the previous call */
+    const float *h_normal, *h_ids;  /* normal, ids of the previous call */
+    const float *h_length;          /* [H][W]: o_length of the previous call */
+    /* outputs */
+    double *o_colour;               /* [K][H][W][3] */
+    double *o_variance;             /* [K][H][W]; present iff variance is */
+    float *o_length;                /* [H][W] */
+    float *o_colour_f32;            /* [K][H][W][3] or NULL: o_colour rounded once, what dtof_denoise_async takes as its colour */
+} dtof_temporal_buffers;
+/* DEVICE pointers in *d_buffers (the struct itself is host memory); one launch on the scene's stream, no host wait, no scratch. */
+int dtof_denoise_temporal_async(dtof_scene *scene, const dtof_temporal_buffers *d_buffers, int n_planes, int32_t width, int32_t height,
+                                const dtof_temporal_params *params);
+/* The same with HOST pointers and no scene: uploads, runs, downloads and synchronises once. */
+int dtof_denoise_temporal(const dtof_temporal_buffers *buffers, int n_planes, int32_t width, int32_t height, const dtof_temporal_params *params);
 
 /* ---------------------------------------------------------------- adaptive sampling (opt-in)
  * A dense base pass, then further passes only over the pixels whose ESTIMATED error is still above a tolerance; the estimate comes from the moment film of the passes so

@@ -4,6 +4,8 @@
 #include "dtof_host.h"
 #include "dtof_reconstruct.h"
 #include "dtof_denoise.h"
+#include "dtof_temporal.h"
+#include "dtof_world_to_pixel.h"
 #include "dtof_film64.h"
 #include "dtof_moments.h"
 #include "dtof_adaptive.h"
@@ -650,7 +652,7 @@ static AovArgs aov_args(const dtof_scene *sc, const int32_t *types, int n_types)
     if (!types) throw std::runtime_error("null argument");
     if (n_types < 1) throw std::runtime_error("No AOVs were specified!");
     need_sensor(sc);
-    AovArgs a; a.film = nullptr; a.values = nullptr; a.n_channels = 0; a.slots[0] = a.slots[1] = a.slots[2] = 0;
+    AovArgs a; memset(&a, 0, sizeof a);
     for (int i = 0; i < n_types; ++i) {
         if (types[i] < 0 || types[i] >= kAovTypes) throw std::runtime_error("AOV type " + std::to_string(types[i]) + " is not one of the DTOF_AOV_* constants");
         for (int k = 0; k < kAovTypeChannels[types[i]]; ++k, ++a.n_channels) {
@@ -670,11 +672,8 @@ int dtof_render_aovs(dtof_scene *sc, uint32_t seed, uint32_t spp, uint32_t n_pas
         render_cells(sc, rows_request(seed, spp, 0, 0), &a, n_passes, 1 + (int) a.n_channels, developed, out_planes, stats);
     });
 }
-int dtof_sample_aov_lanes(dtof_scene *sc, uint32_t seed, uint32_t spp, const int32_t *types, int n_types, uint64_t lane_begin, uint64_t n, float *out_lanes12,
-                          float *out_values) {
-    return guarded([&] {
-        if (!sc || !out_lanes12 || !out_values) throw std::runtime_error("null argument");
-        AovArgs a = aov_args(sc, types, n_types);
+// the per-lane entries of the aov and the flow film: the channels of `a` for lanes [lane_begin, lane_begin + n)
+static void sample_channel_lanes(dtof_scene *sc, AovArgs a, uint32_t seed, uint32_t spp, uint64_t lane_begin, uint64_t n, float *out_lanes12, float *out_values) {
         ensure_device(sc);
         sc->stop = false;
         if (n == 0) return;
@@ -687,6 +686,37 @@ int dtof_sample_aov_lanes(dtof_scene *sc, uint32_t seed, uint32_t spp, const int
         { RenderRequest rq; rq.seed = seed; rq.spp = spp; rq.lane_dump = lanes.data(); rq.dump_begin = lane_begin; rq.dump_n = n; rq.aov = &a; render_rows(sc, rq); }
         HIP_CHECK(hipMemcpy(out_values, d_values.p, (size_t) n * a.n_channels * sizeof(float), hipMemcpyDeviceToHost));
         for (uint64_t i = 0; i < n; ++i) { memcpy(out_lanes12 + 12 * i, &lanes[i], 36); memcpy(out_lanes12 + 12 * i + 9, own[i].rgb, 12); }
+}
+int dtof_sample_aov_lanes(dtof_scene *sc, uint32_t seed, uint32_t spp, const int32_t *types, int n_types, uint64_t lane_begin, uint64_t n, float *out_lanes12,
+                          float *out_values) {
+    return guarded([&] {
+        if (!sc || !out_lanes12 || !out_values) throw std::runtime_error("null argument");
+        sample_channel_lanes(sc, aov_args(sc, types, n_types), seed, spp, lane_begin, n, out_lanes12, out_values);
+    });
+}
+
+// ---------------------------------------------------------------- the flow film (k_aov<LDS, FLOW = true>, dtof_aov.hip)
+// the request of both entries: the aov request with the private channel table (20, 21) and S
+static AovArgs flow_args(const dtof_scene *sc) {
+    need_sensor(sc);
+    AovArgs a; memset(&a, 0, sizeof a);
+    a.n_channels = 2; a.slots[0] = (uint64_t) kAovSlots | ((uint64_t) (kAovSlots + 1) << 5u);
+    a.flow = 1;
+    world_to_pixel(sc->host.sensor, a.S);
+    return a;
+}
+int dtof_render_flow(dtof_scene *sc, uint32_t seed, uint32_t spp, uint32_t n_passes, int developed, double *out_planes, dtof_render_stats *stats) {
+    return guarded([&] {
+        if (!sc || !out_planes) throw std::runtime_error("null argument");
+        if (n_passes == 0) throw std::runtime_error("the flow film needs at least one pass");
+        AovArgs a = flow_args(sc);
+        render_cells(sc, rows_request(seed, spp, 0, 0), &a, n_passes, 3, developed, out_planes, stats);
+    });
+}
+int dtof_sample_flow_lanes(dtof_scene *sc, uint32_t seed, uint32_t spp, uint64_t lane_begin, uint64_t n, float *out_lanes12, float *out_flow2) {
+    return guarded([&] {
+        if (!sc || !out_lanes12 || !out_flow2) throw std::runtime_error("null argument");
+        sample_channel_lanes(sc, flow_args(sc), seed, spp, lane_begin, n, out_lanes12, out_flow2);
     });
 }
 
@@ -743,6 +773,45 @@ int dtof_denoise(const float *colour, int n_planes, int32_t width, int32_t heigh
         round_trip({ { colour, k * n * 3 * sizeof(float) }, { variance, variance ? k * n * sizeof(double) : 0 }, { normal, normal ? n * 3 * sizeof(float) : 0 }, { position, position ? n * 3 * sizeof(float) : 0 } },
                    { { out_colour, k * n * 3 * sizeof(double) }, { out_variance, out_variance ? k * n * sizeof(double) : 0 } }, [&](void *const *in, void *const *out) {
             launch_denoise(a, (const float *) in[0], (const double *) in[1], (const float *) in[2], (const float *) in[3], (double *) out[0], (double *) out[1], d_scratch.p, nullptr);
+        });
+    });
+}
+
+// ---------------------------------------------------------------- denoiser, temporal stage (dtof_temporal.hip)
+// every refusal of the two entries (temporal_check, dtof_temporal_args.h), before a device is touched
+static TemporalArgs temporal_args(const dtof_temporal_buffers *b, int n_planes, int32_t width, int32_t height, const dtof_temporal_params *p) {
+    if (!b) throw std::runtime_error("dtof_denoise_temporal: null argument");
+    const TemporalBuffers t { b->colour, b->variance, b->normal, b->ids, b->flow, b->h_colour, b->h_variance, b->h_normal, b->h_ids, b->h_length,
+                              b->o_colour, b->o_variance, b->o_length, b->o_colour_f32 };
+    TemporalArgs a;
+    const std::string err = temporal_check(t, n_planes, width, height, p == nullptr, p ? p->alpha_min : 0.0, p ? p->max_length : 0.0, p ? p->tau_normal : 0.0, &a);
+    if (!err.empty()) throw std::runtime_error("dtof_denoise_temporal: " + err);
+    return a;
+}
+int dtof_denoise_temporal_async(dtof_scene *sc, const dtof_temporal_buffers *b, int n_planes, int32_t width, int32_t height, const dtof_temporal_params *params) {
+    return guarded([&] {
+        if (!sc) throw std::runtime_error("null argument");
+        const TemporalArgs a = temporal_args(b, n_planes, width, height, params);
+        ensure_device(sc);
+        const TemporalDeviceBuffers d { b->colour, b->variance, b->normal, b->ids, b->flow, b->h_colour, b->h_variance, b->h_normal, b->h_ids, b->h_length,
+                                        b->o_colour, b->o_variance, b->o_length, b->o_colour_f32 };
+        launch_temporal(a, d, sc->stream);
+        HIP_CHECK(hipGetLastError());
+    });
+}
+int dtof_denoise_temporal(const dtof_temporal_buffers *b, int n_planes, int32_t width, int32_t height, const dtof_temporal_params *params) {
+    return guarded([&] {
+        const TemporalArgs a = temporal_args(b, n_planes, width, height, params);
+        const size_t n = (size_t) width * height, k = (size_t) n_planes;
+        auto sized = [](const void *p, size_t bytes) { return HostArray { p, p ? bytes : 0 }; };
+        round_trip({ sized(b->colour, k * n * 12), sized(b->variance, k * n * 8), sized(b->normal, n * 12), sized(b->ids, n * 4), sized(b->flow, n * 8),
+                     sized(b->h_colour, k * n * 24), sized(b->h_variance, k * n * 8), sized(b->h_normal, n * 12), sized(b->h_ids, n * 4), sized(b->h_length, n * 4) },
+                   { sized(b->o_colour, k * n * 24), sized(b->o_variance, k * n * 8), sized(b->o_length, n * 4), sized(b->o_colour_f32, k * n * 12) },
+                   [&](void *const *in, void *const *out) {
+            const TemporalDeviceBuffers d { (const float *) in[0], (const double *) in[1], (const float *) in[2], (const float *) in[3], (const float *) in[4],
+                                            (const double *) in[5], (const double *) in[6], (const float *) in[7], (const float *) in[8], (const float *) in[9],
+                                            (double *) out[0], (double *) out[1], (float *) out[2], (float *) out[3] };
+            launch_temporal(a, d, nullptr);
         });
     });
 }

@@ -1,6 +1,7 @@
 // dtof_abi_scene.hip -- the C ABI (include/dtof.h) of the scene object: load / free / last error, the integrator and sampler plugins, scene info and export,
 // the caller's film layout and stream, cancellation and the plan-facts counters.  No entry here launches a kernel.
 #include "dtof_host.h"
+#include "dtof_world_to_pixel.h"
 #include <cmath>
 #include <map>
 
@@ -129,6 +130,16 @@ int dtof_scene_get_info(const dtof_scene *sc, dtof_scene_info *info) {
         info->filter_radius = se.filter_radius;
         info->filter_halo = se.filter == FILTER_BOX ? 0 : (int32_t) std::ceil(se.filter_radius - .5f);
         info->has_alpha = se.alpha ? 1 : 0;
+    });
+}
+
+int dtof_scene_world_to_pixel(const dtof_scene *sc, double *out12) {
+    return guarded([&] {
+        if (!sc || !out12) throw std::runtime_error("null argument");
+        need_sensor(sc);
+        double s[12];
+        world_to_pixel(sc->host.sensor, s);
+        memcpy(out12, s, sizeof s);
     });
 }
 

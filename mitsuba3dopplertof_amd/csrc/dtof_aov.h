@@ -29,11 +29,19 @@ constexpr uint32_t kAovSlotsPerWord = 12;
 // first slot and channel count of type t (the DTOF_AOV_* constants of include/dtof.h, in their order)
 constexpr int kAovTypeSlot[kAovTypes] = { 0, 1, 4, 6, 9, 12, 15, 18, 19 }, kAovTypeChannels[kAovTypes] = { 1, 3, 2, 3, 3, 3, 3, 1, 1 };
 
+// The FLOW film (dtof_render_flow, dtof_sample_flow_lanes; the definition: include/dtof.h) is the same kernel compiled with two more values per lane, the motion
+// vector of the camera ray's hit over the shutter interval:
+//   20, 21       flow x, y                                 (no counterpart in the reference's aov integrator: the nine types above are not extended)
+// Only a request with AovArgs::flow set reaches those instantiations; its private channel table is (20, 21).
+constexpr int kAovFlowSlots = kAovSlots + 2;
+
 struct AovArgs {
     double *film;            // cells of kMomentCell doubles per pixel of the crop window, or
     float *values;           // ... nullptr, or [n_lanes][n_channels]: the values of the batch's lanes instead of the splat
     uint32_t n_channels;     // 1 .. kAovMaxChannels
     uint64_t slots[3];       // slot[c] = the 5 bits from bit 5 * (c % kAovSlotsPerWord) of word c / kAovSlotsPerWord
+    uint32_t flow;           // 1: the FLOW instantiations, whose lanes have the values 20 and 21; S is read only then
+    double S[12];            // world to film pixel, rows x, y, w (dtof_world_to_pixel.h)
 };
 
 // One batch behind k_generate: q.ray_a / ray_b / pos of lanes [0, rp.n_lanes).  Stages the scene like launch_velocity.

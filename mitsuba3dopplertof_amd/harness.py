@@ -173,6 +173,74 @@ def run_scene_velocity_map_denoised(scene, total_spp, offsets=(0.0, 0.25), denoi
     return velocity_map_denoised(scene, n_pass, single, offsets, exposure_time, w_g, **(denoiser or {}))
 
 
+class TemporalVelocityMap:
+    """velocity_map_denoised over the frames of an animation, with the denoiser's temporal stage between the films and the spatial levels: every frame's four ToF
+    films are blended with the history of the frames before, reprojected through the flow film (Scene.render_flow times `flow_scale`, the frame interval over
+    the exposure) and rejected where the aov film's shape_index or shading normal says the surface is another.  Exactly two offsets, as there.  `denoiser_kw`:
+    levels and sigmas of Denoiser, and alpha_min, max_length, tau_normal of its temporal stage.  The loop over the frames' scenes stays with the caller:
+
+        tvm = TemporalVelocityMap((0.0, 0.25), 0.0015, 30)
+        for i, scene in enumerate(frames):
+            noisy, spatial, temporal = tvm.frame(scene, n_passes, spp, seed=i * n_passes)
+
+    The state is the history of the last frame (`history`; None before the first); `details` holds the last frame's films, variances, guides and flow.  The
+    sharded renders and the command line have no temporal mode."""
+
+    def __init__(self, offsets=(0.0, 0.25), exposure_time=0.0015, w_g=30, flow_scale=1.0, **denoiser_kw):
+        self.offsets = [float(o) for o in offsets]
+        if len(self.offsets) != 2:
+            raise ValueError("a denoised velocity map takes two offsets: the four films of one traversal")
+        self.exposure_time, self.w_g, self.flow_scale = exposure_time, w_g, float(flow_scale)
+        self.temporal_kw = {k: denoiser_kw.pop(k) for k in ("alpha_min", "max_length", "tau_normal") if k in denoiser_kw}
+        self.denoiser_kw = denoiser_kw
+        self.history, self.details = None, None
+
+    def frame(self, scene, n_passes, spp, seed=0):
+        """One frame: passes of `spp` samples with seeds seed, seed + 1, ... -> (noisy map, spatially denoised map, temporally and spatially denoised map), (H, W)"""
+        from . import Denoiser
+        t, w_g = self.exposure_time, self.w_g
+        variants = [(0.0, o) for o in self.offsets] + [(1.0, o) for o in self.offsets]
+        acc = None
+        for i in range(n_passes):
+            img = scene.render(seed=seed + i, spp=spp, variants=variants).astype(np.float32)
+            acc = img if acc is None else acc + img
+        stats = scene.last_stats
+        tof = [to_tof_image(im, t) for im in acc / np.float32(n_passes)]
+        noisy_map = calc_velocity_from_homo_heteros(tof[:2], tof[2:], t, w_g)
+        m = scene.render_moments(seed=seed, spp=spp, n_passes=n_passes, variants=variants)
+        n_samples = scene.last_stats["n_paths"] / float(tof[0].shape[0] * tof[0].shape[1])
+        variance = moment_statistics(m, n_samples)["variance"][..., 1] / n_samples * (t * t)
+        guides = scene.render_aovs("p:position,n:sh_normal,i:shape_index", seed=seed, spp=spp, n_passes=n_passes)
+        flow = (scene.render_flow(seed=seed, spp=spp, n_passes=n_passes) * self.flow_scale).astype(np.float32)
+        scene.last_stats = stats
+        films = np.repeat(np.stack(tof).astype(np.float32)[..., None], 3, axis=3)      # (4, H, W, 3): a ToF plane replicated, as in velocity_map_denoised
+        h, w = films.shape[1:3]
+        kw = dict(normals=guides["n"], position=guides["p"], variance=variance)
+        spatial, _ = Denoiser((w, h), normals=True, position=True, variance=True, **self.denoiser_kw)(films, **kw)
+        den = Denoiser((w, h), normals=True, position=True, variance=True, temporal=True, ids=True, **self.denoiser_kw, **self.temporal_kw)
+        # the index plane is a filtered mean: a whole number up to rounding where every sample of the footprint met one shape -- made exact, so that frames compare
+        # equal there -- and a fraction on the edges, which matches no history but its own
+        ids = np.where(np.abs(guides["i"] - np.rint(guides["i"])) < 1e-4, np.rint(guides["i"]), guides["i"])
+        out, out_var, self.history = den(films, flow=flow, ids=ids, history=self.history, **kw)
+        maps = [calc_velocity_from_homo_heteros(list(o[:2, ..., 0]), list(o[2:, ..., 0]), t, w_g) for o in (spatial, out)]
+        self.details = {"homodyne": tof[:2], "heterodyne": tof[2:], "variance": variance, "denoised_variance": out_var, "guides": guides, "flow": flow, "denoiser": den}
+        return noisy_map, maps[0], maps[1]
+
+
+def camera_flow(position, S_prev, S_cur):
+    """The flow of STATIC geometry under a moving camera, for Denoiser(temporal=True): `position` (H, W, 3), the aov film's position plane of the current frame;
+    S_prev, S_cur (3, 4), Scene.world_to_pixel() of the previous and of the current frame's scene (what `to_sensor` is for in the reference's denoiser call).
+    flow = pix_cur(p) - pix_prev(p) as (H, W, 2) float32: a point's pixel motion from the previous frame to this one.  NaN -- "no history" to the temporal stage --
+    where the point is not in front of both cameras.  A pixel whose rays missed carries the plane's 0 and a meaningless flow; its id rejects the history."""
+    p = np.concatenate([np.asarray(position, np.float64), np.ones(np.shape(position)[:-1] + (1,))], axis=-1)
+    pix = []
+    for S in (np.asarray(S_prev, np.float64), np.asarray(S_cur, np.float64)):
+        w = p @ S[2]
+        with np.errstate(all="ignore"):
+            pix.append(np.where((w > 0)[..., None], np.stack([p @ S[0], p @ S[1]], axis=-1) / w[..., None], np.nan))
+    return (pix[1] - pix[0]).astype(np.float32)
+
+
 def run_scene_moments(scene, total_spp=1024, variants=((0, 0), (1, 0)), **integrator_kwargs):
     """The moment film of run_scene_doppler_tof_variants' render: the same integrator dictionary, the same passes (min(1024, total_spp) samples each) and seeds
     0, 1, ..., but ONE Scene.render_moments call whose passes all accumulate into one film.  `variants`: up to four (hetero_frequency, hetero_offset) pairs of one
