@@ -657,6 +657,11 @@ uint64_t dtof_scene_plan_facts_launches(const dtof_scene *scene);
 /* The FACTS mask (dtof_kernels.h: kFact*) of the first-bounce kernel compiled with plan facts that the scene's last frame launched, 0 if it launched none: tells the
  * instantiations apart, which the count above cannot. */
 uint32_t dtof_scene_last_plan_facts(const dtof_scene *scene);
+/* Which kernel splatted the last batch of the scene's last frame into the float32 film, and with which shape (csrc/dtof_splat_choice.h: SplatChoice::packed):
+ * bits 0-2 the kernel (1 generic, 2 tent3, 3 x8, 4 pixel, 5 the first-bounce kernel itself, "fused"), bits 3-6 the footprint's width in pixels (15: 15 or more),
+ * bits 7-11 log2 of the lanes of a segment (tent3: seg, x8: seg8) or of the threads per pixel (pixel: parts), bits 12-31 the samples per thread (pixel: chunk).
+ * 0: the frame splatted nothing into a float32 film (no lanes, a lane dump, the float64, moment or aov film).  dtof_render_stats is unchanged. */
+uint32_t dtof_scene_last_splat(const dtof_scene *scene);
 
 /* Per-lane debugging entry (SURVEY 8b "dtof_sample_lanes"): evaluates wavefront lanes
  * [lane_begin, lane_begin+n) exactly as dtof_render would (multi-pass renders: index = pass * wavefront_size + lane, a range must stay

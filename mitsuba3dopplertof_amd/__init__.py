@@ -114,6 +114,9 @@ def _lib():
     if hasattr(L, "dtof_scene_last_plan_facts"):
         L.dtof_scene_last_plan_facts.argtypes = [vp]
         L.dtof_scene_last_plan_facts.restype = C.c_uint32
+    if hasattr(L, "dtof_scene_last_splat"):
+        L.dtof_scene_last_splat.argtypes = [vp]
+        L.dtof_scene_last_splat.restype = C.c_uint32
     L.dtof_sample_lanes.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64, vp]
     L.dtof_sample_lanes_valid.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64, vp, vp]
     L.dtof_develop_rgba.argtypes = [vp, vp, vp, C.c_int64]
@@ -606,6 +609,27 @@ class Scene:
         """(objects of the flat table, index of its one wall) compiled into the kernel the last frame launched, None if that kernel has no shape"""
         m = self.last_plan_mask
         return ((m >> 19) & 0xf, (m >> 23) & 0x7) if m & (1 << 18) else None
+
+    @property
+    def last_splat(self):
+        """which kernel splatted the last batch of the last frame into the float32 film, and its shape (dtof_scene_last_splat): a dict with "kernel" ("generic",
+        "tent3", "x8", "pixel", "fused") and "n" (the footprint is n x n pixels), plus "seg" (tent3), "seg8" (x8) or "parts" and "chunk" (pixel); None if the frame
+        splatted nothing into a float32 film, or the library (an older build timed through DTOF_LIB) has no such entry"""
+        L = _lib()
+        if not hasattr(L, "dtof_scene_last_splat"):
+            return None
+        w = int(L.dtof_scene_last_splat(self._h))
+        kernel = (None, "generic", "tent3", "x8", "pixel", "fused")[w & 7]
+        if kernel is None:
+            return None
+        out = {"kernel": kernel, "n": (w >> 3) & 15}
+        if kernel == "tent3":
+            out["seg"] = 1 << ((w >> 7) & 31)
+        elif kernel == "x8":
+            out["seg8"] = 1 << ((w >> 7) & 31)
+        elif kernel == "pixel":
+            out["parts"], out["chunk"] = 1 << ((w >> 7) & 31), w >> 12
+        return out
 
     def set_integrator(self, props):
         _check(_lib().dtof_scene_set_integrator(self._h, *_plugin_args(props)))

@@ -269,5 +269,6 @@ int dtof_scene_set_stream(dtof_scene *sc, void *hip_stream) {
 void dtof_cancel(dtof_scene *sc) { if (sc) sc->stop = true; }
 uint64_t dtof_scene_plan_facts_launches(const dtof_scene *sc) { return sc ? sc->plan_facts_launches : 0; }
 uint32_t dtof_scene_last_plan_facts(const dtof_scene *sc) { return sc ? sc->last_plan_facts : 0; }
+uint32_t dtof_scene_last_splat(const dtof_scene *sc) { return sc ? sc->last_splat : 0; }
 
 }  // extern "C"

@@ -122,6 +122,7 @@ struct dtof_scene {
     std::atomic<bool> stop { false };
     uint64_t plan_facts_launches = 0;        // first-bounce launches that took a kernel compiled with plan facts, since the scene was loaded (dtof_scene_plan_facts_launches)
     uint32_t last_plan_facts = 0;            // ... and the FACTS mask of the one the last frame launched, 0 if it launched none (dtof_scene_last_plan_facts)
+    uint32_t last_splat = 0;                 // the float32 splat kernel and shape of the last frame's last batch (SplatChoice::packed, kSplatFusedWord; dtof_scene_last_splat)
     // reusable statistics plumbing (creating events / pinned memory per call costs ~0.3 ms)
     std::vector<hipEvent_t> event_pool; size_t events_used = 0;
     // frames enqueued by dtof_render_rows_async and not collected yet: their events (frame, stages) and launch counters; no host synchronisation until dtof_async_collect

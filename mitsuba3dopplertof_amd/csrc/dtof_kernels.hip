@@ -18,6 +18,7 @@
 // Compiled with -ffp-contract=off: an fma is issued exactly where fmaf() is written, so a lane's
 // arithmetic is bit-identical to the scalar restatement in oracle/ (same helper algebra in dtof_math.h).
 #include "dtof_device.h"
+#include "dtof_splat_choice.h"
 #include <algorithm>
 #include <string>
 
@@ -695,37 +696,25 @@ void launch_velocity(const uint8_t *scene, uint32_t scene_bytes, const RenderPar
     if (sw) hipLaunchKernelGGL(k_velocity<true>, dim3(nblk(rp.n_lanes)), dim3(kBlock), lds, s, scene, scene_bytes, sw, rp, q);
     else hipLaunchKernelGGL(k_velocity<false>, dim3(nblk(rp.n_lanes)), dim3(kBlock), lds, s, scene, scene_bytes, sw, rp, q);
 }
-void launch_splat(const RenderParams &rp, const Queues &q, float *film, uint64_t plane_stride, const LaunchSwitches &ls, hipStream_t s) {
-    if (rp.n_lanes == 0) return;
+uint32_t launch_splat(const RenderParams &rp, const Queues &q, float *film, uint64_t plane_stride, const LaunchSwitches &ls, hipStream_t s) {
+    static_assert(kSplatBlock == (uint32_t) kBlock && kSplatSamplesPerLane == kSplatPer, "dtof_splat_choice.h describes these kernels");
     size_t stride = (size_t) plane_stride;   // floats between the films of the batched offsets
-    bool fast = rp.filter == FILTER_TENT && rp.filter_radius <= 1.f && rp.filter_radius > .5f && rp.spp_log2 != 0xffffffffu && rp.spp >= 2;
-    // footprint of the filter in pixels (ImageBlock::put: the pixels within ceil(radius - 0.5) of the sample's): 1 (box), 3 or 5 take the
-    // eight-samples-per-lane kernel when spp is a power of two >= 16
-    const int reach = rp.filter == FILTER_BOX ? 0 : (int) ceilf(rp.filter_radius - .5f);
-    // the Lanczos filter (default radius 3: a 7 x 7 footprint) always takes the per-lane kernel
-    const bool lanczos = rp.filter == FILTER_LANCZOS;
-    if ((rp.filter == FILTER_BOX || (reach >= 1 && reach <= 2)) && !lanczos && rp.spp_log2 != 0xffffffffu && rp.spp >= 2 * kSplatPer && ls.splat == 0) {
-        const uint32_t groups = rp.n_lanes / kSplatPer, seg8 = rp.spp / kSplatPer < 64 ? rp.spp / kSplatPer : 64;
-        const int n = 2 * reach + 1;
-        const uint32_t lds = (kBlock / seg8) * n * n * 16u;
-        if (lds <= 64u * 1024u) {
+    // which kernel, and its shape: splat_choice (dtof_splat_choice.h) decides, this function launches what it says
+    SplatFacts f;
+    f.filter = rp.filter; f.radius = rp.filter_radius; f.spp = rp.spp; f.spp_log2 = rp.spp_log2; f.n_lanes = rp.n_lanes; f.splat_switch = ls.splat;
+    const SplatChoice c = splat_choice(f);
+    const int n = (int) c.n;
+    if (c.kernel == kSplatX8) {
+        const uint32_t groups = rp.n_lanes / kSplatPer, seg8 = c.seg, lds = c.lds;
 #define DTOF_SPLAT_X8(NN_, F_) hipLaunchKernelGGL((k_splat_x8<NN_, F_>), dim3(nblk(groups)), dim3(kBlock), lds, s, rp, q, film, stride, seg8)
-            if (n == 1) DTOF_SPLAT_X8(1, FILTER_BOX);
-            else if (rp.filter == FILTER_TENT) { if (n == 3) DTOF_SPLAT_X8(3, FILTER_TENT); else DTOF_SPLAT_X8(5, FILTER_TENT); }
-            else if (rp.filter == FILTER_GAUSSIAN) { if (n == 3) DTOF_SPLAT_X8(3, FILTER_GAUSSIAN); else DTOF_SPLAT_X8(5, FILTER_GAUSSIAN); }
-            else if (rp.filter == FILTER_MITCHELL) { if (n == 3) DTOF_SPLAT_X8(3, FILTER_MITCHELL); else DTOF_SPLAT_X8(5, FILTER_MITCHELL); }
-            else { if (n == 3) DTOF_SPLAT_X8(3, FILTER_CATMULLROM); else DTOF_SPLAT_X8(5, FILTER_CATMULLROM); }
+        if (n == 1) DTOF_SPLAT_X8(1, FILTER_BOX);
+        else if (rp.filter == FILTER_TENT) { if (n == 3) DTOF_SPLAT_X8(3, FILTER_TENT); else DTOF_SPLAT_X8(5, FILTER_TENT); }
+        else if (rp.filter == FILTER_GAUSSIAN) { if (n == 3) DTOF_SPLAT_X8(3, FILTER_GAUSSIAN); else DTOF_SPLAT_X8(5, FILTER_GAUSSIAN); }
+        else if (rp.filter == FILTER_MITCHELL) { if (n == 3) DTOF_SPLAT_X8(3, FILTER_MITCHELL); else DTOF_SPLAT_X8(5, FILTER_MITCHELL); }
+        else { if (n == 3) DTOF_SPLAT_X8(3, FILTER_CATMULLROM); else DTOF_SPLAT_X8(5, FILTER_CATMULLROM); }
 #undef DTOF_SPLAT_X8
-            return;
-        }
-    }
-    const bool small_pow2_tent = fast && rp.spp < 2 * kSplatPer;   // 2, 4, 8 spp under the radius-1 tent: k_splat_tent3 (one DPP segment per pixel)
-    if ((rp.filter == FILTER_BOX || (reach >= 1 && reach <= 2)) && !lanczos && !small_pow2_tent && ls.splat == 0) {
-        // any other sample count: one thread per pixel; enough threads to fill the chip (parts of a pixel's samples, each >= 8, when the frame is small)
-        const uint32_t n_pixels = rp.n_lanes / rp.spp, n = 2 * reach + 1;
-        uint32_t parts = 1;
-        while ((uint64_t) n_pixels * parts < 131072u && rp.spp / (parts * 2) >= 8) parts *= 2;
-        const uint32_t chunk = (rp.spp + parts - 1) / parts, threads = n_pixels * parts;
+    } else if (c.kernel == kSplatPixel) {
+        const uint32_t parts = c.parts, chunk = c.chunk, threads = rp.n_lanes / rp.spp * parts;
 #define DTOF_SPLAT_PIXEL(NN_, F_) hipLaunchKernelGGL((k_splat_pixel<NN_, F_>), dim3((threads + 63) / 64), dim3(64), 0, s, rp, q, film, stride, parts, chunk, threads)
         if (n == 1) DTOF_SPLAT_PIXEL(1, FILTER_BOX);
         else if (rp.filter == FILTER_TENT) { if (n == 3) DTOF_SPLAT_PIXEL(3, FILTER_TENT); else DTOF_SPLAT_PIXEL(5, FILTER_TENT); }
@@ -733,14 +722,12 @@ void launch_splat(const RenderParams &rp, const Queues &q, float *film, uint64_t
         else if (rp.filter == FILTER_MITCHELL) { if (n == 3) DTOF_SPLAT_PIXEL(3, FILTER_MITCHELL); else DTOF_SPLAT_PIXEL(5, FILTER_MITCHELL); }
         else { if (n == 3) DTOF_SPLAT_PIXEL(3, FILTER_CATMULLROM); else DTOF_SPLAT_PIXEL(5, FILTER_CATMULLROM); }
 #undef DTOF_SPLAT_PIXEL
-        return;
-    }
-    if (fast && ls.splat != 2) {
-        uint32_t seg = rp.spp < 64 ? rp.spp : 64;
-        hipLaunchKernelGGL(k_splat_tent3, dim3(nblk(rp.n_lanes)), dim3(kBlock), 0, s, rp, q, film, stride, seg);
-    } else {
+    } else if (c.kernel == kSplatTent3) {
+        hipLaunchKernelGGL(k_splat_tent3, dim3(nblk(rp.n_lanes)), dim3(kBlock), 0, s, rp, q, film, stride, c.seg);
+    } else if (c.kernel == kSplatGeneric) {
         hipLaunchKernelGGL(k_splat_generic, dim3(nblk(rp.n_lanes)), dim3(kBlock), 0, s, rp, q, film, stride);
     }
+    return c.packed();
 }
 void launch_develop(const float *film, float *rgb, int64_t n, hipStream_t s) {
     if (n == 0) return;

@@ -9,6 +9,7 @@
 #include "dtof_host.h"
 #include "dtof_film64.h"
 #include "dtof_moments.h"
+#include "dtof_splat_choice.h"
 #include <dlfcn.h>
 #include <cstdio>
 #include <cstdlib>
@@ -501,7 +502,7 @@ void render_rows(dtof_scene *sc, const RenderRequest &rq) {
     check_pixel_list(sc, rq);
     ensure_device(sc);
     const FramePlan p = plan_frame(sc, rq);
-    sc->last_plan_facts = 0;
+    sc->last_plan_facts = 0; sc->last_splat = 0;
     RenderParams rp = p.rp;
     dtof_render_stats *const stats = rq.stats;
     const Queues q = sc->ws.prepare((uint32_t) p.batch, rp.n_offsets, rp.want_valid, p.launch.defer != 0, sc->id_shift);
@@ -597,7 +598,7 @@ void render_rows(dtof_scene *sc, const RenderRequest &rq) {
             // a request may name BOTH the moment film and the float64 film: one traversal, two films (the alpha plane of an rgba scene then goes to the float64 film only)
             if (rq.moments) launch_splat_moments(rp, q, rq.moments, s);
             if (rq.film64) launch_splat_f64(rp, q, rq.film64, rq.film64_stride, s);
-            if (!rq.moments && !rq.film64) launch_splat(rp, q, rq.film, rq.film_stride, p.launch, s);
+            if (!rq.moments && !rq.film64) sc->last_splat = launch_splat(rp, q, rq.film, rq.film_stride, p.launch, s);
             if (sc->host.sensor.alpha && (rq.film64 || !rq.moments)) {   // the alpha film (plane K behind the K offset films): the same splat over (valid, 0, 0) -- ImageBlock::put of aovs[3] (integrator.cpp:528-533)
                 RenderParams ra = rp; ra.n_offsets = 1;
                 Queues qa = q; qa.res = q.valid_out;
@@ -605,7 +606,7 @@ void render_rows(dtof_scene *sc, const RenderRequest &rq) {
                 else launch_splat(ra, qa, rq.film + (size_t) rp.n_offsets * rq.film_stride, rq.film_stride, p.launch, s);
             }
             tm.end(kStageSplat, t, s);
-        }
+        } else if (fused_splat_done) sc->last_splat = kSplatFusedWord;
         HIP_CHECK(hipGetLastError());   // a rejected launch (LDS size, launch bounds, grid) must not pass for an empty film
         HIP_CHECK(hipEventRecord(batch_done[batch_index & 1], s));
         if (stats) {   // per-iteration totals of this batch are reduced on the device; one small copy after the last batch

@@ -80,9 +80,10 @@ def gaussian_eval(x, radius, stddev):
     return np.maximum(_estrin10(x * x, gc), F32(0))
 
 
-def footprint(orc, osc, pos, spw):
+def footprint(orc, osc, pos, spw, first=None):
     """The taps of every lane: (flat pixel index (N, T) int64, in-bounds mask (N, T), weight w = wx * wy (N, T) float32 -- None for the box filter, whose one tap
-    adds the value itself)"""
+    adds the value itself).  first: the film pixel (N, 2) the footprint starts at instead of floor(pos) - n -- what a splat that anchors a sample at another pixel
+    than its own would compute (splat_ref's mutations; no expected value is built with it)."""
     se = osc.flat.sensor
     W, H = int(se["crop_w"]), int(se["crop_h"])
     N = len(pos)
@@ -93,7 +94,7 @@ def footprint(orc, osc, pos, spw):
     n = int(np.ceil(radius - F32(.5)))
     cnt = 2 * n + 1
     pos = np.ascontiguousarray(pos, F32)
-    pix = np.floor(pos).astype(np.int32) - np.int32(n)                  # (N, 2): x, y
+    pix = np.floor(pos).astype(np.int32) - np.int32(n) if first is None else np.asarray(first, np.int32).reshape(N, 2)      # (N, 2): x, y
     rel = (pix.astype(F32) + F32(.5)) - pos                             # (float) pix + .5f - pos, left to right, float32
     anchor = pix - np.asarray([se["crop_x"], se["crop_y"]], np.int32)
     L = orc.lib()
