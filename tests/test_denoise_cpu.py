@@ -235,7 +235,7 @@ def test_denoiser_checks_shapes_and_arguments(mi, monkeypatch):
             C.memset(out, 0, k * w * h * 3 * 8)
             return 0
 
-    monkeypatch.setattr(mi, "_lib", lambda: FakeLib())
+    monkeypatch.setattr(mi._abi, "_lib", lambda: FakeLib())
     w, h = 7, 5
     d = mi.Denoiser((w, h))
     out = d(np.ones((h, w, 3), np.float64))      # any float type is taken and converted

@@ -139,14 +139,14 @@ def test_the_python_property_unpacks_the_word(mi):
             return self.w
     sc = object.__new__(mi.Scene)
     sc._h = None
-    real = mi._lib
+    real = mi._abi._lib
     try:
         for word, want in ((0x9b, cases.x8(3, 2)), (0x31b, cases.x8(3, 64)), (0xd19c, cases.pixel(3, 8, 13)), (0x19a, cases.tent3(8)), (0x39, cases.generic(7)),
                            (5 | (3 << 3), cases.FUSED), (0, None)):
-            mi._lib = lambda w=word: Lib(w)
+            mi._abi._lib = lambda w=word: Lib(w)
             assert sc.last_splat == want, (hex(word), sc.last_splat)
     finally:
-        mi._lib = real
+        mi._abi._lib = real
         sc._h = None
     hdr = open(os.path.join(ROOT, "include", "dtof.h")).read()
     assert re.search(r"\buint32_t\s+dtof_scene_last_splat\s*\(const dtof_scene \*scene\)\s*;", hdr)

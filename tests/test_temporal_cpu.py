@@ -324,7 +324,7 @@ def test_denoiser_temporal_mode_checks_its_arguments(mi, monkeypatch):
             calls.append(("spatial", k, w, h, variance is not None, normal is not None, position is not None))
             return 0
 
-    monkeypatch.setattr(mi, "_lib", lambda: FakeLib())
+    monkeypatch.setattr(mi._abi, "_lib", lambda: FakeLib())
     w, h = 7, 5
     flow = np.zeros((h, w, 2))
     plain = mi.Denoiser((w, h), temporal=True)
