@@ -380,6 +380,72 @@ int dtof_develop_rgba_f64_async(dtof_scene *scene, const double *d_film64_rgbw, 
 int dtof_render_velocity_map_f64(dtof_scene *scene, uint32_t n_passes, uint32_t spp, const float *offsets, int n_offsets, double exposure_time, double w_g_mhz,
                                  double *out_velocity, double *out_velocity_pairs_or_null, float *out_tof_or_null, dtof_render_stats *stats);
 
+/* ---------------------------------------------------------------- modulation frequency per variant (opt-in)
+ * The illumination frequency w_g is in the position of hetero_frequency and hetero_offset: it enters eval_modulation_weight (src/integrators/dopplertofpath.cpp:60-77)
+ * through two prefactors, w_g itself and phi = 2 pi w_g / 300 * path_length, and nothing else of a path reads it.  The `_freq` entries below take one frequency per
+ * variant, w_g_mhz[n_variants] in MHz like the plugin property: film k is, bit for bit per lane, the render of a scene whose integrator carries
+ * hetero_frequency = variants[k].hetero_frequency, hetero_offset = variants[k].hetero_offset and w_g = w_g_mhz[k] (the constructor's roundings, :62-69:
+ * w_g = (float) (2 pi (double) f 1e6), phi_coef = (float) ((2 pi (double) f) / 300), f a float32).  w_g_mhz_or_null == NULL makes each of them the entry without
+ * `_freq`, bit for bit.  Refusals, DTOF_ERR_INVALID before any device call: those of the variants forms; frequencies without variants (variants == NULL or
+ * n_variants <= 0); a frequency that is not finite or not > 0.
+ * Out of scope: the device-film entries (rows, stripes and their async forms), the moment, pixel-list and adaptive entries and dtof_render_velocity_map keep the
+ * integrator's single w_g. */
+
+/* dtof_render_variants with a frequency per film (Integrator::render, include/mitsuba/render/integrator.h:74-79, on n_variants integrators that differ in w_g too). */
+int dtof_render_variants_freq(dtof_scene *scene, uint32_t seed, uint32_t spp, const dtof_modulation *variants, const float *w_g_mhz_or_null, int n_variants,
+                              float *out_rgb, dtof_render_stats *stats);
+/* dtof_render_variants_f64 with a frequency per film (ImageBlock::put, src/render/imageblock.cpp:414-531, and HDRFilm::develop, src/films/hdrfilm.cpp:305-406, with a
+ * double accumulator -- the accumulator type is all that differs). */
+int dtof_render_variants_freq_f64(dtof_scene *scene, uint32_t seed, uint32_t spp, const dtof_modulation *variants, const float *w_g_mhz_or_null, int n_variants,
+                                  float *out_images, double *out_films_or_null, dtof_render_stats *stats);
+/* dtof_sample_lanes_variants with a frequency per film (render_sample, src/render/integrator.cpp:476-530, per lane and film). */
+int dtof_sample_lanes_variants_freq(dtof_scene *scene, uint32_t seed, uint32_t spp, const dtof_modulation *variants, const float *w_g_mhz_or_null, int n_variants,
+                                    uint64_t lane_begin, uint64_t n, float *out_lanes12, uint32_t *out_valid, float *out_rgb);
+
+/* ---------------------------------------------------------------- depth map (opt-in)
+ * The range half of a correlation time-of-flight camera: the wrapped phase of the homodyne I / Q films at every modulation frequency, and with two or more frequencies
+ * the unwrapped path length, on the device.  With the sinusoidal low-pass weight amp * cos(phase + phi) (dopplertofpath.cpp:60-77, waveform_utils.h:36-62) the film at
+ * hetero_offset 0 is A cos(phi) and the one at 0.25 is -A sin(phi), phi = 2 pi w_g / 300 * path_length: hence the minus sign below.  Other waveforms are accepted;
+ * the harmonic error they put into the phase is a property of the camera, not of this code.  Per pixel, with F frequencies (every output EQUALS this, word for word;
+ * NaN payloads are unspecified):
+ *   I_j, Q_j  the float32 ToF values of planes i_planes[j], q_planes[j] of the sum: sum / (float) n_passes, ((0.2126f r + 0.7152f g) + 0.0722f b) * (float) exposure_time
+ *             (to_tof_image, doppler_tutorials/src/utils/image_utils.py:20-31, as dtof_velocity_map_async forms it)
+ *   ph_j      = atan2(-Q_j, I_j) in float32 (the kernels' atan2, bit for bit the oracle's orc_atan2f); p = (double) ph_j, + 2 pi (6.283185307179586) if p < 0;
+ *             frac_j = p / 2 pi;  amp_j = sqrt((double) I_j (double) I_j + (double) Q_j (double) Q_j)
+ *   L_j       = 300.0 / w_g_mhz[j] (the constant of dopplertofpath.cpp:64), w_j = frac_j * L_j
+ *   F == 1    path = w_0, wraps 0, residual 0
+ *   F > 1     for n = 0 .. N - 1, N = (int64) floor(max_path_length / L_0) + 1: c = w_0 + (double) n * L_0; for j >= 1 in order m_j = rint((c - w_j) / L_j)
+ *             (ties to even; negative: 0), e_j = w_j + m_j * L_j, r_j = e_j - c; err = sum of r_j * r_j from 0.0 in j order.  The candidate with the smallest err wins,
+ *             the first on ties, a NaN never; if none wins every output of the pixel is NaN and its wraps are -1.
+ *             S = amp_0 + amp_1 + ...; path = S > 0 ? (amp_0 * c + amp_1 * e_1 + ...) / S : 0, both summed left to right
+ *   outputs   depth = 0.5 * path, residual = sqrt(err), wraps[j] (n, m_1, ...), amplitude[j] = amp_j, phase[j] = ph_j
+ * A max_path_length of exactly the unambiguous range (300 / gcd of whole-MHz frequencies) admits the first candidate of the NEXT period, which agrees with the other
+ * frequencies as well as n = 0 does up to rounding: pass a length just below the range to stay inside the first period.
+ * Refusals (DTOF_ERR_INVALID before any device call): null arguments, n_frequencies outside [1, 4], frequencies that are not finite, not > 0 or not distinct, a plane
+ * index outside the 2 * n_frequencies planes, n_passes = 0, an exposure_time that is not finite or not > 0, with two or more frequencies a max_path_length for which
+ * N is outside [1, 4096], negative sizes, misaligned buffers. */
+
+/* The films a depth map needs: frequency j contributes (0, 0) and (0, 0.25) at w_g_mhz[j]; frequencies are grouped two per traversal -- (0, 0, f0), (0, .25, f0),
+ * (0, 0, f1), (0, .25, f1) -- so an I / Q pair never straddles two traversals; an odd last frequency is a group of two films.  Writes the 2 * n_frequencies variants and
+ * their frequencies in order: I of frequency j is film 2 j, Q is film 2 j + 1 (dopplertofpath.cpp:26-35,60-77; no device needed). */
+int dtof_depth_map_variants(const float *w_g_mhz, int n_frequencies, dtof_modulation *out_variants, float *out_w_g_mhz);
+/* The reconstruction above over the sum of n_passes developed passes (render_multi_pass, doppler_tutorials/src/program_runner.py:11-31; to_tof_image,
+ * doppler_tutorials/src/utils/image_utils.py:20-31): d_rgb_sum[2 * n_frequencies][n_pixels][3] as dtof_develop_accumulate_async leaves it; i_planes, q_planes and
+ * w_g_mhz are host arrays read before the call returns.  d_depth[n_pixels] double; d_residual_or_null[n_pixels] double; d_wraps_or_null[n_frequencies][n_pixels] int32;
+ * d_amplitude_or_null[n_frequencies][n_pixels] double; d_phase_or_null[n_frequencies][n_pixels] float32.  Enqueued on the scene's stream without a host wait. */
+int dtof_depth_map_async(dtof_scene *scene, const float *d_rgb_sum, int n_frequencies, const int32_t *i_planes, const int32_t *q_planes, const double *w_g_mhz,
+                         uint32_t n_passes, double exposure_time, double max_path_length, int64_t n_pixels,
+                         double *d_depth, double *d_residual_or_null, int32_t *d_wraps_or_null, double *d_amplitude_or_null, float *d_phase_or_null);
+/* The loop of dtof_render_velocity_map (render_multi_pass, doppler_tutorials/src/program_runner.py:11-31, per film) with the groups of dtof_depth_map_variants: per
+ * group and pass i = 0 .. n_passes - 1 the library's own film (film64 != 0: its float64 film, as dtof_render_velocity_map_f64) is cleared, rendered with seed i and
+ * developed into the running sum; then one reconstruction, one copy per requested output and ONE host synchronisation.  out_depth[H * W] double and the optional
+ * outputs as in dtof_depth_map_async; out_tof_or_null[2 * n_frequencies][H * W] float32, plane k the ToF image of film k of dtof_depth_map_variants.  `stats` sums the
+ * traversals: n_paths = W * H * spp * n_passes * ceil(n_frequencies / 2).  The caller's dtof_scene_set_film_layout state is neither read nor changed.  An integrator
+ * other than `dopplertofpath` fails with DTOF_ERR_INVALID. */
+int dtof_render_depth_map(dtof_scene *scene, uint32_t n_passes, uint32_t spp, const float *w_g_mhz, int n_frequencies, double exposure_time, double max_path_length,
+                          int film64, double *out_depth, double *out_residual_or_null, int32_t *out_wraps_or_null, double *out_amplitude_or_null,
+                          float *out_phase_or_null, float *out_tof_or_null, dtof_render_stats *stats);
+
 /* ---------------------------------------------------------------- moment film (opt-in)
  * What the reference's `moment` integrator records (src/integrators/moment.cpp:85-104): besides the image, the XYZ of every sample (srgb_to_xyz,
  * include/mitsuba/core/spectrum.h:396-402) and its square, as AOVs that ImageBlock::put filters like the image (src/render/imageblock.cpp:414-531) -- here for every

@@ -15,9 +15,10 @@ from ._abi import (MAX_VARIANTS, DtofError, _AdaptiveParams, _check, _DenoisePar
 from ._denoiser import Denoiser
 from ._plugins import (ETimeSampling, Integrator, Sampler, load_dict, load_file, load_string, render, render_multi_pass, set_variant, to_tof_image,   # noqa: F401
                        variant, variants)
-from ._scene import (ADAPTIVE_MODES, AOV_TYPES, COMPONENTS, FILMS, FLAT_GEOMETRY, MAX_VELOCITY_OFFSETS, MOMENT_PLANES, Scene, _adaptive_params, _aov_parse,   # noqa: F401
-                     _film64, _moment_dict, _plugin_args, _variant_array, adaptive_select, aov_channels, eval_component, velocity_map_variants)
+from ._scene import (ADAPTIVE_MODES, AOV_TYPES, COMPONENTS, DEPTH_OUTPUTS, FILMS, FLAT_GEOMETRY, MAX_DEPTH_FREQUENCIES, MAX_VELOCITY_OFFSETS, MOMENT_PLANES, Scene, _adaptive_params, _aov_parse,   # noqa: F401
+                     _film64, _moment_dict, _plugin_args, _variant_array, _variant_freq, adaptive_select, aov_channels, default_max_path_length, depth_map_variants, eval_component,
+                     velocity_map_variants)
 
 __all__ = ["load_file", "load_string", "load_dict", "Scene", "Integrator", "Sampler", "DtofError", "render",
            "render_multi_pass", "to_tof_image", "lib_path", "ETimeSampling", "velocity_map_variants", "MOMENT_PLANES", "aov_channels", "AOV_TYPES", "Denoiser", "adaptive_select",
-           "ADAPTIVE_MODES"]
+           "ADAPTIVE_MODES", "depth_map_variants"]

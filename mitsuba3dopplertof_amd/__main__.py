@@ -5,6 +5,11 @@ plugins this library implements:
                                                [--offsets 0,0.25,0.5,0.75] [--film float64] [-v]
     python -m mitsuba3dopplertof_amd scene.xml --velocity-map 0,0.25 [--w-g 30 --exposure-time 0.0015] [--spp N] [-o out.npy]
         the radial-velocity map of the scene's dopplertofpath integrator (float64 .npy), reconstructed on the GPU: passes of min(1024, N) samples, seeds 0, 1, ...
+    python -m mitsuba3dopplertof_amd scene.xml --depth-map 30,40 [--max-path-length M] [--exposure-time 0.0015] [--film float64] [--spp N] [-o out.npy]
+        the depth map (metres, float64 .npy) from the homodyne I / Q films at the given modulation frequencies (MHz), two frequencies per traversal, reconstructed and
+        unwrapped on the GPU (Scene.render_depth_map); the wrap counts and the residual go to the output's _wraps and _residual siblings
+    python -m mitsuba3dopplertof_amd scene.xml --variants 0:0:30,0:0.25:30,0:0:40,0:0.25:40 [--spp N] [-o out.exr]
+        one image per hetero_frequency:hetero_offset:w_g triple, every four of them from one traversal (<out>_variant_<k>)
     python -m mitsuba3dopplertof_amd scene.xml --moments [--variants 0:0,1:0] [--passes N] [--spp N] [-o out.npz]
         the per-pixel moment film of one traversal per pass (weight, mean, m2, cross: Scene.render_moments), written with np.savez
     python -m mitsuba3dopplertof_amd scene.xml --aovs dd:depth,nn:sh_normal [--passes N] [--spp N] [-o out.npz]
@@ -40,14 +45,20 @@ def parser():
     ap.add_argument("-m", "--mode", default="hip_rgb", help="accepted for command-line compatibility (only hip_rgb exists)")
     ap.add_argument("--velocity-map", default=None, metavar="OFFSETS",
                     help="comma separated hetero_offset values: write the radial-velocity map of their homodyne / heterodyne films (float64 .npy) instead of an image")
+    ap.add_argument("--depth-map", default=None, metavar="MHZ",
+                    help="comma separated modulation frequencies in MHz (1 .. 4, distinct): write the depth map of their homodyne I / Q films (float64 .npy, metres) "
+                         "instead of an image; wrap counts and residual go to the _wraps and _residual siblings")
+    ap.add_argument("--max-path-length", type=float, default=None, metavar="M",
+                    help="--depth-map: the longest path (metres) the unwrapping tries; default 300 / gcd of whole-MHz frequencies")
     ap.add_argument("--w-g", type=float, default=30.0, help="--velocity-map: illumination frequency in MHz")
-    ap.add_argument("--exposure-time", type=float, default=0.0015, help="--velocity-map: exposure time in seconds")
+    ap.add_argument("--exposure-time", type=float, default=0.0015, help="--velocity-map, --depth-map: exposure time in seconds")
     ap.add_argument("--film", default="float32", choices=("float32", "float64"),
                     help="the film's accumulator: float64 sums the splat in double on the GPU (order-independent images and velocity maps; single GPU)")
     ap.add_argument("--moments", action="store_true",
                     help="write the per-pixel moment film (sample mean, second moments and the variants' cross moments, float64 .npz) instead of an image")
     ap.add_argument("--variants", default=None, metavar="F:O,F:O",
-                    help="--moments: up to four hetero_frequency:hetero_offset pairs evaluated in ONE traversal (default: the integrator's own pair)")
+                    help="--moments: up to four hetero_frequency:hetero_offset pairs evaluated in ONE traversal (default: the integrator's own pair); alone: "
+                         "hetero_frequency:hetero_offset:w_g triples, one image each at its own illumination frequency (MHz)")
     ap.add_argument("--passes", type=int, default=1, help="--moments, --aovs: passes with seeds --seed, --seed + 1, ... that accumulate into one film")
     ap.add_argument("--aovs", default=None, metavar="NAME:TYPE,...",
                     help="write the geometry channels under each pixel (depth, position, uv, geo_normal, sh_normal, dp_du, dp_dv, prim_index, shape_index; float64 "
@@ -187,13 +198,54 @@ def check_velocity_map_args(ap, args):
         ap.error("--velocity-map expects comma separated numbers")
 
 
-def parse_variants(text):
-    """'f:o,f:o,...' -> [(hetero_frequency, hetero_offset), ...]"""
-    pairs = []
+def parse_variants(text, triples=False):
+    """'f:o,f:o,...' -> [(hetero_frequency, hetero_offset), ...]; triples=True: 'f:o:w_g,...' -> [(hetero_frequency, hetero_offset, w_g_mhz), ...].  Anything else,
+    a mixture of the two included, is a ValueError."""
+    out = []
     for item in text.split(","):
-        f, o = item.split(":")
-        pairs.append((float(f), float(o)))
-    return pairs
+        parts = item.split(":")
+        if len(parts) != (3 if triples else 2):
+            raise ValueError("--variants expects hetero_frequency:hetero_offset%s items" % (":w_g" if triples else ""))
+        out.append(tuple(float(x) for x in parts))
+    return out
+
+
+def check_variant_triples(ap, args):
+    """--variants without --moments / --adaptive: hetero_frequency:hetero_offset:w_g triples of a plain render, refused before the scene is loaded"""
+    try:
+        parse_variants(args.variants, triples=True)
+    except ValueError:
+        ap.error("--variants and --passes belong to --moments; alone, --variants takes hetero_frequency:hetero_offset:w_g triples (all of them triples)")
+    if args.offsets is not None:
+        ap.error("--variants replaces --offsets: do not combine them")
+    if args.stripes > 0 or int(os.environ.get("WORLD_SIZE", "1")) > 1:
+        ap.error("--variants is a single-GPU feature: it cannot be combined with --stripes or a multi-GPU launch")
+    if args.velocity_map is not None or args.denoise:
+        ap.error("--variants triples make plain images: do not combine them with --velocity-map or --denoise")
+
+
+def check_depth_map_args(ap, args):
+    """what --depth-map cannot be combined with, refused before the scene is loaded"""
+    if args.velocity_map is not None or args.moments or args.aovs is not None or args.adaptive is not None or args.denoise:
+        ap.error("--depth-map is an output of its own: do not combine it with --velocity-map, --moments, --aovs, --adaptive or --denoise")
+    if args.stripes > 0 or int(os.environ.get("WORLD_SIZE", "1")) > 1:
+        ap.error("--depth-map is a single-GPU feature")
+    if args.offsets is not None or args.variants is not None:
+        ap.error("--depth-map renders its own films: do not combine it with --offsets or --variants")
+    if args.seed != 0:
+        ap.error("--depth-map renders the seeds 0, 1, ... of its passes: --seed does not apply")
+    if args.output is not None and not args.output.lower().endswith(".npy"):
+        ap.error("--depth-map writes a float64 .npy file")
+    try:
+        f = [float(x) for x in args.depth_map.split(",")]
+    except ValueError:
+        ap.error("--depth-map expects comma separated numbers")
+    if not 1 <= len(f) <= 4 or len(set(np.float32(x) for x in f)) != len(f) or not all(np.isfinite(x) and x > 0 for x in f):
+        ap.error("--depth-map takes between 1 and 4 distinct frequencies, each finite and > 0")
+    if args.max_path_length is None and any(x != int(x) for x in f):
+        ap.error("--depth-map: --max-path-length is required unless every frequency is a whole number of MHz")
+    if args.max_path_length is not None and not (np.isfinite(args.max_path_length) and args.max_path_length >= 0):
+        ap.error("--max-path-length must be finite and >= 0")
 
 
 def check_moments_args(ap, args):
@@ -269,6 +321,30 @@ def moments(args, scene):
     return 0
 
 
+def _sibling(path, tag):
+    base, ext = os.path.splitext(path)
+    return base + "_" + tag + ext
+
+
+def depth_map(args, scene):
+    """--depth-map: the passes of harness._passes, one traversal per two frequencies and pass, everything behind the film splat on the GPU (Scene.render_depth_map)"""
+    from mitsuba3dopplertof_amd.harness import _passes
+    frequencies = [float(x) for x in args.depth_map.split(",")]
+    out = args.output or os.path.splitext(args.scene)[0] + "_depth.npy"
+    single, n_pass = _passes(args.spp or scene.info()["sample_count"])
+    t0 = time.time()
+    os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+    d = scene.render_depth_map(n_pass, single, frequencies, exposure_time=args.exposure_time, max_path_length=args.max_path_length, film=args.film,
+                               outputs=("depth", "wraps", "residual"))
+    dt = time.time() - t0
+    np.save(out, d["depth"])
+    np.save(_sibling(out, "wraps"), d["wraps"])
+    np.save(_sibling(out, "residual"), d["residual"])
+    if args.verbose:
+        print("Depth map finished. (took %.1f ms, %d passes of %d spp, %s)" % (dt * 1e3, n_pass, single, scene.last_stats))
+    return 0
+
+
 def velocity_map(args, scene):
     """--velocity-map: the passes of harness._passes (the sampler's sample count when --spp is 0), one traversal per two offsets and pass, everything behind the film
     splat on the GPU (Scene.render_velocity_map)"""
@@ -300,8 +376,14 @@ def main(argv=None):
         check_aovs_args(ap, args)
     elif args.moments:
         check_moments_args(ap, args)
-    elif (args.variants is not None and args.adaptive is None) or args.passes != 1:
+    elif args.passes != 1:
         ap.error("--variants and --passes belong to --moments")
+    elif args.variants is not None and args.adaptive is None and args.depth_map is None:
+        check_variant_triples(ap, args)
+    if args.depth_map is not None:
+        check_depth_map_args(ap, args)
+    elif args.max_path_length is not None:
+        ap.error("--max-path-length belongs to --depth-map")
     if args.velocity_map is not None:
         check_velocity_map_args(ap, args)
     if args.denoise:
@@ -324,6 +406,8 @@ def main(argv=None):
         scene = mi.load_file(args.scene, **defines)
         if args.adaptive is not None:
             return adaptive(args, scene)
+        if args.depth_map is not None:
+            return depth_map(args, scene)
         if args.velocity_map is not None:
             return velocity_map(args, scene)
         if args.moments:
@@ -332,6 +416,7 @@ def main(argv=None):
             return aovs(args, scene)
         t0 = time.time()
         offsets = [float(x) for x in args.offsets.split(",")] if args.offsets else None
+        triples = parse_variants(args.variants, triples=True) if args.variants else None      # a plain render's --variants (check_variant_triples)
         world = int(os.environ.get("WORLD_SIZE", "1"))
         if world > 1:   # launched by torch.distributed.run: shard the rows, one film gather (distributed.py)
             import torch
@@ -352,7 +437,7 @@ def main(argv=None):
             d = scene.render_denoised(seed=args.seed, spp=args.spp, **args.denoise_kw)
             img, noisy = d["denoised"], d["image"]
         else:
-            img = scene.render(seed=args.seed, spp=args.spp, offsets=offsets, film=args.film)
+            img = scene.render(seed=args.seed, spp=args.spp, offsets=offsets, variants=triples, film=args.film)
         dt = time.time() - t0
     except mi.DtofError as e:
         print("Error: %s" % e, file=sys.stderr)
@@ -365,6 +450,10 @@ def main(argv=None):
         else:
             write_image(out, img.astype(np.float32))
         write_image(_noisy_sibling(out), noisy)
+    elif triples is not None:
+        base, ext = os.path.splitext(out)
+        for k in range(len(triples)):
+            write_image("%s_variant_%d%s" % (base, k, ext), img[k])
     elif offsets is None:
         write_image(out, img)
     else:

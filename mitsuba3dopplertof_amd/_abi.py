@@ -123,6 +123,14 @@ SIGNATURES = {
     "dtof_develop_f64_async": (_int, [_vp, _vp, _vp, _i64]),
     "dtof_develop_rgba_f64_async": (_int, [_vp, _vp, _vp, _vp, _i64]),
     "dtof_render_velocity_map_f64": (_int, _velocity),
+    # modulation frequency per variant
+    "dtof_render_variants_freq": (_int, [_vp, _u32, _u32, _vp, _vp, _int, _vp, _st]),
+    "dtof_render_variants_freq_f64": (_int, [_vp, _u32, _u32, _vp, _vp, _int, _vp, _vp, _st]),
+    "dtof_sample_lanes_variants_freq": (_int, [_vp, _u32, _u32, _vp, _vp, _int, _u64, _u64, _vp, _vp, _vp]),
+    # depth map
+    "dtof_depth_map_variants": (_int, [_vp, _int, _vp, _vp]),
+    "dtof_depth_map_async": (_int, [_vp, _vp, _int, _vp, _vp, _vp, _u32, _f64, _f64, _i64, _vp, _vp, _vp, _vp, _vp]),
+    "dtof_render_depth_map": (_int, [_vp, _u32, _u32, _vp, _int, _f64, _f64, _int, _vp, _vp, _vp, _vp, _vp, _vp, _st]),
     # moment film
     "dtof_moment_planes": (_int, [_int]),
     "dtof_render_moments": (_int, [_vp, _u32, _u32, _u32, _vp, _int, _int, _vp, _st]),

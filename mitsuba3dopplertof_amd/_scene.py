@@ -1,5 +1,6 @@
 """Scene: a loaded scene and every call over it -- renders, films, lane dumps, ray queries -- and the module-level functions over the same entries."""
 import ctypes as C
+import math
 
 import numpy as np
 
@@ -52,6 +53,21 @@ def _variant_array(variants):
     if v.ndim != 2 or v.shape[1] != 2:
         raise DtofError("variants must be a sequence of (hetero_frequency, hetero_offset) pairs")
     return v
+
+
+def _variant_freq(variants):
+    """pairs, or (hetero_frequency, hetero_offset, w_g_mhz) triples -> ((n, 2) float32 array like dtof_modulation[n], (n,) float32 frequencies or None for pairs).
+    All pairs or all triples: a mixture is refused."""
+    try:
+        widths = {len(v) for v in variants}
+    except TypeError:
+        widths = set()
+    if widths == {3}:
+        v = np.ascontiguousarray(variants, dtype=np.float32)
+        return np.ascontiguousarray(v[:, :2]), np.ascontiguousarray(v[:, 2])
+    if 3 in widths:
+        raise DtofError("variants are all (hetero_frequency, hetero_offset) pairs or all (hetero_frequency, hetero_offset, w_g_mhz) triples, not a mixture")
+    return _variant_array(variants), None
 
 
 def _either(offsets, variants):
@@ -192,6 +208,27 @@ def velocity_map_variants(offsets):
     return out
 
 
+MAX_DEPTH_FREQUENCIES = 4   # modulation frequencies one depth map combines (kMaxDepthFrequencies)
+DEPTH_OUTPUTS = ("depth", "residual", "wraps", "amplitude", "phase", "tof")
+
+
+def depth_map_variants(frequencies):
+    """The (hetero_frequency, hetero_offset, w_g_mhz) films of a depth map in the order they are rendered (dtof_depth_map_variants): frequency j contributes (0, 0, f_j)
+    and (0, 0.25, f_j), two frequencies share one traversal -> (2 * len(frequencies), 3) float32"""
+    f = np.ascontiguousarray(frequencies, dtype=np.float32).reshape(-1)
+    var, freq = np.zeros((2 * len(f), 2), np.float32), np.zeros(2 * len(f), np.float32)
+    _check(_abi._lib().dtof_depth_map_variants(f.ctypes.data, len(f), var.ctypes.data, freq.ctypes.data))
+    return np.concatenate([var, freq[:, None]], axis=1)
+
+
+def default_max_path_length(frequencies):
+    """300 / gcd of the frequencies (metres of path): the unambiguous range of whole-MHz frequencies; anything else has to say its own"""
+    f = [float(np.float32(x)) for x in frequencies]
+    if not f or any(x != int(x) or x <= 0 for x in f):
+        raise DtofError("max_path_length is required unless every frequency is a whole number of MHz")
+    return 300.0 / math.gcd(*[int(x) for x in f])
+
+
 def _lane_dict(out, **more):
     """the dict of the lane dumps from their (n, 12) records; `more`: the call's further arrays (an `rgb` of its own replaces the records')"""
     return {"sample_pos": out[:, 0:2], "time": out[:, 2], "ray_o": out[:, 3:6], "ray_d": out[:, 6:9], "rgb": out[:, 9:12], **more}
@@ -220,13 +257,18 @@ class Scene:
         self.last_stats = _stats(entry, *args)
         return self.last_stats
 
-    def _grouped(self, name, seed, spp, var, images, *films):
+    def _grouped(self, name, seed, spp, var, images, *films, freq=None):
         """dtof_render_variants / _f64 over the variants `var` (None: the integrator's own pair), MAX_VARIANTS of them per traversal, into `images`, one per variant;
-        last_stats sums the traversals"""
+        last_stats sums the traversals.  `freq`: the variants' own w_g (MHz), which takes the call through dtof_render_variants_freq / _freq_f64"""
         total = None
         for g in range(0, len(images), MAX_VARIANTS):
             group = None if var is None else var[g:g + MAX_VARIANTS]
-            d = _stats(getattr(_abi._lib(), name), self._h, seed, spp, _ptr(group), 0 if group is None else len(group), images[g:g + MAX_VARIANTS].ctypes.data, *films)
+            n = 0 if group is None else len(group)
+            tail = (images[g:g + MAX_VARIANTS].ctypes.data,) + films
+            if freq is None:
+                d = _stats(getattr(_abi._lib(), name), self._h, seed, spp, _ptr(group), n, *tail)
+            else:
+                d = _stats(getattr(_abi._lib(), name.replace("variants", "variants_freq")), self._h, seed, spp, _ptr(group), freq[g:g + MAX_VARIANTS].ctypes.data, n, *tail)
             total = d if total is None else {key: total[key] + d[key] for key in d}
         self.last_stats = total
 
@@ -318,7 +360,8 @@ class Scene:
     def render(self, seed=0, spp=0, offsets=None, sensor=0, variants=None, film="float32"):
         """Developed image (H, W, 3) float32 -- (H, W, 4) for an rgba film; with `offsets` (list of hetero_offset values) -> (K, H, W, 3 | 4).
         `variants`: list of (hetero_frequency, hetero_offset) pairs -> (K, H, W, 3 | 4), image k that of an integrator carrying pair k; every four of them
-        share one traversal (dtof_render_variants), last_stats then sums the traversals.
+        share one traversal (dtof_render_variants), last_stats then sums the traversals.  (hetero_frequency, hetero_offset, w_g_mhz) triples give every film its own
+        illumination frequency as well (dtof_render_variants_freq); all pairs or all triples.
         film="float64": the same images from a film accumulated and developed in double (dtof_render_variants_f64); offsets are then variants at the integrator's
         own frequency, every four of them one traversal."""
         _either(offsets, variants)
@@ -333,9 +376,9 @@ class Scene:
         w, h = self.size
         ch = 4 if self.info()["has_alpha"] else 3
         if variants is not None:
-            var = _variant_array(variants)
+            var, freq = _variant_freq(variants)
             out = np.zeros((len(var), h, w, ch), np.float32)
-            self._grouped("dtof_render_variants", seed, spp, var, out)
+            self._grouped("dtof_render_variants", seed, spp, var, out, freq=freq)
         elif offsets is None:
             out = np.zeros((h, w, ch), np.float32)
             self._timed(_abi._lib().dtof_render, self._h, sensor, seed, spp, out.ctypes.data)
@@ -349,19 +392,19 @@ class Scene:
         """(images (K, H, W, 3 | 4), films (planes, H, W, 4) float64 or None) through dtof_render_variants_f64, four variants per traversal; None: the integrator's own pair"""
         w, h = self.size
         alpha = 1 if self.info()["has_alpha"] else 0
-        var = None if variants is None else _variant_array(variants)
+        var, freq = (None, None) if variants is None else _variant_freq(variants)
         k = 1 if var is None else len(var)
         if want_films and k > MAX_VARIANTS:
             raise DtofError("at most 4 modulation variants can be batched per traversal")
         images = np.zeros((k, h, w, 3 + alpha), np.float32)
         films = np.zeros((k + alpha, h, w, 4), np.float64) if want_films else None
-        self._grouped("dtof_render_variants_f64", seed, spp, var, images, _ptr(films))
+        self._grouped("dtof_render_variants_f64", seed, spp, var, images, _ptr(films), freq=freq)
         return images, films
 
     def render_film64(self, seed=0, spp=0, variants=None):
         """One traversal into the float64 film (dtof_render_variants_f64) -> (images (K, H, W, 3 | 4) float32, films (K, H, W, 4) float64 -- one more plane, the alpha
         film, behind the K colour planes of an rgba scene).  The images are the films developed in double: (float) (RGB / (W == 0 ? 1 : W)).  `variants`: up to four
-        (hetero_frequency, hetero_offset) pairs; None: the integrator's own pair (K = 1)."""
+        (hetero_frequency, hetero_offset) pairs or (hetero_frequency, hetero_offset, w_g_mhz) triples; None: the integrator's own pair (K = 1)."""
         return self._render_f64(seed, spp, variants, True)
 
     def render_moments(self, seed=0, spp=0, n_passes=1, variants=None, raw=False):
@@ -562,6 +605,41 @@ class Scene:
         films = {"homodyne": homo, "heterodyne": hetero}
         return (v, films, per_pair) if pairs else (v, films)
 
+    def depth_map_async(self, d_rgb_sum_ptr, i_planes, q_planes, frequencies, n_passes, n_pixels, d_depth_ptr, exposure_time=0.0015, max_path_length=None,
+                        d_residual_ptr=None, d_wraps_ptr=None, d_amplitude_ptr=None, d_phase_ptr=None):
+        """enqueue the depth map of the sum of `n_passes` passes (dtof_depth_map_async): frequency j (MHz) has its I film in plane i_planes[j] and its Q film in plane
+        q_planes[j] of the 2 * F planes of the sum; d_depth [n_pixels] float64, optionally d_residual [n_pixels] float64, d_wraps [F][n_pixels] int32,
+        d_amplitude [F][n_pixels] float64 and d_phase [F][n_pixels] float32"""
+        ip, qp = np.ascontiguousarray(i_planes, dtype=np.int32).reshape(-1), np.ascontiguousarray(q_planes, dtype=np.int32).reshape(-1)
+        f = np.ascontiguousarray(frequencies, dtype=np.float64).reshape(-1)
+        if not len(ip) == len(qp) == len(f):
+            raise DtofError("as many I planes and Q planes as frequencies")
+        if max_path_length is None:
+            max_path_length = default_max_path_length(f)
+        _check(_abi._lib().dtof_depth_map_async(self._h, d_rgb_sum_ptr, len(f), ip.ctypes.data, qp.ctypes.data, f.ctypes.data, int(n_passes), float(exposure_time),
+                                           float(max_path_length), int(n_pixels), d_depth_ptr, d_residual_ptr, d_wraps_ptr, d_amplitude_ptr, d_phase_ptr))
+
+    def render_depth_map(self, n_passes, spp, frequencies=(30.0, 40.0), exposure_time=0.0015, max_path_length=None, film="float32", outputs=DEPTH_OUTPUTS):
+        """The depth map of `n_passes` passes (seeds 0 .. n_passes - 1) of `spp` samples at the modulation `frequencies` (MHz), reconstructed on the device
+        (dtof_render_depth_map): the I / Q films of two frequencies share one traversal per pass and never leave the GPU.  Returns a dict of the requested `outputs`:
+        "depth" (H, W) float64 metres (half the unwrapped path length; always there), "residual" (H, W) float64, "wraps" (F, H, W) int32, "amplitude" (F, H, W) float64,
+        "phase" (F, H, W) float32, "tof" (2 F, H, W) float32 in the order of depth_map_variants -- the values harness.calc_depth_from_homodynes computes from the same
+        films.  max_path_length=None: 300 / gcd of whole-MHz frequencies.  film="float64": every pass is splatted and developed in double."""
+        unknown = set(outputs) - set(DEPTH_OUTPUTS)
+        if unknown:
+            raise DtofError("unknown depth-map outputs %s; known: %s" % (sorted(unknown), ", ".join(DEPTH_OUTPUTS)))
+        f = np.ascontiguousarray([float(x) for x in frequencies], dtype=np.float32)
+        if max_path_length is None:
+            max_path_length = default_max_path_length(f)
+        n = len(f)
+        w, h = self.size
+        shapes = {"depth": ((h, w), np.float64), "residual": ((h, w), np.float64), "wraps": ((n, h, w), np.int32), "amplitude": ((n, h, w), np.float64),
+                  "phase": ((n, h, w), np.float32), "tof": ((2 * n, h, w), np.float32)}
+        out = {k: np.zeros(*shapes[k]) for k in DEPTH_OUTPUTS if k == "depth" or k in outputs}
+        self._timed(_abi._lib().dtof_render_depth_map, self._h, int(n_passes), int(spp), f.ctypes.data, n, float(exposure_time), float(max_path_length),
+                    int(_film64(film)), out["depth"].ctypes.data, *[_ptr(out.get(k)) for k in DEPTH_OUTPUTS[1:]])
+        return out
+
     def collect(self, max_frames=4096):
         """wait for the frames enqueued by render_rows_async -> (summed stats dict, per-frame GPU milliseconds)"""
         st, ms, n = _Stats(), np.zeros(max_frames, np.float64), C.c_uint32(0)
@@ -581,10 +659,16 @@ class Scene:
 
     def sample_lanes_variants(self, seed, spp, lane_begin, n, variants=None):
         """sample_lanes through the batched kernels (dtof_sample_lanes_variants): the lanes are evaluated once for up to four (hetero_frequency, hetero_offset)
-        pairs; `rgb` is (K, n, 3), plane k the lanes' results with pair k, everything else is shared by the variants.  None: the integrator's own pair (K = 1)."""
-        var, ptr, k, _ = _variant_args(variants)
+        pairs; `rgb` is (K, n, 3), plane k the lanes' results with pair k, everything else is shared by the variants.  None: the integrator's own pair (K = 1).
+        (hetero_frequency, hetero_offset, w_g_mhz) triples: film k at its own illumination frequency (dtof_sample_lanes_variants_freq)."""
+        var, freq = (None, None) if variants is None else _variant_freq(variants)
+        k = 0 if var is None else len(var)
         out, valid, rgb = np.zeros((n, 12), np.float32), np.zeros(n, np.uint32), np.zeros((max(k, 1), n, 3), np.float32)
-        _check(_abi._lib().dtof_sample_lanes_variants(self._h, seed, spp, ptr, k, lane_begin, n, out.ctypes.data, valid.ctypes.data, rgb.ctypes.data))
+        if freq is None:
+            _check(_abi._lib().dtof_sample_lanes_variants(self._h, seed, spp, _ptr(var), k, lane_begin, n, out.ctypes.data, valid.ctypes.data, rgb.ctypes.data))
+        else:
+            _check(_abi._lib().dtof_sample_lanes_variants_freq(self._h, seed, spp, _ptr(var), freq.ctypes.data, k, lane_begin, n, out.ctypes.data, valid.ctypes.data,
+                                                            rgb.ctypes.data))
         return _lane_dict(out, rgb=rgb, valid=valid)
 
     def sample_lanes_pixels(self, seed, spp, pixels, variants=None):

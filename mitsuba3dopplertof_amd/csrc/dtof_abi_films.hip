@@ -3,6 +3,7 @@
 // (dtof_render.hip) or in one of the launchers of the small kernel files.
 #include "dtof_host.h"
 #include "dtof_reconstruct.h"
+#include "dtof_depth.h"
 #include "dtof_denoise.h"
 #include "dtof_temporal.h"
 #include "dtof_world_to_pixel.h"
@@ -57,6 +58,16 @@ static void set_variants(RenderRequest &rq, const dtof_modulation *variants, int
     if (!variants || n_variants <= 0) return;
     if (n_variants > kMaxOffsets) throw std::runtime_error("at most 4 modulation variants can be batched per traversal");
     rq.variants = variants; rq.n_variants = n_variants;
+}
+// ... and of the `_freq` entries: a frequency per variant, or null = the entry without `_freq`.  Frequencies without variants and a frequency that is not finite or
+// not > 0 are refused here, before anything is enqueued
+static void set_variants_freq(RenderRequest &rq, const dtof_modulation *variants, const float *w_g_mhz, int n_variants) {
+    set_variants(rq, variants, n_variants);
+    if (!w_g_mhz) return;
+    if (rq.n_variants <= 0) throw std::runtime_error("modulation frequencies come with the variants they belong to: variants is null or n_variants is not positive");
+    for (int k = 0; k < n_variants; ++k)
+        if (!std::isfinite(w_g_mhz[k]) || !(w_g_mhz[k] > 0.f)) throw std::runtime_error("w_g_mhz[" + std::to_string(k) + "] must be finite and > 0");
+    rq.w_g_mhz = w_g_mhz;
 }
 // The device-film entry points: a rows or stripes request with the call's offsets or variants (their count is refused before a null scene or film is), the null and
 // stripe checks, the caller's film layout, and for the async forms the events a refused frame took go back to the pool
@@ -169,6 +180,14 @@ int dtof_render_variants(dtof_scene *sc, uint32_t seed, uint32_t spp, const dtof
 int dtof_render_variants_f64(dtof_scene *sc, uint32_t seed, uint32_t spp, const dtof_modulation *variants, int n_variants, float *out_images, double *out_films,
                              dtof_render_stats *stats) {
     return guarded([&] { RenderRequest rq = rows_request(seed, spp, 0, 0, stats); set_variants(rq, variants, n_variants); render_host_films<double>(sc, rq, out_images, out_films); });
+}
+int dtof_render_variants_freq(dtof_scene *sc, uint32_t seed, uint32_t spp, const dtof_modulation *variants, const float *w_g_mhz, int n_variants, float *out_rgb,
+                              dtof_render_stats *stats) {
+    return guarded([&] { RenderRequest rq = rows_request(seed, spp, 0, 0, stats); set_variants_freq(rq, variants, w_g_mhz, n_variants); render_host_films<float>(sc, rq, out_rgb); });
+}
+int dtof_render_variants_freq_f64(dtof_scene *sc, uint32_t seed, uint32_t spp, const dtof_modulation *variants, const float *w_g_mhz, int n_variants, float *out_images,
+                                  double *out_films, dtof_render_stats *stats) {
+    return guarded([&] { RenderRequest rq = rows_request(seed, spp, 0, 0, stats); set_variants_freq(rq, variants, w_g_mhz, n_variants); render_host_films<double>(sc, rq, out_images, out_films); });
 }
 int dtof_render(dtof_scene *sc, uint32_t sensor_index, uint32_t seed, uint32_t spp, float *out_rgb, dtof_render_stats *stats) {
     if (sensor_index != 0) { g_last_error = "Scene::render(): sensor index " + std::to_string(sensor_index) + " is out of bounds!"; return DTOF_ERR_INVALID; }
@@ -341,7 +360,139 @@ template <typename T> static void velocity_map_render(dtof_scene *sc, uint32_t n
     sc->deferred.resize(first_frame);
     if (sc->deferred.empty()) sc->events_used = 0;
 }
+
+// ---------------------------------------------------------------- depth map (dtof_depth.hip)
+// The checks the entries share, made before a device is touched; the frequencies as the doubles the kernel's wavelengths are formed from
+static void check_depth_frequencies(const double *w_g_mhz, int n_frequencies) {
+    if (n_frequencies < 1 || n_frequencies > kMaxDepthFrequencies) throw std::runtime_error("between 1 and 4 modulation frequencies make a depth map");
+    for (int j = 0; j < n_frequencies; ++j) {
+        if (!std::isfinite(w_g_mhz[j]) || !(w_g_mhz[j] > 0)) throw std::runtime_error("w_g_mhz[" + std::to_string(j) + "] must be finite and > 0");
+        for (int k = 0; k < j; ++k) if (w_g_mhz[k] == w_g_mhz[j]) throw std::runtime_error("the modulation frequencies of a depth map must be distinct");
+    }
+}
+static DepthMapArgs depth_args(int n_frequencies, const int32_t *i_planes, const int32_t *q_planes, const double *w_g_mhz, uint32_t n_passes, double exposure_time,
+                               double max_path_length) {
+    check_depth_frequencies(w_g_mhz, n_frequencies);
+    if (n_passes == 0) throw std::runtime_error("n_passes must be at least 1");
+    if (!std::isfinite(exposure_time) || !(exposure_time > 0)) throw std::runtime_error("exposure_time must be finite and > 0");
+    DepthMapArgs a; memset(&a, 0, sizeof a);
+    a.n_frequencies = n_frequencies; a.n_candidates = 1;
+    for (int j = 0; j < n_frequencies; ++j) {
+        if (i_planes[j] < 0 || i_planes[j] >= 2 * n_frequencies || q_planes[j] < 0 || q_planes[j] >= 2 * n_frequencies)
+            throw std::runtime_error("frequency " + std::to_string(j) + ": plane index outside the " + std::to_string(2 * n_frequencies) + " planes of the sum");
+        a.i_plane[j] = i_planes[j]; a.q_plane[j] = q_planes[j];
+        a.wavelength[j] = 300.0 / w_g_mhz[j];
+    }
+    if (n_frequencies > 1) {   // N = (int64) floor(max_path_length / L_0) + 1 candidates of the first frequency's wrap count
+        const double q = std::floor(max_path_length / a.wavelength[0]);
+        if (!(q >= 0.0) || !(q <= (double) (kMaxDepthCandidates - 1)))   // a NaN fails both
+            throw std::runtime_error("max_path_length must give between 1 and 4096 wrap candidates of the first frequency (floor(max_path_length / (300 / w_g_mhz[0])) + 1)");
+        a.n_candidates = (int32_t) ((int64_t) q + 1);
+    }
+    a.n_passes = (float) n_passes; a.exposure_time = (float) exposure_time;
+    return a;
+}
+// dtof_render_depth_map over the library's own float32 or float64 film: the loop of velocity_map_render with the groups of dtof_depth_map_variants
+template <typename T> static void depth_map_render(dtof_scene *sc, uint32_t n_passes, uint32_t spp, const float *w_g_mhz, int n_freq, double exposure_time, double max_path_length,
+                                                   double *out_depth, double *out_residual, int32_t *out_wraps, double *out_amplitude, float *out_phase, float *out_tof,
+                                                   dtof_render_stats *stats) {
+    using F = OwnFilm<T>;
+    if (!sc || !w_g_mhz || !out_depth) throw std::runtime_error("null argument");
+    if (n_freq < 1 || n_freq > kMaxDepthFrequencies) throw std::runtime_error("between 1 and 4 modulation frequencies make a depth map");
+    dtof_modulation variants[2 * kMaxDepthFrequencies]; float freq[2 * kMaxDepthFrequencies];
+    if (dtof_depth_map_variants(w_g_mhz, n_freq, variants, freq) != DTOF_OK) throw std::runtime_error(g_last_error);
+    double f64[kMaxDepthFrequencies]; int32_t ip[kMaxDepthFrequencies], qp[kMaxDepthFrequencies];
+    for (int j = 0; j < n_freq; ++j) { f64[j] = (double) w_g_mhz[j]; ip[j] = 2 * j; qp[j] = 2 * j + 1; }
+    const DepthMapArgs a = depth_args(n_freq, ip, qp, f64, n_passes, exposure_time, max_path_length);
+    need_doppler_for(sc, true);
+    need_sensor(sc);
+    ensure_device(sc);
+    sc->stop = false;
+    const HostSensor &se = sc->host.sensor;
+    const size_t px = (size_t) se.crop_w * se.crop_h, nf = (size_t) n_freq;
+    const int alpha = se.alpha ? 1 : 0;
+    F::buf(sc).ensure(px * 4 * (kMaxOffsets + alpha));   // the library's own film: the caller's declared layout is not consulted
+    T *const film = F::buf(sc).p;
+    // the passes' sum and the ToF images in the velocity map's buffers; its maps buffer holds depth, residual and the amplitudes (doubles), then wraps and phases (words)
+    sc->d_vm_sum.ensure(px * 3 * 2 * nf); sc->d_vm_tof.ensure(px * 2 * nf); sc->d_vm_maps.ensure(px * (2 + nf) + (px * 2 * nf + 1) / 2);
+    double *const d_depth = sc->d_vm_maps.p, *const d_residual = d_depth + px, *const d_amplitude = d_residual + px;
+    int32_t *const d_wraps = (int32_t *) (d_amplitude + px * nf); float *const d_phase = (float *) (d_wraps + px * nf);
+    const hipStream_t s = sc->stream;
+    const size_t first_frame = sc->deferred.size();   // frames the caller has not collected yet stay theirs
+    try {
+        for (int g = 0; g < n_freq; g += 2) {
+            const int films = 2 * std::min(2, n_freq - g);
+            for (uint32_t pass = 0; pass < n_passes; ++pass) {
+                HIP_CHECK(hipMemsetAsync(film, 0, px * 4 * (films + alpha) * sizeof(T), s));
+                dtof_render_stats frame;
+                RenderRequest rq = rows_request(pass, spp, 0, se.crop_h, &frame, true);
+                F::attach(rq, film, px * 4);
+                set_variants_freq(rq, variants + 2 * g, freq + 2 * g, films);
+                render_rows(sc, rq);
+                F::develop_accumulate(film, films, sc->d_vm_sum.p + px * 3 * 2 * g, (int64_t) px, pass == 0, s);   // the alpha plane behind them is left out
+            }
+        }
+        launch_depth_map(sc->d_vm_sum.p, a, (int64_t) px, d_depth, out_residual ? d_residual : nullptr, out_wraps ? d_wraps : nullptr, out_amplitude ? d_amplitude : nullptr,
+                         out_phase ? d_phase : nullptr, out_tof ? sc->d_vm_tof.p : nullptr, s);
+        HIP_CHECK(hipGetLastError());
+        HIP_CHECK(hipMemcpyAsync(out_depth, d_depth, px * sizeof(double), hipMemcpyDeviceToHost, s));
+        if (out_residual) HIP_CHECK(hipMemcpyAsync(out_residual, d_residual, px * sizeof(double), hipMemcpyDeviceToHost, s));
+        if (out_wraps) HIP_CHECK(hipMemcpyAsync(out_wraps, d_wraps, px * nf * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+        if (out_amplitude) HIP_CHECK(hipMemcpyAsync(out_amplitude, d_amplitude, px * nf * sizeof(double), hipMemcpyDeviceToHost, s));
+        if (out_phase) HIP_CHECK(hipMemcpyAsync(out_phase, d_phase, px * nf * sizeof(float), hipMemcpyDeviceToHost, s));
+        if (out_tof) HIP_CHECK(hipMemcpyAsync(out_tof, sc->d_vm_tof.p, px * 2 * nf * sizeof(float), hipMemcpyDeviceToHost, s));
+        HIP_CHECK(hipStreamSynchronize(s));
+        dtof_render_stats sum; memset(&sum, 0, sizeof sum);
+        for (size_t i = first_frame; i < sc->deferred.size(); ++i) add_deferred_frame(&sum, sc->deferred[i]);
+        if (stats) *stats = sum;
+    } catch (...) {   // the frames of this call leave the list either way (their events go back to the pool once no frame is in flight)
+        if (sc->deferred.size() > first_frame) { (void) hipStreamSynchronize(s); sc->deferred.resize(first_frame); }
+        if (sc->deferred.empty()) sc->events_used = 0;
+        throw;
+    }
+    sc->deferred.resize(first_frame);
+    if (sc->deferred.empty()) sc->events_used = 0;
+}
 extern "C" {
+int dtof_depth_map_variants(const float *w_g_mhz, int n_frequencies, dtof_modulation *out_variants, float *out_w_g_mhz) {
+    return guarded([&] {
+        if (!w_g_mhz || !out_variants || !out_w_g_mhz) throw std::runtime_error("null argument");
+        if (n_frequencies < 1 || n_frequencies > kMaxDepthFrequencies) throw std::runtime_error("between 1 and 4 modulation frequencies make a depth map");
+        double f64[kMaxDepthFrequencies];
+        for (int j = 0; j < n_frequencies; ++j) f64[j] = (double) w_g_mhz[j];
+        check_depth_frequencies(f64, n_frequencies);
+        for (int j = 0; j < n_frequencies; ++j) {   // two frequencies per traversal are four consecutive films: an I / Q pair never straddles two traversals
+            out_variants[2 * j] = dtof_modulation { 0.f, 0.f }; out_variants[2 * j + 1] = dtof_modulation { 0.f, 0.25f };
+            out_w_g_mhz[2 * j] = out_w_g_mhz[2 * j + 1] = w_g_mhz[j];
+        }
+    });
+}
+int dtof_depth_map_async(dtof_scene *sc, const float *d_rgb_sum, int n_frequencies, const int32_t *i_planes, const int32_t *q_planes, const double *w_g_mhz,
+                         uint32_t n_passes, double exposure_time, double max_path_length, int64_t n_pixels,
+                         double *d_depth, double *d_residual, int32_t *d_wraps, double *d_amplitude, float *d_phase) {
+    return guarded([&] {
+        if (!sc || !d_rgb_sum || !i_planes || !q_planes || !w_g_mhz || !d_depth) throw std::runtime_error("null argument");
+        if (n_frequencies < 1 || n_frequencies > kMaxDepthFrequencies) throw std::runtime_error("between 1 and 4 modulation frequencies make a depth map");
+        const DepthMapArgs a = depth_args(n_frequencies, i_planes, q_planes, w_g_mhz, n_passes, exposure_time, max_path_length);
+        check_grid(n_pixels);
+        if ((uintptr_t) d_rgb_sum % 4 != 0 || (uintptr_t) d_depth % 8 != 0 || (uintptr_t) d_residual % 8 != 0 || (uintptr_t) d_wraps % 4 != 0 ||
+            (uintptr_t) d_amplitude % 8 != 0 || (uintptr_t) d_phase % 4 != 0)
+            throw std::runtime_error("misaligned buffer");
+        ensure_device(sc);
+        launch_depth_map(d_rgb_sum, a, n_pixels, d_depth, d_residual, d_wraps, d_amplitude, d_phase, nullptr, sc->stream);
+        HIP_CHECK(hipGetLastError());
+    });
+}
+int dtof_render_depth_map(dtof_scene *sc, uint32_t n_passes, uint32_t spp, const float *w_g_mhz, int n_frequencies, double exposure_time, double max_path_length,
+                          int film64, double *out_depth, double *out_residual, int32_t *out_wraps, double *out_amplitude, float *out_phase, float *out_tof,
+                          dtof_render_stats *stats) {
+    return guarded([&] {
+        if (film64) depth_map_render<double>(sc, n_passes, spp, w_g_mhz, n_frequencies, exposure_time, max_path_length, out_depth, out_residual, out_wraps, out_amplitude,
+                                             out_phase, out_tof, stats);
+        else depth_map_render<float>(sc, n_passes, spp, w_g_mhz, n_frequencies, exposure_time, max_path_length, out_depth, out_residual, out_wraps, out_amplitude, out_phase,
+                                     out_tof, stats);
+    });
+}
 int dtof_render_velocity_map(dtof_scene *sc, uint32_t n_passes, uint32_t spp, const float *offsets, int n_offsets, double exposure_time, double w_g_mhz,
                              double *out_velocity, double *out_velocity_pairs, float *out_tof, dtof_render_stats *stats) {
     return guarded([&] { velocity_map_render<float>(sc, n_passes, spp, offsets, n_offsets, exposure_time, w_g_mhz, out_velocity, out_velocity_pairs, out_tof, stats); });
@@ -848,6 +999,16 @@ int dtof_sample_lanes_variants(dtof_scene *sc, uint32_t seed, uint32_t spp, cons
         if (!sc || !out || !out_rgb) throw std::runtime_error("null argument");
         RenderRequest rq = rows_request(seed, spp, 0, 0);
         set_variants(rq, variants, n_variants);
+        need_doppler_for(sc, rq.n_variants > 0);
+        dump_lanes(sc, rq, lane_begin, n, out, valid, out_rgb);
+    });
+}
+int dtof_sample_lanes_variants_freq(dtof_scene *sc, uint32_t seed, uint32_t spp, const dtof_modulation *variants, const float *w_g_mhz, int n_variants,
+                                    uint64_t lane_begin, uint64_t n, float *out, uint32_t *valid, float *out_rgb) {
+    return guarded([&] {
+        if (!sc || !out || !out_rgb) throw std::runtime_error("null argument");
+        RenderRequest rq = rows_request(seed, spp, 0, 0);
+        set_variants_freq(rq, variants, w_g_mhz, n_variants);
         need_doppler_for(sc, rq.n_variants > 0);
         dump_lanes(sc, rq, lane_begin, n, out, valid, out_rgb);
     });

@@ -164,6 +164,7 @@ struct RenderRequest {
     bool stripes = false; int32_t stripe_rows = 0, stripe_period = 0;   // stripes: only the rows [row_begin + k * stripe_period, ... + stripe_rows) (interleaved shards)
     const float *offsets = nullptr; int n_offsets = 0;                // batched hetero_offset values, or
     const dtof_modulation *variants = nullptr; int n_variants = 0;   // ... batched (hetero_frequency, hetero_offset) pairs (at most one of the two)
+    const float *w_g_mhz = nullptr;               // with variants: film k's illumination frequency w_g (MHz), n_variants of them; null = the integrator's own for every film
     int films() const { return n_variants > 0 ? n_variants : n_offsets > 0 ? n_offsets : 1; }   // colour films the call writes
     float4 *lane_planes = nullptr;                // lane dumps: [films()][dump_n] results of every film (q.res), besides film 0's in lane_dump
     float *film = nullptr; uint64_t film_stride = 0;   // K films (and the alpha film behind them) film_stride floats apart
@@ -227,7 +228,7 @@ struct FramePlan {
 void ensure_device(dtof_scene *sc);
 void set_filter(RenderParams &rp, int32_t filter, float radius, float stddev, float B, float C);
 RenderParams make_params(const dtof_scene *sc, uint32_t seed, uint32_t spp, const float *offsets, int n_offsets, uint32_t sample_count = 0,
-                         const dtof_modulation *variants = nullptr, int n_variants = 0);
+                         const dtof_modulation *variants = nullptr, int n_variants = 0, const float *w_g_mhz = nullptr);
 double stage_ms(const std::vector<std::pair<hipEvent_t, hipEvent_t>> &ev);
 SceneTraits scene_traits(const dtof_scene &sc);
 FlatChoice flat_choice(const SceneTraits &t, bool fused, bool memo_on, bool flat_on);

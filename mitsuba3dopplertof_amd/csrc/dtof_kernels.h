@@ -9,7 +9,7 @@ namespace dtof {
 
 constexpr uint32_t kChunkBlocks = 8; // 64-lane chunks of a 512-lane queue segment (RenderParams::chunk_blocks)
 constexpr uint32_t kMaxInline = 4;  // iterations of the bounce loop the fused first-bounce kernel may run itself (RenderParams::inline_iters)
-constexpr int kMaxOffsets = 4;      // modulation variants (hetero_frequency, hetero_offset) evaluated per traversal (K), one film each
+constexpr int kMaxOffsets = 4;      // modulation variants (hetero_frequency, hetero_offset, w_g) evaluated per traversal (K), one film each
 
 // Everything a kernel needs besides the scene blob and the queues; passed by value.
 struct RenderParams {
@@ -32,8 +32,10 @@ struct RenderParams {
     int32_t time_sampling; float antithetic_shift; int32_t stratify;
     uint32_t n_stratum; float inv_n_stratum, inv_tcn;
     // ---- integrator (src/integrators/dopplertofpath.cpp:19-77)
-    float T, w_g, phi_coef, amp, g_1, g_0;
-    float w_d[kMaxOffsets], phase[kMaxOffsets]; int32_t n_offsets;   // per film: the heterodyne frequency and the phase offset (only eval_modulation_weight reads them); n_offsets = K
+    float T, amp, g_1, g_0;
+    // per film: the illumination frequency with the path-length prefactor that follows from it, the heterodyne frequency and the phase offset (only
+    // eval_modulation_weight reads the four); n_offsets = K.  A one-film kernel reads element 0.
+    float w_g[kMaxOffsets], phi_coef[kMaxOffsets], w_d[kMaxOffsets], phase[kMaxOffsets]; int32_t n_offsets;
     int32_t wave_type, low_pass;
     uint32_t path_correlation_depth, max_depth, rr_depth;
     int32_t has_area;                             // scene has area emitters: emitter-hit term + prev_si / prev_bsdf_pdf state
@@ -120,7 +122,7 @@ struct ShadeArgs {
     uint32_t n_seg, res_small_off, res_small_words, res_memo;   // resident stage (RESW != 0): segments of the batch; byte offset / uint4 count of the record block copied to LDS; 1 = the instance memo has LDS
     uint32_t res_park_off;   // resident stage with several films: word offset (behind the memo) of the film-state columns, kParkWords words per thread behind the stack columns
 };
-static_assert(sizeof(ShadeArgs) == 896, "ShadeArgs is k_shade's kernarg block: its layout, order and types do not change (888 + RenderParams::pixels, the last field of rp)");
+static_assert(sizeof(ShadeArgs) == 920, "ShadeArgs is k_shade's kernarg block: its layout, order and types do not change (896 + the six floats that made RenderParams::w_g and ::phi_coef per film)");
 // Resident kernels of several films keep the films' running results in LDS instead of registers (k_shade: RES_LDS): kParkWords of the 3 * kMaxOffsets floats per
 // thread -- what Domino's stage leaves free of the CU's 160 KiB at 16 waves (64 KiB node planes + 3 KiB records + 48 KiB stack columns) -- the last one stays a register
 constexpr uint32_t kParkWords = 11;

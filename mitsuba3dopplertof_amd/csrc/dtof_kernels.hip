@@ -798,7 +798,7 @@ __global__ void k_sampler_next_time(RenderParams rp, SamplerState st, uint32_t s
 __global__ void k_waveform_eval(RenderParams rp, const float *t, const float *len, float *out, int mode, uint32_t n) {
     uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
-    out[i] = mode == 0 ? modulation_weight(rp, rp.w_d[0], rp.phase[0], t[i], len[i]) : mode == 1 ? waveform(t[i], rp.wave_type) : waveform_low_pass(t[i], rp.wave_type);
+    out[i] = mode == 0 ? modulation_weight(rp, rp.w_d[0], rp.phase[0], rp.phi_coef[0], rp.w_g[0], t[i], len[i]) : mode == 1 ? waveform(t[i], rp.wave_type) : waveform_low_pass(t[i], rp.wave_type);
 }
 void launch_sampler_seed(const RenderParams &rp, const SamplerState &st, hipStream_t s) {
     if (st.n) hipLaunchKernelGGL(k_sampler_seed, dim3(nblk(st.n)), dim3(kBlock), 0, s, rp, st);

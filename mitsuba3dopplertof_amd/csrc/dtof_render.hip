@@ -79,9 +79,9 @@ void set_filter(RenderParams &rp, int32_t filter, float radius, float stddev, fl
 }
 // spp = samples per wavefront (per pass); sample_count = Sampler::sample_count() of the whole render (0: the same)
 // offsets / n_offsets: batched hetero_offset values at the integrator's own frequency; variants / n_variants: batched (hetero_frequency, hetero_offset) pairs.
-// At most one of the two is given (n > 0); neither: the integrator's own pair.
+// At most one of the two is given (n > 0); neither: the integrator's own pair.  w_g_mhz (with variants only): film k's illumination frequency, null = the integrator's own.
 RenderParams make_params(const dtof_scene *sc, uint32_t seed, uint32_t spp, const float *offsets, int n_offsets, uint32_t sample_count,
-                         const dtof_modulation *variants, int n_variants) {
+                         const dtof_modulation *variants, int n_variants, const float *w_g_mhz) {
     const HostSensor &se = sc->host.sensor; const PluginParams &pp = sc->pp;
     RenderParams rp; memset(&rp, 0, sizeof rp);
     sample_to_camera(se, rp.s2c);
@@ -113,11 +113,12 @@ RenderParams make_params(const dtof_scene *sc, uint32_t seed, uint32_t spp, cons
     // eval_modulation_weight's scalar prefactors are folded in double and rounded to float32 once
     // (they multiply JIT float32 arrays), dopplertofpath.cpp:62-69
     rp.T = pp.time;
-    rp.w_g = (float) (2 * M_PI * (double) pp.w_g_mhz * 1e6);
+    const auto w_g_of = [](float mhz) { return (float) (2 * M_PI * (double) mhz * 1e6); };
+    const auto phi_coef_of = [](float mhz) { return (float) ((2 * M_PI * (double) mhz) / 300); };
+    for (int k = 0; k < kMaxOffsets; ++k) { rp.w_g[k] = w_g_of(pp.w_g_mhz); rp.phi_coef[k] = phi_coef_of(pp.w_g_mhz); }
     const auto w_d_of = [&](float hetero_frequency) { return (float) (2 * M_PI / (double) pp.time * (double) hetero_frequency); };
     const auto phase_of = [](float hetero_offset) { return (float) ((double) (hetero_offset * 2) * M_PI); };   // dopplertofpath.cpp:30-32
     for (int k = 0; k < kMaxOffsets; ++k) rp.w_d[k] = w_d_of(pp.hetero_frequency);
-    rp.phi_coef = (float) ((2 * M_PI * (double) pp.w_g_mhz) / 300);
     rp.amp = (float) (0.5 * (double) pp.g_1);
     rp.g_1 = pp.g_1; rp.g_0 = pp.g_0;
     rp.wave_type = pp.wave_type; rp.low_pass = pp.low_frequency_component_only;
@@ -125,6 +126,7 @@ RenderParams make_params(const dtof_scene *sc, uint32_t seed, uint32_t spp, cons
         if (n_variants > kMaxOffsets) throw std::runtime_error("at most 4 modulation variants can be batched per traversal");
         rp.n_offsets = n_variants;
         for (int k = 0; k < n_variants; ++k) { rp.w_d[k] = w_d_of(variants[k].hetero_frequency); rp.phase[k] = phase_of(variants[k].hetero_offset); }
+        if (w_g_mhz) for (int k = 0; k < n_variants; ++k) { rp.w_g[k] = w_g_of(w_g_mhz[k]); rp.phi_coef[k] = phi_coef_of(w_g_mhz[k]); }   // ... and w_g = w_g_mhz[k] (:62-69)
     } else if (n_offsets <= 0) { rp.n_offsets = 1; rp.phase[0] = pp.phase_offset; }
     else {
         if (n_offsets > kMaxOffsets) throw std::runtime_error("at most 4 modulation offsets can be batched per traversal");
@@ -340,7 +342,7 @@ void plan_lanes(FramePlan &p, const dtof_scene *sc, const RenderRequest &rq) {
         throw std::runtime_error("sample count must be at least time_correlate_number when per-interval stratification is on");
     if (sc->pp.integrator == 0 && sc->pp.sampler_kind == SAMPLER_CORRELATED && sc->pp.time_sampling == TIME_ANTITHETIC_MIRROR && sc->pp.time_correlate_number != 2)
         throw std::runtime_error("antithetic_mirror time sampling needs time_correlate_number == 2");   // Assert(m_time_correlate_number == 2), correlated.cpp:142
-    p.rp = make_params(sc, rq.seed, spp, rq.offsets, rq.n_offsets, sample_count, rq.variants, rq.n_variants);
+    p.rp = make_params(sc, rq.seed, spp, rq.offsets, rq.n_offsets, sample_count, rq.variants, rq.n_variants, rq.w_g_mhz);
     p.rp.n_passes = p.n_passes;
     // lane dumps address (pass, lane) as pass * wavefront + lane and must stay inside one pass
     uint64_t dump_begin = rq.dump_begin;

@@ -86,18 +86,18 @@ DTOF_D float waveform_low_pass(float _t, int type) {
     float r = 2.f - 4.f * c;
     return fmin_(fmax_(2.0f * r, -2.0f), 2.0f);
 }
-// eval_modulation_weight -- dopplertofpath.cpp:60-77; w_d, phase: the film's (RenderParams::w_d[k], ::phase[k])
+// eval_modulation_weight -- dopplertofpath.cpp:60-77; w_d, phase, phi_coef, w_g: the film's four numbers (RenderParams::w_d[k], ::phase[k], ::phi_coef[k], ::w_g[k])
 // FACTS: kFactSineLowPass -- the low-pass weight of the sinusoidal wave is the only form compiled: amp * cos_(fmod_pos(w_d * t + phase + phi))
 template <uint32_t FACTS = 0>
-DTOF_D float modulation_weight(const RenderParams &rp, float w_d, float phase, float ray_time, float path_length) {
+DTOF_D float modulation_weight(const RenderParams &rp, float w_d, float phase, float phi_coef, float w_g, float ray_time, float path_length) {
     constexpr bool F_SINE_LP = (FACTS & kFactSineLowPass) != 0;
-    float phi = rp.phi_coef * path_length;
+    float phi = phi_coef * path_length;
     if (F_SINE_LP || rp.low_pass) {
         float t = w_d * ray_time + phase + phi;
         return rp.amp * waveform_low_pass(t, F_SINE_LP ? (int) WAVE_SIN : rp.wave_type);
     }
-    float t1 = rp.w_g * ray_time - phi;
-    float t2 = (rp.w_g + w_d) * ray_time + phase;
+    float t1 = w_g * ray_time - phi;
+    float t2 = (w_g + w_d) * ray_time + phase;
     float g_t = rp.g_1 * waveform(t1, rp.wave_type) + rp.g_0;
     float s_t = waveform(t2, rp.wave_type);
     return s_t * g_t;

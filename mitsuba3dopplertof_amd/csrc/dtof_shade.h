@@ -739,7 +739,7 @@ __global__ __launch_bounds__(RESW ? RESW * 64 : kShadeBlock, RESW ? RESW / 4 : (
 #pragma unroll
             for (int k = 0; k < KMAX; ++k) if (KMAX == 1 || k < rp.n_offsets) {
                 V3 v = le * mis_bsdf;
-                if (rp.integrator == 0) v = v * modulation_weight<FACTS>(rp, rp.w_d[k], rp.phase[k], time_, stv.w);
+                if (rp.integrator == 0) v = v * modulation_weight<FACTS>(rp, rp.w_d[k], rp.phase[k], rp.phi_coef[k], rp.w_g[k], time_, stv.w);
                 const float4 r = res_get(k);
                 res_put(k, make_float4(fmaf(stv.x, v.x, r.x), fmaf(stv.y, v.y, r.y), fmaf(stv.z, v.z, r.z), 0.f));
             }
@@ -787,7 +787,7 @@ __global__ __launch_bounds__(RESW ? RESW * 64 : kShadeBlock, RESW ? RESW / 4 : (
 #pragma unroll
                     for (int k = 0; k < KMAX; ++k) if (KMAX == 1 || k < rp.n_offsets) {
                         V3 v = le * mis_bsdf;
-                        if (!plain) v = v * modulation_weight<FACTS>(rp, rp.w_d[k], rp.phase[k], time, path_length);
+                        if (!plain) v = v * modulation_weight<FACTS>(rp, rp.w_d[k], rp.phase[k], rp.phi_coef[k], rp.w_g[k], time, path_length);
                         float4 r;
                         if constexpr (RES_LDS) r = res_get(k); else r = rcur[k];
                         const float4 acc = make_float4(fmaf(thr.x, v.x, r.x), fmaf(thr.y, v.y, r.y), fmaf(thr.z, v.z, r.z), 0.f);
@@ -859,7 +859,7 @@ __global__ __launch_bounds__(RESW ? RESW * 64 : kShadeBlock, RESW ? RESW / 4 : (
                 for (int k = 0; k < KMAX; ++k) if (KMAX == 1 || k < rp.n_offsets) {
                     float4 r = AREA ? rcur[k] : res_get(k);
                     V3 v = mk(bsdf_val.x * em_weight.x * mis_em, bsdf_val.y * em_weight.y * mis_em, bsdf_val.z * em_weight.z * mis_em);
-                    if (!plain) { float lw = modulation_weight<FACTS>(rp, rp.w_d[k], rp.phase[k], time, path_length + ds_dist); v = v * lw; }
+                    if (!plain) { float lw = modulation_weight<FACTS>(rp, rp.w_d[k], rp.phase[k], rp.phi_coef[k], rp.w_g[k], time, path_length + ds_dist); v = v * lw; }
                     float3 c = make_float3(fmaf(thr.x, v.x, r.x), fmaf(thr.y, v.y, r.y), fmaf(thr.z, v.z, r.z));
                     cand[k] = c;
                     nonzero |= f2u(c.x) != f2u(r.x) || f2u(c.y) != f2u(r.y) || f2u(c.z) != f2u(r.z);
@@ -949,7 +949,7 @@ __global__ __launch_bounds__(RESW ? RESW * 64 : kShadeBlock, RESW ? RESW / 4 : (
 #pragma unroll
                 for (int k = 0; k < KMAX; ++k) if (k < rp.n_offsets) {
                     V3 v = pend_v;
-                    if (!plain_) v = v * modulation_weight<FACTS>(rp, rp.w_d[k], rp.phase[k], shb.w, pend_len);   // shb.w: the ray time (the shadow ray carries it)
+                    if (!plain_) v = v * modulation_weight<FACTS>(rp, rp.w_d[k], rp.phase[k], rp.phi_coef[k], rp.w_g[k], shb.w, pend_len);   // shb.w: the ray time (the shadow ray carries it)
                     const float4 r = res_get(k);
                     res_put(k, make_float4(fmaf(pend_thr.x, v.x, r.x), fmaf(pend_thr.y, v.y, r.y), fmaf(pend_thr.z, v.z, r.z), 0.f));
                 }

@@ -368,3 +368,149 @@ def calc_velocity_from_homo_heteros(homodynes, heterodynes, exposure_time=0.0015
         conf = np.abs(homodyne) + 1e-5 * 0.0015
         num, den = num + ratio * conf, den + conf
     return _velocity_from_ratio(num / den, exposure_time, w_g)
+
+
+# ------------------------------------------------------------------------------------------------ depth map (the host route of Scene.render_depth_map)
+_TWO_PI = 6.283185307179586
+
+
+def _fma32(a, b, c):
+    """fmaf on float32 arrays, correctly rounded: the product of two float32 is exact in double; the double sum is rounded to ODD (its error term from the two-sum
+    decides), so that the second rounding, to float32, sees what it would have seen of the exact value"""
+    a, b, c = (np.asarray(x, np.float32).astype(np.float64) for x in (a, b, c))
+    with np.errstate(all="ignore"):
+        return _fma32_quiet(a, b, c)
+
+
+def _fma32_quiet(a, b, c):
+    p = a * b
+    s = p + c
+    bb = s - p
+    err = (p - (s - bb)) + (c - bb)
+    fix = np.isfinite(s) & (err != 0) & ((s.view(np.int64) & 1) == 0)
+    s = np.where(fix, np.nextafter(s, np.where(err > 0, np.inf, -np.inf)), s)
+    return s.astype(np.float32)
+
+
+def _atan2f(y, x):
+    """atan2_ of csrc/dtof_math.h on float32 arrays, operation for operation (every float32 operation rounded once)"""
+    f = np.float32
+    y, x = np.asarray(y, f), np.asarray(x, f)
+    with np.errstate(all="ignore"):
+        return _atan2f_quiet(y, x, f)
+
+
+def _atan2f_quiet(y, x, f):
+    xa, ya = np.abs(x), np.abs(y)
+    mn, mx = np.where(ya < xa, ya, xa), np.where(xa > ya, xa, ya)
+    scale = mn / mx
+    z = scale * scale
+    z2 = z * z
+    z4 = z2 * z2
+    p01, p23 = _fma32(z, f(-0.33326497518773606976), f(0.99999934166683966009)), _fma32(z, f(-0.13486708938456973185), f(0.19881342388439013552))
+    p45, p6 = _fma32(z, f(-0.37006525670417265220e-1), f(0.83863120428809689910e-1)), f(0.78613793713198150252e-2)
+    poly = _fma32(z4, _fma32(z2, p6, p45), _fma32(z2, p23, p01))
+    t = scale * poly
+    pi = f(3.14159265358979323846)
+    t = np.where(ya > xa, f(0.5) * pi - t, t)
+    t = np.where(x < 0, pi - t, t)
+    r = np.where(y < 0, -t, t)
+    return np.where(mx != 0, r, f(0)).astype(f)
+
+
+def calc_depth_from_homodynes(i_images, q_images, frequencies, max_path_length, _atan2=_atan2f):
+    """The depth map of include/dtof.h ("depth map") in numpy, from the float32 ToF images of the homodyne films at hetero_offset 0 (i_images[j]) and 0.25
+    (q_images[j]) rendered at frequencies[j] MHz: the wrapped phase atan2(-Q, I) of every frequency and, with two or more, the wrap counts -- tried for the first
+    frequency up to max_path_length -- on which the frequencies agree best.  Returns a dict: "depth" (half the path length, metres), "residual" float64, "wraps"
+    (F, ...) int32, "amplitude" (F, ...) float64, "phase" (F, ...) float32.  Scene.render_depth_map computes the same words on the device."""
+    I = [np.ascontiguousarray(a, np.float32) for a in i_images]
+    Q = [np.ascontiguousarray(a, np.float32) for a in q_images]
+    n_freq = len(frequencies)
+    if not 1 <= n_freq <= 4 or len(I) != n_freq or len(Q) != n_freq:
+        raise ValueError("between 1 and 4 frequencies, each with an I and a Q image")
+    shape = I[0].shape
+    with np.errstate(all="ignore"):
+        L = [300.0 / float(f) for f in frequencies]
+        ph = [np.asarray(_atan2(-Q[j], I[j]), np.float32).reshape(shape) for j in range(n_freq)]
+        w, amp = [], []
+        for j in range(n_freq):
+            p = ph[j].astype(np.float64)
+            p = np.where(p < 0, p + _TWO_PI, p)
+            w.append((p / _TWO_PI) * L[j])
+            i64, q64 = I[j].astype(np.float64), Q[j].astype(np.float64)
+            amp.append(np.sqrt(i64 * i64 + q64 * q64))
+        if n_freq == 1:
+            return {"depth": 0.5 * w[0], "residual": np.zeros(shape), "wraps": np.zeros((1,) + shape, np.int32), "amplitude": np.stack(amp), "phase": np.stack(ph)}
+        n_cand = np.floor(max_path_length / L[0])
+        if not 0 <= n_cand <= 4095:
+            raise ValueError("max_path_length must give between 1 and 4096 wrap candidates of the first frequency")
+        won = np.zeros(shape, bool)
+        best_err, best_c = np.zeros(shape), np.zeros(shape)
+        best_e, best_m = [np.zeros(shape) for _ in range(n_freq)], [np.zeros(shape) for _ in range(n_freq)]
+        for n in range(int(n_cand) + 1):
+            c = w[0] + float(n) * L[0]
+            err, e, m = np.zeros(shape), [None], [np.full(shape, float(n))]
+            for j in range(1, n_freq):
+                mj = np.rint((c - w[j]) / L[j])
+                mj = np.where(mj < 0, 0.0, mj)
+                ej = w[j] + mj * L[j]
+                r = ej - c
+                err = err + r * r
+                e.append(ej); m.append(mj)
+            take = np.where(won, err < best_err, err == err)      # the first wins on ties, a NaN never
+            won = won | take
+            best_err, best_c = np.where(take, err, best_err), np.where(take, c, best_c)
+            for j in range(n_freq):
+                best_m[j] = np.where(take, m[j], best_m[j])
+                if j:
+                    best_e[j] = np.where(take, e[j], best_e[j])
+        S, num = amp[0], amp[0] * best_c
+        for j in range(1, n_freq):
+            S, num = S + amp[j], num + amp[j] * best_e[j]
+        path = np.where(S > 0, num / S, 0.0)
+        nan = np.float64("nan")
+        return {"depth": np.where(won, 0.5 * path, nan), "residual": np.where(won, np.sqrt(best_err), nan),
+                "wraps": np.stack([np.where(won, best_m[j], -1.0).astype(np.int32) for j in range(n_freq)]),
+                "amplitude": np.stack([np.where(won, amp[j], nan) for j in range(n_freq)]),
+                "phase": np.stack([np.where(won, ph[j], np.float32("nan")).astype(np.float32) for j in range(n_freq)])}
+
+
+def _depth_setup(scene, frequencies, max_path_length, integrator_kwargs):
+    from ._scene import default_max_path_length
+    integrator_kwargs = dict(integrator_kwargs)
+    for k in ("hetero_offset", "hetero_frequency", "w_g"):
+        integrator_kwargs.pop(k, None)
+    freq = [float(np.float32(f)) for f in frequencies]
+    scene.set_integrator(doppler_integrator_dict(hetero_frequency=0.0, hetero_offset=0.0, w_g=freq[0], **integrator_kwargs))
+    return freq, default_max_path_length(freq) if max_path_length is None else float(max_path_length), integrator_kwargs.get("exposure_time", 0.0015)
+
+
+def run_scene_depth_map(scene, total_spp=1024, frequencies=(30.0, 40.0), max_path_length=None, film="float32", **integrator_kwargs):
+    """The depth map on the host from ONE traversal per pass and pair of frequencies: the I / Q films of every frequency are (0, 0, f) and (0, 0.25, f) variants of the
+    same paths (Scene.render(variants=triples)), averaged over the passes, turned into ToF images and handed to calc_depth_from_homodynes.  Returns its dict with
+    "tof", the (2 F, H, W) ToF images in the order of depth_map_variants, added."""
+    from ._scene import depth_map_variants
+    freq, max_path_length, exposure_time = _depth_setup(scene, frequencies, max_path_length, integrator_kwargs)
+    single, n_pass = _passes(total_spp)
+    triples = [tuple(float(x) for x in v) for v in depth_map_variants(freq)]
+    images, stats = [], []
+    for g in range(0, len(triples), 4):
+        acc = None
+        for i in range(n_pass):
+            img = scene.render(seed=i, spp=single, variants=triples[g:g + 4], film=film).astype(np.float32)
+            stats.append(scene.last_stats)
+            acc = img if acc is None else acc + img
+        images += list(acc / np.float32(n_pass))
+    scene.pass_stats = stats
+    tof = [to_tof_image(im, exposure_time) for im in images]
+    out = calc_depth_from_homodynes(tof[0::2], tof[1::2], freq, max_path_length)
+    out["tof"] = np.stack(tof)
+    return out
+
+
+def run_scene_depth_map_device(scene, total_spp=1024, frequencies=(30.0, 40.0), max_path_length=None, film="float32", **integrator_kwargs):
+    """run_scene_depth_map with everything behind the film splat on the GPU (Scene.render_depth_map): the same integrator, passes, seeds and traversals; the same dict,
+    word for word."""
+    freq, max_path_length, exposure_time = _depth_setup(scene, frequencies, max_path_length, integrator_kwargs)
+    single, n_pass = _passes(total_spp)
+    return scene.render_depth_map(n_pass, single, freq, exposure_time, max_path_length, film=film)
