@@ -130,6 +130,9 @@ int dtof_scene_get_info(const dtof_scene *scene, dtof_scene_info *info);
  *                             (initialize_sh_frame, include/mitsuba/render/interaction.h:258-268) as precomputed for the kernels; zeros for an instance
  * kind 26: what a frame plan takes from the flat table (automatic pipeline, default switches) -> 4 floats: the one instance is the memo object of one rectangle
  *                             (0 / 1), the table's shape is compiled into kernels (0 / 1: at most 8 objects), its object count, the index of the instance
+ * kind 27: the triangles in the order the device keeps them -> for every mesh shape (objects ascending, the shapes of a group ascending): its top-level object,
+ *                             its index in the object's group, its triangle count, then per triangle IN THE BLAS'S ORDER its face index in the mesh's own order;
+ *                             all as uint32 bit patterns.  What maps a face to the `primitive` dtof_surface_eval takes.
  * kind 10: roughplastic tables -> per roughplastic shape the 64 values of m_external_transmittance (roughplastic.cpp:222-257)
  * Returns the number of floats written (<= capacity) through *n_written. */
 int dtof_scene_export(const dtof_scene *scene, int kind, float *out, size_t capacity, size_t *n_written);
@@ -818,6 +821,18 @@ int dtof_pair_setup_lanes(dtof_scene *scene, int form, uint32_t seed, uint32_t s
  * launched or written, for a form the scene does not meet -- no half-float nodes (forms 1 to 4), an analytic shape, a stack deeper than 64 entries or a TLAS of more
  * than 16 nodes for form 2 (forms 1 to 3) -- and for n above 2^24; non-finite ray components are taken as they are. */
 int dtof_tree_query(dtof_scene *scene, int form, int any, uint32_t n, const float *rays8, float *out3, int32_t *ids3);
+/* The surface-interaction fill (PreliminaryIntersection::compute_surface_interaction, include/mitsuba/render/interaction.h:675-701, through the shapes' and the
+ * instance's own, and Interaction::offset_p, :161-165) over arrays of HITS, through the instantiations and argument patterns of it that the kernels of a frame
+ * carry.  A hit is given, not traced: in10 = o[3], d[3], time, t, b1, b2 (prim_uv); ids3 = object, shape in its group, primitive -- a triangle by its index IN THE
+ * BLAS'S ORDER (dtof_scene_export kind 27 maps faces to it), ignored for any other shape.  form 0: the mesh kernels' instantiation, the instance matrix derived per
+ * hit; 1: the rectangle-only kernels', no instance memo; 2: ... with the scene's one instance as the memo object, its matrix from registers and its inverse read
+ * back from the lane's LDS column; 3: ... both read back from LDS; 4: the one-wall kernels' with their precomputed frames; 5: form 0 with the memo object's
+ * matrices from registers.  want_frame = 0: the form in which a caller reads the cosine wi.z only.  out32 = p, n, sh_frame.n, sh_frame.s, sh_frame.t, wi (3 each),
+ * uv[2], dp_du[3], dp_dv[3], offset_p(d)[3], offset_p(-d)[3]; with want_frame = 0 sh_frame.s / .t, dp_du, dp_dv and wi.x / .y are +0, and form 4 reports dp_du =
+ * dp_dv = +0 always (no kernel of that form reads them).  DTOF_ERR_INVALID, before anything is launched or written, for a scene without a device blob, a form the
+ * scene does not meet -- a shape that is no rectangle or a blob above the 16 KiB LDS stage (forms 1 to 4), no single instance (2, 3, 5), a flat table without the one-wall fact (4) -- an id out of
+ * range (object, shape beyond its group, primitive beyond a mesh's triangles) and n above 2^24; non-finite floats are taken as they are. */
+int dtof_surface_eval(dtof_scene *scene, int form, int want_frame, uint32_t n, const float *in10, const int32_t *ids3, float *out32);
 
 /* ---------------------------------------------------------------- component evaluation
  * The device functions the shade and splat kernels are built from, evaluated over arrays on the GPU: the counterpart of the

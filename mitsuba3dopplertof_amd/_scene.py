@@ -843,6 +843,31 @@ class Scene:
         non-finite components are taken as they are."""
         return self._ray_query("dtof_tree_query", rays8, any, "ids", self.TREE_FORMS, form)
 
+    SURFACE_FORMS = {"mesh": 0, "rect": 1, "rect_memo_regs": 2, "rect_memo_lds": 3, "one_wall": 4, "mesh_memo_regs": 5}
+
+    def surface_eval(self, in10, ids3, form=0, want_frame=True):
+        """The surface-interaction fill over (n, 10) hits o, d, time, t, b1, b2 with (n, 3) ids object, shape in its group, primitive in the BLAS's order
+        (dtof_surface_eval; triangle_order() maps faces).  form: 0 / "mesh", 1 / "rect", 2 / "rect_memo_regs", 3 / "rect_memo_lds", 4 / "one_wall",
+        5 / "mesh_memo_regs" -- the instantiation of compute_surface that runs.  -> (n, 32) float32: p, n, sh_n, sh_s, sh_t, wi, uv, dp_du, dp_dv, offset_p(d),
+        offset_p(-d).  A form the scene does not meet, an id out of range and more than 2^24 hits raise DtofError; non-finite floats are taken as they are."""
+        q = np.ascontiguousarray(in10, np.float32).reshape(-1, 10)
+        ids = np.ascontiguousarray(ids3, np.int32).reshape(-1, 3)
+        if len(ids) != len(q):
+            raise ValueError("surface_eval: %d hits and %d id rows" % (len(q), len(ids)))
+        out = np.zeros((len(q), 32), np.float32)
+        _check(_abi._lib().dtof_surface_eval(self._h, int(self.SURFACE_FORMS.get(form, form)), 1 if want_frame else 0, len(q), q.ctypes.data, ids.ctypes.data, out.ctypes.data))
+        return out
+
+    def triangle_order(self):
+        """{(object, shape in its group): uint32 array, the face index of every triangle in the BLAS's order} for the mesh shapes (dtof_scene_export kind 27)"""
+        w = self.export(27).view(np.uint32)
+        out, at = {}, 0
+        while at < len(w):
+            obj, k, n = (int(x) for x in w[at:at + 3])
+            out[(obj, k)] = w[at + 3:at + 3 + n].copy()
+            at += 3 + n
+        return out
+
     def cancel(self):
         _abi._lib().dtof_cancel(self._h)
 

@@ -5,6 +5,7 @@
 #include "dtof_flat_query.h"
 #include "dtof_pair_setup.h"
 #include "dtof_tree_query.h"
+#include "dtof_surface_query.h"
 #include <cmath>
 #include <memory>
 
@@ -385,6 +386,47 @@ int dtof_tree_query(dtof_scene *sc, int form, int any, uint32_t n, const float *
         ensure_device(sc);
         round_trip({ { rays8, (size_t) n * 32 } }, { { out3, any ? 0 : (size_t) n * 12, 4 }, { ids3, (size_t) n * (any ? 1 : 3) * 4 } }, [&](void *const *in, void *const *out) {
             launch_tree_query(sc->d_blob.p, q, form, any != 0, (const float *) in[0], (float *) out[0], (int32_t *) out[1], n, nullptr);
+        });
+    });
+}
+
+// compute_surface / offset_p over arrays of hits (dtof_surface_query.hip): the surface-interaction fill in the form a frame's kernels run it.  A form the scene does not
+// meet and an id out of range are refused before anything is launched or written: the kernel indexes the blob's tables with the ids as they are.
+int dtof_surface_eval(dtof_scene *sc, int form, int want_frame, uint32_t n, const float *in10, const int32_t *ids3, float *out32) {
+    return guarded([&] {
+        if (!sc || (n && (!in10 || !ids3 || !out32))) throw std::runtime_error("null argument");
+        if (form < 0 || form >= kSurfaceForms) throw std::runtime_error("dtof_surface_eval: form must be 0 (mesh), 1 (rect), 2 (rect_memo_regs), 3 (rect_memo_lds), 4 (one_wall) or 5 (mesh_memo_regs)");
+        if (want_frame != 0 && want_frame != 1) throw std::runtime_error("dtof_surface_eval: want_frame must be 0 or 1");
+        if (n > (1u << 24)) throw std::runtime_error("dtof_surface_eval: more than 2^24 hits in one call");
+        if (sc->blob.size() < sizeof(BlobHeader)) throw std::runtime_error("dtof_surface_eval: the scene has no device blob");
+        const BlobHeader *bh = (const BlobHeader *) sc->blob.data();
+        const DObject *ob = (const DObject *) (sc->blob.data() + bh->off_objects);
+        const DGroup *grp = (const DGroup *) (sc->blob.data() + bh->off_groups);
+        const DShape *shp = (const DShape *) (sc->blob.data() + bh->off_shapes);
+        const SceneTraits t = scene_traits(*sc);
+        const FlatChoice c = default_flat_choice(*sc, t);
+        SurfaceQueryScene q { (uint32_t) sc->blob.size(), t.flat_off, c.flat_objects, t.n_instances == 1 ? t.last_instance : 0xffffffffu };
+        const bool rect_form = form >= 1 && form <= 4, memo_form = form >= 2;
+        if (rect_form) for (uint32_t i = 0; i < bh->n_shapes; ++i)
+            if (shp[i].kind != SHAPE_RECT) throw std::runtime_error("dtof_surface_eval: forms 1 to 4 are the rectangle-only kernels' and the scene has a shape that is not a rectangle");
+        if (rect_form && sc->blob.size() > 16u * 1024u) throw std::runtime_error("dtof_surface_eval: the scene does not fit the LDS stage of forms 1 to 4");   // (launch_shade stages up to 16 KiB)
+        if (memo_form && form != 4 && q.memo_obj == 0xffffffffu) throw std::runtime_error("dtof_surface_eval: the memo forms need a memo object (exactly one instance)");
+        if (form == 4) {
+            if (!(c.facts & kFactOneWall)) throw std::runtime_error("dtof_surface_eval: the one_wall form needs a flat table whose one instance holds one rectangle");
+            q.memo_obj = c.memo_obj;
+        }
+        for (uint32_t i = 0; i < n; ++i) {
+            const int32_t *id = ids3 + (size_t) i * 3;
+            if (id[0] < 0 || (uint32_t) id[0] >= bh->n_objects) throw std::runtime_error("dtof_surface_eval: hit " + std::to_string(i) + ": object out of range");
+            const DObject &o = ob[id[0]];
+            const bool inst = o.kind == OBJ_INSTANCE;
+            if (id[1] < 0 || (uint32_t) id[1] >= (inst ? grp[o.index].n_shapes : 1u)) throw std::runtime_error("dtof_surface_eval: hit " + std::to_string(i) + ": shape beyond its group");
+            const DShape &s = shp[inst ? grp[o.index].first_shape + id[1] : o.index];
+            if (id[2] < 0 || (s.kind == SHAPE_MESH && (uint32_t) id[2] >= s.n_tris)) throw std::runtime_error("dtof_surface_eval: hit " + std::to_string(i) + ": primitive beyond the mesh's triangles");
+        }
+        ensure_device(sc);
+        round_trip({ { in10, (size_t) n * kSurfaceIn * 4 }, { ids3, (size_t) n * 12 } }, { { out32, (size_t) n * kSurfaceOut * 4 } }, [&](void *const *in, void *const *out) {
+            launch_surface_query(sc->d_blob.p, q, form, want_frame != 0, (const float *) in[0], (const int32_t *) in[1], (float *) out[0], n, nullptr);
         });
     });
 }

@@ -204,6 +204,23 @@ int dtof_scene_export(const dtof_scene *sc, int kind, float *out, size_t cap, si
             const FlatChoice c = default_flat_choice(*sc, scene_traits(*sc));
             v.push_back((c.facts & kFactOneWall) ? 1.f : 0.f); v.push_back((c.facts & kFactFlatShape) ? 1.f : 0.f); v.push_back((float) flat_shape_count(c.facts)); v.push_back((float) flat_shape_wall(c.facts));
         }
+        else if (kind == 27) {   // the triangles as the blob orders them: for every mesh shape its object, its index in the object's group, its triangle count and then DTri::face of
+            const BlobHeader *bh = (const BlobHeader *) sc->blob.data();   // each in the BLAS's order -- what maps Hit::prim to the face index of the mesh's own order (integers as bit patterns)
+            const DObject *ob = (const DObject *) (sc->blob.data() + bh->off_objects);
+            const DShape *shp = (const DShape *) (sc->blob.data() + bh->off_shapes);
+            const DGroup *grp = (const DGroup *) (sc->blob.data() + bh->off_groups);
+            const DTri *tri = (const DTri *) (sc->blob.data() + bh->off_tris);
+            const auto word = [&](uint32_t x) { float b; memcpy(&b, &x, 4); v.push_back(b); };
+            for (uint32_t i = 0; i < bh->n_objects; ++i) {
+                const bool inst = ob[i].kind == OBJ_INSTANCE;
+                for (uint32_t k = 0; k < (inst ? grp[ob[i].index].n_shapes : 1u); ++k) {
+                    const DShape &d = shp[inst ? grp[ob[i].index].first_shape + k : ob[i].index];
+                    if (d.kind != SHAPE_MESH) continue;
+                    word(i); word(k); word(d.n_tris);
+                    for (uint32_t f = 0; f < d.n_tris; ++f) word(tri[d.first_tri + f].face);
+                }
+            }
+        }
         else if (kind == 23) for (auto &s : sc->host.shapes) {   // blendbsdf: is one, weight, its texture, kind and two-sidedness of bsdf_1
             v.push_back(s.blend_other ? (s.two_bsdfs ? 2.f : 1.f) : 0.f); v.push_back(s.blend_weight); v.push_back((float) s.tex_blend);   // 1 blendbsdf, 2 twosided with two BSDFs
             v.push_back(s.blend_other ? (float) s.blend_other->bsdf : -1.f); v.push_back(s.blend_other && s.blend_other->twosided ? 1.f : 0.f);

@@ -592,10 +592,7 @@ __global__ __launch_bounds__(RESW ? RESW * 64 : kShadeBlock, RESW ? RESW / 4 : (
     float memo_m[12], memo_inv[12];   // instance memo: the one instance's matrix and inverse at this lane's ray time
     // kFactOneWall: the wall's unit normal and tangent at this lane's ray time, and the plain rectangles' frames (DFlatFrame[n] behind DFlatObject[n], DFlatKinds, DFlatZ[n])
     typename std::conditional<F_FRAMES, WallFrames, NoFrames>::type wf;
-    if constexpr (F_FRAMES) {
-        wf.n = mk(0.f, 0.f, 1.f); wf.s = mk(1.f, 0.f, 0.f);
-        wf.table = (const DFlatFrame *) ((const uint4 *) ((const DFlatObject *) (sv.base + rp.flat_off) + rp.flat_objects) + 1 + rp.flat_objects);
-    }
+    if constexpr (F_FRAMES) wall_frames_init(wf, sv, rp.flat_off, rp.flat_objects);
     V3 pair_wo = mk(0.f, 0.f, 1.f), pair_wo_next = pair_wo;   // PAIR: the BSDF's sampled direction (local frame) of the iteration that runs and of the one after it
     bool lane_on = in_range;
 #ifdef DTOF_TRAVERSAL_STATS   // development builds: lanes without a path carry a poison pattern; DTOF_POISON_CHECK counts it wherever path state is written out (statistic [14])
@@ -659,13 +656,7 @@ __global__ __launch_bounds__(RESW ? RESW * 64 : kShadeBlock, RESW ? RESW / 4 : (
                 o.time = ra.w; o.ray_o[0] = ra.x; o.ray_o[1] = ra.y; o.ray_o[2] = ra.z; o.ray_d[0] = rb.x; o.ray_d[1] = rb.y; o.ray_d[2] = rb.z;
             }
             if (have_memo) instance_memo_fill(sv, ra.w, memo_m, memo_inv);
-            if constexpr (F_FRAMES) {   // what compute_surface evaluates for a hit on the wall, in its order: n = normalize(xf_normal(inv, n)), dp_du = xf_vector(m, dp_du), initialize_sh_frame
-                const DShape &ws = sv.shapes[sv.groups[sv.objects[sv.memo_obj].index].first_shape];
-                wf.n = normalize(xf_normal(memo_inv, mk(ws.n[0], ws.n[1], ws.n[2])));
-                const V3 du = xf_vector(memo_m, mk(ws.dp_du[0], ws.dp_du[1], ws.dp_du[2]));
-                wf.s = normalize(vfma(wf.n, -dot(wf.n, du), du));
-                if (du.x == 0.f && du.y == 0.f && du.z == 0.f) { V3 tt; coordinate_system(wf.n, wf.s, tt); }
-            }
+            if constexpr (F_FRAMES) wall_frames_fill(wf, sv, memo_m, memo_inv);   // (dtof_shading.h)
             Hit h;
             // (WALK_PRIMARY: kFactStratifiedPairs gives lanes 2k and 2k + 1 one pixel jitter from the stream they share and times of their own -- the same o, d and maxt --
             //  and kFactWavePixel has every lane of the wave here)

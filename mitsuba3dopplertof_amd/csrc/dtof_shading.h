@@ -21,6 +21,21 @@ struct Surface { V3 p, n, sh_n, sh_s, sh_t, wi; float u, v; const DShape *shape;
 // does not change along its path: k_shade fills them once per path with the expressions below, in their order), a plain rectangle's tangents from the DFlatFrame table.
 struct WallFrames { V3 n, s; const DFlatFrame *table; };   // table: DFlatFrame[n_objects] of the staged blob
 struct NoFrames {};                                          // (what a kernel without the fact keeps in their place)
+// What a kernel with the fact keeps in `wf`, in two steps (k_shade; k_surface_query of dtof_surface_query.hip, which holds these lines to the oracle): before the
+// first lane the frame of a lane without a path and the table, DFlatFrame[n] behind DFlatObject[n], DFlatKinds, DFlatZ[n] ...
+DTOF_D void wall_frames_init(WallFrames &wf, const SceneView &sv, uint32_t flat_off, uint32_t flat_objects) {
+    wf.n = mk(0.f, 0.f, 1.f); wf.s = mk(1.f, 0.f, 0.f);
+    wf.table = (const DFlatFrame *) ((const uint4 *) ((const DFlatObject *) (sv.base + flat_off) + flat_objects) + 1 + flat_objects);
+}
+// ... and per lane, behind instance_memo_fill, what compute_surface evaluates for a hit on the wall, in its order: n = normalize(xf_normal(inv, n)),
+// dp_du = xf_vector(m, dp_du), initialize_sh_frame
+DTOF_D void wall_frames_fill(WallFrames &wf, const SceneView &sv, const float (&memo_m)[12], const float (&memo_inv)[12]) {
+    const DShape &ws = sv.shapes[sv.groups[sv.objects[sv.memo_obj].index].first_shape];
+    wf.n = normalize(xf_normal(memo_inv, mk(ws.n[0], ws.n[1], ws.n[2])));
+    const V3 du = xf_vector(memo_m, mk(ws.dp_du[0], ws.dp_du[1], ws.dp_du[2]));
+    wf.s = normalize(vfma(wf.n, -dot(wf.n, du), du));
+    if (du.x == 0.f && du.y == 0.f && du.z == 0.f) { V3 tt; coordinate_system(wf.n, wf.s, tt); }
+}
 template <bool MESH, uint32_t FACTS = 0>
 DTOF_D void compute_surface(const SceneView &sv, uint32_t oi, uint32_t shape_k, uint32_t prim, float t, float b1, float b2,
                             V3 o, V3 d, float time, Surface &si, bool use_memo, const float (&memo_m)[12], const float (&memo_inv)[12], bool want_frame = true,

@@ -360,6 +360,15 @@ uint32_t orc_kat_flat_n(const orc_scene *sc, uint32_t n, const float *rays8, flo
 /* scene_closest and scene_occluded over arrays, with all three ids (dtof_tree_query): out3 = t, u, v; ids4 = object, shape, primitive, occluded; prim_t / prim_ids
  * (optional): every primitive's own hit distance per ray and the ids of those slots.  Returns the number of primitive slots. */
 uint32_t orc_kat_tree_n(const orc_scene *sc, uint32_t n, const float *rays8, float *out3, int32_t *ids4, float *prim_t, uint32_t max_prims, int32_t *prim_ids);
+/* compute_si (PreliminaryIntersection::compute_surface_interaction) and offset_p over arrays of HITS (dtof_surface_eval): in10 = o[3], d[3], time, t, b1, b2;
+ * ids3 = object, shape in its group, and for a mesh the FACE index in the mesh's own order (the device's entry takes the triangle's index in its BLAS instead);
+ * out32 = p, n, sh_n, sh_s, sh_t, wi, uv[2], dp_du, dp_dv, offset_p(si, d), offset_p(si, -d).  A hit is taken as given: t, b1, b2 may be what no ray query reports,
+ * the ids must be in range.  ops (optional, ORC_SURF_OPS words per hit, for the tests' classification only): the operand of every discrete decision the hit met,
+ * NaN where it met none -- the disk's r and the sphere's rd (compared with 0), the mesh's uv determinant (compared with 0; only a mesh with texcoords computes
+ * one), whether dp_du was the zero vector at initialize_sh_frame (1 / 0), the keyframe segment instance_to_world read (always 0: AnimatedTransform::eval
+ * interpolates keyframes 0 and 1 only) with its clamped weight, and dot(n, d) as offset_p(si, d) saw it (its sign alone decides). */
+enum { ORC_SURF_DISK_R = 0, ORC_SURF_SPHERE_RD = 1, ORC_SURF_MESH_DET = 2, ORC_SURF_DPDU_ZERO = 3, ORC_SURF_SEGMENT = 4, ORC_SURF_WEIGHT = 5, ORC_SURF_OFFSET_DOT = 6, ORC_SURF_OPS = 7 };
+void     orc_kat_surface_n(const orc_scene *sc, uint32_t n, const float *in10, const int32_t *ids3, float *out32, float *ops);
 void     orc_texture_eval(const orc_texture *tex, float u, float v, float *out3);
 float    orc_texture_eval_1(const orc_texture *tex, float u, float v);   /* Texture::eval_1: a 1-channel texel, the luminance of an RGB texel, the mean of a checkerboard colour */
 void     orc_kat_sphere_sample_direction(const orc_shape *sh, const float *ref, float s_x, float s_y, float *out11);

@@ -202,6 +202,8 @@ def lib():
         L.orc_kat_emitter_n.argtypes = [C.POINTER(OrcScene), C.c_int, C.c_int32, C.c_uint32, C.c_void_p, C.c_void_p]
         L.orc_kat_flat_n.restype = C.c_uint32
         L.orc_kat_flat_n.argtypes = [C.POINTER(OrcScene), C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
+        L.orc_kat_surface_n.restype = None
+        L.orc_kat_surface_n.argtypes = [C.POINTER(OrcScene), C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.orc_kat_tree_n.restype = C.c_uint32
         L.orc_kat_tree_n.argtypes = [C.POINTER(OrcScene), C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
         L.orc_kat_emitter_sample.argtypes = [C.POINTER(OrcScene), C.c_int, C.c_void_p, C.c_float, C.c_float, C.c_void_p]
@@ -492,6 +494,15 @@ class Scene:
         else:
             L.orc_kat_tree_n(C.byref(self.c), n, rays8.ctypes.data, out3.ctypes.data, ids4.ctypes.data, None, 0, None)
         return r
+
+    def surface_n(self, in10, ids3):
+        """orc_kat_surface_n: (n, 10) hits o, d, time, t, b1, b2 and (n, 3) ids object, shape, FACE -> (out (n, 32), ops (n, ORC_SURF_OPS): disk r, sphere rd,
+        mesh det, dp_du zero, keyframe segment, weight, dot(n, d) of offset_p)"""
+        in10, ids3 = np.ascontiguousarray(in10, np.float32).reshape(-1, 10), np.ascontiguousarray(ids3, np.int32).reshape(-1, 3)
+        assert len(in10) == len(ids3)
+        out, ops = np.zeros((len(in10), 32), np.float32), np.zeros((len(in10), 7), np.float32)
+        lib().orc_kat_surface_n(C.byref(self.c), len(in10), in10.ctypes.data, ids3.ctypes.data, out.ctypes.data, ops.ctypes.data)
+        return out, ops
 
     def render(self, pd, seed=0, spp=None, rows=None, threads=1, raw=False):
         spp = spp or pd["sample_count"]
