@@ -2,12 +2,12 @@
 // film, the moment and aov cells, lane dumps), develops one, reconstructs the radial-velocity map or denoises, and dtof_async_collect.  All of them end in render_rows
 // (dtof_render.hip) or in one of the launchers of the small kernel files.
 #include "dtof_host.h"
+#include "dtof_develop.h"
 #include "dtof_reconstruct.h"
 #include "dtof_depth.h"
 #include "dtof_denoise.h"
 #include "dtof_temporal.h"
 #include "dtof_world_to_pixel.h"
-#include "dtof_film64.h"
 #include "dtof_moments.h"
 #include "dtof_adaptive.h"
 #include <cmath>
@@ -53,6 +53,10 @@ static std::pair<int32_t, int32_t> stripe_span(const dtof_scene *sc, int32_t fir
     return {first, (int32_t) (first + ((v_rows - 1) / stripe_rows) * stripe_period + (v_rows - 1) % stripe_rows + 1)};
 }
 
+// The refusal of an exposure time or a modulation frequency that is a NaN, infinite or not above 0; `name` is how the entry's documentation calls the argument
+static bool finite_positive(double v) { return std::isfinite(v) && v > 0; }
+static void need_finite_positive(double v, const std::string &name) { if (!finite_positive(v)) throw std::runtime_error(name + " must be finite and > 0"); }
+
 // The variants arguments of the C ABI as a request carries them: NULL / 0 = the integrator's own pair; the count is checked here, before anything is enqueued
 static void set_variants(RenderRequest &rq, const dtof_modulation *variants, int n_variants) {
     if (!variants || n_variants <= 0) return;
@@ -65,8 +69,7 @@ static void set_variants_freq(RenderRequest &rq, const dtof_modulation *variants
     set_variants(rq, variants, n_variants);
     if (!w_g_mhz) return;
     if (rq.n_variants <= 0) throw std::runtime_error("modulation frequencies come with the variants they belong to: variants is null or n_variants is not positive");
-    for (int k = 0; k < n_variants; ++k)
-        if (!std::isfinite(w_g_mhz[k]) || !(w_g_mhz[k] > 0.f)) throw std::runtime_error("w_g_mhz[" + std::to_string(k) + "] must be finite and > 0");
+    for (int k = 0; k < n_variants; ++k) need_finite_positive(w_g_mhz[k], "w_g_mhz[" + std::to_string(k) + "]");
     rq.w_g_mhz = w_g_mhz;
 }
 // The device-film entry points: a rows or stripes request with the call's offsets or variants (their count is refused before a null scene or film is), the null and
@@ -90,25 +93,35 @@ static int device_film(dtof_scene *sc, RenderRequest rq, const float *offsets, i
     });
 }
 
-// The library's own film, float32 or float64: the buffer it lives in, the fields of a request that name it, its develop launchers, and whether its host-buffer render
-// asks for the sensor before the first HIP call (the float64 one does; the float32 one leaves that to render_rows, behind ensure_device)
+// The library's own film, float32 or float64: the buffer it lives in, the fields of a request that name it, and whether its host-buffer render asks for the sensor
+// before the first HIP call (the float64 one does; the float32 one leaves that to render_rows, behind ensure_device).  Its develop is overloaded (dtof_develop.h)
 template <typename T> struct OwnFilm;
 template <> struct OwnFilm<float> {
     static constexpr bool sensor_first = false;
     static DevBuf<float> &buf(dtof_scene *sc) { return sc->d_film; }
     static void attach(RenderRequest &rq, float *film, uint64_t stride) { rq.film = film; rq.film_stride = stride; }
-    static void develop(const float *film, int k, float *rgb, int64_t px, hipStream_t s) { launch_develop(film, rgb, px * k, s); }
-    static void develop_rgba(const float *film, const float *alpha, float *rgba, int64_t px, hipStream_t s) { launch_develop_rgba(film, alpha, rgba, px, s); }
-    static void develop_accumulate(const float *film, int k, float *sum, int64_t px, bool first, hipStream_t s) { launch_develop_accumulate(film, k, 0, sum, px, first, s); }
 };
 template <> struct OwnFilm<double> {
     static constexpr bool sensor_first = true;
     static DevBuf<double> &buf(dtof_scene *sc) { return sc->d_film64; }
     static void attach(RenderRequest &rq, double *film, uint64_t stride) { rq.film64 = film; rq.film64_stride = stride; }
-    static void develop(const double *film, int k, float *rgb, int64_t px, hipStream_t s) { launch_develop_f64(film, k, 0, rgb, px, s); }
-    static void develop_rgba(const double *film, const double *alpha, float *rgba, int64_t px, hipStream_t s) { launch_develop_rgba_f64(film, alpha, rgba, px, s); }
-    static void develop_accumulate(const double *film, int k, float *sum, int64_t px, bool first, hipStream_t s) { launch_develop_accumulate_f64(film, k, 0, sum, px, first, s); }
 };
+// The k dense colour planes of an own film of px pixels (the alpha plane of an rgba scene behind them) developed into sc->d_rgb and copied out: [k][px][3 or 4]
+template <typename T> static void develop_and_copy(dtof_scene *sc, const T *film, int k, size_t px, float *out) {
+    const bool alpha = sc->host.sensor.alpha;   // rgba: four channels out
+    const size_t ch = alpha ? 4 : 3;
+    sc->d_rgb.ensure(px * ch * k);
+    if (alpha) for (int i = 0; i < k; ++i) launch_develop_rgba(film + px * 4 * i, film + px * 4 * k, sc->d_rgb.p + px * 4 * i, (int64_t) px, sc->stream);
+    else launch_develop(film, k, 0, sc->d_rgb.p, (int64_t) px, sc->stream);
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipMemcpyAsync(out, sc->d_rgb.p, px * ch * k * sizeof(float), hipMemcpyDeviceToHost, sc->stream));
+}
+// `planes` planes of the moment cells (sc->d_moments; sc->d_moment_planes is sized by the caller, before its passes) developed and copied out
+static void develop_cells_and_copy(dtof_scene *sc, int planes, int developed, size_t px, double *out) {
+    launch_develop_moments(sc->d_moments.p, planes, developed != 0, sc->d_moment_planes.p, (int64_t) px, sc->stream);
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipMemcpyAsync(out, sc->d_moment_planes.p, px * planes * sizeof(double), hipMemcpyDeviceToHost, sc->stream));
+}
 
 // The host-buffer renders (dtof_render_offsets / _variants / _variants_f64): the library's own film of rq.films() colour planes (and the alpha plane), developed into
 // out_rgb; out_films: the raw film planes as well, or null
@@ -122,17 +135,14 @@ template <typename T> static void render_host_films(dtof_scene *sc, RenderReques
     const int k = rq.films();
     const HostSensor &se = sc->host.sensor;
     const size_t px = (size_t) se.crop_w * se.crop_h;
-    const int planes = k + (se.alpha ? 1 : 0), ch = se.alpha ? 4 : 3;   // rgba: one more film plane for the alpha channel, four channels out
-    F::buf(sc).ensure(px * 4 * planes); sc->d_rgb.ensure(px * ch * k);
+    const int planes = k + (se.alpha ? 1 : 0);   // rgba: one more film plane for the alpha channel
+    F::buf(sc).ensure(px * 4 * planes);
     T *const film = F::buf(sc).p;
     HIP_CHECK(hipMemsetAsync(film, 0, px * 4 * planes * sizeof(T), sc->stream));
     rq.row_begin = 0; rq.row_end = se.crop_h;
     F::attach(rq, film, px * 4);
     render_rows(sc, rq);
-    if (se.alpha) for (int i = 0; i < k; ++i) F::develop_rgba(film + px * 4 * i, film + px * 4 * k, sc->d_rgb.p + px * 4 * i, (int64_t) px, sc->stream);
-    else F::develop(film, k, sc->d_rgb.p, (int64_t) px, sc->stream);
-    HIP_CHECK(hipGetLastError());
-    HIP_CHECK(hipMemcpyAsync(out_rgb, sc->d_rgb.p, px * ch * k * sizeof(float), hipMemcpyDeviceToHost, sc->stream));
+    develop_and_copy(sc, film, k, px, out_rgb);
     if (out_films) HIP_CHECK(hipMemcpyAsync(out_films, film, px * 4 * planes * sizeof(T), hipMemcpyDeviceToHost, sc->stream));
     HIP_CHECK(hipStreamSynchronize(sc->stream));
 }
@@ -205,19 +215,27 @@ int dtof_develop_async(dtof_scene *sc, const float *d_film, float *d_rgb, int64_
     return guarded([&] {
         if (!sc || !d_film || !d_rgb) throw std::runtime_error("null argument");
         ensure_device(sc);
-        launch_develop(d_film, d_rgb, n_pixels, sc->stream);
+        launch_develop(d_film, 1, 0, d_rgb, n_pixels, sc->stream);
         HIP_CHECK(hipGetLastError());
     });
 }
-// one finished deferred frame added to a statistics block (its stream has been waited for); returns the frame's duration
+// one frame's statistics added to a sum: every field of dtof_render_stats
+static void add_stats(dtof_render_stats &sum, const dtof_render_stats &f) {
+    sum.n_paths += f.n_paths; sum.n_bounces += f.n_bounces; sum.n_shadow_rays += f.n_shadow_rays;
+    sum.ms_total += f.ms_total; sum.ms_generate += f.ms_generate; sum.ms_trace += f.ms_trace; sum.ms_shade += f.ms_shade; sum.ms_shadow += f.ms_shadow; sum.ms_splat += f.ms_splat;
+    sum.n_launches_trace += f.n_launches_trace; sum.n_launches_shade += f.n_launches_shade; sum.n_launches_shadow += f.n_launches_shadow; sum.n_batches += f.n_batches;
+    sum.n_launches_first += f.n_launches_first; sum.ms_first += f.ms_first; sum.n_inline_iterations += f.n_inline_iterations; sum.n_bounces_inline += f.n_bounces_inline;
+    sum.n_fused_splat_launches += f.n_fused_splat_launches; sum.n_plan_facts_launches += f.n_plan_facts_launches;
+}
+// one finished deferred frame added to a statistics block (its stream has been waited for); returns the frame's duration.  The frame's counters (render_rows: paths,
+// batches and launches; the ray counts, which a deferred frame does not read back, hold 0) with the times its events give
 static float add_deferred_frame(dtof_render_stats *sum, const dtof_scene::DeferredFrame &f) {
     float t = 0; HIP_CHECK(hipEventElapsedTime(&t, f.ev0, f.ev1));
-    sum->ms_total += t;
-    sum->ms_generate += stage_ms(f.ev[kStageGenerate]); sum->ms_trace += stage_ms(f.ev[kStageTrace]); sum->ms_first += stage_ms(f.ev[kStageFirst]);
-    sum->ms_shade += stage_ms(f.ev[kStageShade]) + stage_ms(f.ev[kStageFirst]); sum->ms_shadow += stage_ms(f.ev[kStageShadow]); sum->ms_splat += stage_ms(f.ev[kStageSplat]);
-    sum->n_paths += f.counters.n_paths; sum->n_batches += f.counters.n_batches;
-    sum->n_launches_trace += f.counters.n_launches_trace; sum->n_launches_shade += f.counters.n_launches_shade; sum->n_launches_shadow += f.counters.n_launches_shadow;
-    sum->n_launches_first += f.counters.n_launches_first; sum->n_inline_iterations += f.counters.n_inline_iterations; sum->n_fused_splat_launches += f.counters.n_fused_splat_launches; sum->n_plan_facts_launches += f.counters.n_plan_facts_launches;
+    dtof_render_stats frame = f.counters;
+    frame.ms_total = t;
+    frame.ms_generate = stage_ms(f.ev[kStageGenerate]); frame.ms_trace = stage_ms(f.ev[kStageTrace]); frame.ms_first = stage_ms(f.ev[kStageFirst]);
+    frame.ms_shade = stage_ms(f.ev[kStageShade]) + frame.ms_first; frame.ms_shadow = stage_ms(f.ev[kStageShadow]); frame.ms_splat = stage_ms(f.ev[kStageSplat]);
+    add_stats(*sum, frame);
     return t;
 }
 int dtof_async_collect(dtof_scene *sc, dtof_render_stats *sum, double *frame_ms, uint32_t capacity, uint32_t *n_frames) {
@@ -241,8 +259,8 @@ int dtof_async_collect(dtof_scene *sc, dtof_render_stats *sum, double *frame_ms,
 // The checks the three entries share, made before a device is touched: a refused call enqueues and writes nothing.
 static void check_velocity_scalars(uint32_t n_passes, double exposure_time, double w_g_mhz) {
     if (n_passes == 0) throw std::runtime_error("n_passes must be at least 1");
-    if (!std::isfinite(exposure_time) || !(exposure_time > 0)) throw std::runtime_error("exposure_time must be finite and > 0");
-    if (!std::isfinite(w_g_mhz) || !(w_g_mhz > 0)) throw std::runtime_error("w_g_mhz must be finite and > 0");
+    need_finite_positive(exposure_time, "exposure_time");
+    need_finite_positive(w_g_mhz, "w_g_mhz");
 }
 static void check_grid(int64_t n_pixels) {   // one lane per pixel in blocks of 256: the block count is a 32-bit grid dimension
     if (n_pixels < 0) throw std::runtime_error("negative pixel count");
@@ -302,10 +320,52 @@ int dtof_velocity_map_variants(const float *offsets, int n_offsets, dtof_modulat
     });
 }
 }  // extern "C"
-// dtof_render_velocity_map / _f64: the same loop over the library's own float32 or float64 film (double: k_splat_f64 and k_develop_accumulate_f64)
+// The deferred frames a call enqueues itself, from this object's construction on: the passes of a reconstructed map, which run without a host wait in between.
+// collect() is the call's one synchronisation and hands their sum out; leaving the scope, by return or by exception, takes them off sc->deferred (after a wait if they
+// may still be in flight) and gives their events back to the pool once no frame is left.  Frames the caller has not collected yet stay theirs.
+struct OwnFrames {
+    dtof_scene *const sc; const size_t first; bool waited = false;
+    explicit OwnFrames(dtof_scene *scene) : sc(scene), first(scene->deferred.size()) {}
+    OwnFrames(const OwnFrames &) = delete;
+    void collect(dtof_render_stats *stats) {
+        HIP_CHECK(hipStreamSynchronize(sc->stream));
+        waited = true;
+        dtof_render_stats sum; memset(&sum, 0, sizeof sum);
+        for (size_t i = first; i < sc->deferred.size(); ++i) add_deferred_frame(&sum, sc->deferred[i]);
+        if (stats) *stats = sum;
+    }
+    ~OwnFrames() {
+        if (sc->deferred.size() > first) { if (!waited) (void) hipStreamSynchronize(sc->stream); sc->deferred.resize(first); }
+        if (sc->deferred.empty()) sc->events_used = 0;
+    }
+};
+// What both reconstructed maps render: n_films variants (w_g_mhz: a frequency for each, or null) in groups of at most kMaxOffsets films, n_passes passes each (seed =
+// pass), into the library's own float32 or float64 film; every pass is developed and added into sc->d_vm_sum [n_films][px][3].  Every frame is deferred (the caller
+// holds an OwnFrames); the library's own film: the caller's declared layout is not consulted
+template <typename T> static void render_passes_into_sum(dtof_scene *sc, uint32_t n_passes, uint32_t spp, const dtof_modulation *variants, const float *w_g_mhz, int n_films) {
+    using F = OwnFilm<T>;
+    const HostSensor &se = sc->host.sensor;
+    const size_t px = (size_t) se.crop_w * se.crop_h;
+    const int alpha = se.alpha ? 1 : 0;
+    F::buf(sc).ensure(px * 4 * (kMaxOffsets + alpha));
+    sc->d_vm_sum.ensure(px * 3 * n_films);
+    T *const film = F::buf(sc).p;
+    for (int g = 0; g < n_films; g += kMaxOffsets) {
+        const int films = std::min(kMaxOffsets, n_films - g);
+        for (uint32_t pass = 0; pass < n_passes; ++pass) {
+            HIP_CHECK(hipMemsetAsync(film, 0, px * 4 * (films + alpha) * sizeof(T), sc->stream));
+            dtof_render_stats frame;
+            RenderRequest rq = rows_request(pass, spp, 0, se.crop_h, &frame, true);
+            F::attach(rq, film, px * 4);
+            set_variants_freq(rq, variants + g, w_g_mhz ? w_g_mhz + g : nullptr, films);
+            render_rows(sc, rq);
+            launch_develop_accumulate(film, films, 0, sc->d_vm_sum.p + px * 3 * g, (int64_t) px, pass == 0, sc->stream);   // the alpha plane behind them is left out
+        }
+    }
+}
+// dtof_render_velocity_map / _f64 over the library's own float32 or float64 film: the homodyne / heterodyne films of dtof_velocity_map_variants, k_velocity_map
 template <typename T> static void velocity_map_render(dtof_scene *sc, uint32_t n_passes, uint32_t spp, const float *offsets, int n_offsets, double exposure_time, double w_g_mhz,
                                                       double *out_velocity, double *out_velocity_pairs, float *out_tof, dtof_render_stats *stats) {
-    using F = OwnFilm<T>;
     if (!sc || !offsets || !out_velocity) throw std::runtime_error("null argument");
     if (n_offsets < 1 || n_offsets > kMaxVelocityPairs) throw std::runtime_error("between 1 and 16 offsets make a velocity map");
     check_velocity_scalars(n_passes, exposure_time, w_g_mhz);
@@ -321,52 +381,30 @@ template <typename T> static void velocity_map_render(dtof_scene *sc, uint32_t n
     const VelocityMapArgs a = velocity_args(n_offsets, hom, het, n_passes, exposure_time, w_g_mhz);
     ensure_device(sc);
     sc->stop = false;
-    const HostSensor &se = sc->host.sensor;
-    const size_t px = (size_t) se.crop_w * se.crop_h;
-    const int alpha = se.alpha ? 1 : 0;
-    F::buf(sc).ensure(px * 4 * (kMaxOffsets + alpha));   // the library's own film: the caller's declared layout is not consulted
-    T *const film = F::buf(sc).p;
-    sc->d_vm_sum.ensure(px * 3 * 2 * n_offsets); sc->d_vm_tof.ensure(px * 2 * n_offsets); sc->d_vm_maps.ensure(px * (n_offsets + 1));
+    const size_t px = (size_t) sc->host.sensor.crop_w * sc->host.sensor.crop_h;
+    sc->d_vm_tof.ensure(px * 2 * n_offsets); sc->d_vm_maps.ensure(px * (n_offsets + 1));
+    double *const d_pairs = sc->d_vm_maps.p + px;
     const hipStream_t s = sc->stream;
-    const size_t first_frame = sc->deferred.size();   // frames the caller has not collected yet stay his
-    try {
-        for (int g = 0; g < n_offsets; g += 2) {
-            const int films = 2 * std::min(2, n_offsets - g);
-            for (uint32_t pass = 0; pass < n_passes; ++pass) {
-                HIP_CHECK(hipMemsetAsync(film, 0, px * 4 * (films + alpha) * sizeof(T), s));
-                dtof_render_stats frame;
-                RenderRequest rq = rows_request(pass, spp, 0, se.crop_h, &frame, true);
-                F::attach(rq, film, px * 4);
-                set_variants(rq, variants + 2 * g, films);
-                render_rows(sc, rq);
-                F::develop_accumulate(film, films, sc->d_vm_sum.p + px * 3 * 2 * g, (int64_t) px, pass == 0, s);   // the alpha plane behind them is left out
-            }
-        }
-        double *d_pairs = sc->d_vm_maps.p + px;
-        launch_velocity_map(sc->d_vm_sum.p, a, (int64_t) px, out_tof ? sc->d_vm_tof.p : nullptr, out_velocity_pairs ? d_pairs : nullptr, sc->d_vm_maps.p, s);
-        HIP_CHECK(hipGetLastError());
-        HIP_CHECK(hipMemcpyAsync(out_velocity, sc->d_vm_maps.p, px * sizeof(double), hipMemcpyDeviceToHost, s));
-        if (out_velocity_pairs) HIP_CHECK(hipMemcpyAsync(out_velocity_pairs, d_pairs, px * n_offsets * sizeof(double), hipMemcpyDeviceToHost, s));
-        if (out_tof) HIP_CHECK(hipMemcpyAsync(out_tof, sc->d_vm_tof.p, px * 2 * n_offsets * sizeof(float), hipMemcpyDeviceToHost, s));
-        HIP_CHECK(hipStreamSynchronize(s));
-        dtof_render_stats sum; memset(&sum, 0, sizeof sum);
-        for (size_t i = first_frame; i < sc->deferred.size(); ++i) add_deferred_frame(&sum, sc->deferred[i]);
-        if (stats) *stats = sum;
-    } catch (...) {   // the frames of this call leave the list either way (their events go back to the pool once no frame is in flight)
-        if (sc->deferred.size() > first_frame) { (void) hipStreamSynchronize(s); sc->deferred.resize(first_frame); }
-        if (sc->deferred.empty()) sc->events_used = 0;
-        throw;
-    }
-    sc->deferred.resize(first_frame);
-    if (sc->deferred.empty()) sc->events_used = 0;
+    OwnFrames frames(sc);
+    render_passes_into_sum<T>(sc, n_passes, spp, variants, nullptr, 2 * n_offsets);
+    launch_velocity_map(sc->d_vm_sum.p, a, (int64_t) px, out_tof ? sc->d_vm_tof.p : nullptr, out_velocity_pairs ? d_pairs : nullptr, sc->d_vm_maps.p, s);
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipMemcpyAsync(out_velocity, sc->d_vm_maps.p, px * sizeof(double), hipMemcpyDeviceToHost, s));
+    if (out_velocity_pairs) HIP_CHECK(hipMemcpyAsync(out_velocity_pairs, d_pairs, px * n_offsets * sizeof(double), hipMemcpyDeviceToHost, s));
+    if (out_tof) HIP_CHECK(hipMemcpyAsync(out_tof, sc->d_vm_tof.p, px * 2 * n_offsets * sizeof(float), hipMemcpyDeviceToHost, s));
+    frames.collect(stats);
 }
 
 // ---------------------------------------------------------------- depth map (dtof_depth.hip)
-// The checks the entries share, made before a device is touched; the frequencies as the doubles the kernel's wavelengths are formed from
-static void check_depth_frequencies(const double *w_g_mhz, int n_frequencies) {
+// The checks the entries share, made before a device is touched: the count, which every entry looks at before it reads an array of that length, and the frequencies
+// as the doubles the kernel's wavelengths are formed from
+static void check_depth_count(int n_frequencies) {
     if (n_frequencies < 1 || n_frequencies > kMaxDepthFrequencies) throw std::runtime_error("between 1 and 4 modulation frequencies make a depth map");
+}
+static void check_depth_frequencies(const double *w_g_mhz, int n_frequencies) {
+    check_depth_count(n_frequencies);
     for (int j = 0; j < n_frequencies; ++j) {
-        if (!std::isfinite(w_g_mhz[j]) || !(w_g_mhz[j] > 0)) throw std::runtime_error("w_g_mhz[" + std::to_string(j) + "] must be finite and > 0");
+        need_finite_positive(w_g_mhz[j], "w_g_mhz[" + std::to_string(j) + "]");
         for (int k = 0; k < j; ++k) if (w_g_mhz[k] == w_g_mhz[j]) throw std::runtime_error("the modulation frequencies of a depth map must be distinct");
     }
 }
@@ -374,7 +412,7 @@ static DepthMapArgs depth_args(int n_frequencies, const int32_t *i_planes, const
                                double max_path_length) {
     check_depth_frequencies(w_g_mhz, n_frequencies);
     if (n_passes == 0) throw std::runtime_error("n_passes must be at least 1");
-    if (!std::isfinite(exposure_time) || !(exposure_time > 0)) throw std::runtime_error("exposure_time must be finite and > 0");
+    need_finite_positive(exposure_time, "exposure_time");
     DepthMapArgs a; memset(&a, 0, sizeof a);
     a.n_frequencies = n_frequencies; a.n_candidates = 1;
     for (int j = 0; j < n_frequencies; ++j) {
@@ -392,13 +430,12 @@ static DepthMapArgs depth_args(int n_frequencies, const int32_t *i_planes, const
     a.n_passes = (float) n_passes; a.exposure_time = (float) exposure_time;
     return a;
 }
-// dtof_render_depth_map over the library's own float32 or float64 film: the loop of velocity_map_render with the groups of dtof_depth_map_variants
+// dtof_render_depth_map over the library's own float32 or float64 film: the I / Q films of dtof_depth_map_variants at their frequencies, k_depth_map
 template <typename T> static void depth_map_render(dtof_scene *sc, uint32_t n_passes, uint32_t spp, const float *w_g_mhz, int n_freq, double exposure_time, double max_path_length,
                                                    double *out_depth, double *out_residual, int32_t *out_wraps, double *out_amplitude, float *out_phase, float *out_tof,
                                                    dtof_render_stats *stats) {
-    using F = OwnFilm<T>;
     if (!sc || !w_g_mhz || !out_depth) throw std::runtime_error("null argument");
-    if (n_freq < 1 || n_freq > kMaxDepthFrequencies) throw std::runtime_error("between 1 and 4 modulation frequencies make a depth map");
+    check_depth_count(n_freq);
     dtof_modulation variants[2 * kMaxDepthFrequencies]; float freq[2 * kMaxDepthFrequencies];
     if (dtof_depth_map_variants(w_g_mhz, n_freq, variants, freq) != DTOF_OK) throw std::runtime_error(g_last_error);
     double f64[kMaxDepthFrequencies]; int32_t ip[kMaxDepthFrequencies], qp[kMaxDepthFrequencies];
@@ -408,56 +445,30 @@ template <typename T> static void depth_map_render(dtof_scene *sc, uint32_t n_pa
     need_sensor(sc);
     ensure_device(sc);
     sc->stop = false;
-    const HostSensor &se = sc->host.sensor;
-    const size_t px = (size_t) se.crop_w * se.crop_h, nf = (size_t) n_freq;
-    const int alpha = se.alpha ? 1 : 0;
-    F::buf(sc).ensure(px * 4 * (kMaxOffsets + alpha));   // the library's own film: the caller's declared layout is not consulted
-    T *const film = F::buf(sc).p;
-    // the passes' sum and the ToF images in the velocity map's buffers; its maps buffer holds depth, residual and the amplitudes (doubles), then wraps and phases (words)
-    sc->d_vm_sum.ensure(px * 3 * 2 * nf); sc->d_vm_tof.ensure(px * 2 * nf); sc->d_vm_maps.ensure(px * (2 + nf) + (px * 2 * nf + 1) / 2);
+    const size_t px = (size_t) sc->host.sensor.crop_w * sc->host.sensor.crop_h, nf = (size_t) n_freq;
+    // the ToF images in the velocity map's buffer; its maps buffer holds depth, residual and the amplitudes (doubles), then wraps and phases (words)
+    sc->d_vm_tof.ensure(px * 2 * nf); sc->d_vm_maps.ensure(px * (2 + nf) + (px * 2 * nf + 1) / 2);
     double *const d_depth = sc->d_vm_maps.p, *const d_residual = d_depth + px, *const d_amplitude = d_residual + px;
     int32_t *const d_wraps = (int32_t *) (d_amplitude + px * nf); float *const d_phase = (float *) (d_wraps + px * nf);
     const hipStream_t s = sc->stream;
-    const size_t first_frame = sc->deferred.size();   // frames the caller has not collected yet stay theirs
-    try {
-        for (int g = 0; g < n_freq; g += 2) {
-            const int films = 2 * std::min(2, n_freq - g);
-            for (uint32_t pass = 0; pass < n_passes; ++pass) {
-                HIP_CHECK(hipMemsetAsync(film, 0, px * 4 * (films + alpha) * sizeof(T), s));
-                dtof_render_stats frame;
-                RenderRequest rq = rows_request(pass, spp, 0, se.crop_h, &frame, true);
-                F::attach(rq, film, px * 4);
-                set_variants_freq(rq, variants + 2 * g, freq + 2 * g, films);
-                render_rows(sc, rq);
-                F::develop_accumulate(film, films, sc->d_vm_sum.p + px * 3 * 2 * g, (int64_t) px, pass == 0, s);   // the alpha plane behind them is left out
-            }
-        }
-        launch_depth_map(sc->d_vm_sum.p, a, (int64_t) px, d_depth, out_residual ? d_residual : nullptr, out_wraps ? d_wraps : nullptr, out_amplitude ? d_amplitude : nullptr,
-                         out_phase ? d_phase : nullptr, out_tof ? sc->d_vm_tof.p : nullptr, s);
-        HIP_CHECK(hipGetLastError());
-        HIP_CHECK(hipMemcpyAsync(out_depth, d_depth, px * sizeof(double), hipMemcpyDeviceToHost, s));
-        if (out_residual) HIP_CHECK(hipMemcpyAsync(out_residual, d_residual, px * sizeof(double), hipMemcpyDeviceToHost, s));
-        if (out_wraps) HIP_CHECK(hipMemcpyAsync(out_wraps, d_wraps, px * nf * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-        if (out_amplitude) HIP_CHECK(hipMemcpyAsync(out_amplitude, d_amplitude, px * nf * sizeof(double), hipMemcpyDeviceToHost, s));
-        if (out_phase) HIP_CHECK(hipMemcpyAsync(out_phase, d_phase, px * nf * sizeof(float), hipMemcpyDeviceToHost, s));
-        if (out_tof) HIP_CHECK(hipMemcpyAsync(out_tof, sc->d_vm_tof.p, px * 2 * nf * sizeof(float), hipMemcpyDeviceToHost, s));
-        HIP_CHECK(hipStreamSynchronize(s));
-        dtof_render_stats sum; memset(&sum, 0, sizeof sum);
-        for (size_t i = first_frame; i < sc->deferred.size(); ++i) add_deferred_frame(&sum, sc->deferred[i]);
-        if (stats) *stats = sum;
-    } catch (...) {   // the frames of this call leave the list either way (their events go back to the pool once no frame is in flight)
-        if (sc->deferred.size() > first_frame) { (void) hipStreamSynchronize(s); sc->deferred.resize(first_frame); }
-        if (sc->deferred.empty()) sc->events_used = 0;
-        throw;
-    }
-    sc->deferred.resize(first_frame);
-    if (sc->deferred.empty()) sc->events_used = 0;
+    OwnFrames frames(sc);
+    render_passes_into_sum<T>(sc, n_passes, spp, variants, freq, 2 * n_freq);
+    launch_depth_map(sc->d_vm_sum.p, a, (int64_t) px, d_depth, out_residual ? d_residual : nullptr, out_wraps ? d_wraps : nullptr, out_amplitude ? d_amplitude : nullptr,
+                     out_phase ? d_phase : nullptr, out_tof ? sc->d_vm_tof.p : nullptr, s);
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipMemcpyAsync(out_depth, d_depth, px * sizeof(double), hipMemcpyDeviceToHost, s));
+    if (out_residual) HIP_CHECK(hipMemcpyAsync(out_residual, d_residual, px * sizeof(double), hipMemcpyDeviceToHost, s));
+    if (out_wraps) HIP_CHECK(hipMemcpyAsync(out_wraps, d_wraps, px * nf * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    if (out_amplitude) HIP_CHECK(hipMemcpyAsync(out_amplitude, d_amplitude, px * nf * sizeof(double), hipMemcpyDeviceToHost, s));
+    if (out_phase) HIP_CHECK(hipMemcpyAsync(out_phase, d_phase, px * nf * sizeof(float), hipMemcpyDeviceToHost, s));
+    if (out_tof) HIP_CHECK(hipMemcpyAsync(out_tof, sc->d_vm_tof.p, px * 2 * nf * sizeof(float), hipMemcpyDeviceToHost, s));
+    frames.collect(stats);
 }
 extern "C" {
 int dtof_depth_map_variants(const float *w_g_mhz, int n_frequencies, dtof_modulation *out_variants, float *out_w_g_mhz) {
     return guarded([&] {
         if (!w_g_mhz || !out_variants || !out_w_g_mhz) throw std::runtime_error("null argument");
-        if (n_frequencies < 1 || n_frequencies > kMaxDepthFrequencies) throw std::runtime_error("between 1 and 4 modulation frequencies make a depth map");
+        check_depth_count(n_frequencies);
         double f64[kMaxDepthFrequencies];
         for (int j = 0; j < n_frequencies; ++j) f64[j] = (double) w_g_mhz[j];
         check_depth_frequencies(f64, n_frequencies);
@@ -472,7 +483,7 @@ int dtof_depth_map_async(dtof_scene *sc, const float *d_rgb_sum, int n_frequenci
                          double *d_depth, double *d_residual, int32_t *d_wraps, double *d_amplitude, float *d_phase) {
     return guarded([&] {
         if (!sc || !d_rgb_sum || !i_planes || !q_planes || !w_g_mhz || !d_depth) throw std::runtime_error("null argument");
-        if (n_frequencies < 1 || n_frequencies > kMaxDepthFrequencies) throw std::runtime_error("between 1 and 4 modulation frequencies make a depth map");
+        check_depth_count(n_frequencies);
         const DepthMapArgs a = depth_args(n_frequencies, i_planes, q_planes, w_g_mhz, n_passes, exposure_time, max_path_length);
         check_grid(n_pixels);
         if ((uintptr_t) d_rgb_sum % 4 != 0 || (uintptr_t) d_depth % 8 != 0 || (uintptr_t) d_residual % 8 != 0 || (uintptr_t) d_wraps % 4 != 0 ||
@@ -525,13 +536,6 @@ int dtof_render_rows_variants_f64(dtof_scene *sc, uint32_t seed, uint32_t spp, i
 
 // ---------------------------------------------------------------- moment film (dtof_moments.hip)
 int dtof_moment_planes(int n_variants) { return n_variants < 0 || n_variants > kMaxOffsets ? -1 : moment_planes(std::max(n_variants, 1)); }
-static void add_stats(dtof_render_stats &sum, const dtof_render_stats &f) {
-    sum.n_paths += f.n_paths; sum.n_bounces += f.n_bounces; sum.n_shadow_rays += f.n_shadow_rays;
-    sum.ms_total += f.ms_total; sum.ms_generate += f.ms_generate; sum.ms_trace += f.ms_trace; sum.ms_shade += f.ms_shade; sum.ms_shadow += f.ms_shadow; sum.ms_splat += f.ms_splat;
-    sum.n_launches_trace += f.n_launches_trace; sum.n_launches_shade += f.n_launches_shade; sum.n_launches_shadow += f.n_launches_shadow; sum.n_batches += f.n_batches;
-    sum.n_launches_first += f.n_launches_first; sum.ms_first += f.ms_first; sum.n_inline_iterations += f.n_inline_iterations; sum.n_bounces_inline += f.n_bounces_inline;
-    sum.n_fused_splat_launches += f.n_fused_splat_launches; sum.n_plan_facts_launches += f.n_plan_facts_launches;
-}
 // dtof_render_moments / _aovs: n_passes frames (seeds rq.seed, + 1, ...) accumulated into the cell film, `planes` planes developed from it and copied out.  rq carries
 // what the call's passes render beside that (the variants); aov: the channel table of an aov call, whose film the cells become, or null for the moment film
 static void render_cells(dtof_scene *sc, RenderRequest rq, AovArgs *aov, uint32_t n_passes, int planes, int developed, double *out_planes, dtof_render_stats *stats) {
@@ -550,9 +554,7 @@ static void render_cells(dtof_scene *sc, RenderRequest rq, AovArgs *aov, uint32_
         render_rows(sc, rq);
         add_stats(sum, frame);
     }
-    launch_develop_moments(sc->d_moments.p, planes, developed != 0, sc->d_moment_planes.p, (int64_t) px, s);
-    HIP_CHECK(hipGetLastError());
-    HIP_CHECK(hipMemcpyAsync(out_planes, sc->d_moment_planes.p, px * planes * sizeof(double), hipMemcpyDeviceToHost, s));
+    develop_cells_and_copy(sc, planes, developed, px, out_planes);
     HIP_CHECK(hipStreamSynchronize(s));
     if (stats) *stats = sum;
 }
@@ -591,7 +593,7 @@ static AdaptiveArgs adaptive_args(const dtof_adaptive_params *p, int K, uint32_t
             if (h == t) throw std::runtime_error("dtof_adaptive: pair " + std::to_string(i) + " needs two different variants (homodyne == heterodyne)");
             a.hom[i] = h; a.het[i] = t; a.cross[i] = adaptive_cross_plane(K, h, t);
         }
-        if (!(std::isfinite(p->exposure_time) && p->exposure_time > 0.0) || !(std::isfinite(p->w_g_mhz) && p->w_g_mhz > 0.0))
+        if (!finite_positive(p->exposure_time) || !finite_positive(p->w_g_mhz))
             throw std::runtime_error("dtof_adaptive: exposure_time and w_g_mhz must be finite and > 0");
     } else throw std::runtime_error("dtof_adaptive: mode must be DTOF_ADAPTIVE_IMAGE or DTOF_ADAPTIVE_VELOCITY");
     return a;
@@ -677,11 +679,7 @@ int dtof_render_pixels(dtof_scene *sc, uint32_t seed, uint32_t spp, const uint32
         rq.moments = out_moments ? sc->d_moments.p : nullptr;
         if (out_films) { rq.film64 = sc->d_film64.p; rq.film64_stride = px * 4; }
         render_rows(sc, rq);
-        if (out_moments) {
-            launch_develop_moments(sc->d_moments.p, planes, developed != 0, sc->d_moment_planes.p, (int64_t) px, s);
-            HIP_CHECK(hipGetLastError());
-            HIP_CHECK(hipMemcpyAsync(out_moments, sc->d_moment_planes.p, px * planes * sizeof(double), hipMemcpyDeviceToHost, s));
-        }
+        if (out_moments) develop_cells_and_copy(sc, planes, developed, px, out_moments);
         if (out_films) HIP_CHECK(hipMemcpyAsync(out_films, sc->d_film64.p, px * 4 * fplanes * sizeof(double), hipMemcpyDeviceToHost, s));
         HIP_CHECK(hipStreamSynchronize(s));
         if (stats) *stats = frame;
@@ -708,7 +706,7 @@ int dtof_render_adaptive(dtof_scene *sc, uint32_t seed, uint32_t spp, uint32_t b
         if ((uint64_t) spp_each * max_passes > 0xffffffffull) throw std::runtime_error("dtof_render_adaptive: spp * max_passes must fit 32 bits (the count map)");
         ensure_device(sc);
         sc->stop = false;
-        const int K = dense.films(), planes = moment_planes(K), fplanes = K + (se.alpha ? 1 : 0), ch = se.alpha ? 4 : 3;
+        const int K = dense.films(), planes = moment_planes(K), fplanes = K + (se.alpha ? 1 : 0);
         const hipStream_t s = sc->stream;
         const AdaptiveWords w = adaptive_words(sc, px);
         sc->d_adaptive_metric.ensure(px);
@@ -751,20 +749,8 @@ int dtof_render_adaptive(dtof_scene *sc, uint32_t seed, uint32_t spp, uint32_t b
             HIP_CHECK(hipMemcpyAsync(out_metric, sc->d_adaptive_metric.p, px * sizeof(double), hipMemcpyDeviceToHost, s));
         }
         HIP_CHECK(hipMemcpyAsync(out_count, w.count, px * 4, hipMemcpyDeviceToHost, s));
-        if (out_moments) {
-            launch_develop_moments(sc->d_moments.p, planes, developed != 0, sc->d_moment_planes.p, (int64_t) px, s);
-            HIP_CHECK(hipGetLastError());
-            HIP_CHECK(hipMemcpyAsync(out_moments, sc->d_moment_planes.p, px * planes * sizeof(double), hipMemcpyDeviceToHost, s));
-        }
-        if (out_images) {   // the images of dtof_render_variants_f64, from the film all passes accumulated into
-            using F = OwnFilm<double>;
-            const double *film = sc->d_film64.p;
-            sc->d_rgb.ensure(px * ch * K);
-            if (se.alpha) for (int i = 0; i < K; ++i) F::develop_rgba(film + px * 4 * i, film + px * 4 * K, sc->d_rgb.p + px * 4 * i, (int64_t) px, s);
-            else F::develop(film, K, sc->d_rgb.p, (int64_t) px, s);
-            HIP_CHECK(hipGetLastError());
-            HIP_CHECK(hipMemcpyAsync(out_images, sc->d_rgb.p, px * ch * K * sizeof(float), hipMemcpyDeviceToHost, s));
-        }
+        if (out_moments) develop_cells_and_copy(sc, planes, developed, px, out_moments);
+        if (out_images) develop_and_copy(sc, sc->d_film64.p, K, px, out_images);   // the images of dtof_render_variants_f64, from the film all passes accumulated into
         if (out_films) HIP_CHECK(hipMemcpyAsync(out_films, sc->d_film64.p, px * 4 * fplanes * sizeof(double), hipMemcpyDeviceToHost, s));
         HIP_CHECK(hipStreamSynchronize(s));
         if (stats) *stats = sum;
@@ -877,7 +863,7 @@ int dtof_develop_f64_async(dtof_scene *sc, const double *d_film64, float *d_rgb,
         check_grid(n_pixels);
         if ((uintptr_t) d_film64 % 8 != 0 || (uintptr_t) d_rgb % 4 != 0) throw std::runtime_error("the film must be 8-byte aligned, the image 4-byte aligned");
         ensure_device(sc);
-        launch_develop_f64(d_film64, 1, 0, d_rgb, n_pixels, sc->stream);
+        launch_develop(d_film64, 1, 0, d_rgb, n_pixels, sc->stream);
         HIP_CHECK(hipGetLastError());
     });
 }
@@ -888,7 +874,7 @@ int dtof_develop_rgba_f64_async(dtof_scene *sc, const double *d_film64, const do
         if ((uintptr_t) d_film64 % 8 != 0 || (uintptr_t) d_alpha_film64 % 8 != 0 || (uintptr_t) d_rgba % 16 != 0)
             throw std::runtime_error("the films must be 8-byte aligned, the image 16-byte aligned");
         ensure_device(sc);
-        launch_develop_rgba_f64(d_film64, d_alpha_film64, d_rgba, n_pixels, sc->stream);
+        launch_develop_rgba(d_film64, d_alpha_film64, d_rgba, n_pixels, sc->stream);
         HIP_CHECK(hipGetLastError());
     });
 }
@@ -970,7 +956,7 @@ int dtof_denoise_temporal(const dtof_temporal_buffers *b, int n_planes, int32_t 
 int dtof_develop(const float *d_film, float *d_rgb, int64_t n_pixels) {
     return guarded([&] {
         if (!d_film || !d_rgb) throw std::runtime_error("null argument");
-        launch_develop(d_film, d_rgb, n_pixels, nullptr);
+        launch_develop(d_film, 1, 0, d_rgb, n_pixels, nullptr);
         HIP_CHECK(hipGetLastError()); HIP_CHECK(hipStreamSynchronize(nullptr));
     });
 }
@@ -1036,7 +1022,7 @@ int dtof_sample_lanes(dtof_scene *sc, uint32_t seed, uint32_t spp, uint64_t lane
 int dtof_develop_on_stream(const float *d_film, float *d_rgb, int64_t n_pixels, void *hip_stream) {
     return guarded([&] {
         if (!d_film || !d_rgb) throw std::runtime_error("null argument");
-        launch_develop(d_film, d_rgb, n_pixels, (hipStream_t) hip_stream);
+        launch_develop(d_film, 1, 0, d_rgb, n_pixels, (hipStream_t) hip_stream);
         HIP_CHECK(hipGetLastError());
     });
 }

@@ -1,5 +1,5 @@
 // dtof_depth.h -- launcher of the depth-map kernel (dtof_depth.hip): the wrapped phase of the homodyne I / Q films at up to four modulation frequencies and the
-// path length that unwraps them, from the sum that launch_develop_accumulate (dtof_reconstruct.h) leaves.  The definition is the one of include/dtof.h ("depth map").
+// path length that unwraps them, from the sum that launch_develop_accumulate (dtof_develop.h) leaves.  The definition is the one of include/dtof.h ("depth map").
 // Kept out of dtof_kernels.h: nothing of the render kernels reads it.
 #pragma once
 #include <hip/hip_runtime.h>

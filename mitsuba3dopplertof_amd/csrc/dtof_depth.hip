@@ -1,10 +1,11 @@
-// dtof_depth.hip -- the range half of a correlation time-of-flight camera, on the device: from the sum of the developed passes (k_develop_accumulate,
-// dtof_reconstruct.hip) the ToF values of the homodyne I / Q films at every modulation frequency, their wrapped phase, and -- with two or more frequencies -- the wrap
+// dtof_depth.hip -- the range half of a correlation time-of-flight camera, on the device: from the sum of the developed passes (k_develop,
+// dtof_develop.hip) the ToF values (tof_of, dtof_reconstruct.h) of the homodyne I / Q films at every modulation frequency, their wrapped phase, and -- with two or more frequencies -- the wrap
 // counts that make the frequencies agree on one path length.  The definition is written out in include/dtof.h ("depth map") and restated in numpy by
 // tests/depth_ref.py and harness.calc_depth_from_homodynes; every output equals theirs word for word.
 // Elementwise: one lane per pixel, no LDS.  Only atan2_ of dtof_math.h (float32, the oracle's orc_atan2f bit for bit) and IEEE double + - * /, sqrt, floor and rint.
 // Compiled with -ffp-contract=off like every kernel here: no multiply-add below is fused, which the equality with numpy depends on.
 #include "dtof_depth.h"
+#include "dtof_reconstruct.h"
 #include "dtof_math.h"
 
 namespace dtof {
@@ -12,13 +13,6 @@ namespace dtof {
 namespace {
 constexpr int kDepthBlock = 256;
 constexpr double kTwoPiD = 6.283185307179586;
-
-// tof_of of dtof_reconstruct.hip: (sum / n_passes), then luminance * exposure time, all in float32
-__device__ __forceinline__ float tof_of(const float *rgb_sum, int64_t n, int32_t plane, int64_t i, float n_passes, float exposure_time) {
-    const float *p = rgb_sum + ((int64_t) plane * n + i) * 3;
-    const float r = p[0] / n_passes, g = p[1] / n_passes, b = p[2] / n_passes;
-    return ((0.2126f * r + 0.7152f * g) + 0.0722f * b) * exposure_time;
-}
 
 __global__ __launch_bounds__(kDepthBlock) void k_depth_map(const float *rgb_sum, DepthMapArgs a, int64_t n, double *depth, double *residual, int32_t *wraps,
                                                            double *amplitude, float *phase, float *tof) {

@@ -1,6 +1,6 @@
 // dtof_device.h -- what every translation unit with kernels includes: the device function headers (scene view and traversal, samplers and
 // waveforms, surface interaction and BSDF helpers) and the few helpers the kernels and their launchers share (queue segments, hit records,
-// LDS budgeting).  The kernels themselves live in dtof_kernels.hip (generate, trace, shadow, velocity, splat, develop, known-answer kernels)
+// LDS budgeting).  The kernels themselves live in dtof_kernels.hip (generate, trace, shadow, velocity, splat, known-answer kernels)
 // and dtof_shade.h (k_shade, instantiated by the dtof_shade_*.hip files -- one group of instantiations per file so that they compile in parallel).
 #pragma once
 #include "dtof_kernels.h"

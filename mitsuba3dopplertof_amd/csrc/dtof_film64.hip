@@ -1,10 +1,8 @@
-// dtof_film64.hip -- the float64 film: the splat of ImageBlock::put (src/render/imageblock.cpp:414-531) with a double accumulator, and HDRFilm::develop
-// (src/films/hdrfilm.cpp:305-406) taken in double.
-//   splat_f64              : every term is the float32 product the float32 film adds (w = wx * wy, value * w, w for the weight channel; the box filter adds the value
-//                            itself and 1.f -- splat_lane, dtof_device.h); the term is converted to double and from there on only double additions happen.  A double
-//                            sum of a few thousand float32 terms carries ~29 spare bits, so the order of the additions no longer reaches the developed float.
-//   develop_f64 / rgba_f64 : (float) (sum / (w == 0 ? 1 : w)), the division in double
-//   develop_accumulate_f64 : the same develop, then the float32 running sum of k_develop_accumulate (dtof_reconstruct.hip)
+// dtof_film64.hip -- the float64 film: the splat of ImageBlock::put (src/render/imageblock.cpp:414-531) with a double accumulator.  (Its develop, taken in double,
+// is the double instantiation of dtof_develop.hip.)
+//   splat_f64 : every term is the float32 product the float32 film adds (w = wx * wy, value * w, w for the weight channel; the box filter adds the value itself and
+//               1.f -- splat_lane, dtof_device.h); the term is converted to double and from there on only double additions happen.  A double sum of a few thousand
+//               float32 terms carries ~29 spare bits, so the order of the additions no longer reaches the developed float.
 // Compiled with -ffp-contract=off like every kernel here.
 #include "dtof_device.h"
 #include "dtof_splat_runs.h"
@@ -90,56 +88,11 @@ __global__ __launch_bounds__(kFilm64Block) void k_splat_f64(RenderParams rp, Que
         }
     }
 }
-
-__global__ __launch_bounds__(kFilm64Block) void k_develop_f64(const double *film, uint64_t plane_stride, float *rgb, int64_t n) {
-    const int64_t i = (int64_t) blockIdx.x * kFilm64Block + threadIdx.x;
-    if (i >= n) return;
-    const double *f = film + (uint64_t) blockIdx.y * plane_stride + 4 * i;
-    const double w = f[3] == 0.0 ? 1.0 : f[3];
-    float *o = rgb + ((int64_t) blockIdx.y * n + i) * 3;
-    o[0] = (float) (f[0] / w); o[1] = (float) (f[1] / w); o[2] = (float) (f[2] / w);
-}
-
-// pixel_format = rgba (hdrfilm.cpp:339-400): the alpha channel was accumulated into a film of its own, (A, 0, 0, W) with the same weights
-__global__ __launch_bounds__(kFilm64Block) void k_develop_rgba_f64(const double *film, const double *alpha_film, float *rgba, int64_t n) {
-    const int64_t i = (int64_t) blockIdx.x * kFilm64Block + threadIdx.x;
-    if (i >= n) return;
-    const double *f = film + 4 * i, *a = alpha_film + 4 * i;
-    const double w = f[3] == 0.0 ? 1.0 : f[3], wa = a[3] == 0.0 ? 1.0 : a[3];
-    ((float4 *) rgba)[i] = make_float4((float) (f[0] / w), (float) (f[1] / w), (float) (f[2] / w), (float) (a[0] / wa));
-}
-
-__global__ __launch_bounds__(kFilm64Block) void k_develop_accumulate_f64(const double *film, uint64_t plane_stride, float *rgb_sum, int64_t n, int first) {
-    const int64_t i = (int64_t) blockIdx.x * kFilm64Block + threadIdx.x;
-    if (i >= n) return;
-    const double *f = film + (uint64_t) blockIdx.y * plane_stride + 4 * i;
-    const double w = f[3] == 0.0 ? 1.0 : f[3];   // k_develop_f64's expression
-    const float r = (float) (f[0] / w), g = (float) (f[1] / w), b = (float) (f[2] / w);
-    float *o = rgb_sum + ((int64_t) blockIdx.y * n + i) * 3;
-    if (first) { o[0] = r; o[1] = g; o[2] = b; }   // the first pass ASSIGNS (acc = img), as k_develop_accumulate does
-    else { o[0] = o[0] + r; o[1] = o[1] + g; o[2] = o[2] + b; }
-}
-
-dim3 pixel_grid(int64_t n_pixels, int32_t planes) { return dim3((uint32_t) ((n_pixels + kFilm64Block - 1) / kFilm64Block), (uint32_t) planes); }
 }  // namespace
 
 void launch_splat_f64(const RenderParams &rp, const Queues &q, double *film64, uint64_t plane_stride_doubles, hipStream_t s) {
     if (rp.n_lanes == 0) return;
     hipLaunchKernelGGL(k_splat_f64, dim3((rp.n_lanes + kFilm64Block - 1) / kFilm64Block), dim3(kFilm64Block), 0, s, rp, q, film64, (size_t) plane_stride_doubles);
-}
-void launch_develop_f64(const double *film64, int32_t planes, uint64_t plane_stride_doubles, float *rgb, int64_t n_pixels, hipStream_t s) {
-    if (n_pixels <= 0 || planes <= 0) return;
-    const uint64_t stride = plane_stride_doubles ? plane_stride_doubles : (uint64_t) n_pixels * 4;
-    hipLaunchKernelGGL(k_develop_f64, pixel_grid(n_pixels, planes), dim3(kFilm64Block), 0, s, film64, stride, rgb, n_pixels);
-}
-void launch_develop_rgba_f64(const double *film64, const double *alpha_film64, float *rgba, int64_t n_pixels, hipStream_t s) {
-    if (n_pixels <= 0) return;
-    hipLaunchKernelGGL(k_develop_rgba_f64, pixel_grid(n_pixels, 1), dim3(kFilm64Block), 0, s, film64, alpha_film64, rgba, n_pixels);
-}
-void launch_develop_accumulate_f64(const double *film64, int32_t planes, uint64_t plane_stride_doubles, float *rgb_sum, int64_t n_pixels, bool first, hipStream_t s) {
-    if (n_pixels <= 0 || planes <= 0) return;
-    const uint64_t stride = plane_stride_doubles ? plane_stride_doubles : (uint64_t) n_pixels * 4;
-    hipLaunchKernelGGL(k_develop_accumulate_f64, pixel_grid(n_pixels, planes), dim3(kFilm64Block), 0, s, film64, stride, rgb_sum, n_pixels, first ? 1 : 0);
 }
 
 }  // namespace dtof

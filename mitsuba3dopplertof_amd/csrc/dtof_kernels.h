@@ -359,8 +359,6 @@ void launch_shadow(const uint8_t *scene, uint32_t scene_bytes, const RenderParam
 void launch_velocity(const uint8_t *scene, uint32_t scene_bytes, const RenderParams &rp, const Queues &q, uint32_t stack_depth, const LaunchSwitches &ls, hipStream_t s);
 // returns the packed choice of the kernel it launched (dtof_splat_choice.h: SplatChoice::packed), 0 for an empty batch
 uint32_t launch_splat(const RenderParams &rp, const Queues &q, float *film, uint64_t plane_stride, const LaunchSwitches &ls, hipStream_t s);
-void launch_develop(const float *film, float *rgb, int64_t n_pixels, hipStream_t s);
-void launch_develop_rgba(const float *film, const float *alpha_film, float *rgba, int64_t n_pixels, hipStream_t s);   // pixel_format = rgba (hdrfilm.cpp:339-400)
 void launch_lane_dump(const RenderParams &rp, const Queues &q, LaneDebug *out, hipStream_t s);
 void launch_pass_save(const RenderParams &rp, const Queues &q, hipStream_t s);   // multi-pass: main / path stream states of the batch -> rp.pass_rng
 void launch_lane_dump_rays(const RenderParams &rp, const Queues &q, LaneDebug *out, hipStream_t s);

@@ -13,7 +13,7 @@
 //              (src/render/scene.cpp:235-291 test_visibility branch)
 //   splat    : reconstruction-filter splat with per-pixel wave reduction, then float atomics
 //              (src/render/imageblock.cpp:414-531)
-//   develop  : RGB / W (src/films/hdrfilm.cpp:305-406)
+// (The film develop, RGB / W, is dtof_develop.hip's.)
 //
 // Compiled with -ffp-contract=off: an fma is issued exactly where fmaf() is written, so a lane's
 // arithmetic is bit-identical to the scalar restatement in oracle/ (same helper algebra in dtof_math.h).
@@ -497,24 +497,6 @@ __global__ __launch_bounds__(64) void k_splat_pixel(RenderParams rp, Queues q, f
     }
 }
 
-__global__ void k_develop(const float *film, float *rgb, int64_t n) {
-    int64_t i = (int64_t) blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    float4 f = ((const float4 *) film)[i];
-    float w = f.w == 0.f ? 1.f : f.w;
-    rgb[3 * i] = f.x / w; rgb[3 * i + 1] = f.y / w; rgb[3 * i + 2] = f.z / w;
-}
-
-// pixel_format = rgba (hdrfilm.cpp:339-400): the block holds R, G, B, A, W and every channel is divided by W; here the alpha channel was accumulated into a
-// film of its own, (A, 0, 0, W) with the same weights
-__global__ void k_develop_rgba(const float *film, const float *alpha_film, float *rgba, int64_t n) {
-    int64_t i = (int64_t) blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const float4 f = ((const float4 *) film)[i], a = ((const float4 *) alpha_film)[i];
-    const float w = f.w == 0.f ? 1.f : f.w, wa = a.w == 0.f ? 1.f : a.w;
-    ((float4 *) rgba)[i] = make_float4(f.x / w, f.y / w, f.z / w, a.x / wa);
-}
-
 __global__ void k_lane_dump(RenderParams rp, Queues q, LaneDebug *out) {
     uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= rp.n_lanes) return;
@@ -728,14 +710,6 @@ uint32_t launch_splat(const RenderParams &rp, const Queues &q, float *film, uint
         hipLaunchKernelGGL(k_splat_generic, dim3(nblk(rp.n_lanes)), dim3(kBlock), 0, s, rp, q, film, stride);
     }
     return c.packed();
-}
-void launch_develop(const float *film, float *rgb, int64_t n, hipStream_t s) {
-    if (n == 0) return;
-    hipLaunchKernelGGL(k_develop, dim3((uint32_t) ((n + 255) / 256)), dim3(256), 0, s, film, rgb, n);
-}
-void launch_develop_rgba(const float *film, const float *alpha_film, float *rgba, int64_t n, hipStream_t s) {
-    if (n == 0) return;
-    hipLaunchKernelGGL(k_develop_rgba, dim3((uint32_t) ((n + 255) / 256)), dim3(256), 0, s, film, alpha_film, rgba, n);
 }
 // multi-pass renders: the main / path stream states the lanes of this batch ended the pass with (generate_lane wrote the time stream's)
 __global__ void k_pass_save(RenderParams rp, Queues q) {

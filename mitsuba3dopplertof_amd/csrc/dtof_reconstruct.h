@@ -1,5 +1,6 @@
-// dtof_reconstruct.h -- launchers of the two reconstruction kernels (dtof_reconstruct.hip): the developed films of the passes summed on the device, and the
-// radial-velocity map of doppler_tutorials/src/utils/image_utils.py:140-199 from that sum.  Kept out of dtof_kernels.h: nothing of the render kernels reads it.
+// dtof_reconstruct.h -- launcher of the reconstruction kernel (dtof_reconstruct.hip): the radial-velocity map of doppler_tutorials/src/utils/image_utils.py:140-199
+// from the sum of the developed passes that launch_develop_accumulate (dtof_develop.h) leaves, and the ToF value both reconstructed maps start from.
+// Kept out of dtof_kernels.h: nothing of the render kernels reads it.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdint>
@@ -18,8 +19,14 @@ struct VelocityMapArgs {
     double inv_time, w_g_hz, conf_floor;
 };
 
-// rgb / (W == 0 ? 1 : W) of `planes` RGBW film planes `plane_stride_floats` apart, stored into (first) or added to (later passes) the dense sum [planes][n_pixels][3]
-void launch_develop_accumulate(const float *film, int32_t planes, uint64_t plane_stride_floats, float *rgb_sum, int64_t n_pixels, bool first, hipStream_t s);
+// The ToF value of pixel i of plane `plane` of the sum [planes][n][3] (k_velocity_map, and k_depth_map of dtof_depth.hip): (sum / n_passes), then luminance *
+// exposure time, all in float32 (what numpy makes of Python scalars against a float32 image)
+__device__ __forceinline__ float tof_of(const float *rgb_sum, int64_t n, int32_t plane, int64_t i, float n_passes, float exposure_time) {
+    const float *p = rgb_sum + ((int64_t) plane * n + i) * 3;
+    const float r = p[0] / n_passes, g = p[1] / n_passes, b = p[2] / n_passes;
+    return ((0.2126f * r + 0.7152f * g) + 0.0722f * b) * exposure_time;
+}
+
 // tof: [2 * n_pairs][n_pixels] float32 or null; pair_maps: [n_pairs][n_pixels] double or null; velocity: [n_pixels] double
 void launch_velocity_map(const float *rgb_sum, const VelocityMapArgs &a, int64_t n_pixels, float *tof, double *pair_maps, double *velocity, hipStream_t s);
 

@@ -1,34 +1,15 @@
-// dtof_reconstruct.hip -- what follows the film splat of a velocity-map render, on the device:
-//   develop_accumulate : HDRFilm::develop of every film plane of a pass (src/films/hdrfilm.cpp:305-406: RGB / W) and the running float32 sum of the passes
-//                        (render_multi_pass, doppler_tutorials/src/program_runner.py:11-31: acc = img if acc is None else acc + img)
-//   velocity_map       : mean of the passes, to_tof_image (doppler_tutorials/src/utils/image_utils.py:20-31) in float32, then calc_velocity_from_homo_hetero(s)
-//                        (image_utils.py:140-199) in double -- every operation in the order numpy evaluates it, so the map is the host route's bit for bit.
-// Both are elementwise and bound by memory traffic: one lane per pixel (and plane), no LDS.  Compiled with -ffp-contract=off like every kernel here: no
-// multiply-add below is fused, which the bit parity with numpy depends on.
+// dtof_reconstruct.hip -- what follows the develop-accumulate (dtof_develop.hip) of a velocity-map render, on the device:
+//   velocity_map : mean of the passes, to_tof_image (doppler_tutorials/src/utils/image_utils.py:20-31) in float32 (tof_of, dtof_reconstruct.h), then
+//                  calc_velocity_from_homo_hetero(s) (image_utils.py:140-199) in double -- every operation in the order numpy evaluates it, so the map is the host
+//                  route's bit for bit.
+// Elementwise and bound by memory traffic: one lane per pixel, no LDS.  Compiled with -ffp-contract=off like every kernel here: no multiply-add below is fused, which
+// the bit parity with numpy depends on.
 #include "dtof_reconstruct.h"
 
 namespace dtof {
 
 namespace {
 constexpr int kReconBlock = 256;
-
-__global__ __launch_bounds__(kReconBlock) void k_develop_accumulate(const float *film, uint64_t plane_stride, float *rgb_sum, int64_t n, int first) {
-    const int64_t i = (int64_t) blockIdx.x * kReconBlock + threadIdx.x;
-    if (i >= n) return;
-    const float4 f = ((const float4 *) (film + (uint64_t) blockIdx.y * plane_stride))[i];
-    const float w = f.w == 0.f ? 1.f : f.w;   // k_develop's expression
-    const float r = f.x / w, g = f.y / w, b = f.z / w;
-    float *o = rgb_sum + ((int64_t) blockIdx.y * n + i) * 3;
-    if (first) { o[0] = r; o[1] = g; o[2] = b; }   // the first pass ASSIGNS (acc = img): 0 + (-0) would lose the sign
-    else { o[0] = o[0] + r; o[1] = o[1] + g; o[2] = o[2] + b; }
-}
-
-// (sum / n_passes), then luminance * exposure time, all in float32 (what numpy makes of Python scalars against a float32 image)
-__device__ __forceinline__ float tof_of(const float *rgb_sum, int64_t n, int32_t plane, int64_t i, float n_passes, float exposure_time) {
-    const float *p = rgb_sum + ((int64_t) plane * n + i) * 3;
-    const float r = p[0] / n_passes, g = p[1] / n_passes, b = p[2] / n_passes;
-    return ((0.2126f * r + 0.7152f * g) + 0.0722f * b) * exposure_time;
-}
 
 // _velocity_from_ratio: np.clip lets a NaN through (fmin / fmax would return the bound), then dw = ratio / (T (ratio - 1)), v = -(c / 2) dw / w_g
 __device__ __forceinline__ double velocity_of(double ratio, const VelocityMapArgs &a) {
@@ -56,13 +37,6 @@ __global__ __launch_bounds__(kReconBlock) void k_velocity_map(const float *rgb_s
         for (int32_t p = 0; p < 2 * a.n_pairs; ++p) tof[(int64_t) p * n + i] = tof_of(rgb_sum, n, p, i, a.n_passes, a.exposure_time);
 }
 }  // namespace
-
-void launch_develop_accumulate(const float *film, int32_t planes, uint64_t plane_stride_floats, float *rgb_sum, int64_t n_pixels, bool first, hipStream_t s) {
-    if (n_pixels <= 0 || planes <= 0) return;
-    const uint64_t stride = plane_stride_floats ? plane_stride_floats : (uint64_t) n_pixels * 4;
-    hipLaunchKernelGGL(k_develop_accumulate, dim3((uint32_t) ((n_pixels + kReconBlock - 1) / kReconBlock), (uint32_t) planes), dim3(kReconBlock), 0, s,
-                       film, stride, rgb_sum, n_pixels, first ? 1 : 0);
-}
 
 void launch_velocity_map(const float *rgb_sum, const VelocityMapArgs &a, int64_t n_pixels, float *tof, double *pair_maps, double *velocity, hipStream_t s) {
     if (n_pixels <= 0) return;

@@ -22,7 +22,7 @@ def atan2f(orc):
 
 
 def tof_of(rgb_sum, plane, n_passes, exposure_time):
-    """tof_of of dtof_reconstruct.hip: rgb_sum (planes, n, 3) float32 -> (n,) float32"""
+    """tof_of of dtof_reconstruct.h: rgb_sum (planes, n, 3) float32 -> (n,) float32"""
     f = np.float32
     p = np.ascontiguousarray(rgb_sum, f)[plane]
     with np.errstate(all="ignore"):

@@ -1,4 +1,4 @@
-"""The opt-in float64 film (k_splat_f64, k_develop_f64, k_develop_rgba_f64, k_develop_accumulate_f64; Scene.render(film="float64"), render_film64, render_rows_f64,
+"""The opt-in float64 film (k_splat_f64 and the double instantiations k_develop<double, ADD>, k_develop_rgba<double> of dtof_develop.hip; Scene.render(film="float64"), render_film64, render_rows_f64,
 develop_f64_async, render_velocity_map(film="float64")) against the oracle's order-independent film: orc_render_exact sums the same float32 splat terms in float64
 and develops in float64, orc_render_alpha does the same for the alpha channel.
 
@@ -275,6 +275,65 @@ def test_device_film_bands_into_padded_float64_slabs(mi, wall_variants):
     for k, pair in enumerate(K4):
         assert differing(developed[k], develop(films[k])) == 0, k
         hold("dense device film, plane %d" % k, developed[k], films[k], *refs[pair])
+
+
+SYNTHETIC_SIZES = (1, 255, 257)      # one lane, a block less one lane, a block and one lane
+MARGIN, SENT32 = 64, np.float32(-7.5e11)      # sentinel floats on both sides of every output (64 floats keep the rgba image 16-byte aligned)
+
+
+def synthetic_film64(rng, n):
+    """(colour film, alpha film) [n][4] float64, as a splat leaves them: doubles with all 53 bits in use, so that rounding the operands to float32 before the division
+    moves the quotient; W in [0.25, 64).  With room for them: a pixel with W = 0, one with a colour of -0.0, one whose alpha film has a weight of 0"""
+    film = rng.standard_normal((n, 4)) * 10.0 ** rng.uniform(-3, 3, (n, 4))
+    film[:, 3] = rng.uniform(0.25, 64.0, n)
+    alpha = np.zeros((n, 4))
+    alpha[:, 3] = film[:, 3]
+    alpha[:, 0] = alpha[:, 3] * rng.uniform(0.0, 1.0, n)
+    if n >= 3:
+        film[0, 3] = 0.0
+        film[1, :3] = -0.0
+        alpha[2, 3] = 0.0
+    return film, alpha
+
+
+def develop_in_float32(film):
+    """what a kernel that rounded the film to float32 before dividing would return"""
+    f = film.astype(np.float32)
+    return f[..., :3] / np.where(f[..., 3] == 0, np.float32(1), f[..., 3])[..., None]
+
+
+def test_synthetic_float64_films_are_developed_in_double(mi):
+    """dtof_develop_f64_async and dtof_develop_rgba_f64_async on constructed films: numpy's float64 quotient rounded to float32 once, bit for bit, -0.0 and the
+    W = 0 pixels included, nothing written outside the image; at least a quarter of the expected floats are not what a division in float32 gives"""
+    import torch
+    sc = mi.load_file(os.path.join(SCENES, "cornell_wall.xml"), resx=8, resy=8)
+    rng = np.random.default_rng(64)
+    moved = total = 0
+    for n in SYNTHETIC_SIZES:
+        film, alpha = synthetic_film64(rng, n)
+        want_rgb = develop(film)
+        want_rgba = np.concatenate([want_rgb, develop(alpha)[:, :1]], axis=1)
+        in_f32 = np.concatenate([develop_in_float32(film), develop_in_float32(alpha)[:, :1]], axis=1)
+        moved += differing(want_rgba, in_f32); total += want_rgba.size
+        d_film, d_alpha = torch.from_numpy(film).cuda(), torch.from_numpy(alpha).cuda()
+        d_rgb = torch.full((3 * n + 2 * MARGIN,), float(SENT32), dtype=torch.float32, device="cuda")
+        d_rgba = torch.full((4 * n + 2 * MARGIN,), float(SENT32), dtype=torch.float32, device="cuda")
+        torch.cuda.synchronize()
+        sc.develop_f64_async(d_film.data_ptr(), d_rgb.data_ptr() + 4 * MARGIN, n)
+        sc.develop_f64_async(d_film.data_ptr(), d_rgba.data_ptr() + 4 * MARGIN, n, d_alpha_film_ptr=d_alpha.data_ptr())
+        sc.collect()
+        torch.cuda.synchronize()
+        for name, got, want in (("rgb", d_rgb.cpu().numpy(), want_rgb), ("rgba", d_rgba.cpu().numpy(), want_rgba)):
+            bad = differing(got[MARGIN:MARGIN + want.size].reshape(want.shape), want)
+            print("n %d %s: %d of %d floats differ from numpy's" % (n, name, bad, want.size))
+            assert bad == 0, (n, name, bad)
+            assert (got[:MARGIN] == SENT32).all() and (got[MARGIN + want.size:] == SENT32).all(), ("margins", n, name)
+        if n >= 3:      # the constructed pixels are what they were meant to be: divided by 1, -0.0, divided by 1
+            assert differing(want_rgb[0], film[0, :3].astype(np.float32)) == 0 and want_rgb[0].all()
+            assert np.signbit(want_rgb[1]).all() and not want_rgb[1].any()
+            assert want_rgba[2, 3] == np.float32(alpha[2, 0]) != 0
+    print("%d of %d expected floats differ from a division in float32" % (moved, total))
+    assert 4 * moved >= total, (moved, total)
 
 
 def same(got, expected):

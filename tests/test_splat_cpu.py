@@ -120,7 +120,7 @@ def test_the_choice_table(tmp_path):
     assert {k: v for k, v in got.items() if k != "entries" and not k.startswith("count ")} == want
     # launch_splat asks this function and launches what it says: no condition of its own on the filter's radius, the sample count or the switch
     kernels = open(os.path.join(src, "dtof_kernels.hip")).read()
-    body = kernels[kernels.index("uint32_t launch_splat("):kernels.index("void launch_develop(")]
+    body = kernels[kernels.index("uint32_t launch_splat("):kernels.index("__global__ void k_pass_save(")]
     assert "splat_choice(f)" in body and "return c.packed();" in body
     assert not re.search(r"filter_radius\s*[<>]|rp\.spp\s*[<>]|spp_log2\s*[!=]=|ls\.splat\s*[!=]=|ceilf", body)
     for field in ("filter", "radius", "spp", "spp_log2", "n_lanes", "splat_switch"):

@@ -1,4 +1,4 @@
-"""The radial-velocity map reconstructed on the device (k_develop_accumulate, k_velocity_map; dtof_develop_accumulate_async, dtof_velocity_map_async,
+"""The radial-velocity map reconstructed on the device (k_develop<float, ADD> of dtof_develop.hip, k_velocity_map; dtof_develop_accumulate_async, dtof_velocity_map_async,
 dtof_render_velocity_map) against the numpy route of harness.py (to_tof_image, calc_velocity_from_homo_hetero(s), which mirror the reference's image_utils.py).
 
 Every comparison of reconstructed values is EXACT: equal bit patterns wherever the expected value is not a NaN (+-0 and +-inf included), a NaN wherever it is one
@@ -107,7 +107,8 @@ def split_margins(t, n):
 
 
 def run_synthetic(mi, sc, film, n_pairs, exposure_time, w_g, padded):
-    """upload the films, accumulate and reconstruct on the device, develop the same planes with dtof_develop for numpy -> (mismatch counts, expected map)"""
+    """upload the films, accumulate and reconstruct on the device; numpy develops the same planes for its route (rgb / (W == 0 ? 1 : W) in float32), and dtof_develop
+    on every padded plane is held to numpy's develop bit for bit as well -> (mismatch counts, expected map)"""
     import torch
     L = mi._lib()
     passes, planes, n = film.shape[:3]
@@ -117,7 +118,9 @@ def run_synthetic(mi, sc, film, n_pairs, exposure_time, w_g, padded):
     d_tof, p_tof = guarded(torch, planes * n, torch.float32, SENT32)
     d_pairs, p_pairs = guarded(torch, n_pairs * n, torch.float64, SENT64)
     d_v, p_v = guarded(torch, n, torch.float64, SENT64)
-    developed = np.zeros((passes, planes, n, 3), np.float32)
+    with np.errstate(all="ignore"):      # HDRFilm::develop in numpy: float32 throughout
+        developed = film[..., :3] / np.where(film[..., 3] == 0, np.float32(1), film[..., 3])[..., None]
+    assert developed.dtype == np.float32 and developed.shape == (passes, planes, n, 3)
     d_rgb = torch.zeros((n, 3), dtype=torch.float32, device="cuda")
     for p in range(passes):
         host = np.full((planes, stride), 9.0e9, np.float32)      # what lies in the padding must not matter
@@ -125,9 +128,9 @@ def run_synthetic(mi, sc, film, n_pairs, exposure_time, w_g, padded):
         d_film = torch.from_numpy(host).cuda()
         torch.cuda.synchronize()
         sc.develop_accumulate_async(d_film.data_ptr(), planes, p_sum, n, first=(p == 0), plane_stride_floats=stride if padded else 0)
-        for k in range(planes):      # the reference's develop: dtof_develop on the very same plane
+        for k in range(planes):      # the store form of the same kernel, on the very same plane
             assert L.dtof_develop(d_film.data_ptr() + 4 * stride * k, d_rgb.data_ptr(), n) == 0, L.dtof_last_error()
-            developed[p, k] = d_rgb.cpu().numpy()
+            assert same(d_rgb.cpu().numpy(), developed[p, k]) == 0, ("dtof_develop against numpy", n, padded, p, k)
         torch.cuda.synchronize()
     sc.velocity_map_async(p_sum, hom, het, passes, n, p_v, exposure_time=exposure_time, w_g=w_g, d_tof_ptr=p_tof, d_velocity_pairs_ptr=p_pairs)
     torch.cuda.synchronize()

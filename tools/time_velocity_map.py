@@ -41,7 +41,7 @@ def clock(fn):
 
 
 def kernel_times(sc, reps):
-    """GPU milliseconds of k_develop_accumulate (the four films of one pass) and k_velocity_map (two pairs, ToF images and per-pair maps written), HIP events on the
+    """GPU milliseconds of the develop-accumulate (k_develop<float, false> of dtof_develop.hip: the four films of one pass, stored as on a first pass) and k_velocity_map (two pairs, ToF images and per-pair maps written), HIP events on the
     stream the library enqueues on"""
     import torch
     w, h = sc.size
@@ -116,7 +116,7 @@ def main():
                   "                                               %s" % spread(t_renders),
                   "  host tail beyond its renders (ToF images + calc_velocity_from_homo_heteros in numpy): median %.3f ms" % (np.median(t_host) - np.median(t_renders)),
                   "  GPU time of the traversal (library events)   host route median %.3f ms, device route median %.3f ms" % (np.median(gpu_host), np.median(gpu_dev)),
-                  "  k_develop_accumulate (4 films)               %s" % spread(t_acc),
+                  "  develop-accumulate (4 films)                 %s" % spread(t_acc),
                   "  k_velocity_map (2 pairs, all outputs)        %s" % spread(t_map),
                   "  device route / host route (medians): %.3f; device map bit-equal to numpy on its own ToF images: %s" % (np.median(t_dev) / np.median(t_host), same), ""]
         print("\n".join(lines[-11:]), flush=True)
