@@ -7,6 +7,7 @@
 //   scatter  a flagged pixel's slot is its block's prefix + the popcounts of the waves before its own + the popcount of the lanes before it in its wave's ballot
 // Compiled with -ffp-contract=off like every kernel here; double division and square root are correctly rounded.
 #include "dtof_adaptive.h"
+#include "dtof_develop.h"
 #include <vector>
 
 namespace dtof {
@@ -22,7 +23,7 @@ __device__ __forceinline__ bool finite_(double x) { return fabs(x) <= 1.79769313
 struct PixelVerdict { double metric; bool selected; };
 
 __device__ __forceinline__ PixelVerdict judge(const AdaptiveArgs &a, const double *S, int64_t ps, uint32_t cnt) {
-    const double W = S[0], Wd = W == 0.0 ? 1.0 : W, n = (double) cnt;
+    const double Wd = develop_weight(S[0]), n = (double) cnt;
     PixelVerdict v;
     if (a.mode == kAdaptiveImage) {
         double metric = 0.0;

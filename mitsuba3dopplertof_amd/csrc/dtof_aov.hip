@@ -3,15 +3,15 @@
 //            RayFlags::All, aov.cpp:206-207) through trace_rays, the scene staged as k_velocity stages it
 //   surface  compute_surface with the frames on: dp_du / dp_dv come through instances (dtof_shading.h); every value is +0 on a miss (aov.cpp:208)
 //   select   the lane's 20 values stay in registers; channel c is value slot[c], picked by selects on a wave-uniform counter (dtof_aov.h: the slots)
-//   splat    the footprint, float32 weights and run reduction of k_splat_moments_f64 (dtof_moments.hip, dtof_splat_runs.h): the term value * (wx * wy) is a float32
-//            product (the box filter adds the value itself and 1.f), converted to double; runs of lanes with one footprint anchor are summed in the wave and the run's
-//            last lane issues one atomic per cell and channel; footprints wider than 5 x 5 take one atomic per lane, cell and channel
+//   splat    the footprint, the float32 weights, the cell walks and the run reduction of dtof_splat64.h, shared with the float64 film and the moment film: the term
+//            value * (wx * wy) is a float32 product (the box filter adds the value itself and 1.f), converted to double; runs of lanes with one footprint anchor are
+//            summed in the wave and the run's last lane issues one atomic per cell and channel; footprints wider than 5 x 5 take one atomic per lane, cell and
+//            channel.  This file keeps its order: the plane loop outside, the walk inside
 // With AovArgs::values the lane's channels are written out instead of the splat (dtof_sample_aov_lanes): the same code up to the selection.
 // k_aov<LDS, FLOW = true> is the flow film (dtof_render_flow, dtof_sample_flow_lanes): two more values per lane, the screen-space motion of the hit over the shutter
 // interval (flow_of below), through the same selection and the same splat; the FLOW = false instantiations hold none of it (profiles/flow_resource_usage.txt).
 // Compiled with -ffp-contract=off like every kernel here.
-#include "dtof_device.h"
-#include "dtof_splat_runs.h"
+#include "dtof_splat64.h"
 #include "dtof_aov.h"
 
 namespace dtof {
@@ -19,7 +19,7 @@ namespace dtof {
 namespace {
 static_assert(kAovMaxChannels <= 3 * (int) kAovSlotsPerWord && kAovSlots <= 32 && kAovFlowSlots <= 32, "the channel table is three words of twelve 5-bit slots");
 
-// Value j of the lane's 20 for a wave-uniform j.  Twenty scalars and a chain of selects, as in dtof_moments.hip: an array or a struct that is indexed goes to scratch.
+// Value j of the lane's 20 for a wave-uniform j.  Twenty scalars and a chain of selects, like sel() of dtof_splat64.h: an array or a struct that is indexed goes to scratch.
 #define DTOF_AOV_LIST(X) X(0) X(1) X(2) X(3) X(4) X(5) X(6) X(7) X(8) X(9) X(10) X(11) X(12) X(13) X(14) X(15) X(16) X(17) X(18) X(19)
 #define DTOF_AOV_PICK(k) v = j == k ? v##k : v;
 // (the two flow values only in the FLOW instantiations: the others keep their twenty selects)
@@ -30,7 +30,6 @@ DTOF_D uint32_t slot_of(const AovArgs &a, uint32_t c) {
     const uint32_t k = c < kAovSlotsPerWord ? c : c < 2 * kAovSlotsPerWord ? c - kAovSlotsPerWord : c - 2 * kAovSlotsPerWord;
     return (uint32_t) (w >> (5u * k)) & 31u;
 }
-DTOF_D double term(float v, float w, bool box) { return (double) (box ? v : v * w); }   // the box filter adds the value itself (value * 1.f is the same float)
 
 // The motion vector of a hit on an animated object (include/dtof.h: the flow film): the hit point is taken into the object's own frame with the inverse of the
 // keyframes' interpolant at the ray's time, placed with each keyframe, and both positions are projected with S.  All in double, formed from the float32 hit and
@@ -112,63 +111,27 @@ __global__ __launch_bounds__(kBlock) void k_aov(const uint8_t *scene, uint32_t s
         return;
     }
     double *const film = a.film;
-    const int W = rp.crop_w, H = rp.crop_h;
-    const bool box = rp.filter == FILTER_BOX;
-    const int n = box ? 0 : (int) ceilf(rp.filter_radius - .5f), cnt = 2 * n + 1;
-    const float2 p = valid ? q.pos[i] : make_float2(0.f, 0.f);
-    // the footprint's anchor in film coordinates (splat_lane): the box filter splats at the lane's own pixel, every other at floor(position) - n
-    int ax, ay; float relx = 0.f, rely = 0.f;
-    if (box) {
-        const uint32_t pix = fdiv(global_lane(rp, rp.lane_base + (valid ? i : 0u)), rp.d_spp);
-        ay = (int) fdiv(pix, rp.d_w); ax = (int) (pix - (uint32_t) W * (uint32_t) ay);
-    } else {
-        const int pix = (int) floorf(p.x) - n, piy = (int) floorf(p.y) - n;
-        relx = (float) pix + .5f - p.x; rely = (float) piy + .5f - p.y;
-        ax = pix - rp.crop_x; ay = piy - rp.crop_y;
-    }
-    if (cnt > kRunCells) {   // wide footprints (the Lanczos filter's 7 x 7): one atomic per lane, cell and channel
-        if (!valid) return;
+    const Footprint f = footprint_of(rp, i, valid, q.pos);
+    if (f.cnt > kRunCells) {
+        if (valid) walk_wide(rp, f, [&](size_t pixel, float w) {
+            double *cell = film + (size_t) kMomentCell * pixel;
+            add_f64(cell, (double) w);
 #pragma unroll 1
-        for (int ys = 0; ys < cnt; ++ys) {
-            const float wy = filter_weight(rp, rely + (float) ys);
-#pragma unroll 1
-            for (int xs = 0; xs < cnt; ++xs) {
-                const float w = filter_weight(rp, relx + (float) xs) * wy;
-                const int x = ax + xs, y = ay + ys;
-                if ((unsigned) x >= (unsigned) W || (unsigned) y >= (unsigned) H) continue;
-                double *cell = film + (size_t) kMomentCell * ((size_t) y * W + x);
-                add_f64(cell, (double) w);
-#pragma unroll 1
-                for (uint32_t c = 0; c < C; ++c) add_f64(cell + 1 + c, (double) (DTOF_AOV_SEL(slot_of(a, c)) * w));
-            }
-        }
+            for (uint32_t c = 0; c < C; ++c) add_f64(cell + 1 + c, (double) (DTOF_AOV_SEL(slot_of(a, c)) * w));
+        });
         return;
     }
-    const Runs runs = find_runs(ax, ay, valid);
-    const uint32_t dist = runs.dist, steps = runs.steps;
-    static_assert(kRunCells == 5, "five column and five row weights are kept in registers");
-#define DTOF_W(rel, k) (k < cnt && !box ? filter_weight(rp, rel + (float) k) : 0.f)
-    const float wx0 = DTOF_W(relx, 0), wx1 = DTOF_W(relx, 1), wx2 = DTOF_W(relx, 2), wx3 = DTOF_W(relx, 3), wx4 = DTOF_W(relx, 4);
-    const float wy0 = DTOF_W(rely, 0), wy1 = DTOF_W(rely, 1), wy2 = DTOF_W(rely, 2), wy3 = DTOF_W(rely, 3), wy4 = DTOF_W(rely, 4);
-#undef DTOF_W
+    const RunCells rc = run_cells_of(rp, f, valid);
     // The PLANE loop is the outer one (plane 0: the weight, the value 1; plane 1 + c: channel c), so a channel's value is selected once and not once per cell; the
-    // cell loops inside it redo a cell's address and weight per plane, a handful of instructions against the twenty selects.  All three loops stay rolled: their
-    // counters are scalars.  1.f * w is w, so the weight takes the channels' code.
+    // walk inside it redoes a cell's address and weight per plane, a handful of instructions against the twenty selects (the runs and the ten weights are rc's,
+    // computed once).  The plane loop stays rolled like the walk's: its counter is a scalar.  1.f * w is w, so the weight takes the channels' code.
 #pragma unroll 1
     for (uint32_t pl = 0; pl <= C; ++pl) {
         const float v = pl == 0 ? (valid ? 1.f : 0.f) : DTOF_AOV_SEL(slot_of(a, pl - 1u));
-#pragma unroll 1
-        for (int ys = 0; ys < cnt; ++ys) {
-            float wys = wy0; wys = ys == 1 ? wy1 : wys; wys = ys == 2 ? wy2 : wys; wys = ys == 3 ? wy3 : wys; wys = ys == 4 ? wy4 : wys;
-#pragma unroll 1
-            for (int xs = 0; xs < cnt; ++xs) {
-                const int x = ax + xs, y = ay + ys;
-                const bool write = valid && runs.last && (unsigned) x < (unsigned) W && (unsigned) y < (unsigned) H;   // the same cell for every lane of the run
-                float wxs = wx0; wxs = xs == 1 ? wx1 : wxs; wxs = xs == 2 ? wx2 : wxs; wxs = xs == 3 ? wx3 : wxs; wxs = xs == 4 ? wx4 : wxs;
-                const double sum = run_sum(term(v, wxs * wys, box), dist, steps);
-                if (write) add_f64(film + (size_t) kMomentCell * ((size_t) y * W + x) + pl, sum);
-            }
-        }
+        walk_runs(rp, f, rc, [&](float w, bool write, size_t pixel) {
+            const double sum = run_sum(term(v, w, f.box), rc.dist, rc.steps);
+            if (write) add_f64(film + (size_t) kMomentCell * pixel + pl, sum);
+        });
     }
 }
 #undef DTOF_AOV_SEL

@@ -7,6 +7,11 @@
 
 namespace dtof {
 
+// The weight a developed value is divided by: W == 0 ? 1 : W (HDRFilm::develop).  The one spelling of the rule on the device: the develop kernels and the
+// adaptive metric (dtof_adaptive.hip) call it.
+__device__ __forceinline__ float develop_weight(float w) { return w == 0.f ? 1.f : w; }
+__device__ __forceinline__ double develop_weight(double w) { return w == 0.0 ? 1.0 : w; }
+
 // `planes` RGBW film planes `plane_stride` elements of the film's type apart (0 = dense) into the dense rgb[planes][n_pixels][3].  A float32 film is read with 16-byte
 // loads (every plane 16-byte aligned), a float64 film with 8-byte loads
 void launch_develop(const float *film, int32_t planes, uint64_t plane_stride, float *rgb, int64_t n_pixels, hipStream_t s);

@@ -4,8 +4,11 @@
 //   k_develop      : one lane per pixel and plane into the dense [planes][n][3]; ADD = false stores (a develop, and the first pass of a running sum: acc = img, so
 //                    that -0 survives and what the sum held before does not matter), ADD = true adds in float32 (acc + img, in that order)
 //   k_develop_rgba : colour film and alpha film -- (A, 0, 0, W), accumulated with the same weights -- into [n][4]
-// Elementwise and bound by memory traffic: no LDS.  Compiled with -ffp-contract=off like every kernel here.
+//   k_develop_moments : the cells of the moment film and of the aov film (dtof_moments.h declares its launcher) into dense planes of doubles, every plane but the
+//                    weight divided in double or not
+// The weight rule itself is develop_weight (dtof_develop.h).  Elementwise and bound by memory traffic: no LDS.  Compiled with -ffp-contract=off like every kernel here.
 #include "dtof_develop.h"
+#include "dtof_moments.h"
 
 namespace dtof {
 
@@ -14,11 +17,11 @@ constexpr int kDevelopBlock = 256;
 
 __device__ __forceinline__ float3 developed(const float *pixel) {
     const float4 f = *(const float4 *) pixel;
-    const float w = f.w == 0.f ? 1.f : f.w;
+    const float w = develop_weight(f.w);
     return make_float3(f.x / w, f.y / w, f.z / w);
 }
 __device__ __forceinline__ float3 developed(const double *pixel) {
-    const double w = pixel[3] == 0.0 ? 1.0 : pixel[3];
+    const double w = develop_weight(pixel[3]);
     return make_float3((float) (pixel[0] / w), (float) (pixel[1] / w), (float) (pixel[2] / w));
 }
 
@@ -36,6 +39,15 @@ template <typename T> __global__ __launch_bounds__(kDevelopBlock) void k_develop
     if (i >= n) return;
     const float3 c = developed(film + 4 * i);
     ((float4 *) rgba)[i] = make_float4(c.x, c.y, c.z, developed(alpha_film + 4 * i).x);   // (only the alpha film's A and W are loaded)
+}
+
+// the moment film's cells (dtof_moments.h) into the dense [planes][n] doubles; blockIdx.y = the plane
+__global__ __launch_bounds__(kDevelopBlock) void k_develop_moments(const double *film, double *out, int64_t n, int divide) {
+    const int64_t i = (int64_t) blockIdx.x * kDevelopBlock + threadIdx.x;
+    if (i >= n) return;
+    const double *c = film + (int64_t) kMomentCell * i;
+    const uint32_t pl = blockIdx.y;
+    out[(int64_t) pl * n + i] = pl == 0 || !divide ? c[pl] : c[pl] / develop_weight(c[0]);
 }
 
 dim3 pixel_grid(int64_t n_pixels, int32_t planes) { return dim3((uint32_t) ((n_pixels + kDevelopBlock - 1) / kDevelopBlock), (uint32_t) planes); }
@@ -61,5 +73,9 @@ void launch_develop_accumulate(const double *film, int32_t planes, uint64_t stri
 }
 void launch_develop_rgba(const float *film, const float *alpha_film, float *rgba, int64_t n, hipStream_t s) { develop_rgba(film, alpha_film, rgba, n, s); }
 void launch_develop_rgba(const double *film, const double *alpha_film, float *rgba, int64_t n, hipStream_t s) { develop_rgba(film, alpha_film, rgba, n, s); }
+void launch_develop_moments(const double *film, int32_t planes, bool divide, double *out, int64_t n_pixels, hipStream_t s) {
+    if (n_pixels <= 0 || planes <= 0 || planes > kMomentCell) return;
+    hipLaunchKernelGGL(k_develop_moments, pixel_grid(n_pixels, planes), dim3(kDevelopBlock), 0, s, film, out, n_pixels, divide ? 1 : 0);
+}
 
 }  // namespace dtof

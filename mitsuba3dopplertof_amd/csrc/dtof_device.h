@@ -79,6 +79,17 @@ template <int CTRL, int ROW_MASK = 0xf>
 DTOF_D float dpp_add(float v) {
     return v + __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, ROW_MASK, 0xf, false));
 }
+// The sum of v over every segment of `seg` consecutive lanes (a power of two, 2 .. 64; wave-uniform), in the segment's LAST lane: pairs, quads, row_ror 4 / 8 give
+// every lane of a 16-lane row the row total; row_bcast:15 / :31 carry it into the last lane of 32 / 64 lanes.  One v_add_f32_dpp each, no LDS traffic.
+DTOF_D float segment_sum(float v, uint32_t seg) {
+    v = dpp_add<0xb1>(v);
+    if (seg >= 4) v = dpp_add<0x4e>(v);
+    if (seg >= 8) v = dpp_add<0x124>(v);
+    if (seg >= 16) v = dpp_add<0x128>(v);
+    if (seg >= 32) v = dpp_add<0x142, 0xa>(v);
+    if (seg >= 64) v = dpp_add<0x143, 0xc>(v);
+    return v;
+}
 
 // Generic per-lane splat (any filter radius / any spp): direct float atomics.
 template <int F = -1>   // F >= 0: the filter is known at compile time (no box branch, filter_weight<F>)

@@ -270,20 +270,9 @@ __global__ __launch_bounds__(kBlock) void k_splat_tent3(RenderParams rp, Queues 
                 acc[4 * (3 * ys + xs) + 0] = r.x * w; acc[4 * (3 * ys + xs) + 1] = r.y * w;
                 acc[4 * (3 * ys + xs) + 2] = r.z * w; acc[4 * (3 * ys + xs) + 3] = w;
             }
-        // segment sums with DPP adds (one v_add_f32_dpp each, no LDS traffic): pairs, quads, row_ror 4/8 give every
-        // lane of a 16-lane row the row total; row_bcast:15 / :31 carry it into the last lane of 32 / 64 lanes.
-        // The total of a segment therefore ends up in the segment's LAST lane.
+        // segment sums with DPP adds (segment_sum, dtof_device.h): the total of a segment ends up in the segment's LAST lane
 #pragma unroll
-        for (int c = 0; c < 36; ++c) {
-            float v = acc[c];
-            v = dpp_add<0xb1>(v);
-            if (seg >= 4) v = dpp_add<0x4e>(v);
-            if (seg >= 8) v = dpp_add<0x124>(v);
-            if (seg >= 16) v = dpp_add<0x128>(v);
-            if (seg >= 32) v = dpp_add<0x142, 0xa>(v);
-            if (seg >= 64) v = dpp_add<0x143, 0xc>(v);
-            acc[c] = v;
-        }
+        for (int c = 0; c < 36; ++c) acc[c] = segment_sum(acc[c], seg);
         // Stage the per-segment sums in LDS (9 ds_write_b128 by the segment's last lane) and let the whole block issue
         // the atomics: 36 values per segment become lanes of a few full wave-instructions instead of 36 single-lane
         // atomics that stall their wave once 16 are outstanding.
@@ -376,16 +365,7 @@ __global__ __launch_bounds__(kBlock) void k_splat_x8(RenderParams rp, Queues q, 
             splat_lane(rp, fk, sp.x, sp.y, px, py, sr.x, sr.y, sr.z);
         }
 #pragma unroll
-        for (int c = 0; c < 4 * NN; ++c) {   // segment totals end up in the segment's LAST lane (see k_splat_tent3)
-            float v = acc[c];
-            v = dpp_add<0xb1>(v);
-            if (seg8 >= 4) v = dpp_add<0x4e>(v);
-            if (seg8 >= 8) v = dpp_add<0x124>(v);
-            if (seg8 >= 16) v = dpp_add<0x128>(v);
-            if (seg8 >= 32) v = dpp_add<0x142, 0xa>(v);
-            if (seg8 >= 64) v = dpp_add<0x143, 0xc>(v);
-            acc[c] = v;
-        }
+        for (int c = 0; c < 4 * NN; ++c) acc[c] = segment_sum(acc[c], seg8);   // segment totals end up in the segment's LAST lane
         if (k > 0) __syncthreads();
         const uint32_t sidx_mine = threadIdx.x / seg8;
         if ((threadIdx.x & (seg8 - 1)) == seg8 - 1) {

@@ -21,7 +21,7 @@ constexpr int moment_planes(int K) { return 1 + 6 * K + K * (K - 1) / 2; }
 
 // q.res planes 0 .. rp.n_offsets - 1 of the batch into the cells of `film` (crop_h * crop_w * kMomentCell doubles): the footprint and float32 weights of launch_splat_f64
 void launch_splat_moments(const RenderParams &rp, const Queues &q, double *film, hipStream_t s);
-// out[p][i] = cell i's plane p, for p >= 1 divided in double by (W == 0 ? 1 : W) of the cell when `divide` (plane 0, the weight, is always copied)
+// k_develop_moments (dtof_develop.hip, with the other develop kernels): out[p][i] = cell i's plane p, for p >= 1 divided in double by (W == 0 ? 1 : W) of the cell when `divide` (plane 0, the weight, is always copied)
 void launch_develop_moments(const double *film, int32_t planes, bool divide, double *out, int64_t n_pixels, hipStream_t s);
 
 }  // namespace dtof

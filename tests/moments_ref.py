@@ -138,6 +138,14 @@ def splat(osc, fp, values):
     return sums.reshape(C_, H, W), mags.reshape(C_, H, W)
 
 
+def expected_rgbw(orc, osc, pd, seed, spp):
+    """The raw RGBW film of one render of the oracle's lanes: (sums (4, H, W), sums of magnitudes (4, H, W)), the channels r, g, b and the weight's value 1"""
+    lanes = lanes_of(orc, osc, pd, seed, spp)
+    spw, _ = pass_layout(orc, osc, pd, spp)
+    fp = footprint(orc, osc, lanes["sample_pos"], spw)
+    return splat(osc, fp, np.concatenate([lanes["rgb"], np.ones((len(lanes), 1), F32)], axis=1))
+
+
 def xyz(rgb):
     """srgb_to_xyz in float32, the sums left to right: (N, 3) float32"""
     rgb = np.ascontiguousarray(rgb, F32)

@@ -1,7 +1,7 @@
 """The opt-in float64 film (dtof_render_variants_f64, dtof_render_rows_variants_f64, dtof_develop_f64_async, dtof_develop_rgba_f64_async,
 dtof_render_velocity_map_f64) as far as it can be held without a GPU: the header declares the entries and the library exports them, refusals that need no device come
 back as DTOF_ERR_INVALID and leave the outputs alone, what passes them fails with DTOF_ERR_HIP on a host without a device (there is no CPU fallback), film= takes the
-two names only, and the command line parses --film."""
+two names only, and the command line parses --film; and the expected RGBW sums of the GPU test's signed-weight case against the oracle's exact film."""
 import ctypes as C
 import os
 import re
@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 from conftest import SCENES
+import moments_ref as ref
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 OK, INVALID, HIP = 0, 1, 2
@@ -34,6 +35,25 @@ def test_header_declares_and_library_exports_the_entries(mi):
     # the velocity map takes the arguments of the float32 entry
     flat = lambda name: re.sub(r"\s+", " ", re.search(r"\bint\s+%s\s*\(([^;]*)\)\s*;" % name, hdr).group(1))      # noqa: E731
     assert flat("dtof_render_velocity_map_f64") == flat("dtof_render_velocity_map")
+
+
+def test_expected_rgbw_against_the_exact_oracle(orc):
+    """what test_film64_gpu.py holds its signed-weight case to (moments_ref.expected_rgbw) is, on the tent case, the raw film of orc_render_exact within
+    2^-40 * sum |term| per pixel: both add the same float32 terms in double, in different orders"""
+    osc = orc.Scene(os.path.join(SCENES, "cornell_wall.xml"), dict(resx=16, resy=16))
+    pd = osc.params()
+    w, h = osc.size
+    film = np.zeros((h, w, 4), np.float64)
+    L = orc.lib()
+    L.orc_render_exact.restype = C.c_uint64
+    L.orc_render_exact.argtypes = [C.POINTER(orc.OrcScene), C.POINTER(orc.OrcParams), C.c_uint32, C.c_uint32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int]
+    p = orc.make_params(pd)
+    assert L.orc_render_exact(C.byref(osc.c), C.byref(p), 3, 16, 0, h, film.ctypes.data, None, ref.NCPU) == w * h * 16
+    sums, mags = ref.expected_rgbw(orc, osc, pd, 3, 16)
+    ratios = ref.errors_over_bound(sums, np.moveaxis(film, -1, 0), mags)
+    print("expected_rgbw against orc_render_exact, largest error / bound: r %.3g g %.3g b %.3g w %.3g" % tuple(ratios))
+    assert np.abs(film[..., :3]).max() > 0 and (film[..., 3] > 0).all()
+    assert (ratios <= 1.0).all(), ratios
 
 
 def _wall(mi, **kw):

@@ -7,6 +7,8 @@ Criteria (derived, not measured):
                      double sum of at most ~2^12 terms (relative 2^-53 * 2^12 of the sum of magnitudes) is far below half a float32 ulp of the quotient unless a pixel
                      cancels by more than 2^17, so the rounded quotient moves by at most one ulp
   weight channel     of the raw film, all terms positive: relative difference from the oracle's at most 2^-40 (2^12 additions of relative error 2^-53 each)
+  signed weights     (12_wall_lanczos, the wide per-lane path) all four raw channels against the sums of the oracle's lanes (moments_ref.expected_rgbw, which
+                     test_film64_cpu.py holds to orc_render_exact): |device - expected| <= 2^-40 * sum |term| per pixel, the moment film's criterion
 Every case also prints how many floats differ from the oracle at all (a CPU simulation of 20 random orders found none on the tent scenes); 0 is not asserted."""
 import ctypes as C
 import os
@@ -17,6 +19,7 @@ import numpy as np
 import pytest
 
 from conftest import SCENES
+import moments_ref as ref
 
 pytestmark = pytest.mark.gpu
 
@@ -82,11 +85,23 @@ def hold(what, img, film, ref_img, ref_film):
     assert differing(develop(film), img) == 0, (what, "the returned image is not its film developed in float64")
 
 
+def hold_signed(what, img, film, osc, orc, pd, spp):
+    """a film whose weights are signed (the Lanczos filter): hold()'s weight criterion assumes positive terms, so all four raw channels are held to the sums of the
+    oracle's lanes by the moment film's derived criterion, |device - expected| <= 2^-40 * sum |term| per pixel (moments_ref.errors_over_bound)"""
+    want, mags = ref.expected_rgbw(orc, osc, pd, SEED, spp)
+    ratios = ref.errors_over_bound(np.moveaxis(film, -1, 0), want, mags)
+    print("%s: largest error / bound: r %.3g g %.3g b %.3g w %.3g" % ((what,) + tuple(ratios)))
+    assert np.abs(want[:3]).max() > 0 and (want[3] > 0).any(), what
+    assert (ratios <= 1.0).all(), (what, ratios)
+    assert (want[3] < 0).any() or (mags[3] > np.abs(want[3])).any(), "the Lanczos filter has negative weights"
+    assert differing(develop(film), img) == 0, (what, "the returned image is not its film developed in float64")
+
+
 def _edit(xml, case):
     if case == "gauss":      # tests/test_device_film.py::_gauss: stddev 0.5, radius 2, a 5 x 5 footprint and a halo of 2
         old, new = '<rfilter type="tent" />', '<rfilter type="gaussian" />'
-    elif case == "box":
-        old, new = '<rfilter type="tent" />', '<rfilter type="box" />'
+    elif case in ("box", "lanczos"):      # lanczos: 3 lobes, a 7 x 7 footprint, negative weights
+        old, new = '<rfilter type="tent" />', '<rfilter type="%s" />' % case
     elif case == "crop":
         old, new = '<string name="file_format"', ('<integer name="crop_offset_x" value="5" /><integer name="crop_offset_y" value="3" />'
                                                    '<integer name="crop_width" value="16" /><integer name="crop_height" value="12" /><string name="file_format"')
@@ -109,6 +124,7 @@ CASES = {
     "9_domino_small": ("domino_small.xml", dict(resx=32, resy=32), 4, None, None, {}),                        # mesh kernels
     "10_wall_crop": ("cornell_wall.xml", dict(resx=32, resy=24), 8, "crop", None, {}),                        # a crop window at (5, 3)
     "11_wall_multi_pass": ("cornell_wall.xml", dict(resx=16, resy=16), 16, None, dict(samples_per_pass=4), {}),
+    "12_wall_lanczos": ("cornell_wall.xml", dict(resx=16, resy=16), 4, "lanczos", None, {}),                  # the wide per-lane path, negative weights: hold_signed
 }
 
 
@@ -143,7 +159,10 @@ def test_float64_film_against_the_exact_oracle(mi, orc, case, monkeypatch):
     assert st["n_fused_splat_launches"] == 0 and st["ms_splat"] > 0, st      # the separate splat stage ran, whatever the float32 route of this frame does
     if env.get("DTOF_PIPELINE") == "split":
         assert st["ms_trace"] > 0, st
-    hold(case, images[0], films[0], ref_img, ref_film)
+    if case == "12_wall_lanczos":
+        hold_signed(case, images[0], films[0], osc, orc, pd, spp)
+    else:
+        hold(case, images[0], films[0], ref_img, ref_film)
     again = sc.render(seed=SEED, spp=spp, film="float64")      # the plain form: the same image, from a second traversal
     print("%s: a second call differs in %d floats" % (case, differing(again, images[0])))
     assert again.shape == (h, w, 3) and rel_linf_px(again, images[0]) <= IMG_BOUND

@@ -6,7 +6,8 @@ usage: kernel_resources.py OBJDIR [PARENT_OBJDIR] [--all]      (--all: every ker
 Occupancy (waves per SIMD) follows from the VGPR count as the compiler's resource remarks report it for gfx950: 512 registers per SIMD lane in blocks of 8, at most 8."""
 import os, re, shutil, subprocess, sys, tempfile
 LLVM = os.environ.get("ROCM_LLVM", "/opt/rocm/llvm/bin")
-UNITS = ["dtof_kernels", "dtof_shade_plain", "dtof_shade_mesh", "dtof_shade_spec1", "dtof_shade_spec2", "dtof_shade_res0", "dtof_shade_res1", "dtof_shade_res2"]
+UNITS = ["dtof_kernels", "dtof_shade_plain", "dtof_shade_mesh", "dtof_shade_spec1", "dtof_shade_spec2", "dtof_shade_res0", "dtof_shade_res1", "dtof_shade_res2",
+         "dtof_film64", "dtof_moments", "dtof_aov", "dtof_develop", "dtof_adaptive"]
 FIELDS = [("vgpr", ".vgpr_count"), ("agpr", ".agpr_count"), ("sgpr", ".sgpr_count"), ("vspill", ".vgpr_spill_count"), ("sspill", ".sgpr_spill_count"),
           ("scratch", ".private_segment_fixed_size"), ("lds", ".group_segment_fixed_size")]
 
@@ -40,7 +41,7 @@ def kernels(objdir, tmp, tag):
             sym = re.sub(r"\.kd$", "", get(".symbol").group(1).strip("'"))
             res = {n: int(get(k).group(1)) if get(k) else 0 for n, k in FIELDS}
             res["occ"] = min(8, 512 // max(8, (res["vgpr"] + res["agpr"] + 7) // 8 * 8))
-            name = run(shutil.which("c++filt") or LLVM + "/llvm-cxxfilt", sym).strip().replace("void dtof::", "").split("(")[0]
+            name = run(shutil.which("c++filt") or LLVM + "/llvm-cxxfilt", sym).strip().replace("(anonymous namespace)::", "").replace("void dtof::", "").split("(")[0]
             name = re.sub(r", 0u>$", ">", name)   # FACTS = 0 (k_shade's last template argument): the name the kernel had without it
             m = re.search(r", (\d+)u>$", name)      # ... and a kernel compiled with plan facts (dtof_kernels.h: kFact*): its mask in hex, with the name of the mask
             if m and name.startswith("k_shade<"):
