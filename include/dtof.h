@@ -804,6 +804,11 @@ int dtof_flat_query(dtof_scene *scene, int form, int any, uint32_t n, const floa
  * and 2k + 1 are equal in o, d and maxt bit for bit (their times are their own), and each pair shares the plain rectangles between its two lanes.  Results as above.
  * DTOF_ERR_INVALID, before anything is launched, for an odd n, a pair that differs and a table other than 5 rectangles with the wall at index 2. */
 int dtof_flat_query_pairs(dtof_scene *scene, int any, uint32_t n, const float *rays8, float *out3, int32_t *ids);
+/* The same through the walk of form 2 with the z rows of its four plain rectangles computed on the matrix cores (six 4x4x1 f32 MFMAs per ray, issued by every lane
+ * of a wave in front of the query), which a frame's kernel runs for a vertex's shadow and continuation rays.  Results as above.  zrow8 (may be null): per ray the
+ * eight MFMA values -- the local z of the origin in rectangles 0, 1, 3, 4, then that of the direction -- bit for bit the fmaf chains of the other forms.
+ * DTOF_ERR_INVALID, before anything is launched, for a table other than 5 rectangles with the wall at index 2 and for n above 2^24. */
+int dtof_flat_query_zrow(dtof_scene *scene, int any, uint32_t n, const float *rays8, float *out3, int32_t *ids, float *zrow8);
 /* Lane generation of the headline frame's kernel over arrays: lanes [lane_begin, lane_begin + n) of a render with `seed` and `spp`, walked in 512-lane segments of
  * 64-lane chunks as the first-bounce launch walks them.  form 0: every lane generates itself; form 1: what lanes 2k and 2k + 1 share -- path stream, pixel jitter,
  * sample position, camera ray -- is evaluated once per pair, for the pairs of two consecutive chunks at a time, and fetched by both lanes.  out16: 16 words per lane --

@@ -824,6 +824,16 @@ class Scene:
         and a table other than five rectangles with the wall at index 2 raise DtofError."""
         return self._ray_query("dtof_flat_query_pairs", rays8, any, "obj")
 
+    def flat_query_zrow(self, rays8, any=False, zrows=False):
+        """flat_query in the "shape" walk whose four plain rectangles take their z rows from the matrix cores (dtof_flat_query_zrow), the form a frame's kernel runs for a
+        vertex's shadow and continuation rays.  Same results as flat_query.  zrows=True -> (result, (n, 8) float32): per ray the local z of the origin in rectangles
+        0, 1, 3, 4, then that of the direction, as the MFMAs left them.  A table other than five rectangles with the wall at index 2 raises DtofError."""
+        rays = np.ascontiguousarray(rays8, np.float32).reshape(-1, 8)
+        out, ids, z = np.zeros((len(rays), 3), np.float32), np.zeros(len(rays), np.int32), np.zeros((len(rays), 8), np.float32)
+        _check(_abi._lib().dtof_flat_query_zrow(self._h, 1 if any else 0, len(rays), rays.ctypes.data, None if any else out.ctypes.data, ids.ctypes.data, z.ctypes.data if zrows else None))
+        r = ids if any else {"t": out[:, 0], "u": out[:, 1], "v": out[:, 2], "obj": ids}
+        return (r, z) if zrows else r
+
     def pair_setup_lanes(self, seed, spp, lane_begin, n, form=1):
         """Lane generation of the headline frame's kernel over lanes [lane_begin, lane_begin + n) (dtof_pair_setup_lanes), walked in 512-lane segments of 64-lane chunks
         as the first-bounce launch walks them.  form 0: every lane generates itself; form 1: what the two lanes of a correlated pair share is evaluated once per pair,

@@ -298,10 +298,10 @@ int dtof_ray_intersect_uv(dtof_scene *sc, uint32_t n, const float *rays8, float 
 int dtof_ray_test(dtof_scene *sc, uint32_t n, const float *rays8, int32_t *occluded) { return ray_query(sc, n, rays8, nullptr, occluded, true); }
 
 // what the two flat queries do once the call is accepted: t and c are the table of a frame plan (automatic pipeline, default switches: dtof_scene_export kind 26)
-static void run_flat_query(dtof_scene *sc, const SceneTraits &t, const FlatChoice &c, int form, int any, uint32_t n, const float *rays8, float *out3, int32_t *ids) {
+static void run_flat_query(dtof_scene *sc, const SceneTraits &t, const FlatChoice &c, int form, int any, uint32_t n, const float *rays8, float *out3, int32_t *ids, float *zrow8 = nullptr) {
     ensure_device(sc);
-    round_trip({ { rays8, (size_t) n * 32 } }, { { out3, any ? 0 : (size_t) n * 12, 4 }, { ids, (size_t) n * 4 } }, [&](void *const *in, void *const *out) {
-        launch_flat_query(sc->d_blob.p, (uint32_t) sc->blob.size(), t.flat_off, c.flat_objects, c.memo_obj, form, any != 0, (const float *) in[0], (float *) out[0], (int32_t *) out[1], n, nullptr);
+    round_trip({ { rays8, (size_t) n * 32 } }, { { out3, any ? 0 : (size_t) n * 12, 4 }, { ids, (size_t) n * 4 }, { zrow8, zrow8 ? (size_t) n * 32 : 0 } }, [&](void *const *in, void *const *out) {
+        launch_flat_query(sc->d_blob.p, (uint32_t) sc->blob.size(), t.flat_off, c.flat_objects, c.memo_obj, form, any != 0, (const float *) in[0], (float *) out[0], (int32_t *) out[1], n, nullptr, zrow8 ? (float *) out[2] : nullptr);
     });
 }
 // trace_flat over arrays (dtof_flat_query.hip): the query a frame of this scene runs at every path vertex, in the form asked for
@@ -340,6 +340,21 @@ int dtof_flat_query_pairs(dtof_scene *sc, int any, uint32_t n, const float *rays
             throw std::runtime_error("dtof_flat_query_pairs: the pair form is compiled for a flat table of 5 rectangles whose one instance, of one rectangle, is at index 2" +
                                      (c.flat_objects ? ", this table has " + std::to_string(c.flat_objects) + " objects" : std::string(", this scene has no flat table")));
         run_flat_query(sc, t, c, kFlatQueryPairs, any, n, rays8, out3, ids);
+    });
+}
+
+// ... and the shaped walk with the plain rectangles' z rows computed on the matrix cores (trace_flat: ZROW, dtof_zrow_mfma.h), as k_shade runs a vertex's shadow and
+// continuation queries under that shape; zrow8, if given, receives the eight MFMA values per ray.  The kernel is written for the one shape: any other table is refused here
+int dtof_flat_query_zrow(dtof_scene *sc, int any, uint32_t n, const float *rays8, float *out3, int32_t *ids, float *zrow8) {
+    return guarded([&] {
+        if (!sc || (n && (!rays8 || !ids || (!any && !out3)))) throw std::runtime_error("null argument");
+        if (n > (1u << 24)) throw std::runtime_error("dtof_flat_query_zrow: more than 2^24 rays in one call");
+        const SceneTraits t = scene_traits(*sc);
+        const FlatChoice c = default_flat_choice(*sc, t);
+        if (!kFlatQueryZrowBuilt || c.flat_objects == 0 || !(c.facts & kFactOneWall) || (c.facts & kFlatShapeFields) != (flat_query_facts(2) & kFlatShapeFields))
+            throw std::runtime_error("dtof_flat_query_zrow: the MFMA z rows are compiled for a flat table of 5 rectangles whose one instance, of one rectangle, is at index 2" +
+                                     (c.flat_objects ? ", this table has " + std::to_string(c.flat_objects) + " objects" : std::string(", this scene has no flat table")));
+        run_flat_query(sc, t, c, kFlatQueryZrow, any, n, rays8, out3, ids, zrow8);
     });
 }
 

@@ -2,6 +2,7 @@
 // dtof_reconstruct.h and dtof_film64.h: only the host orchestration reads it, and the translation units of the render kernels do not change with it.
 #pragma once
 #include "dtof_kernels.h"
+#include "dtof_zrow_mfma.h"
 
 namespace dtof {
 
@@ -12,9 +13,12 @@ constexpr uint32_t flat_query_facts(int form) { return form == 2 ? kHeadlineShap
 // ... and, for the launcher only (dtof_flat_query_pairs; dtof_flat_query refuses it), the shaped walk's pair form: rays 2k and 2k + 1 equal but for their times
 constexpr int kFlatQueryPairs = 3;
 constexpr bool kFlatQueryPairsBuilt = pair_walk_shape(flat_query_facts(2));   // the form is written for one shape (trace_flat: PAIR_RAYS)
+// ... and its form with the plain rectangles' z rows from the matrix cores (dtof_flat_query_zrow; trace_flat: ZROW), which also writes those rows to zrow8 if given
+constexpr int kFlatQueryZrow = 4;
+constexpr bool kFlatQueryZrowBuilt = zrow_mfma_shape(flat_query_facts(2));
 // One ray per lane, blocks of one wave: rays = o[3], d[3], time, maxt; closest hit: out3 = t, u, v (inf, 0, 0 on a miss), ids = the object or -1; occlusion: ids = 1 / 0.
 // flat_off, flat_objects, memo_obj: RenderParams::flat_off / flat_objects / memo_obj as a frame plan sets them.  Throws when the blob does not fit the LDS stage.
 void launch_flat_query(const uint8_t *scene, uint32_t scene_bytes, uint32_t flat_off, uint32_t flat_objects, uint32_t memo_obj, int form, bool any,
-                       const float *rays, float *out3, int32_t *ids, uint32_t n, hipStream_t s);
+                       const float *rays, float *out3, int32_t *ids, uint32_t n, hipStream_t s, float *zrow8 = nullptr);
 
 }  // namespace dtof

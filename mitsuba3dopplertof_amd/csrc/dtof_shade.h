@@ -426,6 +426,9 @@ __global__ __launch_bounds__(RESW ? RESW * 64 : kShadeBlock, RESW ? RESW / 4 : (
     static_assert(!F_PAIR || F_WAVE_PIXEL, "a lane reads its partner's registers: the whole wave is active where it does");
     static_assert(!F_PAIR || (!AREA && SPEC == 0 && KMAX == 1 && F_ONE_EMITTER), "a diffuse BSDF picks no lobe and a lone point light samples nothing: of an iteration's six draws only s2x and s2y are read");
     static_assert(!F_PAIR || (F_NO_RR && F_CORRELATED && F_DOPPLER_CORR && F_WHOLE_PATH && F_SINGLE_PASS && (FACTS & kFactStratifiedPairs) != 0), "every draw comes from the stream lanes 2k and 2k + 1 share, none is looked at for roulette, no state outlives the launch");
+    // ... and (m): the z rows of the plain rectangles for the shadow and continuation rays come from the matrix cores, six MFMAs per query issued in front of the
+    // lane-divergent call sites (dtof_zrow_mfma.h; the primary walk keeps the pair form of (k))
+    constexpr bool ZROW = FUSED && F_FLAT && zrow_mfma_shape(FACTS & kFactsFlatTable) && DTOF_FLAT_SHAPE_ANY && DTOF_FLAT_SHAPE_CLOSEST;
     constexpr bool F_FRAMES = F_ONE_WALL && DTOF_WALL_FRAMES;   // shading frames precomputed: the wall's once per path, the plain rectangles' on the host (compute_surface)
     static_assert(!F_FLAT || (!MESH && SPEC == 0 && RESW == 0), "trace_flat serves the staged rectangle-only diffuse kernels");
     static_assert(!F_ONE_WALL || F_FLAT, "the one wall is an object of the flat table");
@@ -517,6 +520,9 @@ __global__ __launch_bounds__(RESW ? RESW * 64 : kShadeBlock, RESW ? RESW / 4 : (
     SceneView sv = RESW ? sv_res : make_view(base);
     if (FUSED) { sv.memo_obj = A0.rp.memo_obj; sv.memo = (float *) (lds + stage_words) + (RESW ? wave_id * kMemoWords * kMemoStride + lane_id : threadIdx.x); sv.memo_m = memo_m_lds; }
     const bool have_memo = F_ONE_WALL || (FUSED && sv.memo_obj != 0xffffffffu);
+    // ZROW: the matrix-side operands of the plain rectangles' z rows, per-lane constants of the launch, read from the staged DFlatZ table with every lane active
+    typename std::conditional<ZROW, ZrowOperands, NoZrow>::type zrow_m;
+    if constexpr (ZROW) zrow_m = zrow_operands((const uint4 *) ((const DFlatObject *) (sv.base + A0.rp.flat_off) + flat_shape_count(FACTS)) + 1);
     PairPart pair_carried = pair_part_zero();   // PAIR_SETUP: the pair values an even chunk leaves for itself and for the chunk after it
     for (uint32_t cbase = sub > 1 ? sub_index * unit_lanes : 0u; cbase < (sub > 1 ? (sub_index + 1) * unit_lanes < count ? (sub_index + 1) * unit_lanes : count : count); cbase += kShadeBlock) {
     uint32_t rebase = 0;
@@ -929,9 +935,12 @@ __global__ __launch_bounds__(RESW ? RESW * 64 : kShadeBlock, RESW ? RESW / 4 : (
         bool commit = false;
         // (Both rays in ONE traversal loop -- a lane going on with its continuation ray while its neighbours are still in their shadow rays -- was built and measured in
         // round 5 and lost by a third: tools/experiments/r05_pair_traversal.patch, profiles/r05_pair_traversal.txt.)
+        // ZROW: every lane of the wave takes part in the MFMAs (uniform control flow; sha / shb are defined in the lanes without a shadow ray, their results unread)
+        typename std::conditional<ZROW, ZrowQuad, NoZrow>::type zq_shadow{}, zq_next{};
+        if constexpr (ZROW) zq_shadow = zrow_mfma(zrow_m, sha.x, sha.y, sha.z, shb.x, shb.y, shb.z);
         if (want_shadow) {   // test_visibility (scene.cpp:266-271): an unoccluded sample commits its candidate result
             Hit hs;
-            commit = (F_FLAT || flat) ? !trace_flat<true, true, FACTS & kFactsFlatTable>(sv, (ConstBytes) A.scene + rp.flat_off, rp.flat_off, flat, stack, mk(sha.x, sha.y, sha.z), mk(shb.x, shb.y, shb.z), shb.w, sha.w, hs)
+            commit = (F_FLAT || flat) ? !trace_flat<true, true, FACTS & kFactsFlatTable, false, ZROW, decltype(zq_shadow)>(sv, (ConstBytes) A.scene + rp.flat_off, rp.flat_off, flat, stack, mk(sha.x, sha.y, sha.z), mk(shb.x, shb.y, shb.z), shb.w, sha.w, hs, zq_shadow)
                           : !trace_scene<true, MESH, true, RESW != 0, kStackStride, S16, 0u, false, RH16>(sv, stack, mk(sha.x, sha.y, sha.z), mk(shb.x, shb.y, shb.z), shb.w, sha.w, hs);
         }
         if constexpr (RES_LDS) {   // the committed sample gets its K modulation weights now (dopplertofpath.cpp:221-226) and is added to the films' running results
@@ -959,9 +968,10 @@ __global__ __launch_bounds__(RESW ? RESW * 64 : kShadeBlock, RESW ? RESW / 4 : (
 #pragma unroll
             for (int k = 0; k < KMAX; ++k) if (KMAX == 1 || k < rp.n_offsets) q.res[(size_t) k * q.capacity + l] = make_float4(cand[k].x, cand[k].y, cand[k].z, 0.f);
         }
+        if constexpr (ZROW) if (trace_next) zq_next = zrow_mfma(zrow_m, nra.x, nra.y, nra.z, nrb.x, nrb.y, nrb.z);   // (uniform; as above)
         if (alive && trace_next) {   // closest hit of the continuation ray, consumed by the next bounce (the Hit lives inside this block: no half-defined registers across the commit above)
             Hit h;
-            bool found = (F_FLAT || flat) ? trace_flat<false, true, FACTS & kFactsFlatTable>(sv, (ConstBytes) A.scene + rp.flat_off, rp.flat_off, flat, stack, mk(nra.x, nra.y, nra.z), mk(nrb.x, nrb.y, nrb.z), nra.w, nrb.w, h)
+            bool found = (F_FLAT || flat) ? trace_flat<false, true, FACTS & kFactsFlatTable, false, ZROW, decltype(zq_next)>(sv, (ConstBytes) A.scene + rp.flat_off, rp.flat_off, flat, stack, mk(nra.x, nra.y, nra.z), mk(nrb.x, nrb.y, nrb.z), nra.w, nrb.w, h, zq_next)
                               : trace_scene<false, MESH, true, RESW != 0, kStackStride, S16, 0u, false, RH16>(sv, stack, mk(nra.x, nra.y, nra.z), mk(nrb.x, nrb.y, nrb.z), nra.w, nrb.w, h);
             if (!FIRST || last) store_hit<MESH>(q, l, h, found);
             if (FIRST) { hh = make_uint4(f2u(h.t), f2u(h.u), f2u(h.v), h.prim); hid = found ? (h.obj | (h.shape << (F_ID24 ? 24u : q.id_shift))) : 0xffffffffu; }

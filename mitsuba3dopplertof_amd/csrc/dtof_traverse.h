@@ -7,6 +7,7 @@
 #include "dtof_flat_cull.h"
 #include "dtof_box_cull.h"
 #include "dtof_pair_walk.h"
+#include "dtof_zrow_mfma.h"
 
 #ifndef DTOF_D
 #define DTOF_D __device__ __forceinline__
@@ -495,8 +496,11 @@ DTOF_D F2 flat_zrow(float z0, float z1, float z2, float z3, V3 ro, V3 rd) {
 //                 1, the odd lane 3 and 4, through z-row and record addresses that differ by a per-lane constant -- and the wall is tested by both.  dtof_pair_walk.h
 //                 has the argument.  One visit is still the one above, operation for operation.  An occlusion query has no such form and takes the sweep as it is: the
 //                 form was built for it and for the queries of iteration 0 and cost more than it saved there, DESIGN 8.3 (k), profiles/pair_walk_ab.txt.
-template <bool ANY, bool MEMO, uint32_t FACTS = 0, bool PAIR_RAYS = false>
-DTOF_D bool trace_flat(const SceneView &sv, ConstBytes flat_table, uint32_t flat_off, uint32_t n_objects, uint32_t *stack, V3 o, V3 d, float time, float maxt, Hit &best) {
+//   ZROW          (a shape of 5 with the wall at 2, not PAIR_RAYS) the caller hands in zq = zrow_mfma of (o, d), computed on the matrix cores in front of a call site
+//                 that may be lane-divergent (dtof_zrow_mfma.h).  The plain rectangles' visits take their z row from it -- the same bits -- and read no
+//                 DFlatZ row; the wall's visit and the occlusion sweep's out-of-line tail keep flat_zrow.
+template <bool ANY, bool MEMO, uint32_t FACTS = 0, bool PAIR_RAYS = false, bool ZROW = false, typename ZQ = NoZrow>
+DTOF_D bool trace_flat(const SceneView &sv, ConstBytes flat_table, uint32_t flat_off, uint32_t n_objects, uint32_t *stack, V3 o, V3 d, float time, float maxt, Hit &best, ZQ zq = ZQ{}) {
     best.t = maxt; best.u = best.v = 0.f; best.obj = 0xffffffffu; best.shape = 0; best.prim = 0;
     bool occluded = false;
     DTOF_STAT(0);
@@ -544,6 +548,8 @@ DTOF_D bool trace_flat(const SceneView &sv, ConstBytes flat_table, uint32_t flat
         constexpr uint32_t N = flat_shape_count(FACTS), WALL = flat_shape_wall(FACTS);
         constexpr bool PAIR = PAIR_RAYS && kPairWalkCompiled;
         static_assert(!PAIR_RAYS || pair_walk_shape(FACTS), "the pair form is written for five rectangles with the wall at index 2: {0, 1} below it, {3, 4} above");
+        static_assert(std::is_same<ZQ, typename std::conditional<ZROW, ZrowQuad, NoZrow>::type>::value, "the z rows come with ZROW and only with it");
+        static_assert(!ZROW || (zrow_mfma_shape(FACTS) && !PAIR_RAYS && (ANY ? DTOF_FLAT_SHAPE_ANY : DTOF_FLAT_SHAPE_CLOSEST)), "the MFMA z rows are those of rectangles 0, 1, 3, 4 around the wall at index 2, for the shaped walks");
         if constexpr (N != 0 && ANY && DTOF_FLAT_SHAPE_ANY) {
             // Occlusion query: ONE sweep over the z rows and their certain-miss tests, then ONE branch -- where no lane of the wave needs a full test (every shadow
             // ray of a closed room) the query ends there, unoccluded.  `occluded` is an OR: the tail may run the full tests in any order, and runs them in ascending one.
@@ -554,8 +560,14 @@ DTOF_D bool trace_flat(const SceneView &sv, ConstBytes flat_table, uint32_t flat
             bool any_need = false;
 #pragma unroll
             for (uint32_t k = 0; k < N; ++k) {
-                const uint4 zr = zts[k];
-                const F2 z = k == WALL ? flat_zrow(u2f(zr.x), u2f(zr.y), u2f(zr.z), u2f(zr.w), wo, wd) : flat_zrow(u2f(zr.x), u2f(zr.y), u2f(zr.z), u2f(zr.w), o, d);
+                F2 z;
+                if constexpr (ZROW) {
+                    if (k == WALL) { const uint4 zr = zts[k]; z = flat_zrow(u2f(zr.x), u2f(zr.y), u2f(zr.z), u2f(zr.w), wo, wd); }
+                    else z = F2{ zq.o[zrow_slot(k)], zq.d[zrow_slot(k)] };
+                } else {
+                    const uint4 zr = zts[k];
+                    z = k == WALL ? flat_zrow(u2f(zr.x), u2f(zr.y), u2f(zr.z), u2f(zr.w), wo, wd) : flat_zrow(u2f(zr.x), u2f(zr.y), u2f(zr.z), u2f(zr.w), o, d);
+                }
                 const bool need = !flat_certain_miss(z.x, z.y, far);
                 DTOF_STAT(kStat); DTOF_STAT_WAVE(kStat + 2);
                 if (!need) DTOF_STAT(kStat + 1);
@@ -585,8 +597,14 @@ DTOF_D bool trace_flat(const SceneView &sv, ConstBytes flat_table, uint32_t flat
             const DFlatObject *lts = (const DFlatObject *) (sv.base + flat_off);
             const uint4 *zts = (const uint4 *) (lts + N) + 1;
             auto visit_at = [&](uint32_t k, const V3 &ro, const V3 &rd) {
-                const uint4 zr = zts[k];
-                const F2 z = flat_zrow(u2f(zr.x), u2f(zr.y), u2f(zr.z), u2f(zr.w), ro, rd);
+                F2 z;
+                if constexpr (ZROW) {
+                    if (k != WALL) z = F2{ zq.o[zrow_slot(k)], zq.d[zrow_slot(k)] };
+                    else { const uint4 zr = zts[k]; z = flat_zrow(u2f(zr.x), u2f(zr.y), u2f(zr.z), u2f(zr.w), ro, rd); }
+                } else {
+                    const uint4 zr = zts[k];
+                    z = flat_zrow(u2f(zr.x), u2f(zr.y), u2f(zr.z), u2f(zr.w), ro, rd);
+                }
                 const bool need = !flat_certain_miss(z.x, z.y, far);
                 DTOF_STAT(kStat); DTOF_STAT_WAVE(kStat + 2);
                 if (!need) DTOF_STAT(kStat + 1);

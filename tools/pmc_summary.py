@@ -17,7 +17,7 @@ import csv, glob, hashlib, json, os, re, sys
 from collections import defaultdict
 
 HERE = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-KERNEL_SOURCES = ("dtof_kernels.hip", "dtof_shade.h", "dtof_device.h", "dtof_kernels.h", "dtof_traverse.h", "dtof_flat_cull.h", "dtof_pair_walk.h", "dtof_pair_setup.h", "dtof_sampling.h", "dtof_shading.h", "dtof_math.h", "dtof_scene.h", "dtof_render.hip", "dtof_host.h", "Makefile")   # the frame path (which kernel a frame launches, and how) with its declarations, not the C ABI's files
+KERNEL_SOURCES = ("dtof_kernels.hip", "dtof_shade.h", "dtof_device.h", "dtof_kernels.h", "dtof_traverse.h", "dtof_flat_cull.h", "dtof_pair_walk.h", "dtof_zrow_mfma.h", "dtof_pair_setup.h", "dtof_sampling.h", "dtof_shading.h", "dtof_math.h", "dtof_scene.h", "dtof_render.hip", "dtof_host.h", "Makefile")   # the frame path (which kernel a frame launches, and how) with its declarations, not the C ABI's files
 
 
 def kernel_sources_sha16(root=HERE):

@@ -53,19 +53,21 @@ def classify(op, args):
 
 def model(asm_lines, symbol):
     start = next(i for i, l in enumerate(asm_lines) if l.startswith(symbol + ":"))
-    n = collections.Counter(); cyc = collections.Counter(); salu = 0
+    n = collections.Counter(); cyc = collections.Counter(); salu = mfma = 0
     for l in asm_lines[start + 1:]:
         if l.startswith(".Lfunc_end"):
             break
         m = re.match(r"\s+(v_[a-z0-9_]+)\s*(.*)", l)
-        if m:
+        if m and m.group(1).startswith("v_mfma_"):   # the matrix pipe's: a class of its own, outside the VALU issue price
+            mfma += 1
+        elif m:
             cl, c = classify(m.group(1), m.group(2).split(";")[0])
             n[cl] += 1; cyc[cl] += c
         elif re.match(r"\s+s_[a-z0-9_]+", l) and not re.match(r"\s+s_(waitcnt|nop|endpgm|barrier|sleep)", l):
             salu += 1
     total_n, total_c = sum(n.values()), sum(cyc.values())
     top = sorted(cyc.items(), key=lambda kv: -kv[1])
-    return {"valu_static": total_n, "salu_static": salu, "avg_cycles_per_valu": round(total_c / total_n, 4),
+    return {"valu_static": total_n, "salu_static": salu, "mfma_static": mfma, "avg_cycles_per_valu": round(total_c / total_n, 4),
             "share_of_cycles": {"fast (2.25)": round(cyc["fast"] / total_c, 4),
                                 "slow (4.1)": round(sum(v for k, v in cyc.items() if k.startswith("slow")) / total_c, 4),
                                 "quarter (8.2)": round(cyc["quarter"] / total_c, 4)},
