@@ -826,6 +826,16 @@ int dtof_pair_setup_lanes(dtof_scene *scene, int form, uint32_t seed, uint32_t s
  * launched or written, for a form the scene does not meet -- no half-float nodes (forms 1 to 4), an analytic shape, a stack deeper than 64 entries or a TLAS of more
  * than 16 nodes for form 2 (forms 1 to 3) -- and for n above 2^24; non-finite ray components are taken as they are. */
 int dtof_tree_query(dtof_scene *scene, int form, int any, uint32_t n, const float *rays8, float *out3, int32_t *ids3);
+/* The tree walk that the FUSED shade kernels run themselves, over arrays, with the instance memo and the stack columns laid out as those kernels lay them out.
+ * form 0 (classic): one wave per block, float nodes, every shape's code, the blob staged in LDS when it is at most 16 KiB; 1 (classic_rect): form 0 with rectangle
+ * code only; 2 (resident): blocks of `waves` waves (8, 12 or 16) whose LDS holds the TLAS as four planes of node pieces and the scene's record block; 3
+ * (resident_16): form 2 with 16-bit child references and 16-bit stack columns; 4 (resident_half): form 2 with two planes of half-float node pieces; 5
+ * (resident_half_16): form 4 with the 16-bit references.  `waves` is read by forms 2 to 5 only.  Rays and answers as dtof_tree_query.  DTOF_ERR_INVALID, before
+ * anything is launched or written and with a message that begins "dtof_fused_query:", for a form the scene does not meet -- a shape other than a rectangle (form
+ * 1); no resident layout (a blob above 16 KiB whose record block is within 24 KiB), a mesh behind a BLAS, more than 1 024 nodes (forms 2, 3), no half-float nodes or
+ * a node count outside 1 025 .. 2 048 (forms 4, 5), 0x7fff objects or more (forms 3, 4, 5), an LDS total above the device's limit, `waves` other than 8, 12 or 16 --
+ * for n above 2^24 and for null arguments; non-finite ray components are taken as they are. */
+int dtof_fused_query(dtof_scene *scene, int form, int waves, int any, uint32_t n, const float *rays8, float *out3, int32_t *ids3);
 /* The surface-interaction fill (PreliminaryIntersection::compute_surface_interaction, include/mitsuba/render/interaction.h:675-701, through the shapes' and the
  * instance's own, and Interaction::offset_p, :161-165) over arrays of HITS, through the instantiations and argument patterns of it that the kernels of a frame
  * carry.  A hit is given, not traced: in10 = o[3], d[3], time, t, b1, b2 (prim_uv); ids3 = object, shape in its group, primitive -- a triangle by its index IN THE

@@ -189,6 +189,7 @@ SIGNATURES = {
     "dtof_flat_query_zrow": (_int, [_vp, _int, _u32, _vp, _vp, _vp, _vp]),
     "dtof_pair_setup_lanes": (_int, [_vp, _int, _u32, _u32, _u64, _u64, _vp]),
     "dtof_tree_query": (_int, [_vp, _int, _int, _u32, _vp, _vp, _vp]),
+    "dtof_fused_query": (_int, [_vp, _int, _int, _int, _u32, _vp, _vp, _vp]),
     "dtof_surface_eval": (_int, [_vp, _int, _int, _u32, _vp, _vp, _vp]),
     # component evaluation
     "dtof_eval_component": (_int, [_int, _vp, _int, _vp, _int, _vp, _int, _u32]),

@@ -853,6 +853,18 @@ class Scene:
         non-finite components are taken as they are."""
         return self._ray_query("dtof_tree_query", rays8, any, "ids", self.TREE_FORMS, form)
 
+    FUSED_FORMS = {"classic": 0, "classic_rect": 1, "resident": 2, "resident_16": 3, "resident_half": 4, "resident_half_16": 5}
+
+    def fused_query(self, rays8, form=0, waves=8, any=False):
+        """The tree walk of the fused shade kernels over an (n, 8) array of rays o, d, time, maxt (dtof_fused_query), with the instance memo and the stack columns in
+        those kernels' layout.  form: 0 / "classic", 1 / "classic_rect", 2 / "resident", 3 / "resident_16", 4 / "resident_half", 5 / "resident_half_16"; waves: 8, 12 or
+        16 waves per block for the resident forms.  Results as tree_query.  A form the scene does not meet, another wave count and more than 2^24 rays raise DtofError."""
+        rays = np.ascontiguousarray(rays8, np.float32).reshape(-1, 8)
+        out, ids = np.zeros((len(rays), 3), np.float32), np.zeros(len(rays) if any else (len(rays), 3), np.int32)
+        _check(_abi._lib().dtof_fused_query(self._h, int(self.FUSED_FORMS.get(form, form)), int(waves), 1 if any else 0, len(rays), rays.ctypes.data,
+                                            None if any else out.ctypes.data, ids.ctypes.data))
+        return ids if any else {"t": out[:, 0], "u": out[:, 1], "v": out[:, 2], "ids": ids}
+
     SURFACE_FORMS = {"mesh": 0, "rect": 1, "rect_memo_regs": 2, "rect_memo_lds": 3, "one_wall": 4, "mesh_memo_regs": 5}
 
     def surface_eval(self, in10, ids3, form=0, want_frame=True):

@@ -5,6 +5,7 @@
 #include "dtof_flat_query.h"
 #include "dtof_pair_setup.h"
 #include "dtof_tree_query.h"
+#include "dtof_fused_query.h"
 #include "dtof_surface_query.h"
 #include <cmath>
 #include <memory>
@@ -401,6 +402,30 @@ int dtof_tree_query(dtof_scene *sc, int form, int any, uint32_t n, const float *
         ensure_device(sc);
         round_trip({ { rays8, (size_t) n * 32 } }, { { out3, any ? 0 : (size_t) n * 12, 4 }, { ids3, (size_t) n * (any ? 1 : 3) * 4 } }, [&](void *const *in, void *const *out) {
             launch_tree_query(sc->d_blob.p, q, form, any != 0, (const float *) in[0], (float *) out[0], (int32_t *) out[1], n, nullptr);
+        });
+    });
+}
+
+// trace_scene over arrays as the FUSED shade kernels run it themselves (dtof_fused_query.hip): the classic launch's walk and the resident stage's, with the instance memo
+// and the stack columns in k_shade's layout.  The refusals are the plan's own conditions (scene_traits, flat_choice, plan_frame), made before anything is launched or written.
+int dtof_fused_query(dtof_scene *sc, int form, int waves, int any, uint32_t n, const float *rays8, float *out3, int32_t *ids3) {
+    return guarded([&] {
+        if (!sc || (n && (!rays8 || !ids3 || (!any && !out3)))) throw std::runtime_error("dtof_fused_query: null argument");
+        if (n > (1u << 24)) throw std::runtime_error("dtof_fused_query: more than 2^24 rays in one call");
+        if (sc->blob.size() < sizeof(BlobHeader)) throw std::runtime_error("dtof_fused_query: the scene has no device blob");
+        const SceneTraits t = scene_traits(*sc);
+        const BlobHeader *bh = (const BlobHeader *) sc->blob.data();
+        const DShape *shp = (const DShape *) (sc->blob.data() + bh->off_shapes);
+        bool only_rects = true;
+        for (uint32_t i = 0; i < bh->n_shapes; ++i) only_rects &= shp[i].kind == SHAPE_RECT;
+        // the memo object as flat_choice picks it for a fused frame: exactly one instance
+        const FusedQueryScene q { (uint32_t) sc->blob.size(), t.stack_depth, t.n_nodes, t.n_objects, t.small_off, t.small_words, flat_choice(t, true, true, false).memo_obj,
+                                  t.has_tris, t.has_blas, t.has_nodes16, t.resident_layout, only_rects };
+        const std::string why = fused_query_refusal(form, (uint32_t) waves, q, form >= 2 && form < kFusedQueryForms ? device_lds_limit() : 0u);
+        if (!why.empty()) throw std::runtime_error("dtof_fused_query: " + why);
+        ensure_device(sc);
+        round_trip({ { rays8, (size_t) n * 32 } }, { { out3, any ? 0 : (size_t) n * 12, 4 }, { ids3, (size_t) n * (any ? 1 : 3) * 4 } }, [&](void *const *in, void *const *out) {
+            launch_fused_query(sc->d_blob.p, q, form, (uint32_t) waves, any != 0, (const float *) in[0], (float *) out[0], (int32_t *) out[1], n, nullptr);
         });
     });
 }
