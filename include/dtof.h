@@ -651,6 +651,61 @@ int dtof_denoise_temporal_async(dtof_scene *scene, const dtof_temporal_buffers *
 /* The same with HOST pointers and no scene: uploads, runs, downloads and synchronises once. */
 int dtof_denoise_temporal(const dtof_temporal_buffers *buffers, int n_planes, int32_t width, int32_t height, const dtof_temporal_params *params);
 
+/* ---------------------------------------------------------------- denoised renders on the device (opt-in)
+ * The denoised images and the denoised velocity map from ONE traversal per pass, with nothing but the requested results crossing to the host.  A pass renders the
+ * float64 film, the moment film and the aov film of "p:position,n:sh_normal" from the same lanes (k_aov, the bounce loop, the splat stage); the films of the passes
+ * (seeds seed, seed + 1, ...) are developed and summed in float32 as dtof_render_velocity_map_f64 sums them, the moment and aov cells accumulate in double.  Then
+ *   INPUTS  (tests/denoise_inputs_ref.py is the definition; K planes, pixel i, Wd = (W == 0 ? 1 : W) of the cell film in question)
+ *     colour    IMAGE: sum / (float) n_passes per channel.  TOF: ((0.2126f r + 0.7152f g) + 0.0722f b) * (float) exposure_time of that mean, replicated into 3 channels
+ *     variance  mean = SY_k / Wd, m2 = SYY_k / Wd of the moment film; v = (m2 - mean * mean) / n_samples, in TOF mode times (exposure_time * exposure_time);
+ *               n_samples = (double) n_paths / (double) n_pixels of the traversals.  All in double
+ *     guides    position c = (float) (S_c / Wd), normal likewise, of the aov film, the division in double
+ *     sigma_position, if automatic: 1 % of the largest per-axis extent (double) max - (double) min of the positions whose three words are finite; 1.0 if that is not > 0
+ *   DENOISE  dtof_denoise_async's launches over those arguments (levels, sigma_normal, sigma_luminance of `params`; its sigma_position unless automatic)
+ *   MAP      TOF mode: the noisy map is dtof_velocity_map_async's of the sum; the denoised map the same arithmetic from the ratio onwards over channel 0 of the
+ *            denoised planes (doubles), i.e. calc_velocity_from_homo_heteros of doppler_tutorials/src/utils/image_utils.py:170-199 of those planes
+ * The colour of this route is the FLOAT64 film's image: every pass is dtof_render_variants_f64's image, rounded to float32 once before the float32 pass sum, as in
+ * dtof_render_velocity_map_f64.  (Denoising the images of dtof_render_variants on the host reads the float32 film instead.)  An alpha plane is rendered into the float64
+ * film of an rgba scene as always, and is neither returned nor denoised.
+ * `outputs`: HOST pointers, each NULL or an array of the stated size; only what is named is copied, after one wait at the end.  K = the number of colour planes. */
+typedef struct dtof_denoised_outputs {
+    double *denoised;            /* required: [K][H][W][3], the denoised colour */
+    double *denoised_map;        /* TOF mode: required, [H][W]; IMAGE mode: not read */
+    float *sum;                  /* [K][H][W][3]: the float32 sum of the developed passes */
+    double *moments;             /* [dtof_moment_planes(K)][H][W]: the raw (undivided) moment planes of dtof_render_moments */
+    double *aovs;                /* [7][H][W]: the raw aov planes of dtof_render_aovs for "p:position,n:sh_normal" (weight, position, normal) */
+    float *colour;               /* [K][H][W][3]: the denoiser's colour argument */
+    double *variance;            /* [K][H][W]: ... its variance argument */
+    float *normal, *position;    /* [H][W][3]: ... its guides */
+    double *denoised_variance;   /* [K][H][W] */
+    double *noisy_map;           /* TOF mode: [H][W]; IMAGE mode: not read */
+    double *sigma_position;      /* one double: the sigma_position the denoiser ran with */
+} dtof_denoised_outputs;
+#define DTOF_DENOISE_INPUTS_IMAGE 0
+#define DTOF_DENOISE_INPUTS_TOF   1
+/* The INPUTS stage alone over DEVICE pointers: d_rgb_sum [n_planes][n_pixels][3] float32 as dtof_develop_accumulate_async leaves it, d_moment_cells and d_aov_cells
+ * n_pixels cells of 32 doubles (cell[p] = raw plane p; the aov cells: weight, position, normal) -> d_colour [n_planes][n_pixels][3] float32, d_variance
+ * [n_planes][n_pixels] double, d_normal / d_position [n_pixels][3] float32, and -- if d_extent_or_null is given -- 8 words: the per-axis min (3 float32) and max
+ * (3 float32) of the positions whose three words are finite (+inf / -inf without one), their count (uint32) and 0.  One launch, three with the extent, on the
+ * scene's stream; no atomics, no host wait.  DTOF_ERR_INVALID before any HIP call: a null pointer (but d_extent_or_null), a mode other than the two, n_planes outside
+ * 1 .. 4, n_passes == 0, n_samples not finite or not > 0, in TOF mode an exposure_time not finite or not > 0, n_pixels < 0 or > 2^31 - 1, a misaligned buffer, an output
+ * that overlaps an input or another output. */
+int dtof_denoise_inputs_async(dtof_scene *scene, int mode, const float *d_rgb_sum, const double *d_moment_cells, const double *d_aov_cells, int n_planes,
+                              int64_t n_pixels, uint32_t n_passes, double n_samples, double exposure_time, float *d_colour, double *d_variance, float *d_normal,
+                              float *d_position, uint32_t *d_extent_or_null);
+/* IMAGE mode: the images of `variants_or_null` / n_variants (NULL / 0: the integrator's own pair, K = 1) and their jointly denoised versions.  sigma_position_auto != 0:
+ * params->sigma_position is not read.  stats sums the passes: n_paths = W * H * spp * n_passes, one traversal per pass.
+ * DTOF_ERR_INVALID before any device call, with no output touched: a null scene, params, outputs or outputs->denoised; n_passes == 0; more than four variants (or a
+ * negative count, or a count without variants); variants under an integrator other than dopplertofpath; levels outside 1 .. 6; a sigma that dtof_denoise refuses
+ * (sigma_position only when it is read); a scene without a sensor or with a film wider or higher than 65535 pixels. */
+int dtof_render_denoised(dtof_scene *scene, uint32_t seed, uint32_t spp, uint32_t n_passes, const dtof_modulation *variants_or_null, int n_variants,
+                         const dtof_denoise_params *params, int sigma_position_auto, const dtof_denoised_outputs *outputs, dtof_render_stats *stats);
+/* TOF mode: the four films of dtof_velocity_map_variants for the two `offsets` (planes: (0, o0), (0, o1), (1, o0), (1, o1)), denoised jointly as ToF planes, the noisy
+ * velocity map and the map of the denoised planes.  Refused like dtof_render_denoised, and: null offsets or outputs->denoised_map; exposure_time or w_g_mhz not
+ * finite or not > 0; an integrator other than dopplertofpath. */
+int dtof_render_velocity_map_denoised(dtof_scene *scene, uint32_t seed, uint32_t spp, uint32_t n_passes, const float offsets[2], double exposure_time, double w_g_mhz,
+                                      const dtof_denoise_params *params, int sigma_position_auto, const dtof_denoised_outputs *outputs, dtof_render_stats *stats);
+
 /* ---------------------------------------------------------------- adaptive sampling (opt-in)
  * A dense base pass, then further passes only over the pixels whose ESTIMATED error is still above a tolerance; the estimate comes from the moment film of the passes so
  * far.  The reference renders every pixel in every pass (render_multi_pass, doppler_tutorials/src/program_runner.py:11-31); this has no counterpart there.

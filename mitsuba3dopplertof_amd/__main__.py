@@ -14,7 +14,7 @@ plugins this library implements:
         the per-pixel moment film of one traversal per pass (weight, mean, m2, cross: Scene.render_moments), written with np.savez
     python -m mitsuba3dopplertof_amd scene.xml --aovs dd:depth,nn:sh_normal [--passes N] [--spp N] [-o out.npz]
         the geometry channels of the reference's `aov` integrator along the scene integrator's camera rays (Scene.render_aovs), written with np.savez
-    python -m mitsuba3dopplertof_amd scene.xml --denoise [--denoise-levels 5] [--denoise-sigma n,x,l] [--velocity-map 0,0.25] [--spp N] [-o out.exr|.npy]
+    python -m mitsuba3dopplertof_amd scene.xml --denoise [--denoise-route host|device] [--denoise-levels 5] [--denoise-sigma n,x,l] [--velocity-map 0,0.25] [--spp N] [-o out.exr|.npy]
         the image (or, with --velocity-map and two offsets, the velocity map) with the joint variance-guided a-trous denoiser behind the films (Denoiser): the
         denoised result goes to the output file, the noisy one to its _noisy sibling
     python -m mitsuba3dopplertof_amd scene.xml --adaptive TOL [--adaptive-mode image|velocity] [--base-passes 1] [--max-passes 4] [--variants ...] [--velocity-map 0,0.25]
@@ -67,6 +67,9 @@ def parser():
                     help="denoise the image, or the four films of a --velocity-map of two offsets, guided by the moment film's variance and the aov film's position and "
                          "shading normal (three traversals); the noisy result is written to the output's _noisy sibling")
     ap.add_argument("--denoise-levels", type=int, default=None, metavar="L", help="--denoise: a-trous levels, 1 .. 6 (default 5)")
+    ap.add_argument("--denoise-route", default="host", choices=("host", "device"),
+                    help="--denoise: host renders the images, the moment film and the aov film in three traversals and forms the denoiser's arguments with numpy; "
+                         "device renders the three films in ONE traversal and keeps everything up to the result on the GPU (the float64 film's images)")
     ap.add_argument("--denoise-sigma", default=None, metavar="N,X,L",
                     help="--denoise: sigma_normal,sigma_position,sigma_luminance (default 0.1, 1 %% of the scene's extent, 4)")
     ap.add_argument("--adaptive", type=float, default=None, metavar="TOL",
@@ -149,6 +152,8 @@ def check_denoise_args(ap, args):
         ap.error("--denoise filters an image or a velocity map: --moments and --aovs write the films it is guided by, run them separately")
     if args.stripes > 0 or int(os.environ.get("WORLD_SIZE", "1")) > 1:
         ap.error("--denoise is a single-GPU feature: it cannot be combined with --stripes or a multi-GPU launch")
+    if args.film == "float64" and args.denoise_route == "device":
+        ap.error("--denoise-route device renders the float64 film already: do not combine it with --film float64")
     if args.film == "float64":
         ap.error("--denoise reads the float32 images: do not combine it with --film float64")
     if args.offsets is not None:
@@ -354,7 +359,10 @@ def velocity_map(args, scene):
     single, n_pass = _passes(args.spp or scene.info()["sample_count"])
     t0 = time.time()
     os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
-    if args.denoise:   # the host route: the films have to reach the denoiser before the ratio is formed
+    if args.denoise and args.denoise_route == "device":   # one traversal per pass, the films, the denoiser and both maps on the GPU
+        noisy, v = scene.render_velocity_map_denoised(n_pass, single, offsets, exposure_time=args.exposure_time, w_g=args.w_g, **args.denoise_kw)
+        np.save(_noisy_sibling(out), noisy)
+    elif args.denoise:   # the host route: three traversals per pass, the films reach the denoiser through numpy
         from mitsuba3dopplertof_amd.harness import velocity_map_denoised
         noisy, v = velocity_map_denoised(scene, n_pass, single, offsets, exposure_time=args.exposure_time, w_g=args.w_g, **args.denoise_kw)
         np.save(_noisy_sibling(out), noisy)
@@ -388,8 +396,8 @@ def main(argv=None):
         check_velocity_map_args(ap, args)
     if args.denoise:
         args.denoise_kw = check_denoise_args(ap, args)
-    elif args.denoise_levels is not None or args.denoise_sigma is not None:
-        ap.error("--denoise-levels and --denoise-sigma belong to --denoise")
+    elif args.denoise_levels is not None or args.denoise_sigma is not None or args.denoise_route != "host":
+        ap.error("--denoise-levels, --denoise-sigma and --denoise-route belong to --denoise")
     if args.adaptive is not None:
         check_adaptive_args(ap, args)
     elif args.adaptive_mode != "image" or args.base_passes != 1 or args.max_passes != 4:
@@ -434,7 +442,8 @@ def main(argv=None):
             if img is None:
                 return 0
         elif args.denoise:
-            d = scene.render_denoised(seed=args.seed, spp=args.spp, **args.denoise_kw)
+            render = scene.render_denoised_device if args.denoise_route == "device" else scene.render_denoised
+            d = render(seed=args.seed, spp=args.spp, **args.denoise_kw)
             img, noisy = d["denoised"], d["image"]
         else:
             img = scene.render(seed=args.seed, spp=args.spp, offsets=offsets, variants=triples, film=args.film)

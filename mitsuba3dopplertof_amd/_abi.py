@@ -58,6 +58,11 @@ class _TemporalBuffers(C.Structure):   # dtof_temporal_buffers
                                                 "o_colour", "o_variance", "o_length", "o_colour_f32")]
 
 
+class _DenoisedOutputs(C.Structure):   # dtof_denoised_outputs
+    _fields_ = [(name, C.c_void_p) for name in ("denoised", "denoised_map", "sum", "moments", "aovs", "colour", "variance", "normal", "position",
+                                                "denoised_variance", "noisy_map", "sigma_position")]
+
+
 class _AdaptiveParams(C.Structure):   # dtof_adaptive_params
     _fields_ = [("mode", C.c_int32), ("n_pairs", C.c_int32), ("homodyne", C.c_int32 * 2), ("heterodyne", C.c_int32 * 2),
                 ("tol", C.c_double), ("floor", C.c_double), ("exposure_time", C.c_double), ("w_g_mhz", C.c_double)]
@@ -148,6 +153,10 @@ SIGNATURES = {
     # denoiser, temporal stage
     "dtof_denoise_temporal_async": (_int, [_vp, _vp, _int, _i32, _i32, _vp]),
     "dtof_denoise_temporal": (_int, [_vp, _int, _i32, _i32, _vp]),
+    # denoised renders on the device
+    "dtof_denoise_inputs_async": (_int, [_vp, _int, _vp, _vp, _vp, _int, _i64, _u32, _f64, _f64, _vp, _vp, _vp, _vp, _vp]),
+    "dtof_render_denoised": (_int, [_vp, _u32, _u32, _u32, _vp, _int, _vp, _int, _vp, _st]),
+    "dtof_render_velocity_map_denoised": (_int, [_vp, _u32, _u32, _u32, _vp, _f64, _f64, _vp, _int, _vp, _st]),
     # adaptive sampling
     "dtof_adaptive_select": (_int, [_vp, _i64, _int, _vp, _u32, _vp, _vp, _vp, _vp]),
     "dtof_render_pixels": (_int, [_vp, _u32, _u32, _vp, _u32, _vp, _int, _int, _vp, _vp, _st]),

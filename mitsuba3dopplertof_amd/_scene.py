@@ -5,7 +5,7 @@ import math
 import numpy as np
 
 from . import _abi
-from ._abi import MAX_VARIANTS, DtofError, _AdaptiveParams, _check, _Info, _ptr, _release, _Stats
+from ._abi import MAX_VARIANTS, DtofError, _AdaptiveParams, _check, _DenoisedOutputs, _DenoiseParams, _Info, _ptr, _release, _Stats
 from ._denoiser import Denoiser
 
 
@@ -428,8 +428,8 @@ class Scene:
         """The images of render(variants=...) and their jointly denoised versions (Denoiser), guided by what the moment film and the aov film provide.  THREE
         renders with the same seeds seed, seed + 1, ...: render() for the images (the float32 mean of the passes), render_moments for the variance of every
         variant's luminance estimate -- (m2_Y - mean_Y^2) / (samples per pixel x passes), harness.moment_statistics -- and render_aovs("p:position,n:sh_normal") for
-        the guides; then ONE Denoiser call over all variants, which therefore share their weights.  That these are three traversals of the scene is accepted for
-        now: fusing them on the device is a later step.  `variants`: up to four (hetero_frequency, hetero_offset) pairs; None: the integrator's own pair.
+        the guides; then ONE Denoiser call over all variants, which therefore share their weights.  These are three traversals of the scene with numpy between the films and
+        the denoiser, the host route; render_denoised_device is the device route: one traversal per pass, everything up to the result on the GPU.  `variants`: up to four (hetero_frequency, hetero_offset) pairs; None: the integrator's own pair.
         `denoiser_kw`: levels and the sigmas of Denoiser.  Returns a dict: "image" (K, H, W, 3 | 4) float32 -- (H, W, 3 | 4) without variants --, "denoised"
         float64 (the first three channels: an alpha plane is not denoised), "variance" and "denoised_variance" (K, H, W) -- (H, W) -- float64, and "denoiser"."""
         from .harness import moment_statistics
@@ -455,6 +455,75 @@ class Scene:
             variance = variance[0]
         denoised, denoised_variance = den(noisy, normals=guides["n"], position=guides["p"], variance=variance)
         return {"image": image, "denoised": denoised, "variance": variance, "denoised_variance": denoised_variance, "denoiser": den}
+
+    def _denoised_call(self, entry, head, k, tof, details, denoiser_kw):
+        """dtof_render_denoised / dtof_render_velocity_map_denoised: `head` is the entry's arguments between the scene and `params` -> the dict of every array the
+        call was asked for (details: the intermediate films as well) and "sigma_position" """
+        kw = dict(levels=5, sigma_normal=0.1, sigma_position=None, sigma_luminance=4.0)
+        unknown = set(denoiser_kw) - set(kw)
+        if unknown:
+            raise DtofError("unknown denoiser arguments %s; known: %s" % (sorted(unknown), ", ".join(kw)))
+        kw.update(denoiser_kw)
+        auto = kw["sigma_position"] is None
+        prm = _DenoiseParams(int(kw["levels"]), float(kw["sigma_normal"]), 1.0 if auto else float(kw["sigma_position"]), float(kw["sigma_luminance"]))
+        w, h = self.size
+        arrays = {"denoised": np.zeros((k, h, w, 3), np.float64), "denoised_variance": np.zeros((k, h, w), np.float64),
+                  "sum": np.zeros((k, h, w, 3), np.float32), "variance": np.zeros((k, h, w), np.float64), "sigma_position": np.zeros(1, np.float64)}
+        if tof:
+            arrays.update(denoised_map=np.zeros((h, w), np.float64), noisy_map=np.zeros((h, w), np.float64))
+        if details or tof:
+            arrays.update(colour=np.zeros((k, h, w, 3), np.float32))
+        if details:
+            arrays.update(moments=np.zeros((MOMENT_PLANES(k), h, w), np.float64), aovs=np.zeros((7, h, w), np.float64),
+                          normal=np.zeros((h, w, 3), np.float32), position=np.zeros((h, w, 3), np.float32))
+        out = _DenoisedOutputs(**{name: a.ctypes.data for name, a in arrays.items()})
+        self._timed(entry, self._h, *head, C.byref(prm), 1 if auto else 0, C.byref(out))
+        arrays["sigma_position"] = float(arrays["sigma_position"][0])
+        return arrays
+
+    def render_denoised_device(self, seed=0, spp=0, n_passes=1, variants=None, details=False, **denoiser_kw):
+        """render_denoised from ONE traversal per pass, on the device until the result (dtof_render_denoised): every pass renders the float64 film, the moment film
+        and the aov film of "p:position,n:sh_normal" from the same lanes; the pass mean, the variance, the guides, the automatic sigma_position, the denoiser and
+        nothing else run behind them on the GPU, and only the results cross to the host.  Same arguments; `denoiser_kw`: levels, sigma_normal, sigma_position (None:
+        1 % of the extent of the finite positions), sigma_luminance.  Returns the keys of render_denoised without "denoiser" and with "sigma_position", the one the
+        denoiser ran with.  The images are those of the FLOAT64 film -- render(film="float64") of every pass, summed in float32 and divided by the passes -- where
+        render_denoised reads the float32 film; "image" has three channels (an alpha plane is neither returned nor denoised).  details=True adds "sum" (K, H, W, 3)
+        float32, "moments" and "aovs" (the raw planes of render_moments(raw=True) / render_aovs(raw=True), (P, H, W) and (7, H, W) float64) and the denoiser's arguments
+        "colour", "normal", "position".  last_stats sums the passes: one traversal each."""
+        if variants is not None and not 1 <= len(variants) <= MAX_VARIANTS:
+            raise DtofError("between 1 and 4 modulation variants can be denoised jointly")
+        if int(n_passes) < 1:
+            raise DtofError("n_passes must be at least 1")
+        var, var_ptr, n_var, _ = _variant_args(variants)
+        r = self._denoised_call(_abi._lib().dtof_render_denoised, (int(seed), int(spp), int(n_passes), var_ptr, n_var), max(n_var, 1), False, details, denoiser_kw)
+        image = r["sum"] / np.float32(n_passes)
+        out = {"image": image, "denoised": r["denoised"], "variance": r["variance"], "denoised_variance": r["denoised_variance"], "sigma_position": r["sigma_position"]}
+        if variants is None:
+            out.update({name: out[name][0] for name in ("image", "denoised", "variance", "denoised_variance")})
+        if details:
+            out.update({name: r[name] for name in ("sum", "moments", "aovs", "colour", "normal", "position")})
+        return out
+
+    def render_velocity_map_denoised(self, n_passes, spp, offsets=(0.0, 0.25), exposure_time=0.0015, w_g=30, seed=0, details=False, **denoiser_kw):
+        """harness.velocity_map_denoised from ONE traversal per pass, on the device until the result (dtof_render_velocity_map_denoised): the four films (0, o0),
+        (0, o1), (1, o0), (1, o1) of the two `offsets`, the moment film and the aov film from the same lanes; the ToF planes, their variances, the guides, the denoiser
+        and both maps on the GPU.  Passes of `spp` samples with seeds seed, seed + 1, ...  Returns (noisy map (H, W), denoised map (H, W)) float64 -- bit for bit
+        calc_velocity_from_homo_heteros of the ToF planes and of the denoised planes left in `denoise_details`: "homodyne", "heterodyne" (float32 ToF images),
+        "denoised_homodyne", "denoised_heterodyne", "variance", "denoised_variance", "sigma_position", and with details=True "sum", "moments", "aovs", "colour",
+        "normal", "position" as render_denoised_device returns them.  The films are the FLOAT64 film's, as in render_velocity_map(film="float64")."""
+        off = np.ascontiguousarray([float(o) for o in offsets], dtype=np.float32)
+        if len(off) != 2:
+            raise DtofError("a denoised velocity map takes two offsets: the four films of one traversal")
+        if int(n_passes) < 1:
+            raise DtofError("n_passes must be at least 1")
+        r = self._denoised_call(_abi._lib().dtof_render_velocity_map_denoised, (int(seed), int(spp), int(n_passes), off.ctypes.data, float(exposure_time), float(w_g)),
+                                4, True, details, denoiser_kw)
+        tof, den = r["colour"][..., 0], r["denoised"][..., 0]
+        self.denoise_details = {"homodyne": list(tof[:2]), "heterodyne": list(tof[2:]), "denoised_homodyne": list(den[:2]), "denoised_heterodyne": list(den[2:]),
+                                "variance": r["variance"], "denoised_variance": r["denoised_variance"], "sigma_position": r["sigma_position"]}
+        if details:
+            self.denoise_details.update({name: r[name] for name in ("sum", "moments", "aovs", "colour", "normal", "position")}, denoised=r["denoised"])
+        return r["noisy_map"], r["denoised_map"]
 
     @property
     def aovs(self):

@@ -1,11 +1,13 @@
 // dtof_abi_films.hip -- the C ABI (include/dtof.h) of rendering: every entry that renders into a film (the caller's device film, the library's own float32 / float64
-// film, the moment and aov cells, lane dumps), develops one, reconstructs the radial-velocity map or denoises, and dtof_async_collect.  All of them end in render_rows
+// film, the moment and aov cells, lane dumps), develops one, reconstructs the radial-velocity map or denoises -- the denoised renders that do all of that from one
+// traversal among them -- and dtof_async_collect.  All of them end in render_rows
 // (dtof_render.hip) or in one of the launchers of the small kernel files.
 #include "dtof_host.h"
 #include "dtof_develop.h"
 #include "dtof_reconstruct.h"
 #include "dtof_depth.h"
 #include "dtof_denoise.h"
+#include "dtof_denoise_inputs.h"
 #include "dtof_temporal.h"
 #include "dtof_world_to_pixel.h"
 #include "dtof_moments.h"
@@ -950,6 +952,151 @@ int dtof_denoise_temporal(const dtof_temporal_buffers *b, int n_planes, int32_t 
                                             (double *) out[0], (double *) out[1], (float *) out[2], (float *) out[3] };
             launch_temporal(a, d, nullptr);
         });
+    });
+}
+
+// ---------------------------------------------------------------- denoised renders on the device (dtof_denoise_inputs.hip)
+int dtof_denoise_inputs_async(dtof_scene *sc, int mode, const float *d_rgb_sum, const double *d_moment_cells, const double *d_aov_cells, int n_planes, int64_t n_pixels,
+                              uint32_t n_passes, double n_samples, double exposure_time, float *d_colour, double *d_variance, float *d_normal, float *d_position,
+                              uint32_t *d_extent) {
+    return guarded([&] {
+        if (!sc) throw std::runtime_error("null argument");
+        const DenoiseInputsBuffers b { d_rgb_sum, d_moment_cells, d_aov_cells, d_colour, d_variance, d_normal, d_position, d_extent };
+        DenoiseInputsArgs a;
+        const std::string err = denoise_inputs_check(b, mode, n_planes, n_pixels, n_passes, n_samples, exposure_time, &a);
+        if (!err.empty()) throw std::runtime_error("dtof_denoise_inputs: " + err);
+        ensure_device(sc);
+        if (d_extent) sc->d_denoise_extent.ensure((size_t) (kMaxDenoiseExtentBlocks + 1) * kDenoiseExtentWords);
+        launch_denoise_inputs(a, d_rgb_sum, d_moment_cells, d_aov_cells, d_colour, d_variance, d_normal, d_position, sc->stream);
+        if (d_extent) launch_position_extent(d_position, n_pixels, sc->d_denoise_extent.p, d_extent, sc->stream);
+        HIP_CHECK(hipGetLastError());
+    });
+}
+// What the two denoised renders are refused for before any device call (include/dtof.h lists it), beside what only the TOF entry takes
+static void check_denoised_call(const dtof_scene *sc, uint32_t n_passes, const dtof_modulation *variants, int n_variants, bool doppler_only, const dtof_denoise_params *params,
+                                bool sigma_auto, const dtof_denoised_outputs *out) {
+    if (!sc || !params || !out || !out->denoised) throw std::runtime_error("null argument");
+    if (n_passes == 0) throw std::runtime_error("n_passes must be at least 1");
+    if (n_variants < 0 || n_variants > kMaxOffsets) throw std::runtime_error("between 0 and 4 modulation variants can be denoised jointly");
+    if (n_variants > 0 && !variants) throw std::runtime_error("null argument: n_variants > 0 without variants");
+    need_doppler_for(sc, doppler_only || n_variants > 0);
+    // levels and the sigmas exactly as the denoiser's entries refuse them: denoise_check over a 1 x 1 image of every guide (an automatic sigma_position is not read)
+    alignas(8) static const char dummy[6][128] = {};
+    const DenoiseBuffers b { dummy[0], dummy[1], dummy[2], dummy[3], dummy[4], dummy[5] };
+    DenoiseArgs a;
+    const std::string err = denoise_check(b, std::max(n_variants, 1), 1, 1, false, params->levels, params->sigma_normal, sigma_auto ? 1.0 : params->sigma_position,
+                                          params->sigma_luminance, &a);
+    if (!err.empty()) throw std::runtime_error("dtof_denoise: " + err);
+    need_sensor(sc);
+    if (sc->host.sensor.crop_w > kMaxDenoiseExtent || sc->host.sensor.crop_h > kMaxDenoiseExtent) throw std::runtime_error("dtof_denoise: width and height must not exceed 65535");
+}
+// Both entries behind their checks.  mode: kDenoiseInputsImage | kDenoiseInputsTof; variants / n_variants: the request's (null / 0: the integrator's own pair);
+// exposure_time, w_g_mhz: read in TOF mode only.  Every buffer is sized before the first launch: nothing is freed while the passes are in flight.
+static void denoised_render(dtof_scene *sc, int mode, uint32_t seed, uint32_t spp, uint32_t n_passes, const dtof_modulation *variants, int n_variants, double exposure_time,
+                            double w_g_mhz, const dtof_denoise_params *params, bool sigma_auto, const dtof_denoised_outputs *out, dtof_render_stats *stats) {
+    const bool tof = mode == kDenoiseInputsTof;
+    const int32_t types[2] = { DTOF_AOV_POSITION, DTOF_AOV_SH_NORMAL };
+    AovArgs aov = aov_args(sc, types, 2);
+    ensure_device(sc);
+    sc->stop = false;
+    const HostSensor &se = sc->host.sensor;
+    const size_t px = (size_t) se.crop_w * se.crop_h, K = (size_t) std::max(n_variants, 1);
+    const int alpha = se.alpha ? 1 : 0, planes = moment_planes((int) K), aov_planes = 1 + (int) aov.n_channels;
+    const uint32_t spp_each = spp ? spp : sc->pp.sample_count;
+    const double n_samples = (double) ((uint64_t) px * spp_each * n_passes) / (double) px;   // n_paths / n_pixels of the traversals, as the host route forms it
+    int32_t hom[2] = { 0, 1 }, het[2] = { 2, 3 };
+    VelocityMapArgs va; memset(&va, 0, sizeof va);
+    if (tof) va = velocity_args(2, hom, het, n_passes, exposure_time, w_g_mhz);
+    const DenoiseInputsArgs ia = denoise_inputs_pack(mode, (int) K, (int64_t) px, n_passes, n_samples, exposure_time);
+    // the denoiser's arguments and results, the maps (doubles), then the float32 arrays
+    sc->d_film64.ensure(px * 4 * (K + alpha)); sc->d_vm_sum.ensure(px * 3 * K);
+    sc->d_moments.ensure(px * kMomentCell); sc->d_aov_cells.ensure(px * kMomentCell);
+    if (out->moments || out->aovs) sc->d_moment_planes.ensure(px * (size_t) (planes + aov_planes));
+    sc->d_denoise_io.ensure(K * px * 5 + 2 * px + (K * px * 3 + 6 * px + 1) / 2);
+    sc->d_denoise_extent.ensure((size_t) (kMaxDenoiseExtentBlocks + 1) * kDenoiseExtentWords);
+    double *const d_out_colour = sc->d_denoise_io.p, *const d_out_variance = d_out_colour + K * px * 3, *const d_variance = d_out_variance + K * px;
+    double *const d_noisy_map = d_variance + K * px, *const d_denoised_map = d_noisy_map + px;
+    float *const d_colour = (float *) (d_denoised_map + px), *const d_normal = d_colour + K * px * 3, *const d_position = d_normal + px * 3;
+    uint32_t *const d_extent = sc->d_denoise_extent.p + (size_t) kMaxDenoiseExtentBlocks * kDenoiseExtentWords;
+    {
+        DenoiseArgs sized; memset(&sized, 0, sizeof sized);
+        sized.width = se.crop_w; sized.height = se.crop_h; sized.n_planes = (int32_t) K; sized.has_variance = 1;
+        sc->d_denoise.ensure(denoise_scratch_doubles(sized));
+    }
+    const hipStream_t s = sc->stream;
+    double *const film = sc->d_film64.p;
+    HIP_CHECK(hipMemsetAsync(sc->d_moments.p, 0, px * kMomentCell * sizeof(double), s));   // once: the raw sums of the passes add up
+    HIP_CHECK(hipMemsetAsync(sc->d_aov_cells.p, 0, px * kMomentCell * sizeof(double), s));
+    aov.film = sc->d_aov_cells.p;
+    OwnFrames frames(sc);
+    for (uint32_t pass = 0; pass < n_passes; ++pass) {   // one traversal per pass: the float64 film, the moment cells and the aov cells from the same lanes
+        HIP_CHECK(hipMemsetAsync(film, 0, px * 4 * (K + alpha) * sizeof(double), s));
+        dtof_render_stats frame;
+        RenderRequest rq = rows_request(seed + pass, spp, 0, se.crop_h, &frame, true);
+        rq.film64 = film; rq.film64_stride = px * 4; rq.moments = sc->d_moments.p; rq.aov = &aov;
+        set_variants(rq, variants, n_variants);
+        render_rows(sc, rq);
+        launch_develop_accumulate(film, (int32_t) K, 0, sc->d_vm_sum.p, (int64_t) px, pass == 0, s);   // the alpha plane behind them is left out
+    }
+    launch_denoise_inputs(ia, sc->d_vm_sum.p, sc->d_moments.p, sc->d_aov_cells.p, d_colour, d_variance, d_normal, d_position, s);
+    HIP_CHECK(hipGetLastError());
+    double sigma_position = params->sigma_position;
+    if (sigma_auto) {   // a copy of a few words and one wait
+        launch_position_extent(d_position, (int64_t) px, sc->d_denoise_extent.p, d_extent, s);
+        HIP_CHECK(hipGetLastError());
+        uint32_t words[kDenoiseExtentWords];
+        HIP_CHECK(hipMemcpyAsync(words, d_extent, sizeof words, hipMemcpyDeviceToHost, s));
+        HIP_CHECK(hipStreamSynchronize(s));
+        sigma_position = denoise_sigma_position_of(words);
+    }
+    dtof_denoise_params used = *params;
+    used.sigma_position = sigma_position;
+    const DenoiseArgs da = denoise_args(d_colour, (int) K, se.crop_w, se.crop_h, d_variance, d_normal, d_position, &used, d_out_colour, d_out_variance);
+    launch_denoise(da, d_colour, d_variance, d_normal, d_position, d_out_colour, d_out_variance, sc->d_denoise.p, s);
+    HIP_CHECK(hipGetLastError());
+    if (tof) {
+        launch_velocity_map(sc->d_vm_sum.p, va, (int64_t) px, nullptr, nullptr, d_noisy_map, s);
+        launch_velocity_map_planes(d_out_colour, va, (int64_t) px, d_denoised_map, s);
+        HIP_CHECK(hipGetLastError());
+    }
+    const auto copy_out = [&](void *host, const void *dev, size_t bytes) { if (host) HIP_CHECK(hipMemcpyAsync(host, dev, bytes, hipMemcpyDeviceToHost, s)); };
+    copy_out(out->denoised, d_out_colour, K * px * 3 * sizeof(double));
+    copy_out(out->denoised_variance, d_out_variance, K * px * sizeof(double));
+    copy_out(out->sum, sc->d_vm_sum.p, K * px * 3 * sizeof(float));
+    copy_out(out->colour, d_colour, K * px * 3 * sizeof(float));
+    copy_out(out->variance, d_variance, K * px * sizeof(double));
+    copy_out(out->normal, d_normal, px * 3 * sizeof(float));
+    copy_out(out->position, d_position, px * 3 * sizeof(float));
+    if (tof) { copy_out(out->denoised_map, d_denoised_map, px * sizeof(double)); copy_out(out->noisy_map, d_noisy_map, px * sizeof(double)); }
+    if (out->moments) {
+        launch_develop_moments(sc->d_moments.p, planes, false, sc->d_moment_planes.p, (int64_t) px, s);
+        copy_out(out->moments, sc->d_moment_planes.p, px * planes * sizeof(double));
+    }
+    if (out->aovs) {
+        double *const d_planes = sc->d_moment_planes.p + px * (size_t) planes;
+        launch_develop_moments(sc->d_aov_cells.p, aov_planes, false, d_planes, (int64_t) px, s);
+        copy_out(out->aovs, d_planes, px * aov_planes * sizeof(double));
+    }
+    HIP_CHECK(hipGetLastError());
+    frames.collect(stats);
+    if (out->sigma_position) *out->sigma_position = sigma_position;
+}
+int dtof_render_denoised(dtof_scene *sc, uint32_t seed, uint32_t spp, uint32_t n_passes, const dtof_modulation *variants, int n_variants, const dtof_denoise_params *params,
+                         int sigma_position_auto, const dtof_denoised_outputs *outputs, dtof_render_stats *stats) {
+    return guarded([&] {
+        check_denoised_call(sc, n_passes, variants, n_variants, false, params, sigma_position_auto != 0, outputs);
+        denoised_render(sc, kDenoiseInputsImage, seed, spp, n_passes, variants, n_variants, 0.0, 0.0, params, sigma_position_auto != 0, outputs, stats);
+    });
+}
+int dtof_render_velocity_map_denoised(dtof_scene *sc, uint32_t seed, uint32_t spp, uint32_t n_passes, const float offsets[2], double exposure_time, double w_g_mhz,
+                                      const dtof_denoise_params *params, int sigma_position_auto, const dtof_denoised_outputs *outputs, dtof_render_stats *stats) {
+    return guarded([&] {
+        if (!offsets || !outputs || !outputs->denoised_map) throw std::runtime_error("null argument");
+        dtof_modulation variants[4];
+        if (dtof_velocity_map_variants(offsets, 2, variants) != DTOF_OK) throw std::runtime_error(g_last_error);
+        check_denoised_call(sc, n_passes, variants, 4, true, params, sigma_position_auto != 0, outputs);
+        check_velocity_scalars(n_passes, exposure_time, w_g_mhz);
+        denoised_render(sc, kDenoiseInputsTof, seed, spp, n_passes, variants, 4, exposure_time, w_g_mhz, params, sigma_position_auto != 0, outputs, stats);
     });
 }
 

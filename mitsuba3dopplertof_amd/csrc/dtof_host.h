@@ -110,7 +110,9 @@ struct dtof_scene {
     dtof::DevBuf<double> d_film64;   // the library's own float64 film (dtof_render_variants_f64, dtof_render_velocity_map_f64)
     dtof::DevBuf<double> d_moments, d_moment_planes;   // the moment film (dtof_render_moments) or the aov film (dtof_render_aovs) of the call: cells of kMomentCell doubles per pixel, and the dense planes copied out
     dtof::DevBuf<uint32_t> d_adaptive; dtof::DevBuf<double> d_adaptive_metric;   // dtof_render_adaptive / _pixels: count, the pass's list, its length and the selection's scratch; the metric map
+    dtof::DevBuf<double> d_aov_cells;   // the aov cells of a request that names the moment film as well (dtof_render_denoised, dtof_render_velocity_map_denoised): both cell films at once
     dtof::DevBuf<double> d_denoise;   // dtof_denoise_async: the guide records and the two sets of working planes
+    dtof::DevBuf<double> d_denoise_io; dtof::DevBuf<uint32_t> d_denoise_extent;   // the denoised renders: the denoiser's arguments and results; the extent reduction's block records and result
     dtof::DevBuf<float> d_vm_sum, d_vm_tof; dtof::DevBuf<double> d_vm_maps;   // dtof_render_velocity_map: the passes' sum, the ToF images, the per-pair maps and the combined map
     // the caller's device film as declared with dtof_scene_set_film_layout (0 = not declared: colour planes only, W * H * 4 apart)
     int32_t film_planes = 0; uint64_t film_plane_stride = 0;
@@ -171,7 +173,9 @@ struct RenderRequest {
     double *film64 = nullptr; uint64_t film64_stride = 0;   // ... or the float64 film, film64_stride doubles apart: the separate splat stage accumulates in double (dtof_film64.hip)
     double *moments = nullptr;                    // ... or the moment film (dtof_moments.h: cells of kMomentCell doubles), likewise the separate splat stage's; no alpha film
     const AovArgs *aov = nullptr;                 // ... or the geometry channels of the `aov` integrator (dtof_aov.h): k_aov takes the shade loop's place behind k_generate and
-                                                  // splats into aov->film itself, or -- with a lane dump -- writes the dumped lanes' channels to aov->values ([dump_n][n_channels])
+                                                  // splats into aov->film itself, or -- with a lane dump -- writes the dumped lanes' channels to aov->values ([dump_n][n_channels]).
+                                                  // Named TOGETHER with film64 and / or moments (rows form, no lane dump): one traversal, three films -- k_aov, then the bounce
+                                                  // loop in every pass, then the splat stage of film64 + moments; aov->film is then a cell film of its own
     dtof_render_stats *stats = nullptr;
     LaneDebug *lane_dump = nullptr; uint64_t dump_begin = 0, dump_n = 0;   // lane_dump != nullptr: evaluate only lanes [dump_begin, dump_begin + dump_n) and copy their records out
     bool deferred = false;                        // dtof_render_rows_async: timings by events, no counters read back, no synchronisation at the end

@@ -29,5 +29,7 @@ __device__ __forceinline__ float tof_of(const float *rgb_sum, int64_t n, int32_t
 
 // tof: [2 * n_pairs][n_pixels] float32 or null; pair_maps: [n_pairs][n_pixels] double or null; velocity: [n_pixels] double
 void launch_velocity_map(const float *rgb_sum, const VelocityMapArgs &a, int64_t n_pixels, float *tof, double *pair_maps, double *velocity, hipStream_t s);
+// ... of double ToF planes [2 * n_pairs][n_pixels][3], channel 0 of each (the denoiser's output of the replicated ToF films): the combined map alone
+void launch_velocity_map_planes(const double *planes, const VelocityMapArgs &a, int64_t n_pixels, double *velocity, hipStream_t s);
 
 }  // namespace dtof

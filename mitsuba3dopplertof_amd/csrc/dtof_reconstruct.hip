@@ -36,7 +36,28 @@ __global__ __launch_bounds__(kReconBlock) void k_velocity_map(const float *rgb_s
     if (tof)
         for (int32_t p = 0; p < 2 * a.n_pairs; ++p) tof[(int64_t) p * n + i] = tof_of(rgb_sum, n, p, i, a.n_passes, a.exposure_time);
 }
+
+// The same map of DOUBLE ToF planes: channel 0 of planes[2 * n_pairs][n][3], the denoiser's output of the replicated ToF films.  From the ratio onwards it is
+// k_velocity_map's arithmetic, i.e. harness.calc_velocity_from_homo_heteros of those planes; n_passes and exposure_time of `a` are not read.
+__global__ __launch_bounds__(kReconBlock) void k_velocity_map_planes(const double *planes, VelocityMapArgs a, int64_t n, double *velocity) {
+    const int64_t i = (int64_t) blockIdx.x * kReconBlock + threadIdx.x;
+    if (i >= n) return;
+    double num = 0.0, den = 0.0;
+    for (int32_t k = 0; k < a.n_pairs; ++k) {
+        const double hom = planes[((int64_t) a.hom[k] * n + i) * 3], het = planes[((int64_t) a.het[k] * n + i) * 3];
+        const double mag = fabs(hom);
+        const double ratio = mag > 0.0 ? het / hom : 0.0;
+        const double conf = mag + a.conf_floor;
+        num = num + ratio * conf; den = den + conf;
+    }
+    velocity[i] = velocity_of(num / den, a);
+}
 }  // namespace
+
+void launch_velocity_map_planes(const double *planes, const VelocityMapArgs &a, int64_t n_pixels, double *velocity, hipStream_t s) {
+    if (n_pixels <= 0) return;
+    hipLaunchKernelGGL(k_velocity_map_planes, dim3((uint32_t) ((n_pixels + kReconBlock - 1) / kReconBlock)), dim3(kReconBlock), 0, s, planes, a, n_pixels, velocity);
+}
 
 void launch_velocity_map(const float *rgb_sum, const VelocityMapArgs &a, int64_t n_pixels, float *tof, double *pair_maps, double *velocity, hipStream_t s) {
     if (n_pixels <= 0) return;

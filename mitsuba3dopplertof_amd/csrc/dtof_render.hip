@@ -502,6 +502,8 @@ FramePlan plan_frame(const dtof_scene *sc, const RenderRequest &rq) {
 void render_rows(dtof_scene *sc, const RenderRequest &rq) {
     need_sensor(sc);
     check_pixel_list(sc, rq);
+    // a guard for internal callers: no entry of the C ABI forms this request (a lane dump never splats, so the films such a request names would stay empty)
+    if (rq.aov && (rq.film64 || rq.moments) && rq.lane_dump) throw std::runtime_error("a lane dump cannot be combined with an aov request that names a film");
     ensure_device(sc);
     const FramePlan p = plan_frame(sc, rq);
     sc->last_plan_facts = 0; sc->last_splat = 0;
@@ -525,6 +527,9 @@ void render_rows(dtof_scene *sc, const RenderRequest &rq) {
     // An aov call runs k_aov where the integrator would run.  The integrator itself still runs in every pass that another pass follows: a later pass draws its lanes
     // from the streams the paths of the earlier one left behind (Sampler::advance, sampler.cpp:52-55), and the lanes of an aov render are the scene integrator's own.
     const bool aov = rq.aov != nullptr;
+    // An aov request that names the float64 film and / or the moment film as well: the integrator runs in EVERY pass behind k_aov and the splat stage fills those films
+    // from the same lanes -- one traversal, three films.  (The float32 film is not part of the combination: the splat stage writes it only when neither is named.)
+    const bool aov_films = aov && (rq.film64 != nullptr || rq.moments != nullptr);
     // The host runs at most two batches ahead of the device: dtof_cancel (Integrator::cancel, integrator.h:96-109) is looked at when a
     // batch is enqueued, so an unbounded run-ahead would leave nothing to cancel once the launches of a long render are queued.
     hipEvent_t batch_done[2] = { sc->take_event(), sc->take_event() };
@@ -545,13 +550,14 @@ void render_rows(dtof_scene *sc, const RenderRequest &rq) {
         }
         const uint32_t *qin = nullptr, *count_in = nullptr; uint32_t it = 0;
         bool fused_splat_done = false;   // the first-bounce kernel of this batch splatted its lanes itself
-        const bool integrate = !aov || (p.n_passes > 1 && pass + 1 < p.run_passes);
+        const bool integrate = !aov || (p.n_passes > 1 && pass + 1 < p.run_passes) || aov_films;
         if (aov && (!rq.lane_dump || dump_now)) {   // before the shade loop of a multi-pass render overwrites the camera rays
             AovArgs a = *rq.aov;
             if (a.values) a.values += (size_t) (b0 - p.first) * a.n_channels;
             t = tm.begin(kStageTrace, s); launch_aov(blob, blob_bytes, rp, q, a, stack_depth, p.launch, s); tm.end(kStageTrace, t, s);
         }
-        if (velocity && !aov) { t = tm.begin(kStageTrace, s); launch_velocity(blob, blob_bytes, rp, q, stack_depth, p.launch, s); tm.end(kStageTrace, t, s); }
+        // (k_velocity reads the camera rays k_aov read and leaves them alone; an aov request that names a film needs its results for the splat stage)
+        if (velocity && (!aov || aov_films)) { t = tm.begin(kStageTrace, s); launch_velocity(blob, blob_bytes, rp, q, stack_depth, p.launch, s); tm.end(kStageTrace, t, s); }
         for (; !velocity && integrate && p.iteration_runs(it); ++it) {
             if (it >= 8 && (it & 3) == 0) {   // unbounded depth: stop once every segment has drained
                 std::vector<uint32_t> alive(n_seg);
@@ -595,7 +601,7 @@ void render_rows(dtof_scene *sc, const RenderRequest &rq) {
                 for (int k = 0; k < rp.n_offsets; ++k)
                     HIP_CHECK(hipMemcpyAsync(rq.lane_planes + (size_t) k * rq.dump_n + (b0 - p.first), q.res + (size_t) k * q.capacity, (size_t) rp.n_lanes * sizeof(float4), hipMemcpyDeviceToHost, s));
             HIP_CHECK(hipStreamSynchronize(s));
-        } else if (!rq.lane_dump && !fused_splat_done && !aov) {
+        } else if (!rq.lane_dump && !fused_splat_done && (!aov || aov_films)) {
             t = tm.begin(kStageSplat, s);
             // a request may name BOTH the moment film and the float64 film: one traversal, two films (the alpha plane of an rgba scene then goes to the float64 film only)
             if (rq.moments) launch_splat_moments(rp, q, rq.moments, s);

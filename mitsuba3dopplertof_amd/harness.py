@@ -130,7 +130,8 @@ def velocity_map_denoised(scene, n_passes, spp, offsets=(0.0, 0.25), exposure_ti
     (m2_Y - mean_Y^2) / (passes x spp) times exposure_time^2 (Y of the moment film is a luminance with the coefficients of srgb_to_xyz rather than to_tof_image's
     rounded ones); the guides are the position and shading normal of the aov film.  The luminance of a ToF plane is the plane itself: it is handed to the denoiser
     REPLICATED into three channels (the weights (0.2126 + 0.7152) + 0.0722 sum to 1 up to rounding, and the three outputs are equal) and channel 0 of the result is
-    taken -- the C entry has no one-channel path.  These are three traversals per pass (images, moments, aovs); fusing them on the device is a later step.
+    taken -- the C entry has no one-channel path.  These are three traversals per pass (images, moments, aovs) with numpy between the films and the denoiser: the
+    host route.  Scene.render_velocity_map_denoised is the device route: one traversal per pass and everything up to the maps on the GPU.
     `denoiser_kw`: levels and the sigmas of Denoiser.  Returns (noisy map (H, W), denoised map (H, W)); the films, their variances, the guides and the Denoiser are
     left in scene.denoise_details."""
     from . import Denoiser
@@ -171,6 +172,19 @@ def run_scene_velocity_map_denoised(scene, total_spp, offsets=(0.0, 0.25), denoi
     scene.set_integrator(doppler_integrator_dict(hetero_frequency=0.0, hetero_offset=0.0, **integrator_kwargs))
     exposure_time, w_g = integrator_kwargs.get("exposure_time", 0.0015), integrator_kwargs.get("w_g", 30)
     return velocity_map_denoised(scene, n_pass, single, offsets, exposure_time, w_g, **(denoiser or {}))
+
+
+def run_scene_velocity_map_denoised_device(scene, total_spp, offsets=(0.0, 0.25), denoiser=None, details=False, **integrator_kwargs):
+    """run_scene_velocity_map_denoised with ONE traversal per pass and everything behind it on the GPU (Scene.render_velocity_map_denoised): the same integrator
+    dictionary, passes and seeds; the float64 film, the moment film and the aov film come from the same lanes, and only the maps (and what scene.denoise_details
+    holds) cross to the host.  The films are the float64 film's, so the maps are those of the host route up to the float32 film's rounding.  Same return value."""
+    single, n_pass = _passes(total_spp)
+    integrator_kwargs = dict(integrator_kwargs)
+    integrator_kwargs.pop("hetero_offset", None)
+    integrator_kwargs.pop("hetero_frequency", None)
+    scene.set_integrator(doppler_integrator_dict(hetero_frequency=0.0, hetero_offset=0.0, **integrator_kwargs))
+    exposure_time, w_g = integrator_kwargs.get("exposure_time", 0.0015), integrator_kwargs.get("w_g", 30)
+    return scene.render_velocity_map_denoised(n_pass, single, [float(o) for o in offsets], exposure_time, w_g, details=details, **(denoiser or {}))
 
 
 class TemporalVelocityMap:
